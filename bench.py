@@ -3,7 +3,12 @@
 batch-256 synthetic 224x224 RGB frames (configs[1]), plus queries/s of the
 top-10 scan over a 1M x 512 matrix (configs[2]) as a secondary object.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value` = frames/s over the K steps,
+`ms_per_step` = one step's share of them).  --full adds every secondary leg after the timed steps: the 50,000-frame sustained
+job, the per-kernel roofline, the search (configs[2]), resize and host end-to-end legs and the CPU baselines.  --dump-outputs
+DIR writes the embeddings of the last timed step (seeded inputs: the same arrays from run to run) as DIR/<name>.npy.
 
 N>1: one rank per GPU under torch.distributed.run (RCCL).  Typed as above WITHOUT a launcher
 (WORLD_SIZE unset), this process starts the N ranks itself — before touching any GPU — relays rank 0's
@@ -203,7 +208,36 @@ def parse():
     ap.add_argument("--streams", type=int, default=3,
                     help="batches in flight per GPU: consecutive steps alternate between this many encoder "
                          "handles on separate HIP streams, so one batch's tail workgroups overlap the next batch")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary leg: the 50,000-frame sustained job, the per-kernel "
+                         "roofline, the search / resize / host end-to-end legs, the CPU baselines and the exchange's gather check "
+                         "(the --no-* switches above select among them); without it a run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, floating point as float32, integers (ids) as float64.  An array past
+    its share of the 64 MB budget is written as a fixed, seeded sample of its rows (in row order, the row numbers beside it
+    as <name>_rows.npy), so two builds run with the same arguments compare output for output."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // (2 * max(len(arrays), 1))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+        if a.nbytes > share:
+            keep = max(1, share // (a[:1].nbytes + 8))           # the sample and its float64 row numbers fit the share
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def gemm_flops(cls, rows, cfg):
@@ -265,6 +299,8 @@ def rehearse_cpu(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     ids = torch.arange(40, dtype=torch.int32).view(4, 10)
     gid, _ = sharded_topk(ids, torch.rand((4, 10), generator=g).sort(dim=1).values, rank * 40, 10)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"gathered_rows": rows.numpy()})
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": world * args.steps * BATCH / float(t.item()), "unit": "frames/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -426,6 +462,9 @@ def run_config4(args, torch, dist, dev, local, rank, world, comm, exchange, back
         a, b = job()
         ingest.append(max_over_ranks(a))
         search.append(max_over_ranks(b))
+    if rank == 0 and args.dump_outputs:              # the last job's embeddings of all 4,000 frames and this rank's answers
+        dump_outputs(args.dump_outputs, {"embeddings": allrows.cpu().numpy(), "search_ids": d_ids.cpu().numpy(),
+                                         "search_distances": d_dist.cpu().numpy()})
     t_ing, t_q = float(np.median(ingest)), float(np.median(search))
     return {"metric": METRIC, "value": total / t_ing, "unit": "frames/s", "n_gpus": world, "steps": max(1, args.steps),
             "warmup": max(1, args.warmup), "ms_per_step": 1e3 * (t_ing + t_q), "higher_is_better": True, "scaling": "strong",
@@ -573,10 +612,10 @@ def main():
             self.gathers = 0
 
         def out(self, st, n):
-            """Where the next batch's embeddings go (a device pointer); the encode runs on stream st."""
+            """Where the next batch's embeddings go (its n rows of the bucket); the encode runs on stream st."""
             if self.ev_gat[self.b] is not None:
                 st.wait_event(self.ev_gat[self.b])           # the bucket's previous gather has read it
-            return self.local[self.b][self.rows:].data_ptr()
+            return self.local[self.b][self.rows:self.rows + n]
 
         def encoded(self, st, n):
             self.ev_enc[self.b][self.slot].record(st)
@@ -627,14 +666,18 @@ def main():
     xchg = Exchange() if gather else None
 
     def step(i, n=None):
+        """Encode batch i on its stream; returns the rows its embeddings go to (complete after the next fence)."""
         j = i % nstreams
         n = BATCH if n is None else n
         with torch.cuda.stream(streams[j]):
             if xchg is None:
-                encs[j].encode_device(pool[i % len(pool)].data_ptr(), n, embs[j].data_ptr())
+                dst = embs[j][:n]
+                encs[j].encode_device(pool[i % len(pool)].data_ptr(), n, dst.data_ptr())
             else:
-                encs[j].encode_device(pool[i % len(pool)].data_ptr(), n, xchg.out(streams[j], n))
+                dst = xchg.out(streams[j], n)
+                encs[j].encode_device(pool[i % len(pool)].data_ptr(), n, dst.data_ptr())
                 xchg.encoded(streams[j], n)
+        return dst
 
     def fence():
         if xchg is not None:
@@ -706,16 +749,18 @@ def main():
     fence()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        last = step(i)
     fence()
     own_elapsed = time.perf_counter() - t0
     elapsed = max_over_ranks(own_elapsed)
     frames_per_s = world * args.steps * BATCH / elapsed
-    gather_check = xchg.check() if xchg is not None else None        # outside the timed region
+    if rank == 0 and args.dump_outputs:             # before any later leg reuses the buffers; rank 0's own frame shard at N > 1
+        dump_outputs(args.dump_outputs, {"embeddings": last.cpu().numpy()})
+    gather_check = xchg.check() if xchg is not None and args.full else None        # outside the timed region
 
     # one whole configs[1] job per rank: 50,000 frames = 195 batches of 256 + a ragged batch of 80
     sustained = None
-    if args.model == "b32" and not args.no_sustained:
+    if args.full and args.model == "b32" and not args.no_sustained:
         job = 50_000
         full, tail = divmod(job, BATCH)
         fence()
@@ -740,7 +785,7 @@ def main():
     out = {
         "metric": METRIC, "value": frames_per_s, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None,
+        "scaling": "weak", "vs_baseline": None, "full": args.full,
         "dtype": {"bf16": "bf16", "fp16": "fp16 MFMA operands (every GEMM group), fp32 accumulate", "mixed": "fp16 MFMA operands (bf16 for the patch-embed GEMM), fp32 accumulate"}.get(args.dtype, args.dtype),
         # BASELINE.json configs[1] says bf16: same operand width and MFMA rate as fp16, three mantissa bits fewer
         "dtype_note": ("configs[1] names bf16; the default here is fp16 MFMA operands (same 16-bit width, same MFMA rate, fp32 accumulation) because plain bf16 "
@@ -772,7 +817,7 @@ def main():
                                                          else 2 * cfg.patches * (cfg.hidden * cfg.hidden + 2 * cfg.hidden * cfg.mlp))},
     }
 
-    if rank == 0:
+    if args.full and rank == 0:
         # ---- roofline of the dominant kernel: per-class HIP-event timing on the launch stream ----
         torch.cuda.synchronize(dev)
         enc.profile_begin()
@@ -827,7 +872,7 @@ def main():
 
     cpu_legs = []        # CPU baselines / checks, run after every GPU leg (the GPU work is then contiguous on the box's clock)
     # ---- secondary: queries/s, top-10 over a row-sharded 1M x 512 matrix (configs[2]) ----
-    if not args.no_search:
+    if args.full and not args.no_search:
         n_rows, nq, k = args.search_rows // world, args.search_queries, 10
         dimq = args.search_dim
         g2 = torch.Generator(device=dev)
@@ -1047,7 +1092,7 @@ def main():
         idx.close()
 
     # ---- preprocessing leg: Pillow-exact resize of device-resident 1080p frames to 224x224 ----
-    if rank == 0 and world == 1 and not args.no_preprocess:
+    if args.full and rank == 0 and world == 1 and not args.no_preprocess:
         from video_quierer_amd.preprocess import BILINEAR, FramePreprocessor
         pn, ph, pw = 64, 1080, 1920
         pre = FramePreprocessor(local)
@@ -1095,7 +1140,7 @@ def main():
     # ---- the product path end to end, PCIe and host staging included (never `value`): host frame
     # dicts as frame_extractor.py yields them -> FeatureExtractor.extract_from_video_frames (pipelined ingest, two handles)
     # -> OptimizedHNSWIndex.add_batch (row-wise numpy normalisation as hnsw.py:157, one device append) -> one search_batch ----
-    if rank == 0 and world == 1 and args.model == "b32" and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and args.model == "b32" and not args.no_e2e:
         from video_quierer_amd.core.feature_extractor import FeatureExtractor
         hrng = np.random.default_rng(0)
         distinct = [hrng.integers(0, 255, (224, 224, 3), dtype=np.uint8) for _ in range(1024)]
@@ -1135,7 +1180,7 @@ def main():
     for leg in cpu_legs:
         leg()
     # ---- CPU baseline: the fp32 oracle (a port of the reference's CPU path) on a bounded sample ----
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         from oracle import clip_vit_oracle
         # the GPU box exposes all host cores but grants a one-GPU job a share of 16: more threads than
         # that only oversubscribe (a 256-thread run measured 0.44 frames/s)

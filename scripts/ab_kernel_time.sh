@@ -7,7 +7,7 @@ mkdir -p $O
 for lib in "$@"; do
   n=${lib%.so}
   ( export VQ_AMD_LIB=$PWD/video-quierer_amd/lib/$lib VQ_BENCH_CONCURRENT=1
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n.stats -o p -- python3 bench.py --steps ${AB_STEPS:-12} --warmup 3 --streams 1 --no-cpu-baseline --no-sustained --no-search --no-preprocess --no-e2e $AB_ARGS > $O/$n.bench_1stream.json 2> $O/$n.stats.err
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n.stats -o p -- python3 bench.py --full --steps ${AB_STEPS:-12} --warmup 3 --streams 1 --no-cpu-baseline --no-sustained --no-search --no-preprocess --no-e2e $AB_ARGS > $O/$n.bench_1stream.json 2> $O/$n.stats.err
     find $O/$n.stats -name '*kernel_stats.csv' -exec cp {} $O/$n.kernel_stats.csv \;
     rm -rf $O/$n.stats
     python3 - $O/$n.kernel_stats.csv "$lib" "${KERNEL:-attention}" <<'PY'

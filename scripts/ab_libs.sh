@@ -16,9 +16,9 @@ done | tee $O/frames_per_s.txt
 for lib in "$@"; do
   n=${lib%.so}
   ( export VQ_AMD_LIB=$PWD/video-quierer_amd/lib/$lib VQ_BENCH_CONCURRENT=1
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n.stats -o p -- python3 bench.py --steps 30 --warmup 6 --streams 1 --no-cpu-baseline --no-sustained --no-search --no-preprocess --no-e2e > $O/$n.bench_1stream.json 2> $O/$n.stats.err
-    timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/$n.fetch -o p -- python3 bench.py --steps 3 --warmup 1 --streams 1 --no-sustained --no-cpu-baseline --no-search --no-preprocess --no-e2e > /dev/null 2> $O/$n.fetch.err
-    timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/$n.write -o p -- python3 bench.py --steps 3 --warmup 1 --streams 1 --no-sustained --no-cpu-baseline --no-search --no-preprocess --no-e2e > /dev/null 2> $O/$n.write.err
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n.stats -o p -- python3 bench.py --full --steps 30 --warmup 6 --streams 1 --no-cpu-baseline --no-sustained --no-search --no-preprocess --no-e2e > $O/$n.bench_1stream.json 2> $O/$n.stats.err
+    timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/$n.fetch -o p -- python3 bench.py --full --steps 3 --warmup 1 --streams 1 --no-sustained --no-cpu-baseline --no-search --no-preprocess --no-e2e > /dev/null 2> $O/$n.fetch.err
+    timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/$n.write -o p -- python3 bench.py --full --steps 3 --warmup 1 --streams 1 --no-sustained --no-cpu-baseline --no-search --no-preprocess --no-e2e > /dev/null 2> $O/$n.write.err
     python3 scripts/pmc_traffic.py $O/$n.fetch $O/$n.write $O/$n.pmc_traffic.json "$lib, one batch at a time" > /dev/null
     find $O/$n.stats -name '*kernel_stats.csv' -exec cp {} $O/$n.kernel_stats.csv \;
     rm -rf $O/$n.stats $O/$n.fetch $O/$n.write

@@ -21,6 +21,9 @@ Produces
   ref_index_50.pkl(.sha256), ref_index_50_results.npz, simple_index.npz, ref_simple_index_cache.pkl
                              (`make_golden.py interop`) files WRITTEN by the real reference classes and the result
                              lists the real classes return (persistence / live-index fixtures).
+  build_index_50_refload.npz (`make_golden.py refload`) the committed build-written build_index_50.pkl as the REAL
+                             HNSWIndex.load sees it: the file's SHA-256, parameters, rows, the flat-graph walk and
+                             the lists after a re-add under random.seed(3).
   knn_ref_10000.npz, knn_ref_100000.npz
                              (`make_golden.py knn_big 10000`, `... knn_big 100000`) the REAL OptimizedHNSWIndex over a
                              10k / 100k-row prefix of configs[2]'s recipe, built under the caller's STRING ids
@@ -376,7 +379,40 @@ def capture_interop():
     np.savez_compressed(os.path.join(HERE, "simple_index.npz"), **out)
 
 
+def capture_refload():
+    """The committed build-written file (build_index_50.pkl, from tests/test_gpu_parity.py::
+    test_index_save_writes_the_reference_layout) loaded by the REAL reference HNSWIndex.load (hnsw.py:341-380): the SHA-256
+    of the file it read, its parameters, its rows in the interop ids' order, what its walk over the file's flat graph returns
+    for the first query, and the lists the real class returns after re-adding the rows under random.seed(3).
+    $VQ_REFERENCE_DIR names the reference checkout."""
+    sys.path.insert(0, os.path.join(os.environ["VQ_REFERENCE_DIR"], "src"))
+    from indexes.hnsw import HNSWIndex                 # the real reference
+
+    path = os.path.join(HERE, "build_index_50.pkl")
+    with open(path, "rb") as f:
+        digest = hashlib.sha256(f.read()).hexdigest()
+    vecs, ids, qs = interop_vectors()
+    ref = HNSWIndex(dimension=8)
+    ref.load(path)
+    flat = ref.search(qs[0], 5)
+    random.seed(3)
+    rebuilt = HNSWIndex(dimension=64)
+    rebuilt.add_batch([ref.data[i] for i in ids], ids)
+    res = [rebuilt.search(q, 5) for q in qs]
+    np.savez_compressed(os.path.join(HERE, "build_index_50_refload.npz"),
+                        sha256=digest, dimension=ref.dimension, size=ref.size(), entry_point=ref.entry_point,
+                        M=ref.M, max_M=ref.max_M, ef_construction=ref.ef_construction, ef_search=ref.ef_search,
+                        level_generation_factor=ref.level_generation_factor,
+                        data=np.stack([ref.data[i] for i in ids]),
+                        flat_search_ids=np.array([r["id"] for r in flat]),
+                        rebuilt_ids=np.array([[r["id"] for r in rr] for rr in res]),
+                        rebuilt_dist=np.array([[r["distance"] for r in rr] for rr in res], dtype=np.float32))
+
+
 if __name__ == "__main__":
+    if "refload" in sys.argv[1:]:
+        capture_refload()
+        sys.exit(0)
     if "knn_big" in sys.argv[1:]:
         capture_knn_big(int(sys.argv[sys.argv.index("knn_big") + 1]))
         sys.exit(0)

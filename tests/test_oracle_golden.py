@@ -266,33 +266,48 @@ def test_reference_written_index_file_equals_exact_oracle():
 
 
 def test_reference_class_loads_a_build_written_index_file():
-    """Build-container only (needs /root/reference): the file the GPU build's HNSWIndex.save wrote
-    (tests/golden/build_index_50.pkl, produced on the GPU box by tests/test_gpu_parity.py::
-    test_index_save_writes_the_reference_layout) loads with the REAL class — same rows, same ids, same parameters.
-    It carries no navigable graph: searching it with the reference needs a re-add, shown here."""
-    import os
-    import sys
-    import pytest
-    if not os.path.isdir("/root/reference/src") or not os.path.exists(_golden("build_index_50.pkl")):
-        pytest.skip("needs /root/reference and the committed build-written file")
-    # by file path under a private name: `indexes.hnsw` may already be this build's drop-in (install_dropin())
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_reference_hnsw", "/root/reference/src/indexes/hnsw.py")
-    ref_mod = importlib.util.module_from_spec(spec)
-    sys.dont_write_bytecode = True
-    spec.loader.exec_module(ref_mod)
-    HNSWIndex = ref_mod.HNSWIndex
+    """The file the GPU build's HNSWIndex.save wrote (tests/golden/build_index_50.pkl, produced on the GPU box by
+    tests/test_gpu_parity.py::test_index_save_writes_the_reference_layout) loads with the REAL class — same rows, same ids,
+    same parameters.  It carries no navigable graph: searching it with the reference needs a re-add.
+    What the real class saw is the fixture build_index_50_refload.npz (make_golden.py refload), keyed by the SHA-256 of the
+    file it loaded; the load (hnsw.py:341-380), the flat-graph walk and the re-add are restated here on the committed file."""
+    import pickle
+    with open(_golden("build_index_50.pkl"), "rb") as f:
+        raw = f.read()
+    seen = np.load(_golden("build_index_50_refload.npz"))
+    assert hashlib.sha256(raw).hexdigest() == str(seen["sha256"]) == open(_golden("build_index_50.pkl.sha256")).read().strip()
     vecs, ids, qs = _interop_vectors()
-    ref = HNSWIndex(dimension=8)
-    ref.load(_golden("build_index_50.pkl"))
-    assert ref.dimension == 64 and ref.size() == 50 and ref.entry_point in ids
-    assert np.array_equal(np.stack([ref.data[i] for i in ids]), np.stack([v / np.linalg.norm(v) for v in vecs]).astype(np.float32))
-    assert len(ref.search(qs[0], 5)) == 1          # flat graph: the reference's walk sees the entry point only
-    random.seed(3)
-    rebuilt = HNSWIndex(dimension=64)
-    rebuilt.add_batch([ref.data[i] for i in ids], ids)
+    unit = np.stack([v / np.linalg.norm(v) for v in vecs]).astype(np.float32)
+    # the real class after load(): parameters, rows, a walk that sees the entry point only, the lists after a re-add
+    assert int(seen["dimension"]) == 64 and int(seen["size"]) == 50 and str(seen["entry_point"]) in ids
+    assert np.array_equal(seen["data"], unit)
+    assert len(seen["flat_search_ids"]) == 1
     gold = np.load(_golden("ref_index_50_results.npz"))
-    assert [[r["id"] for r in rebuilt.search(q, 5)] for q in qs] == [list(r) for r in gold["ids"]]
+    assert [list(r) for r in seen["rebuilt_ids"]] == [list(r) for r in gold["ids"]]
+    # the same from the committed file: every field load() reads, restored as it restores them
+    s = pickle.loads(raw)
+    for key in ("dimension", "M", "max_M", "ef_construction", "ef_search", "level_generation_factor", "element_count", "entry_point"):
+        assert s[key] == seen["size" if key == "element_count" else key].item(), key
+    assert np.array_equal(np.stack([s["data"][i] for i in ids]), seen["data"])
+    h = hnsw_oracle.HnswOracle(s["dimension"], M=s["M"], ef_construction=s["ef_construction"], ef_search=s["ef_search"],
+                               max_M=s["max_M"], level_generation_factor=s["level_generation_factor"])
+    for i, (node, v) in enumerate(s["data"].items()):
+        h.ids.append(node)
+        h.row_of[node] = i
+        h.vec.append(v)
+        h.level.append(s["levels"][node])
+        h.adj.append([set() for _ in range(s["levels"][node] + 1)])
+    for lv, nodes in s["graph"].items():
+        for node, nbrs in nodes.items():
+            h.adj[h.row_of[node]][int(lv)] = {h.row_of[n] for n in nbrs}
+    h.entry = h.row_of[s["entry_point"]]
+    assert [r["id"] for r in h.search(qs[0], 5)] == list(seen["flat_search_ids"])
+    random.seed(3)
+    rebuilt = hnsw_oracle.HnswOracle(64)
+    rebuilt.add_batch([s["data"][i] for i in ids], ids)
+    res = [rebuilt.search(q, 5) for q in qs]
+    assert [[r["id"] for r in rr] for rr in res] == [list(r) for r in seen["rebuilt_ids"]]
+    assert np.array_equal(np.array([[r["distance"] for r in rr] for rr in res], dtype=np.float32), seen["rebuilt_dist"])
 
 
 def test_simple_index_fixture_is_reversed_argsort_of_dots():
