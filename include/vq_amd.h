@@ -231,6 +231,28 @@ int vq_index_search_device(vq_index* idx, const void* d_queries_f32, int nq, int
 int vq_index_synchronize(vq_index* idx);
 int vq_index_set_stream(vq_index* idx, void* hip_stream);
 
+/* Grouped search: the k best GROUPS (videos), one best row (frame) each — what video_search_system.py:296-342 builds on the
+ * host by over-fetching search(q, k * 2) and keeping each video's first row, which returns fewer than k videos once the top
+ * 2k frames span fewer than k of them.
+ *   vq_index_set_groups: group_of_row [n] labels every row, dense in [0, n_groups) (every group holds a row), n = the current
+ *   size; all of it is checked (VQ_ERR_INVALID).  n = 0 clears the labels.  The library keeps them with a by-group row list.
+ *   Lifetime as the id ranks: after vq_index_add* a grouped search is refused (VQ_ERR_INVALID) until the labels are set again;
+ *   vq_index_update_rows keeps them, vq_index_clear drops them.  Synchronous.
+ *   vq_index_search_grouped: per query, a group's best row is its row with the smallest (distance, tie rank) — distance and
+ *   tie rank as vq_index_search — and groups are ordered by their best row's (distance, tie rank).  groups / rows / dist are
+ *   [nq][k]: the first min(k, n_groups) groups, their best row numbers and distances; unused slots are -1 / -1 / +inf.  This is
+ *   the plain search's exhaustive (distance, id) list with every row dropped whose group came earlier.  mode as vq_index_search
+ *   (2 = fp16 group-max scan + exact re-score of the candidate groups with proof, for dim 256, 512 or 768; mode 0 takes it
+ *   under the plain search's rule); queries the proof does not cover (|q|^2 outside [0.25, 4], not finite, too many candidate
+ *   groups) are answered by the exact path on the device.  The _device form takes device pointers and is asynchronous on the
+ *   index's stream.  After a grouped search vq_index_last_search_stats reports [0] queries answered by the fp16 path, [1] rows
+ *   re-scored exactly (summed over queries), [2] queries answered by the exact path. */
+int vq_index_set_groups(vq_index* idx, const int32_t* group_of_row, int64_t n, int32_t n_groups);
+int vq_index_search_grouped(vq_index* idx, const float* queries, int nq, int k, int mode,
+                            int32_t* groups, int32_t* rows, float* dist);
+int vq_index_search_grouped_device(vq_index* idx, const void* d_queries_f32, int nq, int k, int mode,
+                                   void* d_groups_i32, void* d_rows_i32, void* d_dist_f32);
+
 /* save / load support (hnsw.py:306-380): the stored (normalised) rows. */
 int vq_index_export(vq_index* idx, float* rows /*[size][dim]*/);
 /* Single stored rows (the reference reads `self.data[node_id]`, a dict lookup): out [n][dim] = rows row_numbers[0..n). */
@@ -284,7 +306,9 @@ int vq_index_profile_end(vq_index* idx, float* ms /*[VQ_IDX_NCLASS]*/, int* laun
 const char* vq_index_profile_class_name(int cls);
 /* counters of the last fp16-scan search: [0] queries verified exact by the
  * margin test, [1] queries that needed block rescans, [2] queries sent to the
- * full exact scan */
+ * full exact scan.  After vq_index_search_grouped*: [0] queries answered by the
+ * fp16 path, [1] candidate rows re-scored exactly (summed over queries), [2]
+ * queries answered by the exact path. */
 int vq_index_last_search_stats(vq_index* idx, int64_t* stats /*[3]*/);
 
 /* ------------------------------------------------------------------ frame preprocessing

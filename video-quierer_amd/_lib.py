@@ -105,6 +105,10 @@ SIGNATURES = {
     "vq_index_set_id_ranks": (c_int, [c_void_p, POINTER(c_int32), c_int64]),
     "vq_index_search": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, POINTER(c_int32), POINTER(c_float)]),
     "vq_index_search_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vq_index_set_groups": (c_int, [c_void_p, POINTER(c_int32), c_int64, c_int32]),
+    "vq_index_search_grouped": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32),
+                                        POINTER(c_float)]),
+    "vq_index_search_grouped_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vq_index_synchronize": (c_int, [c_void_p]),
     "vq_index_set_stream": (c_int, [c_void_p, c_void_p]),
     "vq_index_export": (c_int, [c_void_p, POINTER(c_float)]),

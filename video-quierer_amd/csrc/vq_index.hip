@@ -8,12 +8,14 @@
 #include "knn_fallback.h"
 #include "knn_scan_deep.h"
 #include "knn_scan_fold.h"
+#include "knn_grouped.h"
 
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <tuple>
 #include <vector>
 
 namespace vq {
@@ -42,6 +44,19 @@ struct vq_index {
     // number of rows they cover (0 = none set: ties come back in row order).  A search with rank_n != size is refused.
     int32_t* d_rank = nullptr; int32_t* d_rank_inv = nullptr; int64_t rank_cap = 0, rank_n = 0;
     TieOrder tie() const { return rank_n ? TieOrder{d_rank, d_rank_inv} : TieOrder{nullptr, nullptr}; }
+    // group labels (vq_index_set_groups): label per row, padded with -1 to whole 128-row streams; the by-group CSR row list
+    // (goff [n_groups + 1], grows [n]); per stream the label its 128 rows share, or -1.  group_n = the rows they cover (0 = none
+    // set); a grouped search with group_n != size is refused.
+    int32_t* d_group = nullptr; int32_t* d_goff = nullptr; int32_t* d_grows = nullptr; int32_t* d_sgroup = nullptr;
+    int64_t group_n = 0, group_cap = 0; int32_t n_groups = 0;
+    // grouped-search scratch (knn_grouped.h) and its outcome counters (pinned copy read by last_search_stats)
+    uint32_t* d_gbest = nullptr; int64_t gbest_cap = 0;
+    int32_t* d_gcand = nullptr; int64_t gcand_cap = 0;              // cand [qc][CAND] | pref [qc][CAND + 1] | n [qc] | flags [qc] | thr [qc]
+    uint64_t* d_gkeys = nullptr; int64_t gkeys_cap = 0;             // best [qc][CAND] (fp16 path), per-block lists (exact path / redo)
+    uint64_t* d_gpart = nullptr; int64_t gpart_cap = 0;
+    unsigned long long* d_gcounters = nullptr; unsigned long long* h_gcounters = nullptr;
+    int32_t* d_gout = nullptr; int64_t gout_cap = 0;                // vq_index_search_grouped: device results [3][nq][k]
+    bool gstats_pending = false;
     // fp16 scan scratch
     uint16_t* d_q16 = nullptr; int64_t q16_cap = 0;
     uint32_t* d_keys = nullptr; int64_t keys_cap = 0;
@@ -403,6 +418,7 @@ int search_fp16(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_i
 
 int search_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode, int32_t* d_ids, float* d_dist, bool host_sync = false) {
     VQ_CHECK(mode >= 0 && mode <= 2, "vq_index_search: mode %d unknown", mode);
+    x->gstats_pending = false;
     VQ_CHECK(x->rank_n == 0 || x->rank_n == x->size, "vq_index_search: the id ranks cover %lld rows, the index holds %lld "
              "(call vq_index_set_id_ranks again after adding rows, or clear them)", (long long)x->rank_n, (long long)x->size);
     // rows were added un-normalised ON THE DEVICE since the last look (vq_index_add_device: the one add that does not block):
@@ -414,6 +430,140 @@ int search_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode
     // auto: the MFMA scan pays once the matrix is large enough to amortise its fixed costs
     const bool use_fp16 = mode == 2 || (mode == 0 && fp16_ok && x->size >= 16384);
     return use_fp16 ? search_fp16(x, d_queries, nq, k, d_ids, d_dist, host_sync) : search_exact(x, d_queries, nq, k, d_ids, d_dist);
+}
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device only: remembered per (device, kernel).
+int set_dyn_lds(const void* fn, size_t bytes) {
+    static std::mutex mu;
+    static std::vector<std::tuple<int, const void*, size_t>> done;
+    int dev = 0;
+    VQ_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    for (const auto& t : done)
+        if (std::get<0>(t) == dev && std::get<1>(t) == fn && std::get<2>(t) >= bytes) return 0;
+    VQ_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done.emplace_back(dev, fn, bytes);
+    return 0;
+}
+
+// ---- grouped search (knn_grouped.h) ----
+int grouped_lpg(const vq_index* x) {                  // lanes per group in group_block_topk_kernel, from the mean group size
+    const int64_t mean = x->size / std::max<int32_t>(1, x->n_groups);
+    return mean >= 256 ? 64 : mean >= 64 ? 16 : mean >= 8 ? 4 : 1;
+}
+
+// Exact path: the plain path's fp64-chain distances for a slice of queries -> group minima and each block's k best -> merge.
+int search_grouped_exact(vq_index* x, const float* d_queries, int nq, int k, int32_t* groups, int32_t* rows_out, float* dist) {
+    const int64_t n = x->size, ld = round_up(n, 64);
+    const int G = x->n_groups, nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK);
+    int64_t qslice = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)128 << 20) / ld));          // 512 MiB of distances per slice
+    qslice = std::max<int64_t>(1, std::min<int64_t>(qslice, ((int64_t)32 << 20) / ((int64_t)nblocks * kl)));   // 256 MiB of block lists
+    VQ_TRY(reserve_buf(x->d_dist, x->dist_cap, qslice * ld));
+    VQ_TRY(reserve_buf(x->d_gpart, x->gpart_cap, qslice * nblocks * kl));
+    const size_t qbytes = (size_t)EDS_MAX_Q * x->dim * 8;
+    const bool small_ok = qbytes <= ((size_t)96 << 10);
+    if (small_ok && nq <= EDS_MAX_Q) VQ_TRY(set_dyn_lds((const void*)exact_dist_small_kernel, qbytes));
+    for (int64_t q0 = 0; q0 < nq; q0 += qslice) {
+        const int cur = (int)std::min<int64_t>(qslice, nq - q0);
+        const float* qp = d_queries + q0 * x->dim;
+        {
+            Prof p(x, I_EXACT_DIST);
+            if (small_ok && nq <= EDS_MAX_Q)
+                hipLaunchKernelGGL(exact_dist_small_kernel, dim3(cdiv(n, 64)), dim3(256), qbytes, x->stream, x->rows, n, x->dim, qp, cur, x->d_dist, ld);
+            else
+                hipLaunchKernelGGL(exact_dist_kernel, dim3(cdiv(n, 64), cdiv(cur, 32)), dim3(256), 0, x->stream, x->rows, n, x->dim, qp, cur, x->d_dist, ld);
+        }
+        {
+            Prof p(x, I_SELECT);
+            hipLaunchKernelGGL(group_block_topk_kernel<true>, dim3(nblocks, cur), dim3(256), 0, x->stream, x->d_dist, ld, nullptr, x->dim, nullptr,
+                               x->d_goff, x->d_grows, G, grouped_lpg(x), kl, nblocks, x->d_gpart, nullptr, x->tie());
+            hipLaunchKernelGGL(group_merge_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gpart, nblocks * kl, k, x->d_group,
+                               groups + q0 * k, rows_out + q0 * k, dist + q0 * k, nullptr, x->tie());
+        }
+    }
+    VQ_HIP(hipGetLastError());
+    x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = nq;
+    x->stats_pending = false; x->gstats_pending = false;
+    return 0;
+}
+
+// fp16 path: group-max scan -> threshold + candidates -> exact re-score of the candidates' rows; flagged queries are redone
+// exactly on the device (group_block_topk_kernel<false> computes their distances itself), so nothing here waits.
+int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int32_t* groups, int32_t* rows_out, float* dist) {
+    const int64_t n = x->size, streams = cdiv(n, SCAN_STREAM_ROWS), CA = GRP_CAND_MAX;
+    const int G = x->n_groups, nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK);
+    int64_t qc = std::max<int64_t>(16, ((int64_t)64 << 20) / G / 16 * 16);          // gbest [qc][G]: <= 256 MiB
+    qc = std::min<int64_t>(std::min<int64_t>(qc, round_up(nq, 16)), 1024);
+    while (qc > 16 && qc * nblocks * kl > ((int64_t)32 << 20)) qc -= 16;               // the redo's block lists: <= 256 MiB
+    VQ_TRY(reserve_buf(x->d_q16, x->q16_cap, qc * x->dim));
+    VQ_TRY(reserve_buf(x->d_gbest, x->gbest_cap, qc * G));
+    VQ_TRY(reserve_buf(x->d_gcand, x->gcand_cap, qc * CA + qc * (CA + 1) + 3 * qc));
+    VQ_TRY(reserve_buf(x->d_gkeys, x->gkeys_cap, qc * CA));
+    VQ_TRY(reserve_buf(x->d_gpart, x->gpart_cap, qc * nblocks * kl));
+    if (!x->d_gcounters) {
+        VQ_HIP(hipMalloc((void**)&x->d_gcounters, 3 * sizeof(unsigned long long)));
+        VQ_HIP(hipHostMalloc((void**)&x->h_gcounters, 3 * sizeof(unsigned long long)));
+    }
+    int32_t* cand = x->d_gcand;
+    int32_t* pref = cand + qc * CA;
+    int32_t* cn = pref + qc * (CA + 1);
+    int32_t* flags = cn + qc;
+    float* thr = (float*)(flags + qc);
+    VQ_HIP(hipMemsetAsync(x->d_gcounters, 0, 3 * sizeof(unsigned long long), x->stream));
+    const float eps_rows = scan_eps_unit(x->dim) * x->row_norm_max;
+    auto scan = x->dim == 768 ? scan3_group_max_kernel<24> : x->dim == 512 ? scan3_group_max_kernel<16> : scan3_group_max_kernel<8>;
+    for (int64_t q0 = 0; q0 < nq; q0 += qc) {
+        const int cur = (int)std::min<int64_t>(qc, nq - q0);
+        const int64_t q_pad = round_up(cur, 16);
+        const float* qp = d_queries + q0 * x->dim;
+        {
+            Prof p(x, I_TO_F16);
+            const int64_t total4 = q_pad * x->dim / 4;
+            hipLaunchKernelGGL(queries_to_f16_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 2048)), dim3(256), 0, x->stream,
+                               qp, x->d_q16, cur, q_pad, x->dim);
+        }
+        VQ_HIP(hipMemsetAsync(x->d_gbest, 0, (size_t)cur * G * 4, x->stream));
+        {
+            Prof p(x, I_MFMA_SCAN);
+            hipLaunchKernelGGL(scan, dim3(cdiv(streams, 4), (int)(q_pad / 16)), dim3(256), 0, x->stream, x->d_q16, x->rows16, streams,
+                               x->d_group, x->d_sgroup, cur, G, x->d_gbest);
+        }
+        {
+            Prof p(x, I_RESCORE);
+            hipLaunchKernelGGL(group_threshold_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gbest, G, k, qp, x->dim, eps_rows, x->d_goff,
+                               cand, pref, cn, thr, x->d_gkeys, flags);
+            hipLaunchKernelGGL(group_rescore_kernel, dim3(GRP_RESCORE_SPLITS, cur), dim3(256), 0, x->stream, x->d_q16, qp, x->rows, x->rows16,
+                               x->dim, x->d_goff, x->d_grows, cand, pref, cn, thr, flags, x->d_gkeys, x->d_gcounters, x->tie());
+            hipLaunchKernelGGL(group_finalize_kernel, dim3(cur), dim3(256), 0, x->stream, cn, x->d_gkeys, k, G, x->d_group, flags,
+                               groups + q0 * k, rows_out + q0 * k, dist + q0 * k, x->d_gcounters, x->tie());
+        }
+        {
+            Prof p(x, I_EXACT_DIST);                 // the exact redo of flagged queries (every workgroup of an unflagged query leaves at once)
+            hipLaunchKernelGGL(group_block_topk_kernel<false>, dim3(nblocks, cur), dim3(256), 0, x->stream, nullptr, 0, x->rows, x->dim, qp,
+                               x->d_goff, x->d_grows, G, grouped_lpg(x), kl, nblocks, x->d_gpart, flags, x->tie());
+            hipLaunchKernelGGL(group_merge_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gpart, nblocks * kl, k, x->d_group,
+                               groups + q0 * k, rows_out + q0 * k, dist + q0 * k, flags, x->tie());
+        }
+    }
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+    x->stats_pending = false; x->gstats_pending = true;
+    return 0;
+}
+
+int search_grouped_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode, int32_t* groups, int32_t* rows_out, float* dist) {
+    VQ_CHECK(mode >= 0 && mode <= 2, "vq_index_search_grouped: mode %d unknown", mode);
+    VQ_CHECK(x->rank_n == 0 || x->rank_n == x->size, "vq_index_search_grouped: the id ranks cover %lld rows, the index holds %lld "
+             "(call vq_index_set_id_ranks again after adding rows, or clear them)", (long long)x->rank_n, (long long)x->size);
+    VQ_CHECK(x->group_n == x->size, "vq_index_search_grouped: the group labels cover %lld rows, the index holds %lld "
+             "(call vq_index_set_groups after adding rows)", (long long)x->group_n, (long long)x->size);
+    if (mode != 1) VQ_TRY(refresh_norm_range(x));
+    const bool fp16_ok = (x->dim == 256 || x->dim == 512 || x->dim == 768) && k <= RV_K_MAX && x->size >= 1 && x->near_unit;
+    if (mode == 2) VQ_CHECK(fp16_ok, "vq_index_search_grouped: the fp16 scan needs dim 256, 512 or 768, k <= %d and near-unit rows "
+                                     "(0.5 <= |row|^2 <= 2; rows added with normalize=0 are measured)", RV_K_MAX);
+    const bool use_fp16 = mode == 2 || (mode == 0 && fp16_ok && x->size >= 16384);       // the plain search's rule
+    return use_fp16 ? search_grouped_fp16(x, d_queries, nq, k, groups, rows_out, dist)
+                    : search_grouped_exact(x, d_queries, nq, k, groups, rows_out, dist);
 }
 
 }  // namespace
@@ -471,6 +621,9 @@ int vq_index_destroy(vq_index* x) {
     if (x->h_q) (void)hipHostFree(x->h_q);
     if (x->h_res) (void)hipHostFree(x->h_res);
     (void)hipFree(x->d_norm_range); (void)hipFree(x->d_rank);
+    (void)hipFree(x->d_group); (void)hipFree(x->d_gbest); (void)hipFree(x->d_gcand); (void)hipFree(x->d_gkeys); (void)hipFree(x->d_gpart);
+    (void)hipFree(x->d_gcounters); (void)hipFree(x->d_gout);
+    if (x->h_gcounters) (void)hipHostFree(x->h_gcounters);
     delete x;
     return 0;
 }
@@ -492,6 +645,7 @@ int vq_index_clear(vq_index* x) {
     }
     x->norm_dirty = false; x->near_unit = true; x->row_norm_max = 1.0f;
     x->rank_n = 0;
+    x->group_n = 0; x->n_groups = 0;
     return 0;
 }
 
@@ -522,6 +676,53 @@ int vq_index_set_id_ranks(vq_index* x, const int32_t* rank_of_row, int64_t n) {
     VQ_HIP(hipMemcpyAsync(x->d_rank_inv, inv.data(), (size_t)n * 4, hipMemcpyHostToDevice, x->stream));
     VQ_HIP(hipStreamSynchronize(x->stream));                       // `inv` is this frame's, `rank_of_row` the caller's
     x->rank_n = n;
+    return 0;
+}
+
+int vq_index_set_groups(vq_index* x, const int32_t* group_of_row, int64_t n, int32_t n_groups) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && n >= 0 && (n == 0 || group_of_row), "vq_index_set_groups: bad argument");
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (n == 0) { x->group_n = 0; x->n_groups = 0; return 0; }
+    VQ_CHECK(n == x->size, "vq_index_set_groups: %lld labels for an index of %lld rows", (long long)n, (long long)x->size);
+    VQ_CHECK(n_groups >= 1 && n_groups <= n, "vq_index_set_groups: n_groups %d outside [1, %lld]", (int)n_groups, (long long)n);
+    // dense labels, checked here: the kernels index per-group arrays with them.  By-group row list: a stable counting sort.
+    std::vector<int32_t> off((size_t)n_groups + 1, 0);
+    for (int64_t r = 0; r < n; ++r) {
+        const int32_t g = group_of_row[r];
+        VQ_CHECK(g >= 0 && g < n_groups, "vq_index_set_groups: row %lld has label %d outside [0, %d)", (long long)r, (int)g, (int)n_groups);
+        ++off[(size_t)g + 1];
+    }
+    for (int32_t g = 0; g < n_groups; ++g)
+        VQ_CHECK(off[(size_t)g + 1] > 0, "vq_index_set_groups: group %d has no rows (labels must be dense in [0, %d))", (int)g, (int)n_groups);
+    for (int32_t g = 0; g < n_groups; ++g) off[(size_t)g + 1] += off[(size_t)g];
+    const int64_t n_pad = round_up(n, SCAN_STREAM_ROWS), streams = n_pad / SCAN_STREAM_ROWS;
+    // one host block mirrors the device layout: labels [n_pad] (-1 past n) | goff [n_groups + 1] | grows [n] | stream label [streams]
+    const int64_t total = n_pad + n_groups + 1 + n + streams;
+    std::vector<int32_t> h((size_t)total);
+    int32_t* lab = h.data(); int32_t* goff = lab + n_pad; int32_t* grows = goff + n_groups + 1; int32_t* sg = grows + n;
+    std::memcpy(lab, group_of_row, (size_t)n * 4);
+    std::fill(lab + n, lab + n_pad, -1);
+    std::memcpy(goff, off.data(), off.size() * 4);
+    for (int64_t r = 0; r < n; ++r) grows[off[(size_t)lab[r]]++] = (int32_t)r;
+    for (int64_t s = 0; s < streams; ++s) {
+        const int32_t* l = lab + s * SCAN_STREAM_ROWS;
+        bool same = l[0] >= 0;
+        for (int i = 1; i < SCAN_STREAM_ROWS && same; ++i) same = l[i] == l[0];
+        sg[s] = same ? l[0] : -1;
+    }
+    if (total > x->group_cap) {
+        VQ_HIP(hipStreamSynchronize(x->stream));                   // a search in flight may still read the old arrays
+        (void)hipFree(x->d_group); x->d_group = nullptr; x->group_cap = 0; x->group_n = 0; x->n_groups = 0;
+        const int64_t cap = total + total / 4 + 1024;
+        hipError_t e = hipMalloc((void**)&x->d_group, (size_t)cap * 4);
+        if (e != hipSuccess) return fail(VQ_ERR_OOM, "vq_index_set_groups: hipMalloc failed: %s", hipGetErrorString(e));
+        x->group_cap = cap;
+    }
+    VQ_HIP(hipMemcpyAsync(x->d_group, h.data(), (size_t)total * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));                       // `h` is this frame's
+    x->d_goff = x->d_group + n_pad; x->d_grows = x->d_goff + n_groups + 1; x->d_sgroup = x->d_grows + n;
+    x->group_n = n; x->n_groups = n_groups;
     return 0;
 }
 
@@ -693,6 +894,44 @@ int vq_index_search(vq_index* x, const float* queries, int nq, int k, int mode, 
     return 0;
 }
 
+int vq_index_search_grouped_device(vq_index* x, const void* d_queries, int nq, int k, int mode, void* d_groups, void* d_rows, void* d_dist) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && (nq == 0 || (d_queries && d_groups && d_rows && d_dist)),
+             "vq_index_search_grouped_device: bad argument");
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) {
+        const int64_t count = (int64_t)nq * k;
+        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, (int32_t*)d_groups, (float*)d_dist, count);
+        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, (int32_t*)d_rows, (float*)d_dist, count);
+        VQ_HIP(hipGetLastError());
+        return 0;
+    }
+    return search_grouped_dispatch(x, (const float*)d_queries, nq, k, mode, (int32_t*)d_groups, (int32_t*)d_rows, (float*)d_dist);
+}
+
+int vq_index_search_grouped(vq_index* x, const float* queries, int nq, int k, int mode, int32_t* groups, int32_t* rows, float* dist) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && (nq == 0 || (queries && groups && rows && dist)), "vq_index_search_grouped: bad argument");
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    if (x->size == 0) {
+        for (int64_t i = 0; i < count; ++i) { groups[i] = -1; rows[i] = -1; dist[i] = __builtin_inff(); }
+        return 0;
+    }
+    VQ_TRY(reserve_buf(x->d_q, x->q_cap, (int64_t)nq * x->dim));
+    VQ_TRY(reserve_buf(x->d_gout, x->gout_cap, 3 * count));
+    int32_t* d_g = x->d_gout; int32_t* d_r = d_g + count; float* d_d = (float*)(d_r + count);
+    VQ_HIP(hipMemcpyAsync(x->d_q, queries, (size_t)nq * x->dim * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_TRY(search_grouped_dispatch(x, x->d_q, nq, k, mode, d_g, d_r, d_d));
+    VQ_HIP(hipMemcpyAsync(groups, d_g, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(rows, d_r, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(dist, d_d, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
 int vq_index_synchronize(vq_index* x) {
     VQ_CHECK(x, "vq_index_synchronize: null handle");
     VQ_HIP(hipStreamSynchronize(x->stream));
@@ -767,6 +1006,11 @@ int vq_index_last_search_stats(vq_index* x, int64_t* stats) {
         VQ_HIP(hipStreamSynchronize(x->stream));
         for (int i = 0; i < 3; ++i) x->stats[i] = x->h_counters[1 + i];
         x->stats_pending = false;
+    }
+    if (x->gstats_pending) {                   // ... and so do the grouped fp16 path's
+        VQ_HIP(hipStreamSynchronize(x->stream));
+        for (int i = 0; i < 3; ++i) x->stats[i] = (int64_t)x->h_gcounters[i];
+        x->gstats_pending = false;
     }
     for (int i = 0; i < 3; ++i) stats[i] = x->stats[i];
     return 0;

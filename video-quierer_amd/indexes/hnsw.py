@@ -23,13 +23,49 @@ import time
 from collections.abc import Mapping
 from concurrent.futures import ThreadPoolExecutor
 from ctypes import POINTER, c_float, c_int32, c_int64, c_void_p
-from typing import Dict, Hashable, List, Optional, Sequence
+from typing import Callable, Dict, Hashable, List, Optional, Sequence
 
 import numpy as np
 
 from video_quierer_amd import _lib
 
 MODE_AUTO, MODE_EXACT, MODE_FP16 = 0, 1, 2
+
+
+def video_of(node_id: Hashable) -> Hashable:
+    """The default group of a node id for ``search_grouped``: the reference caller's frame ids are ``f"{video_id}_{i}"``
+    (video_search_system.py:164-166), so a string id's video is everything before its LAST underscore (video ids may
+    contain ``_``); any other id is its own group."""
+    return node_id.rsplit("_", 1)[0] if isinstance(node_id, str) else node_id
+
+
+class _GroupLabels:
+    """Dense int labels of the rows for ``vq_index_set_groups``, kept like the tie order: group keys are mapped to ints
+    incrementally (only rows added since the last upload are labelled), uploaded by the first grouped search after an add;
+    a different ``group_of`` (or a reloaded index) relabels everything.  Derived state: never saved."""
+
+    def __init__(self, group_of: Callable[[Hashable], Hashable], ids: List[Hashable]):
+        self.group_of, self.ids = group_of, ids
+        self.index: Dict[Hashable, int] = {}
+        self.keys: List[Hashable] = []
+        self.labels = np.empty(0, dtype=np.int32)
+        self.uploaded = -1                        # rows the device labels cover
+
+    def extend(self) -> bool:
+        """Label the rows added since the last call; True when the device labels are stale."""
+        n = len(self.ids)
+        if len(self.labels) < n:
+            index, keys, fn = self.index, self.keys, self.group_of
+            new = np.empty(n - len(self.labels), dtype=np.int32)
+            for j, nid in enumerate(self.ids[len(self.labels):]):
+                key = fn(nid)
+                g = index.get(key)
+                if g is None:
+                    g = index[key] = len(keys)
+                    keys.append(key)
+                new[j] = g
+            self.labels = np.concatenate([self.labels, new])
+        return self.uploaded != n
 
 
 class _RowView(Mapping):
@@ -374,6 +410,64 @@ class HNSWIndex:
             _lib.check(_lib.load().vq_index_search_device(self._h, c_void_p(d_queries), int(nq), int(k),
                                                           int(self.search_mode if mode is None else mode),
                                                           c_void_p(d_ids), c_void_p(d_dist)))
+
+    # -- grouped query: the k best videos, one best frame each ----------------------------
+    def _sync_groups(self, group_of: Optional[Callable[[Hashable], Hashable]]) -> _GroupLabels:
+        fn = video_of if group_of is None else group_of
+        gl = getattr(self, "_groups", None)
+        # relabel when the mapping changed or the id list was replaced (load); add_batch only appends to it
+        if gl is None or gl.group_of is not fn or gl.ids is not self._ids or len(gl.labels) > len(self._ids):
+            gl = self._groups = _GroupLabels(fn, self._ids)
+        if gl.extend():
+            n = len(gl.labels)
+            _lib.check(_lib.load().vq_index_set_groups(self._h, gl.labels.ctypes.data_as(POINTER(c_int32)), n, len(gl.keys)))
+            gl.uploaded = n
+        return gl
+
+    def _grouped_many(self, queries: Sequence[np.ndarray], k: int, group_of) -> List[List[Dict]]:
+        unit = np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32)
+        if unit.shape[1] != self.dimension:
+            raise ValueError(f"query dimension {unit.shape[1]} != index dimension {self.dimension}")
+        if k <= 0 or not self._ids:
+            return [[] for _ in queries]
+        if not self._identity:
+            self._sync_tie_order()
+        gl = self._sync_groups(group_of)
+        kk = min(int(k), len(gl.keys))
+        nq = unit.shape[0]
+        groups = np.empty((nq, kk), dtype=np.int32)
+        rows = np.empty((nq, kk), dtype=np.int32)
+        dist = np.empty((nq, kk), dtype=np.float32)
+        _lib.check(_lib.load().vq_index_search_grouped(self._h, _lib.fptr(unit), nq, kk, int(self.search_mode),
+                                                       groups.ctypes.data_as(POINTER(c_int32)),
+                                                       rows.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist)))
+        keys, names, identity = gl.keys, self._ids, self._identity
+        return [[{"group": keys[g], "id": int(r) if identity else names[r], "distance": d, "score": np.float32(1.0) - d}
+                 for g, r, d in zip(rg.tolist(), rr.tolist(), rd) if r >= 0]
+                for rg, rr, rd in zip(groups, rows, dist)]
+
+    def search_grouped(self, query: np.ndarray, k: int = 5,
+                       group_of: Optional[Callable[[Hashable], Hashable]] = None) -> List[Dict]:
+        """The k best GROUPS (videos) for one query, each with its best row: ``[{'group', 'id', 'distance', 'score'}]``.
+        Exactly the plain search's exhaustive (distance, id) list with every row dropped whose group came earlier — what
+        video_search_system.py:296-342 builds from ``search(q, k * 2)`` (it returns fewer than k videos once the top 2k
+        frames span fewer than k of them; this never does while the index holds k groups).  ``group_of`` maps a node id to
+        its group key (default ``video_of``: the caller's ``f"{video_id}_{i}"`` convention); a caller holding the metadata
+        passes ``lambda nid: meta[nid]['video_id']`` — keep passing the SAME callable, a different one relabels every row."""
+        if self.entry_point is None or self.element_count == 0:
+            return []
+        with self.lock:
+            return self._grouped_many([query], k, group_of)[0]
+
+    def search_grouped_batch(self, queries: List[np.ndarray], k: int = 5,
+                             group_of: Optional[Callable[[Hashable], Hashable]] = None) -> List[List[Dict]]:
+        """``search_grouped`` for a batch of queries, one device pass."""
+        if len(queries) == 0:
+            return []
+        if self.entry_point is None or self.element_count == 0:
+            return [[] for _ in queries]
+        with self.lock:
+            return self._grouped_many(queries, k, group_of)
 
     def synchronize(self) -> None:
         _lib.check(_lib.load().vq_index_synchronize(self._h))
