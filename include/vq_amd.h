@@ -198,6 +198,18 @@ int vq_index_add_device(vq_index* idx, const void* d_rows_f32, int64_t n, int no
  * reference's sequential assignments do.  normalize as vq_index_add.  The result is bit-identical to an index built
  * from scratch with the updated rows.  Synchronous. */
 int vq_index_update_rows(vq_index* idx, const float* rows, const int64_t* row_numbers, int64_t n, int normalize);
+/* Removal of rows (the reference drops a video's frames from its index, video_search_system.py:427-463): row_numbers [n], each in
+ * [0, size), else VQ_ERR_INVALID and the index is unchanged; a row named twice is removed once; n = 0 is a no-op.  The survivors
+ * keep their relative order and are renumbered densely (row r becomes r minus the removed rows below it), and the stored rows
+ * (fp32 master and fp16 scan copy) are bit-identical to what vq_index_add of the survivors stores.  Id ranks that cover the index
+ * stay valid: a survivor's new rank is its old rank minus the removed rows of smaller rank — exactly the ranks of the surviving ids
+ * — so no vq_index_set_id_ranks call is needed; stale ranks are dropped.  Group labels that cover the index stay valid too, with a
+ * canonical new numbering: groups left without rows are dropped and the others keep their old order, renumbered densely (old
+ * group g becomes g minus the emptied groups below it); the result is what vq_index_set_groups would build from those labels.
+ * Stale labels are dropped.  The |row|^2 range is kept (it still covers every survivor).  Rows move on the device, through at
+ * most 256 MiB of scratch.  Synchronous.  A sharded index (vq_index_search_sharded) is not renumbered across shards: removing
+ * rows from one shard shifts the row_offset of every shard behind it, which the caller passes. */
+int vq_index_remove_rows(vq_index* idx, const int64_t* row_numbers, int64_t n);
 int vq_index_size(vq_index* idx, int64_t* n);
 int vq_index_clear(vq_index* idx);
 /* The tie order of the result lists.  The reference returns `sorted(candidates)[:k]` over (distance, id) tuples

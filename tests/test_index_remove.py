@@ -1,0 +1,437 @@
+"""Row removal (vq_index_remove_rows, HNSWIndex.remove / remove_batch / remove_group, SimpleVideoIndex.remove_video): the pruned
+index must be indistinguishable from one built from the survivors in their old order.  Every comparison is bit for bit against
+the C oracle on the survivors and against a freshly built index of them: ids, groups, distances and stored rows."""
+from ctypes import POINTER, byref, c_int32, c_int64, c_void_p
+
+import numpy as np
+import pytest
+
+from conftest import knn_big_ids, knn_big_inputs
+from oracle import knn_oracle
+from test_grouped_search import _expected
+
+pytestmark = pytest.mark.gpu
+
+
+def _i32(a):
+    return a.ctypes.data_as(POINTER(c_int32))
+
+
+def _i64(a):
+    return np.ascontiguousarray(a, dtype=np.int64).ctypes.data_as(POINTER(c_int64))
+
+
+def _unit(qs):
+    return np.stack([q / np.linalg.norm(q) for q in qs]).astype(np.float32)
+
+
+def _ranks(ids):
+    order = sorted(range(len(ids)), key=ids.__getitem__)
+    rank = np.empty(len(ids), dtype=np.int32)
+    rank[order] = np.arange(len(ids), dtype=np.int32)
+    return rank
+
+
+class _C:
+    """A bare C-ABI index handle."""
+
+    def __init__(self, lib, dim):
+        self.lib, self.L, self.h = lib, lib.load(), c_void_p()
+        lib.check(self.L.vq_index_create(dim, byref(self.h)))
+        self.dim = dim
+
+    def add(self, rows, normalize=1):
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        self.lib.check(self.L.vq_index_add(self.h, self.lib.fptr(rows), len(rows), normalize))
+
+    def size(self):
+        n = c_int64()
+        self.lib.check(self.L.vq_index_size(self.h, byref(n)))
+        return n.value
+
+    def export(self):
+        out = np.empty((self.size(), self.dim), np.float32)
+        if len(out):
+            self.lib.check(self.L.vq_index_export(self.h, self.lib.fptr(out)))
+        return out
+
+    def remove(self, rows):
+        rows = np.asarray(rows, dtype=np.int64)
+        return self.L.vq_index_remove_rows(self.h, _i64(rows), len(rows))
+
+    def ranks(self, rank):
+        self.lib.check(self.L.vq_index_set_id_ranks(self.h, None if rank is None else _i32(rank), 0 if rank is None else len(rank)))
+
+    def groups(self, lab, n_groups):
+        self.lib.check(self.L.vq_index_set_groups(self.h, _i32(lab), len(lab), n_groups))
+
+    def search(self, qs, k, mode):
+        ids = np.empty((len(qs), k), np.int32); dist = np.empty((len(qs), k), np.float32)
+        rc = self.L.vq_index_search(self.h, self.lib.fptr(qs), len(qs), k, mode, _i32(ids), self.lib.fptr(dist))
+        return rc, ids, dist
+
+    def grouped(self, qs, k, mode):
+        g = np.empty((len(qs), k), np.int32); r = np.empty((len(qs), k), np.int32); d = np.empty((len(qs), k), np.float32)
+        self.lib.check(self.L.vq_index_search_grouped(self.h, self.lib.fptr(qs), len(qs), k, mode, _i32(g), _i32(r), self.lib.fptr(d)))
+        return g, r, d
+
+    def close(self):
+        self.lib.check(self.L.vq_index_destroy(self.h))
+
+
+def _oracle(stored, uq, k, tie=None):
+    """(distance, tie) order over the survivors' stored rows; tie = None: row order."""
+    n = len(stored)
+    tie = np.arange(n) if tie is None else tie
+    ids = np.full((len(uq), k), -1, np.int32); dist = np.full((len(uq), k), np.inf, np.float32)
+    for j, q in enumerate(uq):
+        d = knn_oracle.distances(stored, q)
+        o = np.lexsort((tie, d))[:k]
+        ids[j, :len(o)] = o; dist[j, :len(o)] = d[o]
+    return ids, dist
+
+
+def _check_plain(idx, fresh, stored, uq, ks, modes, tie=None):
+    for k in ks:
+        want = _oracle(stored, uq, k, tie)
+        for mode in modes:
+            rc, ids, dist = idx.search(uq, k, mode)
+            assert rc == 0, idx.L.vq_last_error()
+            assert np.array_equal(ids, want[0]), f"k {k} mode {mode}: ids differ from the oracle"
+            assert np.array_equal(dist, want[1]), f"k {k} mode {mode}: distances differ from the oracle"
+            if fresh is not None:
+                _, fi, fd = fresh.search(uq, k, mode)
+                assert np.array_equal(ids, fi) and np.array_equal(dist, fd), f"k {k} mode {mode}: differs from a fresh index"
+
+
+def test_c_abi_remove_ten_percent_with_string_id_ranks(gpu_lib):
+    n = 10_000
+    rows, qs = knn_big_inputs(n, nq=16)
+    ids = knn_big_ids(n)
+    uq = _unit(qs)
+    idx = _C(gpu_lib, 512)
+    idx.add(rows)
+    stored_all = idx.export()
+    idx.ranks(_ranks(ids))
+    rng = np.random.default_rng(42)
+    gone = rng.choice(n, n // 10, replace=False)
+    gone = np.concatenate([gone, gone[:1], [3, 5000]])               # a duplicate in the call; one planted duplicate row goes
+    keep = np.ones(n, bool); keep[gone] = False
+    assert idx.remove(gone) == 0
+    surv_ids = [i for i, kp in zip(ids, keep) if kp]
+    assert idx.size() == keep.sum()
+    assert np.array_equal(idx.export(), stored_all[keep])            # stored rows: the survivors', bit for bit, old order
+    fresh = _C(gpu_lib, 512)
+    fresh.add(rows[keep])
+    fresh.ranks(_ranks(surv_ids))
+    assert np.array_equal(fresh.export(), stored_all[keep])
+    # no vq_index_set_id_ranks after the removal: the renumbered ranks are the survivors' own
+    _check_plain(idx, fresh, stored_all[keep], uq, (10, 20, 40), (0, 1, 2), tie=_ranks(surv_ids))
+    idx.close(); fresh.close()
+
+
+@pytest.mark.parametrize("dim", [256, 132])
+def test_c_abi_edge_cases(gpu_lib, dim):
+    """First row, last rows, rows across a 2048-row range boundary, everything; sizes that are not multiples of 128; an
+    out-of-range row.  dim 132: rows that are not a multiple of 8 floats (exact scan only)."""
+    rng = np.random.default_rng(dim)
+    n = 5_000
+    rows = rng.standard_normal((n, dim)).astype(np.float32)
+    rows[4321] = rows[17]                                            # a tie that survives every step
+    uq = _unit(np.concatenate([rng.standard_normal((5, dim)).astype(np.float32), rows[17:18]]))
+    modes = (1, 2) if dim % 64 == 0 else (1,)
+    idx = _C(gpu_lib, dim)
+    idx.add(rows)
+    stored = idx.export()
+    alive = np.arange(n)
+    for pick in (lambda s: [0], lambda s: [s - 3, s - 2, s - 1], lambda s: list(range(2040, 2061)) + [4095, 4096]):
+        step = pick(alive.size)
+        assert idx.remove(step) == 0, idx.L.vq_last_error()
+        alive = np.delete(alive, step)
+        assert idx.size() == alive.size and alive.size % 128 != 0
+        assert np.array_equal(idx.export(), stored[alive])
+        fresh = _C(gpu_lib, dim)
+        fresh.add(rows[alive])
+        _check_plain(idx, fresh, stored[alive], uq, (1, 10), modes)
+        fresh.close()
+    before = idx.export()
+    for bad in ([alive.size], [-1], [0, alive.size + 5]):
+        assert idx.remove(bad) == -1 and b"outside" in idx.L.vq_last_error()      # VQ_ERR_INVALID
+        assert idx.size() == alive.size and np.array_equal(idx.export(), before)
+    assert idx.remove([]) == 0 and idx.size() == alive.size
+    assert idx.remove(np.arange(alive.size)[::-1]) == 0 and idx.size() == 0
+    rc, ids, dist = idx.search(uq, 4, 1)
+    assert rc == 0 and np.all(ids == -1) and np.all(np.isinf(dist))
+    idx.add(rows[:777])
+    assert np.array_equal(idx.export(), stored[:777])
+    _check_plain(idx, None, stored[:777], uq, (10,), modes)
+    idx.close()
+
+
+def test_ties_with_current_and_stale_ranks(gpu_lib):
+    rng = np.random.default_rng(3)
+    dim, n = 512, 3_000
+    rows = rng.standard_normal((n, dim)).astype(np.float32)
+    for r in (100, 900, 2500, 2999):
+        rows[r] = rows[7]                                            # five tied rows
+    ids = [f"clip{(r * 7919) % 13}_{r}" for r in range(n)]          # an id order unrelated to the row order
+    uq = _unit(np.stack([rows[7], rng.standard_normal(dim).astype(np.float32)]))
+    idx = _C(gpu_lib, dim)
+    idx.add(rows)
+    stored = idx.export()
+    idx.ranks(_ranks(ids))
+    gone = [900, 5, 2001]
+    keep = np.ones(n, bool); keep[gone] = False
+    assert idx.remove(gone) == 0
+    surv = [i for i, kp in zip(ids, keep) if kp]
+    _check_plain(idx, None, stored[keep], uq, (3, 10), (1, 2), tie=_ranks(surv))
+    rc, got, _ = idx.search(uq[:1], 4, 1)
+    assert [surv[r] for r in got[0]] == sorted(surv[r] for r in got[0])            # the tied rows in the caller's id order
+    # stale ranks (rows added since they were set): searches are refused until the removal drops them (contract)
+    idx.add(rows[:2])
+    assert idx.search(uq, 3, 1)[0] < 0
+    assert idx.remove([0]) == 0
+    stored2 = np.concatenate([stored[keep], stored[:2]])[1:]
+    _check_plain(idx, None, stored2, uq, (6,), (1, 2))                          # ties back in row order
+    idx.close()
+
+
+def test_groups_after_removal(gpu_lib):
+    rng = np.random.default_rng(8)
+    dim, n = 512, 20_000
+    rows = rng.standard_normal((n, dim)).astype(np.float32)
+    lens = [1, 7, 500, 3000, 130, 2]
+    lab = np.concatenate([np.full(lens[i % len(lens)], i) for i in range(60)])[:n]
+    lab = np.concatenate([lab, np.full(n - len(lab), 60)]).astype(np.int32)
+    rows[15_000] = rows[40]                                          # tied rows in different groups
+    ids = [f"v{lab[r]}_{r}" for r in range(n)]
+    qs = np.concatenate([rng.standard_normal((6, dim)).astype(np.float32), rows[40:41],
+                         rows[rng.integers(0, n, 9)] + np.float32(0.3) * rng.standard_normal((9, dim)).astype(np.float32)])
+    uq = _unit(qs)
+    idx = _C(gpu_lib, dim)
+    idx.add(rows)
+    stored = idx.export()
+    idx.ranks(_ranks(ids))
+    G = int(lab.max()) + 1
+    idx.groups(lab, G)
+    whole = np.flatnonzero(lab == 3)                                 # a 3000-row group goes entirely
+    part = np.flatnonzero(lab == 9)[::2]                             # half of another
+    single = np.flatnonzero(lab == 6)                                # a one-row group
+    gone = np.concatenate([whole, part, single])
+    keep = np.ones(n, bool); keep[gone] = False
+    assert idx.remove(gone) == 0
+    alive = np.bincount(lab[keep], minlength=G) > 0
+    new_lab = (np.cumsum(alive) - 1)[lab[keep]].astype(np.int32)       # the header's canonical numbering
+    assert (~alive).sum() == 2 and new_lab.max() + 1 == G - 2
+    surv = [i for i, kp in zip(ids, keep) if kp]
+    fresh = _C(gpu_lib, dim)
+    fresh.add(rows[keep])
+    fresh.ranks(_ranks(surv))
+    fresh.groups(new_lab, G - 2)
+    for k, mode in ((10, 1), (10, 2), (40, 2), (5, 1)):
+        want = _expected(stored[keep], uq, new_lab, _ranks(surv), k)
+        g, r, d = idx.grouped(uq, k, mode)
+        for j, ww in enumerate(want):
+            m = len(ww)
+            assert r[j, :m].tolist() == [x for x, _ in ww], f"query {j} k {k} mode {mode}: rows"
+            assert g[j, :m].tolist() == [int(new_lab[x]) for x, _ in ww], f"query {j}: groups"
+            assert d[j, :m].tolist() == [y for _, y in ww], f"query {j}: distances"
+        fg, fr, fd = fresh.grouped(uq, k, mode)
+        assert np.array_equal(g, fg) and np.array_equal(r, fr) and np.array_equal(d, fd)
+    _check_plain(idx, fresh, stored[keep], uq, (10,), (1, 2), tie=_ranks(surv))
+    idx.close(); fresh.close()
+
+
+def _py_index(vecs, ids, cls=None):
+    from video_quierer_amd.indexes.hnsw import HNSWIndex
+    idx = (cls or HNSWIndex)(dimension=vecs.shape[1])
+    idx.add_batch(vecs, ids)
+    return idx
+
+
+def _same_results(a, b, qs, k):
+    ra, rb = a.search_batch(list(qs), k), b.search_batch(list(qs), k)
+    assert [[(r["id"], r["distance"]) for r in x] for x in ra] == [[(r["id"], r["distance"]) for r in x] for x in rb]
+    assert [(r["id"], r["distance"]) for r in a.search(qs[0], k)] == [(r["id"], r["distance"]) for r in rb[0]]
+
+
+def _same_grouped(a, b, qs, k, group_of=None):
+    ga = a.search_grouped_batch(list(qs), k, group_of=group_of)
+    gb = b.search_grouped_batch(list(qs), k, group_of=group_of)
+    assert [[(r["group"], r["id"], r["distance"]) for r in x] for x in ga] == \
+           [[(r["group"], r["id"], r["distance"]) for r in x] for x in gb]
+
+
+def test_python_layer_remove_then_search_save_load(gpu_lib, tmp_path):
+    from video_quierer_amd import _lib
+    from video_quierer_amd.indexes.hnsw import HNSWIndex, OptimizedHNSWIndex
+    rng = np.random.default_rng(12)
+    dim = 512
+    lens = [40, 300, 7, 1, 120, 600, 33]
+    ids = [f"video{v}_{i}" for v, ln in enumerate(lens) for i in range(ln)]
+    n = len(ids)
+    vecs = rng.standard_normal((n, dim)).astype(np.float32)
+    vecs[400] = vecs[12]; vecs[1000] = vecs[12]                     # ties across videos
+    qs = np.concatenate([vecs[12:13], rng.standard_normal((7, dim)).astype(np.float32)])
+    idx = _py_index(vecs, ids, OptimizedHNSWIndex)
+    idx.search_grouped_batch(list(qs), 5)                            # labels on the device before the removals
+    idx.search(qs[0], 5)                                             # ranks on the device
+    uploads = []
+    real = _lib.load()
+
+    class Spy:
+        def __getattr__(self, name):
+            fn = getattr(real, name)
+            if name not in ("vq_index_set_groups", "vq_index_set_id_ranks"):
+                return fn
+
+            def traced(h, *args):
+                if h.value == idx._h.value:
+                    uploads.append(name)
+                return fn(h, *args)
+            return traced
+    orig_load = _lib.load
+    _lib.load = lambda: Spy()
+    try:
+        idx.remove("video0_12")
+        with pytest.raises(KeyError):
+            idx.remove("video0_12")
+        with pytest.raises(KeyError):
+            idx.remove_batch(["video1_3", "nope"])                   # atomic: nothing removed
+        assert "video1_3" in idx.data
+        assert idx.remove_batch(["video1_3", "video1_4", "video1_3", "video5_599"]) == 3
+        assert idx.remove_group("video3") == 1                       # a one-frame video: its group disappears
+        assert idx.remove_group("video2") == 7
+        assert idx.remove_group("no_such_video") == 0
+        gone = {"video0_12", "video1_3", "video1_4", "video5_599"} | {f"video2_{i}" for i in range(7)} | {"video3_0"}
+        surv = [i for i in ids if i not in gone]
+        keep = np.array([i not in gone for i in ids])
+        assert idx.size() == len(surv) and len(idx.data) == len(surv) and idx._ids == surv
+        assert "video0_12" not in idx.data and "video0_13" in idx.data and idx.entry_point == "video0_0"
+        fresh = _py_index(vecs[keep], surv)
+        assert np.array_equal(idx.data["video6_5"], fresh.data["video6_5"])
+        for k in (1, 10, 40):
+            _same_results(idx, fresh, qs, k)
+            _same_grouped(idx, fresh, qs, k)
+        assert uploads == []                                          # neither ranks nor labels went up again
+    finally:
+        _lib.load = orig_load
+    stored = idx._export()
+    want = knn_oracle.topk(stored, _unit(qs), 10)[1]
+    assert np.array_equal(np.array([[r["distance"] for r in x] for x in idx.search_batch(list(qs), 10)]), want)
+    # save: the same file as a fresh index of the survivors writes
+    idx.save(str(tmp_path / "pruned.pkl")); fresh.save(str(tmp_path / "fresh.pkl"))
+    assert (tmp_path / "pruned.pkl").read_bytes() == (tmp_path / "fresh.pkl").read_bytes()
+    loaded = HNSWIndex(dimension=dim)
+    loaded.load(str(tmp_path / "pruned.pkl"))
+    _same_results(loaded, fresh, qs, 10)
+    # add after a remove appends; re-adding a removed id appends it as a new row
+    extra = rng.standard_normal((3, dim)).astype(np.float32)
+    for ix in (idx, loaded, fresh):
+        ix.add_batch(extra, ["video0_12", "new_0", "video2_3"])
+    assert idx._ids[-3:] == ["video0_12", "new_0", "video2_3"]
+    for ix in (idx, loaded):
+        _same_results(ix, fresh, qs, 10)
+        _same_grouped(ix, fresh, qs, 10)
+    idx.remove_batch(list(idx._ids))
+    assert idx.size() == 0 and idx.entry_point is None and idx.search(qs[0], 5) == [] and idx.search_grouped(qs[0], 5) == []
+    idx.add_batch(vecs[:50], ids[:50])
+    _same_results(idx, _py_index(vecs[:50], ids[:50]), qs, 10)
+    for ix in (idx, loaded, fresh):
+        ix.close()
+
+
+def test_identity_index_after_a_remove(gpu_lib):
+    rng = np.random.default_rng(4)
+    dim, n = 256, 4_000
+    vecs = rng.standard_normal((n, dim)).astype(np.float32)
+    vecs[3900] = vecs[10]; vecs[2000] = vecs[10]
+    qs = np.concatenate([vecs[10:11], rng.standard_normal((4, dim)).astype(np.float32)])
+    idx = _py_index(vecs, range(n))
+    assert idx._identity
+    gone = [0, 2000, 2001, 3999]
+    idx.remove_batch(gone)
+    surv = [i for i in range(n) if i not in gone]
+    assert not idx._identity and idx._ids == surv
+    fresh = _py_index(vecs[surv], surv)
+    for mode in (1, 2):
+        idx.search_mode = fresh.search_mode = mode
+        _same_results(idx, fresh, qs, 10)
+        _same_grouped(idx, fresh, qs, 5, group_of=lambda nid: nid // 100)
+    idx.close(); fresh.close()
+
+
+def _ref_search(embeddings, metadata, q, k):
+    """video_search_overhaul.py:40-64 restated: E @ (q / (||q|| + 1e-10)), argsort descending."""
+    E = np.vstack(embeddings)
+    sim = E @ (q / (np.linalg.norm(q) + 1e-10))
+    top = np.argsort(sim, kind="stable")[::-1][:k]
+    return [dict(metadata[i], score=float(sim[i])) for i in top]
+
+
+def test_simple_video_index_remove_video(gpu_lib):
+    from video_quierer_amd.overhaul_index import SimpleVideoIndex
+    rng = np.random.default_rng(77)
+    emb = (rng.standard_normal((600, 512)) * rng.uniform(0.5, 3.0, (600, 1))).astype(np.float32)     # not unit length
+    emb[450] = emb[30]; emb[590] = emb[30]; emb[140] = emb[30]        # ties across videos
+    svi = SimpleVideoIndex()
+    for i, e in enumerate(emb[:500]):
+        svi.add_frame(e, f"video_{i // 100}.mp4", i * 0.5)
+    svi.video_hashes = {f"video_{v}.mp4": f"h{v}" for v in range(6)}
+    q = emb[30] * np.float32(2.5)
+    svi.search(q, 3)                                                 # push the first 500 frames
+    dev = svi._dev
+    for i, e in enumerate(emb[500:]):
+        svi.add_frame(e, f"video_{5 + (i % 2)}.mp4", 250 + i * 0.5)  # not yet on the device
+    assert svi.remove_video("video_1.mp4") == 100
+    assert svi.remove_video("video_5.mp4") == 50
+    assert "video_1.mp4" not in svi.video_hashes and "video_5.mp4" not in svi.video_hashes
+    assert svi._dev is dev and svi._pushed == 400                    # removed in place, not rebuilt
+    keep = [i for i in range(600) if not (100 <= i < 200) and not (i >= 500 and i % 2 == 0)]
+    assert [m["frame_id"] for m in svi.metadata] == keep                 # kept as stored
+    qs = [q, emb[7] * np.float32(0.3), rng.standard_normal(512).astype(np.float32)]
+    for qq in qs:
+        for k in (1, 5, 12):
+            got = svi.search(qq, k)
+            want = _ref_search(svi.embeddings, svi.metadata, qq, k)
+            assert [g["frame_id"] for g in got] == [w["frame_id"] for w in want]
+            assert [g["timestamp"] for g in got] == [w["timestamp"] for w in want]
+            sc = np.array([w["score"] for w in want])
+            assert np.abs(np.array([g["score"] for g in got]) - sc).max() <= 4e-6 * max(1.0, np.abs(sc).max())
+    assert svi.remove_video("video_0.mp4") == 100 and svi._dev is dev and svi._pushed == 350     # searches pushed the rest
+    got = svi.search(q, 4)
+    assert [g["frame_id"] for g in got] == [w["frame_id"] for w in _ref_search(svi.embeddings, svi.metadata, q, 4)]
+
+
+@pytest.mark.timeout(900)
+def test_one_million_rows_remove_a_video_and_one_percent(gpu_lib):
+    from video_quierer_amd.indexes.hnsw import OptimizedHNSWIndex
+    rng = np.random.default_rng(2_000_000)
+    n, dim = 1_000_000, 512
+    vecs = rng.standard_normal((n, dim), dtype=np.float32)
+    ids = [f"video{r // 300}_{r % 300}" for r in range(n)]
+    qs = rng.standard_normal((64, dim), dtype=np.float32)
+    qs[:8] = vecs[rng.integers(0, n, 8)] + np.float32(0.3) * rng.standard_normal((8, dim), dtype=np.float32)
+    idx = OptimizedHNSWIndex(dimension=dim)
+    idx.add_batch(vecs, ids)
+    del vecs
+    idx.search(qs[0], 10)                                            # ranks on the device
+    stored = idx._export()
+    assert idx.remove_group("video1666") == 300                      # rows 499,800 .. 500,099
+    gone = rng.choice(n, n // 100, replace=False)
+    gone_ids = [ids[r] for r in gone if not 499_800 <= r < 500_100]
+    assert idx.remove_batch(gone_ids) == len(gone_ids)
+    keep = np.ones(n, bool); keep[499_800:500_100] = False; keep[gone] = False
+    surv = [i for i, kp in zip(ids, keep) if kp]
+    assert idx._ids == surv
+    stored = stored[keep]
+    assert np.array_equal(idx._export(), stored)
+    uq = _unit(qs)
+    want_i, want_d = _oracle(stored, uq, 10, tie=_ranks(surv))
+    res = idx.search_batch(list(qs), 10)
+    assert [[r["id"] for r in x] for x in res] == [[surv[i] for i in row] for row in want_i]
+    assert np.array_equal(np.array([[r["distance"] for r in x] for x in res]), want_d)
+    one = idx.search(qs[0], 10)
+    assert [r["id"] for r in one] == [surv[i] for i in want_i[0]]
+    assert [r["distance"] for r in one] == want_d[0].tolist()
+    idx.close()

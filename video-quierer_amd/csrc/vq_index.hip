@@ -9,6 +9,7 @@
 #include "knn_scan_deep.h"
 #include "knn_scan_fold.h"
 #include "knn_grouped.h"
+#include "knn_remove.h"
 
 #include <algorithm>
 #include <atomic>
@@ -39,7 +40,9 @@ struct vq_index {
     float* d_dist = nullptr; int64_t dist_cap = 0;    // exact distances (elements)
     uint64_t* d_partial = nullptr; int64_t partial_cap = 0;   // per-chunk top-k keys
     int32_t* d_ids = nullptr; float* d_out = nullptr; int64_t out_cap = 0;
-    float* d_upd = nullptr; int64_t upd_cap = 0;      // vq_index_update_rows: staged rows [n][dim] + their row numbers behind them
+    float* d_upd = nullptr; int64_t upd_cap = 0;      // vq_index_update_rows: staged rows [n][dim] + their row numbers behind them;
+                                                      // vq_index_remove_rows: one chunk of moved rows
+    int32_t* d_rmw = nullptr; int64_t rmw_cap = 0;    // vq_index_remove_rows: row maps, prefix sums, rebuilt ranks / labels (words)
     // (distance, id) tie order (vq_index_set_id_ranks): rank of each row's id in the caller's id order + the inverse; rank_n = the
     // number of rows they cover (0 = none set: ties come back in row order).  A search with rank_n != size is refused.
     int32_t* d_rank = nullptr; int32_t* d_rank_inv = nullptr; int64_t rank_cap = 0, rank_n = 0;
@@ -566,6 +569,19 @@ int search_grouped_dispatch(vq_index* x, const float* d_queries, int nq, int k, 
                     : search_grouped_exact(x, d_queries, nq, k, groups, rows_out, dist);
 }
 
+// ---- vq_index_remove_rows (knn_remove.h) ----
+int grid_for(int64_t count) { return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(count, 256), 2048)); }
+
+// exclusive prefix sum of v[0..n) in place, v[n] = total; tiles holds cdiv(n, RM_SCAN_TILE) + 1 words
+int rm_exclusive_scan(vq_index* x, int32_t* v, int64_t n, int32_t* tiles) {
+    const int64_t ntiles = std::max<int64_t>(1, cdiv(n, RM_SCAN_TILE));
+    hipLaunchKernelGGL(rm_scan_tile_sum_kernel, dim3((unsigned)ntiles), dim3(256), 0, x->stream, v, n, tiles);
+    hipLaunchKernelGGL(rm_scan_carry_kernel, dim3(1), dim3(256), 0, x->stream, tiles, ntiles);
+    hipLaunchKernelGGL(rm_scan_apply_kernel, dim3((unsigned)ntiles), dim3(256), 0, x->stream, v, n, tiles, ntiles);
+    VQ_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 // vq_comm.hip: this rank's part of a row-sharded search, on the index's stream (returned so that the exchange is
@@ -616,7 +632,7 @@ int vq_index_destroy(vq_index* x) {
     (void)hipFree(x->rows); (void)hipFree(x->rows16); (void)hipFree(x->d_q); (void)hipFree(x->d_dist);
     (void)hipFree(x->d_ids); (void)hipFree(x->d_out); (void)hipFree(x->d_partial);
     (void)hipFree(x->d_q16); (void)hipFree(x->d_keys); (void)hipFree(x->d_flags); (void)hipFree(x->d_slots);
-    (void)hipFree(x->d_counters); (void)hipFree(x->d_fb_partial); (void)hipFree(x->d_upd);
+    (void)hipFree(x->d_counters); (void)hipFree(x->d_fb_partial); (void)hipFree(x->d_upd); (void)hipFree(x->d_rmw);
     if (x->h_counters) (void)hipHostFree(x->h_counters);
     if (x->h_q) (void)hipHostFree(x->h_q);
     if (x->h_res) (void)hipHostFree(x->h_res);
@@ -813,6 +829,108 @@ int vq_index_update_rows(vq_index* x, const float* rows, const int64_t* row_numb
     VQ_HIP(hipGetLastError());
     VQ_TRY(refresh_norm_range(x));
     VQ_HIP(hipStreamSynchronize(x->stream));      // `rows`, `rn` are the caller's / this frame's
+    return 0;
+}
+
+int vq_index_remove_rows(vq_index* x, const int64_t* row_numbers, int64_t n) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && n >= 0 && (n == 0 || row_numbers), "vq_index_remove_rows: bad argument");
+    if (n == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t size = x->size;
+    std::vector<int64_t> rm(row_numbers, row_numbers + n);
+    for (int64_t i = 0; i < n; ++i)
+        VQ_CHECK(rm[(size_t)i] >= 0 && rm[(size_t)i] < size, "vq_index_remove_rows: row %lld outside [0, %lld)",
+                 (long long)rm[(size_t)i], (long long)size);
+    std::sort(rm.begin(), rm.end());
+    rm.erase(std::unique(rm.begin(), rm.end()), rm.end());      // a row named twice is removed once
+    const int64_t m = (int64_t)rm.size(), n_new = size - m, r0 = rm[0], moved = n_new - r0;
+    const bool ranks = x->rank_n == size, groups = x->group_n == size;      // labels / ranks that cover the index stay valid
+    const int32_t G = groups ? x->n_groups : 0;
+    const int64_t n_pad = round_up(size, SCAN_STREAM_ROWS), streams = n_pad / SCAN_STREAM_ROWS;
+    // scratch words: removed rows (int64) | newrow [size] | src_of [moved] | prefix sums [size + 1] | tile sums | group keep/scan
+    // [G + 1] | new rank_inv [n_new] | new label block (bounded by the old one's size)
+    auto words = [](int64_t c) { return round_up(std::max<int64_t>(c, 1), 4); };
+    const int64_t w_rm = words(2 * m), w_map = words(size), w_src = words(moved), w_S = words(size + 1),
+                  w_tiles = words(cdiv(size, RM_SCAN_TILE) + 2), w_K = words((int64_t)G + 1), w_rinv = ranks ? words(n_new) : 0,
+                  w_grp = groups ? words(n_pad + G + 1 + size + streams) : 0;
+    VQ_TRY(reserve_buf(x->d_rmw, x->rmw_cap, w_rm + w_map + w_src + w_S + w_tiles + w_K + w_rinv + w_grp));
+    int64_t* d_rm = (int64_t*)x->d_rmw;
+    int32_t* newrow = x->d_rmw + w_rm;
+    int32_t* src_of = newrow + w_map;
+    int32_t* S = src_of + w_src;
+    int32_t* tiles = S + w_S;
+    int32_t* K = tiles + w_tiles;
+    int32_t* rinv_new = K + w_K;
+    int32_t* grp = rinv_new + w_rinv;
+    // `rm` feeds an asynchronous copy: whichever way this function is left, the stream is drained before `rm` dies
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{x->stream};
+    VQ_HIP(hipMemcpyAsync(d_rm, rm.data(), (size_t)m * 8, hipMemcpyHostToDevice, x->stream));
+    hipLaunchKernelGGL(remove_row_map_kernel, dim3(grid_for(size)), dim3(256), 0, x->stream, d_rm, m, size, r0, newrow, src_of);
+    VQ_HIP(hipGetLastError());
+    // rows: only survivors at or after the first removed row move, all of them down.  Chunk by chunk in ascending order: gather
+    // into scratch, then store back with the fp16 copy re-derived.  A chunk's sources lie at or above its destinations, and the
+    // destinations lie below every later chunk's sources, so stream order alone makes this safe.
+    if (moved > 0) {
+        const int64_t chunk = std::min<int64_t>(moved, std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)x->dim * 4)));   // <= 256 MiB
+        VQ_TRY(reserve_buf(x->d_upd, x->upd_cap, chunk * x->dim));
+        for (int64_t d0 = 0; d0 < moved; d0 += chunk) {
+            const int64_t cnt = std::min<int64_t>(chunk, moved - d0);
+            const int64_t count4 = cnt * x->dim / 4, dst = (r0 + d0) * x->dim;
+            hipLaunchKernelGGL(remove_gather_rows_kernel, dim3(grid_for(count4)), dim3(256), 0, x->stream, x->rows, x->dim, src_of + d0,
+                               cnt, x->d_upd);
+            if (x->dim % 8 == 0) {
+                hipLaunchKernelGGL(remove_store_rows_kernel, dim3(grid_for(count4 / 2)), dim3(256), 0, x->stream, x->d_upd, count4 / 2,
+                                   x->rows + dst, x->rows16 + dst);
+            } else {
+                VQ_HIP(hipMemcpyAsync(x->rows + dst, x->d_upd, (size_t)count4 * 16, hipMemcpyDeviceToDevice, x->stream));
+                hipLaunchKernelGGL(rows_to_f16_kernel, dim3(grid_for(count4)), dim3(256), 0, x->stream, x->rows + dst, x->rows16 + dst, count4);
+            }
+            VQ_HIP(hipGetLastError());
+        }
+    }
+    // the scans read whole 1024 / 2048-row ranges: the fp16 rows past the new size go back to zeros, as in a fresh allocation
+    VQ_HIP(hipMemsetAsync(x->rows16 + n_new * x->dim, 0, (size_t)m * x->dim * 2, x->stream));
+    // id ranks: a stable compaction of the rank order
+    if (ranks && n_new > 0) {
+        hipLaunchKernelGGL(remove_survivor_flags_kernel, dim3(grid_for(size)), dim3(256), 0, x->stream, x->d_rank_inv, newrow, size, S);
+        VQ_TRY(rm_exclusive_scan(x, S, size, tiles));
+        hipLaunchKernelGGL(remove_renumber_ranks_kernel, dim3(grid_for(size)), dim3(256), 0, x->stream, x->d_rank_inv, newrow, S, size,
+                           x->d_rank, rinv_new);
+        VQ_HIP(hipMemcpyAsync(x->d_rank_inv, rinv_new, (size_t)n_new * 4, hipMemcpyDeviceToDevice, x->stream));
+        VQ_HIP(hipGetLastError());
+        x->rank_n = n_new;
+    } else {
+        x->rank_n = 0;
+    }
+    // group labels: drop emptied groups, renumber the rest in their old order, filter the by-group row list
+    int32_t G_new = 0;
+    if (groups && n_new > 0) {
+        hipLaunchKernelGGL(remove_survivor_flags_kernel, dim3(grid_for(size)), dim3(256), 0, x->stream, x->d_grows, newrow, size, S);
+        VQ_TRY(rm_exclusive_scan(x, S, size, tiles));
+        hipLaunchKernelGGL(remove_group_keep_kernel, dim3(grid_for(G)), dim3(256), 0, x->stream, x->d_goff, S, G, K);
+        VQ_TRY(rm_exclusive_scan(x, K, G, tiles));
+        VQ_HIP(hipMemcpyAsync(&G_new, K + G, 4, hipMemcpyDeviceToHost, x->stream));
+        VQ_HIP(hipStreamSynchronize(x->stream));                     // the new layout's offsets depend on the group count
+        const int64_t n_pad_new = round_up(n_new, SCAN_STREAM_ROWS), streams_new = n_pad_new / SCAN_STREAM_ROWS;
+        int32_t* lab_new = grp;
+        int32_t* goff_new = lab_new + n_pad_new;
+        int32_t* grows_new = goff_new + G_new + 1;
+        int32_t* sg_new = grows_new + n_new;
+        hipLaunchKernelGGL(remove_rebuild_groups_kernel, dim3(grid_for(std::max<int64_t>(size, G))), dim3(256), 0, x->stream, x->d_group,
+                           x->d_goff, x->d_grows, newrow, S, K, size, G, n_new, n_pad_new, lab_new, goff_new, grows_new);
+        hipLaunchKernelGGL(remove_stream_labels_kernel, dim3(grid_for(streams_new)), dim3(256), 0, x->stream, lab_new, streams_new, sg_new);
+        const int64_t total_new = n_pad_new + G_new + 1 + n_new + streams_new;
+        VQ_HIP(hipMemcpyAsync(x->d_group, grp, (size_t)total_new * 4, hipMemcpyDeviceToDevice, x->stream));
+        VQ_HIP(hipGetLastError());
+        x->d_goff = x->d_group + n_pad_new; x->d_grows = x->d_goff + G_new + 1; x->d_sgroup = x->d_grows + n_new;
+        x->group_n = n_new; x->n_groups = G_new;
+    } else {
+        x->group_n = 0; x->n_groups = 0;
+    }
+    // the |row|^2 range stays as it is: it still covers every survivor (conservative, as in vq_index_update_rows)
+    x->size = n_new;
+    VQ_HIP(hipStreamSynchronize(x->stream));
     return 0;
 }
 

@@ -22,6 +22,7 @@ import threading
 import time
 from collections.abc import Mapping
 from concurrent.futures import ThreadPoolExecutor
+from itertools import compress
 from ctypes import POINTER, c_float, c_int32, c_int64, c_void_p
 from typing import Callable, Dict, Hashable, List, Optional, Sequence
 
@@ -66,6 +67,18 @@ class _GroupLabels:
                 new[j] = g
             self.labels = np.concatenate([self.labels, new])
         return self.uploaded != n
+
+    def compact(self, keep: np.ndarray, current: bool) -> None:
+        """The labels of the surviving rows (``keep`` = per-row mask), renumbered as vq_index_remove_rows renumbers the device
+        labels: groups left without rows are dropped, the others keep their order.  ``current``: the device held these labels
+        for every row before the removal (it then keeps them, renumbered, and no upload is due)."""
+        labels = self.labels[keep]
+        alive = np.bincount(labels, minlength=len(self.keys)) > 0
+        self.labels = (np.cumsum(alive, dtype=np.int64) - 1)[labels].astype(np.int32)
+        if not alive.all():
+            self.keys = [key for key, a in zip(self.keys, alive.tolist()) if a]
+            self.index = {key: g for g, key in enumerate(self.keys)}
+        self.uploaded = len(self.labels) if current else -1
 
 
 class _RowView(Mapping):
@@ -334,6 +347,65 @@ class HNSWIndex:
         _lib.check(_lib.load().vq_index_update_rows(self._h, _lib.fptr(unit_vecs), rn.ctypes.data_as(POINTER(ctypes.c_int64)),
                                                     len(rn), 0))
 
+    # -- removal (reference: `del self.data[node_id]`; video_search_system.py:427-463 delete_video) -------------------
+    def remove(self, node_id: Hashable) -> None:
+        """Take one id out of the index; ``KeyError`` for an unknown id, as ``del`` on the reference's ``data`` dict."""
+        self.remove_batch([node_id])
+
+    def remove_batch(self, node_ids: Sequence[Hashable]) -> int:
+        """Take the given ids out of the index, all or none: an unknown id raises ``KeyError`` before anything changes.  An id
+        named twice is removed once.  The survivors keep their order; returns the number of rows removed."""
+        with self.lock:
+            row_of = self._row_of
+            rows = np.fromiter({row_of[nid] for nid in node_ids}, dtype=np.int64)
+            return self._remove_rows(np.sort(rows))
+
+    def remove_group(self, group: Hashable, group_of: Optional[Callable[[Hashable], Hashable]] = None) -> int:
+        """Take every row of one group out (default ``video_of``: the caller's ``delete_video(video_id)``); returns the number
+        of rows removed (0 for a group the index does not hold).  The rows are found through the host group labels."""
+        with self.lock:
+            gl = self._group_labels(group_of)
+            gl.extend()
+            g = gl.index.get(group)
+            if g is None:
+                return 0
+            return self._remove_rows(np.flatnonzero(gl.labels == g).astype(np.int64))
+
+    def _remove_rows(self, rows: np.ndarray) -> int:
+        """rows: sorted, unique, valid row numbers.  The device compacts the matrix, the id ranks and the group labels
+        (vq_index_remove_rows); the host follows: ``_ids`` in place, ``_row_of`` for the rows that moved, the group labels
+        renumbered the same way, so neither the next search nor the next grouped search uploads anything."""
+        m = len(rows)
+        if m == 0:
+            return 0
+        ids = self._ids
+        n = len(ids)
+        gl = getattr(self, "_groups", None)
+        if gl is not None and gl.ids is not ids:
+            gl = None                                            # labels of a replaced id list: relabelled on next use
+        if gl is not None:
+            gl.extend()                                          # host labels for every row (no upload)
+        current = gl is not None and gl.uploaded == n
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        _lib.check(_lib.load().vq_index_remove_rows(self._h, rows.ctypes.data_as(POINTER(c_int64)), m))
+        keep = np.ones(n, dtype=bool)
+        keep[rows] = False
+        first = int(rows[0])
+        row_of = self._row_of
+        for r in rows.tolist():
+            del row_of[ids[r]]
+        tail = list(compress(ids[first:], keep[first:].tolist()))
+        ids[first:] = tail                                       # in place: the group labels hold this list
+        row_of.update(zip(tail, range(first, first + len(tail))))
+        # ids 0..n-1 lose that property once a survivor moves; they still increase with the row, so ties keep coming back in id
+        # order without ranks
+        self._identity = self._identity and not tail
+        self.element_count -= m
+        self.entry_point = ids[0] if ids else None
+        if gl is not None:
+            gl.compact(keep, current)
+        return m
+
     # -- query --------------------------------------------------------------------
     def _raw_search(self, unit_queries: np.ndarray, k: int):
         nq = unit_queries.shape[0]
@@ -412,12 +484,16 @@ class HNSWIndex:
                                                           c_void_p(d_ids), c_void_p(d_dist)))
 
     # -- grouped query: the k best videos, one best frame each ----------------------------
-    def _sync_groups(self, group_of: Optional[Callable[[Hashable], Hashable]]) -> _GroupLabels:
+    def _group_labels(self, group_of: Optional[Callable[[Hashable], Hashable]]) -> _GroupLabels:
         fn = video_of if group_of is None else group_of
         gl = getattr(self, "_groups", None)
         # relabel when the mapping changed or the id list was replaced (load); add_batch only appends to it
         if gl is None or gl.group_of is not fn or gl.ids is not self._ids or len(gl.labels) > len(self._ids):
             gl = self._groups = _GroupLabels(fn, self._ids)
+        return gl
+
+    def _sync_groups(self, group_of: Optional[Callable[[Hashable], Hashable]]) -> _GroupLabels:
+        gl = self._group_labels(group_of)
         if gl.extend():
             n = len(gl.labels)
             _lib.check(_lib.load().vq_index_set_groups(self._h, gl.labels.ctypes.data_as(POINTER(c_int32)), n, len(gl.keys)))

@@ -61,6 +61,32 @@ class SimpleVideoIndex:
         self._dev.entry_point = 0
         self._pushed = n
 
+    def remove_video(self, video_name: str) -> int:
+        """Drop one video: its embeddings, metadata and ``video_hashes`` entry (so the next scan of the library re-processes
+        it, video_search_overhaul.py:391-402, without its old frames staying behind).  Frames already on the device are
+        removed there in place (vq_index_remove_rows); the surviving metadata dicts stay as stored, ``frame_id`` included.
+        Returns the number of frames removed."""
+        self.video_hashes.pop(video_name, None)
+        pos = [i for i, md in enumerate(self.metadata) if md.get("video_name") == video_name]
+        if not pos:
+            return 0
+        gone = set(pos)
+        self.embeddings = [e for i, e in enumerate(self.embeddings) if i not in gone]
+        self.metadata = [md for i, md in enumerate(self.metadata) if i not in gone]
+        on_dev = np.array([i for i in pos if i < self._pushed], dtype=np.int64)
+        if self._dev is not None and len(on_dev):
+            dev = self._dev
+            with dev.lock:
+                dev._row_of = {-i: i for i in range(self._pushed)}      # (_sync_device keeps only the id list)
+                dev._remove_rows(on_dev)
+                # rows keep their order, so the ids stay -position (the tie rule of search) without new ranks
+                n = self._pushed - len(on_dev)
+                dev._ids[:] = [-i for i in range(n)]
+                dev._row_of = {-i: i for i in range(n)}
+                dev.entry_point = 0 if n else None
+            self._pushed = n
+        return len(pos)
+
     def search(self, query_embedding: np.ndarray, k: int = 5) -> List[Dict]:
         if not self.embeddings:
             return []
