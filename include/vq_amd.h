@@ -265,6 +265,41 @@ int vq_index_search_grouped(vq_index* idx, const float* queries, int nq, int k, 
 int vq_index_search_grouped_device(vq_index* idx, const void* d_queries_f32, int nq, int k, int mode,
                                    void* d_groups_i32, void* d_rows_i32, void* d_dist_f32);
 
+/* Filtered search: the plain or grouped search restricted to the rows S whose group label (vq_index_set_groups) is in the set
+ * groups [n_sel] (exclude = 0) or not in it (exclude = 1) — "within this video", "more like this from other videos", "within
+ * this collection".  One filter applies to every query of the call.
+ *   groups is host memory in every form (it is small, and the host sizes S from its own copy of the group offsets, which
+ *   vq_index_set_groups and vq_index_remove_rows keep).  Duplicates are allowed; a label outside [0, n_groups) is
+ *   VQ_ERR_INVALID.  The labels' lifetime is the grouped search's: stale or missing labels are refused (VQ_ERR_INVALID).
+ *   vq_index_search_filtered returns what vq_index_search would return on an index holding only the rows of S, in their
+ *   order, with the same tie ranks restricted to S: the same distances and the same (distance, tie rank) order bit for bit,
+ *   rows reported as row numbers of the full index, unused slots (k > |S|) -1 / +inf.
+ *   vq_index_search_grouped_filtered returns what vq_index_search_grouped would return on that index: the first
+ *   min(k, allowed groups) groups, labels of the full index.
+ *   n_sel = 0, exclude = 0: every slot empty.  n_sel = 0, exclude = 1: exactly vq_index_search / vq_index_search_grouped.
+ *   mode: 1 = the exact gather path (any nq, k <= 1024, any dim: S's row list from the by-group row list, the listed rows'
+ *   fp64-chain distances, the exact path's selection).  2 = the masked fp16 scan (a disallowed video's streams are not read,
+ *   disallowed rows of mixed streams never score) with an exact re-score under the unfiltered proof, every floor taken over
+ *   allowed rows; queries it does not prove are redone by a masked exact fallback on the device.  It exists for dim 256, 512
+ *   or 768, nq <= 96, k <= 100 and near-unit rows; elsewhere mode 2 is VQ_ERR_INVALID, refused before any work is queued.
+ *   0 = the library chooses: the fp16 scan where it exists, on 16,384 rows or more, once S holds at least half the rows (a
+ *   fifth for more than 4 queries; measured crossover), else the gather path.  An empty exclude list runs the unfiltered
+ *   search in any mode.  The _device forms take device queries and results and are asynchronous on the index's stream (the
+ *   filter list goes up from a ring of four pinned slots: a call waits only for the list copy of the call four before it).
+ *   vq_index_last_search_stats after a filtered search: [0] queries proven on the fp16 path (directly or after rescans), [1]
+ *   queries that needed rescans, [2] queries answered exactly (gather path or fallback); after a grouped filtered search the
+ *   grouped meanings hold. */
+int vq_index_search_filtered(vq_index* idx, const float* queries, int nq, int k, int mode,
+                             const int32_t* groups, int32_t n_sel, int exclude, int32_t* ids, float* dist);
+int vq_index_search_filtered_device(vq_index* idx, const void* d_queries_f32, int nq, int k, int mode,
+                                    const int32_t* groups, int32_t n_sel, int exclude, void* d_ids_i32, void* d_dist_f32);
+int vq_index_search_grouped_filtered(vq_index* idx, const float* queries, int nq, int k, int mode,
+                                     const int32_t* groups, int32_t n_sel, int exclude,
+                                     int32_t* groups_out, int32_t* rows, float* dist);
+int vq_index_search_grouped_filtered_device(vq_index* idx, const void* d_queries_f32, int nq, int k, int mode,
+                                            const int32_t* groups, int32_t n_sel, int exclude,
+                                            void* d_groups_i32, void* d_rows_i32, void* d_dist_f32);
+
 /* save / load support (hnsw.py:306-380): the stored (normalised) rows. */
 int vq_index_export(vq_index* idx, float* rows /*[size][dim]*/);
 /* Single stored rows (the reference reads `self.data[node_id]`, a dict lookup): out [n][dim] = rows row_numbers[0..n). */

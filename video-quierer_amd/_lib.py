@@ -110,6 +110,14 @@ SIGNATURES = {
     "vq_index_search_grouped": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32),
                                         POINTER(c_float)]),
     "vq_index_search_grouped_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vq_index_search_filtered": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, POINTER(c_int32), c_int32, c_int,
+                                         POINTER(c_int32), POINTER(c_float)]),
+    "vq_index_search_filtered_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_int32, c_int, c_void_p,
+                                                c_void_p]),
+    "vq_index_search_grouped_filtered": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, POINTER(c_int32), c_int32, c_int,
+                                                 POINTER(c_int32), POINTER(c_int32), POINTER(c_float)]),
+    "vq_index_search_grouped_filtered_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_int32, c_int,
+                                                        c_void_p, c_void_p, c_void_p]),
     "vq_index_synchronize": (c_int, [c_void_p]),
     "vq_index_set_stream": (c_int, [c_void_p, c_void_p]),
     "vq_index_export": (c_int, [c_void_p, POINTER(c_float)]),

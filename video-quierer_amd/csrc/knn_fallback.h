@@ -59,11 +59,14 @@ void collect_flags_kernel(const int32_t* __restrict__ flags, int nq, int32_t* __
     if (tid == 0) { counters[0] = base_s; counters[1] = st[0]; counters[2] = st[1]; counters[3] = st[2]; }
 }
 
+// MASK (filtered search): rows whose group is disallowed never join a list.  MASK = false compiles to the unfiltered kernel.
+template <bool MASK = false>
 __global__ __launch_bounds__(FB_TILE)
 void exact_fallback_kernel(const float* __restrict__ rows, int64_t n, int dim,
                            const float* __restrict__ queries, const int32_t* __restrict__ slots,
                            const int32_t* __restrict__ counters, int slot_base, int slot_cap, int k,
-                           int64_t rows_per_split, uint64_t* __restrict__ partial /*[slot_cap][splits][k]*/, const TieOrder tie) {
+                           int64_t rows_per_split, uint64_t* __restrict__ partial /*[slot_cap][splits][k]*/, const TieOrder tie,
+                           const GroupMask mask = {}) {
     const int count = min(counters[0] - slot_base, slot_cap);          // flagged queries of this round (uniform)
     if (count <= 0) return;
     __shared__ float xs[FB_TILE][FB_PANEL + 1];
@@ -130,13 +133,15 @@ void exact_fallback_kernel(const float* __restrict__ rows, int64_t n, int dim,
             }
             const int64_t row = r0 + tid;
             const uint32_t my_tie = row < r_end ? tie_of(tie, row) : 0u;        // (distance, id) order: TieOrder, vq_common.h
+            bool row_ok = row < r_end;
+            if constexpr (MASK) row_ok = row_ok && group_allowed(mask.bits, mask.group_of[row]);
             // rows that beat the query's current k-th key join its candidate list: one LDS atomic per wave and query
             // (a wave-wide ballot places the lanes), not one per row — the first tiles of a scan accept every row
 #pragma unroll
             for (int j = 0; j < FB_QG; ++j) {
                 if (qidx[j] < 0) continue;                                           // block-uniform
                 const uint64_t key = dist_key(1.0f - (float)acc[j], my_tie);
-                const bool in = row < r_end && key < best[cur_s[j]][j][k - 1];
+                const bool in = row_ok && key < best[cur_s[j]][j][k - 1];
                 const unsigned long long mask = __ballot(in);
                 if (mask == 0) continue;                                             // wave-uniform
                 const int lane = tid & 63;

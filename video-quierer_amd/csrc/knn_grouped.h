@@ -63,13 +63,16 @@ __device__ __forceinline__ void write_group_result(uint64_t key, size_t o, const
 // ---- exact path: per (block of GRP_BLOCK groups, query) the group minima of the (distance, tie) key and the block's k_local
 // smallest of them.  lpg lanes (1, 4, 16 or 64, from the mean group size) share a group and stride its rows; the row's
 // distance is read from dist [nq][ld] (FROM_DIST) or computed by the fp64 chain.  flags != null: only queries whose flag is 2
-// (the fp16 path's exact redo) do anything. ----
-template <bool FROM_DIST>
+// (the fp16 path's exact redo) do anything.  Filtered search (knn_filter.h): MASK skips the groups the mask disallows (they
+// never reach the lists); POS walks a row LIST instead of the CSR row list — goff = the allowed groups' list offsets, the
+// distance and the tie word of list position i are dist[q][i] and tie.rank[i] (no grows).  Both false: the unfiltered kernel. ----
+template <bool FROM_DIST, bool MASK = false, bool POS = false>
 __global__ __launch_bounds__(256)
 void group_block_topk_kernel(const float* __restrict__ dist, int64_t ld, const float* __restrict__ rows, int dim,
                              const float* __restrict__ queries, const int32_t* __restrict__ goff, const int32_t* __restrict__ grows,
                              int n_groups, int lpg, int k_local, int nblocks, uint64_t* __restrict__ partial /*[nq][nblocks][k_local]*/,
-                             const int32_t* __restrict__ flags, const TieOrder tie) {
+                             const int32_t* __restrict__ flags, const TieOrder tie, const uint32_t* __restrict__ allow = nullptr) {
+    static_assert(!POS || FROM_DIST, "a row list is walked over precomputed distances");
     __shared__ uint64_t gk[GRP_BLOCK];
     const int q = blockIdx.y, tid = threadIdx.x;
     if (flags && flags[q] != 2) return;                       // block-uniform
@@ -79,10 +82,12 @@ void group_block_topk_kernel(const float* __restrict__ dist, int64_t ld, const f
     for (int gl = sub; gl < GRP_BLOCK; gl += nsub) {          // lpg iterations for every thread: the shuffles below stay uniform
         const int g = g0 + gl;
         uint64_t best = ~0ull;
-        if (g < n_groups) {
+        bool live = g < n_groups;
+        if constexpr (MASK) live = live && group_allowed(allow, g);
+        if (live) {
             const int e = goff[g + 1];
             for (int i = goff[g] + ls; i < e; i += lpg) {
-                const int r = grows[i];
+                const int r = POS ? i : grows[i];
                 float d;
                 if constexpr (FROM_DIST) d = dist[(int64_t)q * ld + r];
                 else d = 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(rows + (size_t)r * dim, qv, dim) : exact_dot_chain(rows + (size_t)r * dim, qv, dim));
@@ -136,11 +141,13 @@ void group_merge_kernel(const uint64_t* __restrict__ partial, int total /* nbloc
 // ---- fp16 pass 1: group-max scan.  Operand streaming and MFMA loop of scan3_f16_top2_kernel<NKS, 1>; Q16 [q_pad][dim] fp16,
 // 16 queries per blockIdx.y.  group_of is padded with -1 to whole streams; stream_group[s] = the label all 128 rows of stream s
 // share, or -1. ----
-template <int NKS>
+// MASK (filtered search): a disallowed uniform stream is not read; in a mixed stream disallowed rows are skipped like rows
+// past the end, so a disallowed group's gbest stays 0 ("no row seen").  MASK = false compiles to the unfiltered kernel.
+template <int NKS, bool MASK = false>
 __global__ __launch_bounds__(256, 2)
 void scan3_group_max_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __restrict__ X16, int64_t streams,
                             const int32_t* __restrict__ group_of, const int32_t* __restrict__ stream_group, int nq_real, int n_groups,
-                            uint32_t* __restrict__ gbest /*[nq][n_groups]*/) {
+                            uint32_t* __restrict__ gbest /*[nq][n_groups]*/, const uint32_t* __restrict__ allow = nullptr) {
     typedef mfma_op<true> op;
     typedef op::frag frag;
     constexpr int DIM = NKS * 32;
@@ -156,11 +163,13 @@ void scan3_group_max_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) qf[ks] = *(const frag*)(Q16 + (size_t)q * DIM + ks * 32 + g * 8);
     const uint16_t* xrow = X16 + ((size_t)stream * 128 + r16) * DIM + g * 8;
+    const int sg = __builtin_amdgcn_readfirstlane(stream_group[stream]);
+    if constexpr (MASK)
+        if (sg >= 0 && !group_allowed(allow, sg)) return;       // wave-uniform: a disallowed video's stream is not read
     frag xf[NKS];
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) xf[ks] = *(const frag*)(xrow + ks * 32);
 
-    const int sg = __builtin_amdgcn_readfirstlane(stream_group[stream]);
     uint32_t* gb = gbest + (size_t)(qlive ? q : 0) * n_groups;
     const int32_t* lab = group_of + stream * 128 + 4 * g;
     float m = -__builtin_inff();
@@ -181,7 +190,9 @@ void scan3_group_max_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __
         const int lr[4] = {l4.x, l4.y, l4.z, l4.w};
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int L = lr[r];
+            int L = lr[r];
+            if constexpr (MASK)
+                if (sg < 0 && !group_allowed(allow, L)) L = -1;   // a disallowed row of a mixed stream: as a row past the end
             if (L < 0) continue;                           // rows past the end of the index
             if (L != cur) {                                // a run ends: one atomic for it (never in a uniform stream)
                 if (cur >= 0 && qlive) atomicMax(gb + cur, score_key(m));

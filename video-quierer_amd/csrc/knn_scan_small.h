@@ -38,11 +38,14 @@ __host__ __device__ inline int64_t scan3_row_of(int64_t stream, int local) { ret
 // 16 KiB of (mostly zero) fp16 query rows every one of the 31k waves used to fetch (0.5 GB of L2 reads beside the 1 GB matrix
 // stream) and 15 of 16 scattered 8-byte key stores per wave.  Same rounding (_Float16 cast = v_cvt_f16_f32, RNE) as
 // queries_to_f16_kernel: keys bit-identical to the two-launch path.
-template <int NKS, int NQG, bool FUSED = false>             // dim / 32; groups of 16 queries per pass (1 or 2)
+// MASK (filtered search, knn_filter.h): a stream whose shared label is disallowed is not read (its keys say "no row"), a mixed
+// stream's disallowed rows score as the MASKED sentinel, like rows past the end.  MASK = false compiles to the unfiltered kernel.
+template <int NKS, int NQG, bool FUSED = false, bool MASK = false>             // dim / 32; groups of 16 queries per pass (1 or 2)
 __global__ __launch_bounds__(256, 2)
 void scan3_f16_top2_kernel(const uint16_t* __restrict__ Q16 /*[q_pad][dim]; FUSED: const float* [nq_real][dim]*/, const uint16_t* __restrict__ X16,
                            int64_t n_valid, int64_t streams, int64_t q_pad /* % (16 NQG) == 0 */,
-                           uint32_t* __restrict__ keys /*[q_pad][streams][2]*/, int nq_real = 0 /* FUSED only */) {
+                           uint32_t* __restrict__ keys /*[q_pad][streams][2]*/, int nq_real = 0 /* FUSED only */,
+                           const GroupMask mask = {}) {
     typedef mfma_op<true> op;
     typedef op::frag frag;
     constexpr int DIM = NKS * 32;
@@ -74,12 +77,25 @@ void scan3_f16_top2_kernel(const uint16_t* __restrict__ Q16 /*[q_pad][dim]; FUSE
                 qf[qg][ks] = *(const frag*)(Q16 + (size_t)(q0 + qg * SCAN3_QB + r16) * DIM + ks * 32 + g * 8);
     }
 
+    const float NEG = -__builtin_inff(), MASKED = -3.0e38f;   // finite sentinel: see scan_f16_top2_kernel
+    bool mixed = false;
+    if constexpr (MASK) {
+        const int sg = __builtin_amdgcn_readfirstlane(mask.stream_group[stream]);
+        if (sg >= 0 && !group_allowed(mask.bits, sg)) {    // wave-uniform: the whole stream is disallowed, its rows are not read
+#pragma unroll
+            for (int qg = 0; qg < NQG; ++qg)
+                if (g == 0 && (!FUSED || r16 < nq_real))
+                    *(uint2*)(keys + ((size_t)(q0 + qg * SCAN3_QB + r16) * streams + stream) * 2) =
+                        uint2{__builtin_bit_cast(uint32_t, MASKED), __builtin_bit_cast(uint32_t, MASKED)};
+            return;
+        }
+        mixed = sg < 0;
+    }
     const uint16_t* xrow = X16 + ((size_t)stream * 128 + r16) * DIM + g * 8;
     frag xf[NKS];
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) xf[ks] = *(const frag*)(xrow + ks * 32);
 
-    const float NEG = -__builtin_inff(), MASKED = -3.0e38f;   // finite sentinel: see scan_f16_top2_kernel
     float m1[NQG], m2[NQG];
 #pragma unroll
     for (int qg = 0; qg < NQG; ++qg) { m1[qg] = NEG; m2[qg] = NEG; }
@@ -98,6 +114,9 @@ void scan3_f16_top2_kernel(const uint16_t* __restrict__ Q16 /*[q_pad][dim]; FUSE
                 __builtin_amdgcn_sched_barrier(0);      // or the scheduler sinks the load to its use (one register, vmcnt(0) per MFMA)
             }
         }
+        int4 l4 = {0, 0, 0, 0};
+        if constexpr (MASK)
+            if (mixed) l4 = *(const int4*)(mask.group_of + stream * 128 + rb * 16 + 4 * g);   // rows rb*16 + 4g .. +3 (16-byte aligned)
 #pragma unroll
         for (int qg = 0; qg < NQG; ++qg)
 #pragma unroll
@@ -105,6 +124,8 @@ void scan3_f16_top2_kernel(const uint16_t* __restrict__ Q16 /*[q_pad][dim]; FUSE
                 float v = acc[qg][r];
                 const int local = rb * 16 + 4 * g + r;
                 if (ragged && stream * 128 + local >= n_valid) v = MASKED;
+                if constexpr (MASK)
+                    if (mixed && !group_allowed(mask.bits, r == 0 ? l4.x : r == 1 ? l4.y : r == 2 ? l4.z : l4.w)) v = MASKED;
                 const float kf = __builtin_bit_cast(float, (__builtin_bit_cast(uint32_t, v) & ~127u) | (uint32_t)local);
                 m2[qg] = __builtin_amdgcn_fmed3f(m1[qg], m2[qg], kf);
                 m1[qg] = fmaxf(m1[qg], kf);

@@ -76,6 +76,15 @@ __host__ __device__ inline float key_dist(uint64_t k) {
 // only; vq_index_set_id_ranks hands it rank[row] = position of the row's id in the caller's id order (and the library keeps
 // the inverse).  Keys then carry the rank where they used to carry the row, every selection stays what it was, and the
 // kernels that emit ids translate back.  Both pointers null = ids ARE the row numbers.
+// Filtered search (knn_filter.h): the allowed groups as a bitmap, one bit per group label; label -1 (rows past the end) is
+// never allowed.
+struct GroupMask {
+    const int32_t* group_of;   // [n padded to whole 128-row streams] label per row, -1 past the end
+    const int32_t* stream_group; // [streams] the label all 128 rows of a stream share, or -1
+    const uint32_t* bits;      // [cdiv(n_groups, 32)]
+};
+__device__ __forceinline__ bool group_allowed(const uint32_t* bits, int32_t g) { return g >= 0 && ((bits[g >> 5] >> (g & 31)) & 1u); }
+
 struct TieOrder {
     const int32_t* rank;   // [n] rank of row r
     const int32_t* row;    // [n] row of rank t

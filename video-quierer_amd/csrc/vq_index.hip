@@ -10,6 +10,7 @@
 #include "knn_scan_fold.h"
 #include "knn_grouped.h"
 #include "knn_remove.h"
+#include "knn_filter.h"
 
 #include <algorithm>
 #include <atomic>
@@ -52,6 +53,14 @@ struct vq_index {
     // set); a grouped search with group_n != size is refused.
     int32_t* d_group = nullptr; int32_t* d_goff = nullptr; int32_t* d_grows = nullptr; int32_t* d_sgroup = nullptr;
     int64_t group_n = 0, group_cap = 0; int32_t n_groups = 0;
+    std::vector<int32_t> h_goff;    // host mirror of goff (kept by set_groups / remove_rows): a filtered search sizes itself from it
+    // filtered-search scratch (knn_filter.h): allowed groups, their row offsets, the row list and its tie words or the allowed
+    // groups' bitmap; the filter list goes up from a ring of pinned staging slots, each reused once its event (the copy) is done
+    int32_t* d_flt = nullptr; int64_t flt_cap = 0;
+    static constexpr int FLT_STAGE_SLOTS = 4;
+    int32_t* h_flt[FLT_STAGE_SLOTS] = {}; int64_t hflt_cap[FLT_STAGE_SLOTS] = {}; hipEvent_t flt_ev[FLT_STAGE_SLOTS] = {}; int flt_slot = 0;
+    int32_t* d_fcand = nullptr; int64_t fcand_cap = 0;             // masked fp16 path: candidate streams [nq][FLT_CAND] | n [nq] | listed [nq] | thr [nq]
+    uint64_t* d_flist = nullptr; int64_t flist_cap = 0;            // ... re-scored keys [nq][FLT_LIST]
     // grouped-search scratch (knn_grouped.h) and its outcome counters (pinned copy read by last_search_stats)
     uint32_t* d_gbest = nullptr; int64_t gbest_cap = 0;
     int32_t* d_gcand = nullptr; int64_t gcand_cap = 0;              // cand [qc][CAND] | pref [qc][CAND + 1] | n [qc] | flags [qc] | thr [qc]
@@ -239,7 +248,11 @@ static bool large_qpw4() {          // $VQ_AMD_RESCORE_QPW4=1: the four-queries-
 }
 
 // The exact redo of the queries whose proof did not close (knn_fallback.h), sized from the device-side flagged count.
-void launch_fallback(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_ids, float* d_dist_out, const int32_t* counters) {
+// mask (filtered search): the masked kernel, which lists allowed rows only
+void launch_fallback(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_ids, float* d_dist_out, const int32_t* counters,
+                     const GroupMask* mask = nullptr) {
+    auto fb = mask ? exact_fallback_kernel<true> : exact_fallback_kernel<false>;
+    const GroupMask gm = mask ? *mask : GroupMask{};
     const int64_t n = x->size;
     const int fast_splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_FAST_ROWS)));
     const int64_t fast_rows = round_up(cdiv(n, fast_splits), FB_TILE);
@@ -247,13 +260,13 @@ void launch_fallback(vq_index* x, const float* d_queries, int nq, int k, int32_t
     const int64_t fb_rows = round_up(cdiv(n, fb_splits), FB_TILE);
     const int64_t fb_cap = std::max<int64_t>(FB_QG, std::min<int64_t>(round_up(nq, FB_QG), ((int64_t)64 << 20) / ((int64_t)fb_splits * k * 8) / FB_QG * FB_QG));
     Prof p(x, I_EXACT_DIST);
-    hipLaunchKernelGGL(exact_fallback_kernel, dim3(fast_splits, 1), dim3(FB_TILE), 0, x->stream, x->rows, n, x->dim,
-                       d_queries, x->d_slots, counters, 0, FB_FAST_SLOTS, k, fast_rows, x->d_fb_partial, x->tie());
+    hipLaunchKernelGGL(fb, dim3(fast_splits, 1), dim3(FB_TILE), 0, x->stream, x->rows, n, x->dim,
+                       d_queries, x->d_slots, counters, 0, FB_FAST_SLOTS, k, fast_rows, x->d_fb_partial, x->tie(), gm);
     hipLaunchKernelGGL(fallback_merge_kernel, dim3(FB_FAST_SLOTS), dim3(256), 0, x->stream, x->d_fb_partial, fast_splits, k, x->d_slots,
                        counters, 0, FB_FAST_SLOTS, d_ids, d_dist_out, x->tie());
     for (int64_t base = FB_FAST_SLOTS; base < nq; base += fb_cap) {
-        hipLaunchKernelGGL(exact_fallback_kernel, dim3(fb_splits, FB_SLOT_LANES), dim3(FB_TILE), 0, x->stream, x->rows, n, x->dim,
-                           d_queries, x->d_slots, counters, (int)base, (int)fb_cap, k, fb_rows, x->d_fb_partial, x->tie());
+        hipLaunchKernelGGL(fb, dim3(fb_splits, FB_SLOT_LANES), dim3(FB_TILE), 0, x->stream, x->rows, n, x->dim,
+                           d_queries, x->d_slots, counters, (int)base, (int)fb_cap, k, fb_rows, x->d_fb_partial, x->tie(), gm);
         hipLaunchKernelGGL(fallback_merge_kernel, dim3(64), dim3(256), 0, x->stream, x->d_fb_partial, fb_splits, k, x->d_slots,
                            counters, (int)base, (int)fb_cap, d_ids, d_dist_out, x->tie());
     }
@@ -349,9 +362,9 @@ int search_fp16(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_i
                     auto scan3f = x->dim == 768 ? scan3_f16_top2_kernel<24, 1, true> : x->dim == 512 ? scan3_f16_top2_kernel<16, 1, true>
                                                                                                       : scan3_f16_top2_kernel<8, 1, true>;
                     hipLaunchKernelGGL(scan3f, grid, dim3(256), 0, x->stream, (const uint16_t*)(d_queries + q0 * x->dim), x->rows16, n, streams,
-                                       q_pad, x->d_keys, cur);
+                                       q_pad, x->d_keys, cur, GroupMask{});
                 } else
-                hipLaunchKernelGGL(scan3, grid, dim3(256), 0, x->stream, x->d_q16, x->rows16, n, streams, q_pad, x->d_keys, 0);
+                hipLaunchKernelGGL(scan3, grid, dim3(256), 0, x->stream, x->d_q16, x->rows16, n, streams, q_pad, x->d_keys, 0, GroupMask{});
             } else if (ver == 2 || deep) {
                 const int range_groups = cdiv(ranges, 4), q_groups = cdiv(q_tiles, 8);
                 if (ver >= 5) {
@@ -479,7 +492,7 @@ int search_grouped_exact(vq_index* x, const float* d_queries, int nq, int k, int
         {
             Prof p(x, I_SELECT);
             hipLaunchKernelGGL(group_block_topk_kernel<true>, dim3(nblocks, cur), dim3(256), 0, x->stream, x->d_dist, ld, nullptr, x->dim, nullptr,
-                               x->d_goff, x->d_grows, G, grouped_lpg(x), kl, nblocks, x->d_gpart, nullptr, x->tie());
+                               x->d_goff, x->d_grows, G, grouped_lpg(x), kl, nblocks, x->d_gpart, nullptr, x->tie(), nullptr);
             hipLaunchKernelGGL(group_merge_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gpart, nblocks * kl, k, x->d_group,
                                groups + q0 * k, rows_out + q0 * k, dist + q0 * k, nullptr, x->tie());
         }
@@ -492,7 +505,10 @@ int search_grouped_exact(vq_index* x, const float* d_queries, int nq, int k, int
 
 // fp16 path: group-max scan -> threshold + candidates -> exact re-score of the candidates' rows; flagged queries are redone
 // exactly on the device (group_block_topk_kernel<false> computes their distances itself), so nothing here waits.
-int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int32_t* groups, int32_t* rows_out, float* dist) {
+// allow (filtered search): the allowed groups' bitmap, n_allowed of them.  Pass 1 skips the rest, pass 2 selects among the
+// allowed groups only (their gbest stays 0, below every row), the redo walks only allowed groups.
+int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int32_t* groups, int32_t* rows_out, float* dist,
+                        const uint32_t* allow = nullptr, int32_t n_allowed = 0) {
     const int64_t n = x->size, streams = cdiv(n, SCAN_STREAM_ROWS), CA = GRP_CAND_MAX;
     const int G = x->n_groups, nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK);
     int64_t qc = std::max<int64_t>(16, ((int64_t)64 << 20) / G / 16 * 16);          // gbest [qc][G]: <= 256 MiB
@@ -515,6 +531,11 @@ int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int3
     VQ_HIP(hipMemsetAsync(x->d_gcounters, 0, 3 * sizeof(unsigned long long), x->stream));
     const float eps_rows = scan_eps_unit(x->dim) * x->row_norm_max;
     auto scan = x->dim == 768 ? scan3_group_max_kernel<24> : x->dim == 512 ? scan3_group_max_kernel<16> : scan3_group_max_kernel<8>;
+    if (allow) scan = x->dim == 768 ? scan3_group_max_kernel<24, true> : x->dim == 512 ? scan3_group_max_kernel<16, true> : scan3_group_max_kernel<8, true>;
+    auto redo = allow ? group_block_topk_kernel<false, true> : group_block_topk_kernel<false>;
+    // k among the allowed groups: the threshold is the k'-th largest gbest with k' = min(k, allowed) (a disallowed group's 0 is
+    // below it), the finalize test asks for min(k, allowed) re-scored groups
+    const int k_sel = allow ? std::min(k, (int)n_allowed) : k, g_fin = allow ? n_allowed : G;
     for (int64_t q0 = 0; q0 < nq; q0 += qc) {
         const int cur = (int)std::min<int64_t>(qc, nq - q0);
         const int64_t q_pad = round_up(cur, 16);
@@ -529,21 +550,21 @@ int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int3
         {
             Prof p(x, I_MFMA_SCAN);
             hipLaunchKernelGGL(scan, dim3(cdiv(streams, 4), (int)(q_pad / 16)), dim3(256), 0, x->stream, x->d_q16, x->rows16, streams,
-                               x->d_group, x->d_sgroup, cur, G, x->d_gbest);
+                               x->d_group, x->d_sgroup, cur, G, x->d_gbest, allow);
         }
         {
             Prof p(x, I_RESCORE);
-            hipLaunchKernelGGL(group_threshold_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gbest, G, k, qp, x->dim, eps_rows, x->d_goff,
+            hipLaunchKernelGGL(group_threshold_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gbest, G, k_sel, qp, x->dim, eps_rows, x->d_goff,
                                cand, pref, cn, thr, x->d_gkeys, flags);
             hipLaunchKernelGGL(group_rescore_kernel, dim3(GRP_RESCORE_SPLITS, cur), dim3(256), 0, x->stream, x->d_q16, qp, x->rows, x->rows16,
                                x->dim, x->d_goff, x->d_grows, cand, pref, cn, thr, flags, x->d_gkeys, x->d_gcounters, x->tie());
-            hipLaunchKernelGGL(group_finalize_kernel, dim3(cur), dim3(256), 0, x->stream, cn, x->d_gkeys, k, G, x->d_group, flags,
+            hipLaunchKernelGGL(group_finalize_kernel, dim3(cur), dim3(256), 0, x->stream, cn, x->d_gkeys, k, g_fin, x->d_group, flags,
                                groups + q0 * k, rows_out + q0 * k, dist + q0 * k, x->d_gcounters, x->tie());
         }
         {
             Prof p(x, I_EXACT_DIST);                 // the exact redo of flagged queries (every workgroup of an unflagged query leaves at once)
-            hipLaunchKernelGGL(group_block_topk_kernel<false>, dim3(nblocks, cur), dim3(256), 0, x->stream, nullptr, 0, x->rows, x->dim, qp,
-                               x->d_goff, x->d_grows, G, grouped_lpg(x), kl, nblocks, x->d_gpart, flags, x->tie());
+            hipLaunchKernelGGL(redo, dim3(nblocks, cur), dim3(256), 0, x->stream, nullptr, 0, x->rows, x->dim, qp,
+                               x->d_goff, x->d_grows, G, grouped_lpg(x), kl, nblocks, x->d_gpart, flags, x->tie(), allow);
             hipLaunchKernelGGL(group_merge_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gpart, nblocks * kl, k, x->d_group,
                                groups + q0 * k, rows_out + q0 * k, dist + q0 * k, flags, x->tie());
         }
@@ -579,6 +600,321 @@ int rm_exclusive_scan(vq_index* x, int32_t* v, int64_t n, int32_t* tiles) {
     hipLaunchKernelGGL(rm_scan_carry_kernel, dim3(1), dim3(256), 0, x->stream, tiles, ntiles);
     hipLaunchKernelGGL(rm_scan_apply_kernel, dim3((unsigned)ntiles), dim3(256), 0, x->stream, v, n, tiles, ntiles);
     VQ_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- filtered search (knn_filter.h) ----
+struct FilterPlan {
+    int64_t m = 0;                 // |S|: the allowed rows
+    int32_t nA = 0;                // allowed groups
+    bool all = false;              // an empty exclude list: S is the whole index
+    int32_t* soff = nullptr;       // gather path: [nA + 1] list offsets of the allowed groups
+    int32_t* list = nullptr;       // gather path: [m] the rows of S, group after group
+    int32_t* tie_w = nullptr;      // gather path: [m] their tie words
+    uint32_t* bits = nullptr;      // fp16 path: [cdiv(n_groups, 32)] the allowed groups' bitmap
+};
+
+// mode 0 takes the masked fp16 scan once S holds at least this share of the rows (measured, DESIGN.md "Filtered search"): the
+// gather path reads 4 B x dim per allowed row, the masked scan 2 B x dim per row of every stream it does not skip plus its re-score
+// (1M x 512: one query breaks even between 25 % and 60 % of the rows, 32 queries between 10 % and 25 %)
+constexpr int FLT_CROSS_Q1_DEN = 2;       // batches of up to FLT_CROSS_FEW_Q queries: |S| >= n / 2
+constexpr int FLT_CROSS_FEW_Q = 4;
+constexpr int FLT_CROSS_QN_DEN = 5;       // larger batches: |S| >= n / 5
+
+// the masked fp16 path exists for this call
+bool filter_fp16_ok(const vq_index* x, int nq, int k) {
+    return (x->dim == 256 || x->dim == 512 || x->dim == 768) && nq <= SCAN3_MAX_Q && k <= RV_K_MAX && x->size >= 1 && x->near_unit;
+}
+
+// Everything that can refuse a filtered call before any work is queued: the mode, and mode 2 where the masked path does not exist.
+int filter_precheck(vq_index* x, const char* fn, int nq, int k, int mode, int32_t n_sel, int exclude) {
+    VQ_CHECK(mode >= 0 && mode <= 2, "%s: mode %d unknown", fn, mode);
+    if (n_sel == 0 && exclude) return 0;                    // nothing excluded: the unfiltered search, under its own rules
+    if (mode != 1) VQ_TRY(refresh_norm_range(x));
+    if (mode == 2)
+        VQ_CHECK(filter_fp16_ok(x, nq, k), "%s: the masked fp16 scan needs dim 256, 512 or 768, nq <= %d, k <= %d and near-unit rows "
+                 "(0.5 <= |row|^2 <= 2); mode 1 takes any call", fn, SCAN3_MAX_Q, RV_K_MAX);
+    return 0;
+}
+
+// Checks the labels and the filter and sizes S from the host mirror of goff.  Then, on the device, S's row list (gather path) or
+// the allowed groups' bitmap (fp16 path).  The list goes up from a ring of pinned staging slots: a slot is reused only after the
+// copy vq_index::FLT_STAGE_SLOTS calls back has completed, so back-to-back asynchronous calls do not wait for each other.
+int filter_prepare(vq_index* x, const char* fn, const int32_t* groups, int32_t n_sel, int exclude, bool fp16, FilterPlan* p) {
+    VQ_CHECK(x->rank_n == 0 || x->rank_n == x->size, "%s: the id ranks cover %lld rows, the index holds %lld "
+             "(call vq_index_set_id_ranks again after adding rows, or clear them)", fn, (long long)x->rank_n, (long long)x->size);
+    VQ_CHECK(x->group_n == x->size && (int64_t)x->h_goff.size() == (int64_t)x->n_groups + 1, "%s: the group labels cover %lld rows, "
+             "the index holds %lld (call vq_index_set_groups after adding rows)", fn, (long long)x->group_n, (long long)x->size);
+    const int32_t G = x->n_groups;
+    std::vector<int32_t> sel(groups, groups + n_sel);
+    for (int32_t i = 0; i < n_sel; ++i)
+        VQ_CHECK(sel[(size_t)i] >= 0 && sel[(size_t)i] < G, "%s: group %d outside [0, %d)", fn, (int)sel[(size_t)i], (int)G);
+    std::sort(sel.begin(), sel.end());
+    sel.erase(std::unique(sel.begin(), sel.end()), sel.end());           // a group named twice counts once
+    const int32_t ns = (int32_t)sel.size();
+    const int32_t* hg = x->h_goff.data();
+    int64_t in_rows = 0;
+    for (int32_t g : sel) in_rows += hg[g + 1] - hg[g];
+    p->m = exclude ? x->size - in_rows : in_rows;
+    p->nA = exclude ? G - ns : ns;
+    p->all = exclude && ns == 0;
+    if (p->all || p->m == 0) return 0;
+    const int32_t nA = p->nA;
+    const bool list = !fp16;
+    auto words = [](int64_t c) { return round_up(std::max<int64_t>(c, 1), 4); };        // 16-byte aligned regions
+    const int64_t w_A = words(nA), w_soff = words((int64_t)nA + 1), w_K = exclude && list ? words((int64_t)G + 1) : 0,
+                  w_tiles = exclude && list ? words(cdiv(G, RM_SCAN_TILE) + 2) : 0, w_E = exclude ? words(ns) : 0,
+                  w_list = list ? words(p->m) : 0, w_bits = fp16 ? words(cdiv(G, 32)) : 0;
+    VQ_TRY(reserve_buf(x->d_flt, x->flt_cap, w_A + w_soff + w_K + w_tiles + w_E + 2 * w_list + w_bits));
+    int32_t* A = x->d_flt;
+    p->soff = A + w_A;
+    int32_t* K = p->soff + w_soff;
+    int32_t* tiles = K + w_K;
+    int32_t* E = tiles + w_tiles;
+    p->list = list ? E + w_E : nullptr;
+    p->tie_w = list ? E + w_E + w_list : nullptr;
+    p->bits = fp16 ? (uint32_t*)(E + w_E + 2 * w_list) : nullptr;
+    // a staging slot of the ring
+    const int slot = x->flt_slot;
+    x->flt_slot = (slot + 1) % vq_index::FLT_STAGE_SLOTS;
+    if (x->flt_ev[slot]) VQ_HIP(hipEventSynchronize(x->flt_ev[slot]));
+    else VQ_HIP(hipEventCreateWithFlags(&x->flt_ev[slot], hipEventDisableTiming));
+    const int64_t stage = exclude ? ns : w_A + nA + 1;
+    if (stage > x->hflt_cap[slot]) {
+        if (x->h_flt[slot]) (void)hipHostFree(x->h_flt[slot]);
+        x->h_flt[slot] = nullptr; x->hflt_cap[slot] = 0;
+        const int64_t cap = std::max<int64_t>(stage, 16 << 10);
+        VQ_HIP(hipHostMalloc((void**)&x->h_flt[slot], (size_t)cap * 4));
+        x->hflt_cap[slot] = cap;
+    }
+    int32_t* h = x->h_flt[slot];
+    if (!exclude) {
+        // the include list is the allowed groups: A and their offsets go up in one copy
+        std::memcpy(h, sel.data(), (size_t)nA * 4);
+        int32_t* so = h + w_A;
+        int32_t run = 0;
+        for (int32_t j = 0; j < nA; ++j) { so[j] = run; run += hg[sel[(size_t)j] + 1] - hg[sel[(size_t)j]]; }
+        so[nA] = run;
+        VQ_HIP(hipMemcpyAsync(A, h, (size_t)(w_A + nA + 1) * 4, hipMemcpyHostToDevice, x->stream));
+    } else {
+        std::memcpy(h, sel.data(), (size_t)ns * 4);        // ns > 0: an empty exclude list is the unfiltered search
+        VQ_HIP(hipMemcpyAsync(E, h, (size_t)ns * 4, hipMemcpyHostToDevice, x->stream));
+    }
+    VQ_HIP(hipEventRecord(x->flt_ev[slot], x->stream));
+    if (fp16) {
+        VQ_HIP(hipMemsetAsync(p->bits, exclude ? 0xff : 0, (size_t)w_bits * 4, x->stream));
+        hipLaunchKernelGGL(filter_bitmap_kernel, dim3(grid_for(ns)), dim3(256), 0, x->stream, exclude ? E : A, ns, p->bits);
+    } else {
+        if (exclude) {
+            hipLaunchKernelGGL(filter_allowed_kernel, dim3(grid_for(G)), dim3(256), 0, x->stream, E, ns, G, K);
+            VQ_TRY(rm_exclusive_scan(x, K, G, tiles));
+            hipLaunchKernelGGL(filter_compact_groups_kernel, dim3(grid_for(G)), dim3(256), 0, x->stream, K, G, x->d_goff, A, p->soff);
+            VQ_TRY(rm_exclusive_scan(x, p->soff, nA, tiles));
+        }
+        hipLaunchKernelGGL(filter_expand_kernel, dim3((unsigned)std::min<int64_t>(cdiv(nA, 4), 4096)), dim3(256), 0, x->stream, A, p->soff, nA,
+                           x->d_goff, x->d_grows, x->tie(), p->list, p->tie_w);
+    }
+    VQ_HIP(hipGetLastError());
+    return 0;
+}
+
+// distances of the listed rows for queries [0, cur) of a slice
+void filter_dist(vq_index* x, const FilterPlan& p, const float* qp, int cur, int64_t ld) {
+    Prof pr(x, I_EXACT_DIST);
+    if (cur <= 8)
+        hipLaunchKernelGGL(filter_dist_kernel<8>, dim3(cdiv(p.m, 64), 1), dim3(256), 0, x->stream, x->rows, p.list, p.m, x->dim, qp, cur, x->d_dist, ld);
+    else
+        hipLaunchKernelGGL(filter_dist_kernel<32>, dim3(cdiv(p.m, 64), cdiv(cur, 32)), dim3(256), 0, x->stream, x->rows, p.list, p.m, x->dim,
+                           qp, cur, x->d_dist, ld);
+}
+
+// Gather path, plain form: the plain exact path's selection over the list positions (knn_filter.h 4.)
+int search_filtered_gather(vq_index* x, const float* d_queries, int nq, int k, const FilterPlan& p, int32_t* d_ids, float* d_dist_out) {
+    const int64_t m = p.m, ld = round_up(m, 64);
+    const TieOrder ft{p.tie_w, x->rank_n ? x->d_rank_inv : nullptr};
+    const int64_t budget = (int64_t)128 << 20;                 // 512 MiB of fp32 distances per slice
+    const int qslice = (int)std::max<int64_t>(32, std::min<int64_t>(nq, budget / ld) / 32 * 32);
+    VQ_TRY(reserve_buf(x->d_dist, x->dist_cap, (int64_t)std::min(qslice, (int)round_up(nq, 32)) * ld));
+    const bool small_sel = m <= SEL_SMALL_MAX_N;
+    const int nchunks = cdiv(m, SEL_CHUNK);
+    if (!small_sel) VQ_TRY(reserve_buf(x->d_partial, x->partial_cap, (int64_t)std::min(qslice, nq) * nchunks * k));
+    for (int q0 = 0; q0 < nq; q0 += qslice) {
+        const int cur = std::min(qslice, nq - q0);
+        filter_dist(x, p, d_queries + (int64_t)q0 * x->dim, cur, ld);
+        Prof pr(x, I_SELECT);
+        if (small_sel) {
+            hipLaunchKernelGGL(select_small_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_dist, ld, m, k, d_ids + (int64_t)q0 * k,
+                               d_dist_out + (int64_t)q0 * k, ft);
+        } else {
+            hipLaunchKernelGGL(select_chunk_kernel, dim3(cur, nchunks), dim3(256), 0, x->stream, x->d_dist, ld, m, k, nchunks, x->d_partial, ft);
+            hipLaunchKernelGGL(merge_topk_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_partial, nchunks, k, d_ids + (int64_t)q0 * k,
+                               d_dist_out + (int64_t)q0 * k, ft);
+        }
+    }
+    VQ_HIP(hipGetLastError());
+    x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = nq;
+    x->stats_pending = false; x->gstats_pending = false;
+    return 0;
+}
+
+// Gather path, grouped form: group minima over the allowed groups' list ranges -> block top-k -> group_merge_kernel
+int search_grouped_filtered_gather(vq_index* x, const float* d_queries, int nq, int k, const FilterPlan& p, int32_t* groups,
+                                   int32_t* rows_out, float* dist) {
+    const int64_t m = p.m, ld = round_up(m, 64);
+    const TieOrder ft{p.tie_w, x->rank_n ? x->d_rank_inv : nullptr};
+    const int nblocks = cdiv(p.nA, GRP_BLOCK), kl = std::min(k, GRP_BLOCK);
+    int64_t qslice = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)128 << 20) / ld));              // 512 MiB of distances per slice
+    qslice = std::max<int64_t>(1, std::min<int64_t>(qslice, ((int64_t)32 << 20) / ((int64_t)nblocks * kl)));   // 256 MiB of block lists
+    VQ_TRY(reserve_buf(x->d_dist, x->dist_cap, qslice * ld));
+    VQ_TRY(reserve_buf(x->d_gpart, x->gpart_cap, qslice * nblocks * kl));
+    const int64_t mean = m / std::max<int32_t>(1, p.nA);
+    const int lpg = mean >= 256 ? 64 : mean >= 64 ? 16 : mean >= 8 ? 4 : 1;
+    for (int64_t q0 = 0; q0 < nq; q0 += qslice) {
+        const int cur = (int)std::min<int64_t>(qslice, nq - q0);
+        filter_dist(x, p, d_queries + q0 * x->dim, cur, ld);
+        Prof pr(x, I_SELECT);
+        hipLaunchKernelGGL((group_block_topk_kernel<true, false, true>),dim3(nblocks, cur), dim3(256), 0, x->stream, x->d_dist, ld, nullptr, x->dim,
+                           nullptr, p.soff, nullptr, p.nA, lpg, kl, nblocks, x->d_gpart, nullptr, ft, nullptr);
+        hipLaunchKernelGGL(group_merge_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gpart, nblocks * kl, k, x->d_group,
+                           groups + q0 * k, rows_out + q0 * k, dist + q0 * k, nullptr, ft);
+    }
+    VQ_HIP(hipGetLastError());
+    x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = nq;
+    x->stats_pending = false; x->gstats_pending = false;
+    return 0;
+}
+
+// Masked fp16 path, plain form (knn_filter.h): masked stream scan -> stream threshold -> re-score of the candidate streams'
+// allowed rows -> top-k; flagged queries are redone by the masked exact fallback on the device, so nothing here waits.
+int search_filtered_fp16(vq_index* x, const float* d_queries, int nq, int k, const FilterPlan& p, int32_t* d_ids, float* d_dist_out) {
+    const int64_t n = x->size, streams = round_up(n, SCAN_STREAM_ROWS) / SCAN_STREAM_ROWS, q_pad = round_up(nq, SCAN3_QB);
+    VQ_TRY(reserve_buf(x->d_q16, x->q16_cap, q_pad * x->dim));
+    VQ_TRY(reserve_buf(x->d_keys, x->keys_cap, streams * q_pad * 2));
+    VQ_TRY(reserve_buf(x->d_flags, x->flags_cap, q_pad));
+    VQ_TRY(reserve_buf(x->d_slots, x->slots_cap, round_up(nq, 1024)));
+    VQ_TRY(reserve_buf(x->d_fcand, x->fcand_cap, (int64_t)nq * FLT_CAND + 3 * (int64_t)nq));
+    VQ_TRY(reserve_buf(x->d_flist, x->flist_cap, (int64_t)nq * FLT_LIST));
+    if (!x->d_counters) {
+        VQ_HIP(hipMalloc((void**)&x->d_counters, FB_NCOUNTERS * 4));
+        VQ_HIP(hipHostMalloc((void**)&x->h_counters, FB_NCOUNTERS * 4, hipHostMallocMapped));
+        VQ_HIP(hipHostGetDevicePointer((void**)&x->d_counters_host, x->h_counters, 0));
+    }
+    const int fast_splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_FAST_ROWS)));
+    const int fb_splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_SPLIT_ROWS)));
+    const int64_t fb_cap = std::max<int64_t>(FB_QG, std::min<int64_t>(round_up(nq, FB_QG), ((int64_t)64 << 20) / ((int64_t)fb_splits * k * 8) / FB_QG * FB_QG));
+    VQ_TRY(reserve_buf(x->d_fb_partial, x->fbp_cap, std::max<int64_t>(fb_cap * fb_splits, (int64_t)FB_FAST_SLOTS * fast_splits) * k));
+    int32_t* cand = x->d_fcand;
+    int32_t* cn = cand + (int64_t)nq * FLT_CAND;
+    int32_t* ln = cn + nq;
+    float* thr = (float*)(ln + nq);
+    const GroupMask gm{x->d_group, x->d_sgroup, p.bits};
+    {
+        Prof pr(x, I_TO_F16);
+        const int64_t total4 = q_pad * x->dim / 4;
+        hipLaunchKernelGGL(queries_to_f16_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 2048)), dim3(256), 0, x->stream,
+                           d_queries, x->d_q16, nq, q_pad, x->dim);
+    }
+    {
+        Prof pr(x, I_MFMA_SCAN);
+        auto scan = x->dim == 768 ? scan3_f16_top2_kernel<24, 1, false, true> : x->dim == 512 ? scan3_f16_top2_kernel<16, 1, false, true>
+                                                                                              : scan3_f16_top2_kernel<8, 1, false, true>;
+        hipLaunchKernelGGL(scan, dim3(cdiv(streams, 4), (int)(q_pad / SCAN3_QB)), dim3(256), 0, x->stream, x->d_q16, x->rows16, n, streams, q_pad,
+                           x->d_keys, 0, gm);
+    }
+    {
+        Prof pr(x, I_RESCORE);
+        const TieOrder tie = x->tie();
+        hipLaunchKernelGGL(filter_stream_threshold_kernel, dim3(nq), dim3(256), 0, x->stream, x->d_keys, streams, k, d_queries, x->dim,
+                           scan_eps_unit(x->dim) * x->row_norm_max, cand, cn, thr, ln, x->d_flags);
+        hipLaunchKernelGGL(filter_stream_rescore_kernel, dim3(FLT_RESCORE_SPLITS, nq), dim3(256), 0, x->stream, x->d_q16, d_queries, x->rows,
+                           x->rows16, n, x->dim, gm, cand, cn, thr, x->d_flags, x->d_flist, ln, tie);
+        hipLaunchKernelGGL(filter_stream_finalize_kernel, dim3(nq), dim3(256), 0, x->stream, x->d_flist, ln, k, p.m, x->d_flags, d_ids,
+                           d_dist_out, tie);
+    }
+    hipLaunchKernelGGL(collect_flags_kernel, dim3(1), dim3(1024), 0, x->stream, x->d_flags, nq, x->d_slots, x->d_counters);
+    launch_fallback(x, d_queries, nq, k, d_ids, d_dist_out, x->d_counters, &gm);
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(x->h_counters, x->d_counters, FB_NCOUNTERS * 4, hipMemcpyDeviceToHost, x->stream));
+    x->stats_pending = true; x->gstats_pending = false;
+    return 0;
+}
+
+// mode 0: the masked fp16 scan where it exists, the index is large enough for the plain rule (16,384 rows) and S is broad
+bool filter_use_fp16(const vq_index* x, int nq, int k, int mode, int64_t m) {
+    if (mode != 0) return mode == 2;
+    const int den = nq <= FLT_CROSS_FEW_Q ? FLT_CROSS_Q1_DEN : FLT_CROSS_QN_DEN;
+    return filter_fp16_ok(x, nq, k) && x->size >= 16384 && m * den >= x->size;
+}
+
+int filter_fill_empty(vq_index* x, int nq, int k, int32_t* a, int32_t* b, float* dist) {
+    const int64_t count = (int64_t)nq * k;
+    hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, a, dist, count);
+    if (b) hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, b, dist, count);
+    VQ_HIP(hipGetLastError());
+    x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = nq;
+    x->stats_pending = false; x->gstats_pending = false;
+    return 0;
+}
+
+// |S| before any device work: the host mirror of goff (the mode-0 choice needs it to pick what filter_prepare builds)
+int64_t filter_rows(const vq_index* x, const int32_t* sel, int32_t n_sel, int exclude) {
+    if ((int64_t)x->h_goff.size() != (int64_t)x->n_groups + 1) return 0;
+    std::vector<int32_t> s(sel, sel + n_sel);
+    std::sort(s.begin(), s.end());
+    s.erase(std::unique(s.begin(), s.end()), s.end());
+    int64_t in_rows = 0;
+    for (int32_t g : s) if (g >= 0 && g < x->n_groups) in_rows += x->h_goff[(size_t)g + 1] - x->h_goff[(size_t)g];
+    return exclude ? x->size - in_rows : in_rows;
+}
+
+int search_filtered_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode, const int32_t* sel, int32_t n_sel, int exclude,
+                             int32_t* d_ids, float* d_dist) {
+    static const char* fn = "vq_index_search_filtered";
+    VQ_TRY(filter_precheck(x, fn, nq, k, mode, n_sel, exclude));
+    if (n_sel == 0 && exclude) return search_dispatch(x, d_queries, nq, k, mode, d_ids, d_dist);       // nothing excluded: the plain search
+    const bool fp16 = filter_use_fp16(x, nq, k, mode, filter_rows(x, sel, n_sel, exclude));
+    FilterPlan p;
+    VQ_TRY(filter_prepare(x, fn, sel, n_sel, exclude, fp16, &p));
+    if (p.m == 0) return filter_fill_empty(x, nq, k, d_ids, nullptr, d_dist);
+    return fp16 ? search_filtered_fp16(x, d_queries, nq, k, p, d_ids, d_dist) : search_filtered_gather(x, d_queries, nq, k, p, d_ids, d_dist);
+}
+
+int search_grouped_filtered_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode, const int32_t* sel, int32_t n_sel,
+                                     int exclude, int32_t* groups, int32_t* rows_out, float* dist) {
+    static const char* fn = "vq_index_search_grouped_filtered";
+    VQ_TRY(filter_precheck(x, fn, nq, k, mode, n_sel, exclude));
+    if (n_sel == 0 && exclude) return search_grouped_dispatch(x, d_queries, nq, k, mode, groups, rows_out, dist);
+    const bool fp16 = filter_use_fp16(x, nq, k, mode, filter_rows(x, sel, n_sel, exclude));
+    FilterPlan p;
+    VQ_TRY(filter_prepare(x, fn, sel, n_sel, exclude, fp16, &p));
+    if (p.m == 0) return filter_fill_empty(x, nq, k, groups, rows_out, dist);
+    return fp16 ? search_grouped_fp16(x, d_queries, nq, k, groups, rows_out, dist, p.bits, p.nA)
+                : search_grouped_filtered_gather(x, d_queries, nq, k, p, groups, rows_out, dist);
+}
+
+// Host forms of the filtered searches: the queries go up from pinned staging, the results come back through it, one wait.
+int stage_queries(vq_index* x, const float* queries, int nq) {
+    const int64_t q_bytes = (int64_t)nq * x->dim * 4;
+    VQ_TRY(reserve_buf(x->d_q, x->q_cap, (int64_t)nq * x->dim));
+    if (q_bytes > x->hq_cap) {
+        if (x->h_q) (void)hipHostFree(x->h_q);
+        x->h_q = nullptr; x->hq_cap = 0;
+        VQ_HIP(hipHostMalloc((void**)&x->h_q, (size_t)std::max<int64_t>(q_bytes, 64 << 10)));
+        x->hq_cap = std::max<int64_t>(q_bytes, 64 << 10);
+    }
+    std::memcpy(x->h_q, queries, (size_t)q_bytes);
+    VQ_HIP(hipMemcpyAsync(x->d_q, x->h_q, (size_t)q_bytes, hipMemcpyHostToDevice, x->stream));
+    return 0;
+}
+
+int host_results(vq_index* x, int64_t bytes) {          // h_res holds at least `bytes` (pinned; the stream is idle when it is replaced)
+    if (bytes <= x->hres_cap) return 0;
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    if (x->h_res) (void)hipHostFree(x->h_res);
+    x->h_res = nullptr; x->hres_cap = 0;
+    VQ_HIP(hipHostMalloc((void**)&x->h_res, (size_t)std::max<int64_t>(bytes, 64 << 10), hipHostMallocMapped));
+    VQ_HIP(hipHostGetDevicePointer((void**)&x->d_res, x->h_res, 0));
+    x->hres_cap = std::max<int64_t>(bytes, 64 << 10);
     return 0;
 }
 
@@ -638,7 +974,11 @@ int vq_index_destroy(vq_index* x) {
     if (x->h_res) (void)hipHostFree(x->h_res);
     (void)hipFree(x->d_norm_range); (void)hipFree(x->d_rank);
     (void)hipFree(x->d_group); (void)hipFree(x->d_gbest); (void)hipFree(x->d_gcand); (void)hipFree(x->d_gkeys); (void)hipFree(x->d_gpart);
-    (void)hipFree(x->d_gcounters); (void)hipFree(x->d_gout);
+    (void)hipFree(x->d_gcounters); (void)hipFree(x->d_gout); (void)hipFree(x->d_flt); (void)hipFree(x->d_fcand); (void)hipFree(x->d_flist);
+    for (int i = 0; i < vq_index::FLT_STAGE_SLOTS; ++i) {
+        if (x->h_flt[i]) (void)hipHostFree(x->h_flt[i]);
+        if (x->flt_ev[i]) (void)hipEventDestroy(x->flt_ev[i]);
+    }
     if (x->h_gcounters) (void)hipHostFree(x->h_gcounters);
     delete x;
     return 0;
@@ -661,7 +1001,7 @@ int vq_index_clear(vq_index* x) {
     }
     x->norm_dirty = false; x->near_unit = true; x->row_norm_max = 1.0f;
     x->rank_n = 0;
-    x->group_n = 0; x->n_groups = 0;
+    x->group_n = 0; x->n_groups = 0; x->h_goff.clear();
     return 0;
 }
 
@@ -699,7 +1039,7 @@ int vq_index_set_groups(vq_index* x, const int32_t* group_of_row, int64_t n, int
     VQ_TRY(require_init());
     VQ_CHECK(x && n >= 0 && (n == 0 || group_of_row), "vq_index_set_groups: bad argument");
     std::lock_guard<std::mutex> lk(x->mu);
-    if (n == 0) { x->group_n = 0; x->n_groups = 0; return 0; }
+    if (n == 0) { x->group_n = 0; x->n_groups = 0; x->h_goff.clear(); return 0; }
     VQ_CHECK(n == x->size, "vq_index_set_groups: %lld labels for an index of %lld rows", (long long)n, (long long)x->size);
     VQ_CHECK(n_groups >= 1 && n_groups <= n, "vq_index_set_groups: n_groups %d outside [1, %lld]", (int)n_groups, (long long)n);
     // dense labels, checked here: the kernels index per-group arrays with them.  By-group row list: a stable counting sort.
@@ -738,6 +1078,7 @@ int vq_index_set_groups(vq_index* x, const int32_t* group_of_row, int64_t n, int
     VQ_HIP(hipMemcpyAsync(x->d_group, h.data(), (size_t)total * 4, hipMemcpyHostToDevice, x->stream));
     VQ_HIP(hipStreamSynchronize(x->stream));                       // `h` is this frame's
     x->d_goff = x->d_group + n_pad; x->d_grows = x->d_goff + n_groups + 1; x->d_sgroup = x->d_grows + n;
+    x->h_goff.assign(goff, goff + n_groups + 1);
     x->group_n = n; x->n_groups = n_groups;
     return 0;
 }
@@ -924,9 +1265,11 @@ int vq_index_remove_rows(vq_index* x, const int64_t* row_numbers, int64_t n) {
         VQ_HIP(hipMemcpyAsync(x->d_group, grp, (size_t)total_new * 4, hipMemcpyDeviceToDevice, x->stream));
         VQ_HIP(hipGetLastError());
         x->d_goff = x->d_group + n_pad_new; x->d_grows = x->d_goff + G_new + 1; x->d_sgroup = x->d_grows + n_new;
+        x->h_goff.resize((size_t)G_new + 1);                         // the host mirror of goff: read back, waited for below
+        VQ_HIP(hipMemcpyAsync(x->h_goff.data(), goff_new, ((size_t)G_new + 1) * 4, hipMemcpyDeviceToHost, x->stream));
         x->group_n = n_new; x->n_groups = G_new;
     } else {
-        x->group_n = 0; x->n_groups = 0;
+        x->group_n = 0; x->n_groups = 0; x->h_goff.clear();
     }
     // the |row|^2 range stays as it is: it still covers every survivor (conservative, as in vq_index_update_rows)
     x->size = n_new;
@@ -1047,6 +1390,96 @@ int vq_index_search_grouped(vq_index* x, const float* queries, int nq, int k, in
     VQ_HIP(hipMemcpyAsync(rows, d_r, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
     VQ_HIP(hipMemcpyAsync(dist, d_d, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
     VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+int vq_index_search_filtered_device(vq_index* x, const void* d_queries, int nq, int k, int mode, const int32_t* groups, int32_t n_sel,
+                                    int exclude, void* d_ids, void* d_dist) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
+             (nq == 0 || (d_queries && d_ids && d_dist)), "vq_index_search_filtered_device: bad argument");
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) {
+        const int64_t count = (int64_t)nq * k;
+        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, (int32_t*)d_ids, (float*)d_dist, count);
+        VQ_HIP(hipGetLastError());
+        return 0;
+    }
+    return search_filtered_dispatch(x, (const float*)d_queries, nq, k, mode, groups, n_sel, exclude, (int32_t*)d_ids, (float*)d_dist);
+}
+
+int vq_index_search_filtered(vq_index* x, const float* queries, int nq, int k, int mode, const int32_t* groups, int32_t n_sel, int exclude,
+                             int32_t* ids, float* dist) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
+             (nq == 0 || (queries && ids && dist)), "vq_index_search_filtered: bad argument");
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    if (x->size == 0) {
+        for (int64_t i = 0; i < count; ++i) { ids[i] = -1; dist[i] = __builtin_inff(); }
+        return 0;
+    }
+    if (count > x->out_cap) {
+        int64_t c1 = x->out_cap, c2 = x->out_cap;
+        VQ_TRY(reserve_buf(x->d_ids, c1, count));
+        VQ_TRY(reserve_buf(x->d_out, c2, count));
+        x->out_cap = count;
+    }
+    VQ_TRY(filter_precheck(x, "vq_index_search_filtered", nq, k, mode, n_sel, exclude));      // refuse before staging anything
+    VQ_TRY(host_results(x, count * 8));
+    VQ_TRY(stage_queries(x, queries, nq));
+    VQ_TRY(search_filtered_dispatch(x, x->d_q, nq, k, mode, groups, n_sel, exclude, x->d_ids, x->d_out));
+    VQ_HIP(hipMemcpyAsync(x->h_res, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(x->h_res + count * 4, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    std::memcpy(ids, x->h_res, (size_t)count * 4);
+    std::memcpy(dist, x->h_res + count * 4, (size_t)count * 4);
+    return 0;
+}
+
+int vq_index_search_grouped_filtered_device(vq_index* x, const void* d_queries, int nq, int k, int mode, const int32_t* groups,
+                                            int32_t n_sel, int exclude, void* d_groups, void* d_rows, void* d_dist) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
+             (nq == 0 || (d_queries && d_groups && d_rows && d_dist)), "vq_index_search_grouped_filtered_device: bad argument");
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) {
+        const int64_t count = (int64_t)nq * k;
+        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, (int32_t*)d_groups, (float*)d_dist, count);
+        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, (int32_t*)d_rows, (float*)d_dist, count);
+        VQ_HIP(hipGetLastError());
+        return 0;
+    }
+    return search_grouped_filtered_dispatch(x, (const float*)d_queries, nq, k, mode, groups, n_sel, exclude, (int32_t*)d_groups,
+                                            (int32_t*)d_rows, (float*)d_dist);
+}
+
+int vq_index_search_grouped_filtered(vq_index* x, const float* queries, int nq, int k, int mode, const int32_t* groups, int32_t n_sel,
+                                     int exclude, int32_t* groups_out, int32_t* rows, float* dist) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
+             (nq == 0 || (queries && groups_out && rows && dist)), "vq_index_search_grouped_filtered: bad argument");
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    if (x->size == 0) {
+        for (int64_t i = 0; i < count; ++i) { groups_out[i] = -1; rows[i] = -1; dist[i] = __builtin_inff(); }
+        return 0;
+    }
+    VQ_TRY(reserve_buf(x->d_gout, x->gout_cap, 3 * count));
+    int32_t* d_g = x->d_gout; int32_t* d_r = d_g + count; float* d_d = (float*)(d_r + count);
+    VQ_TRY(filter_precheck(x, "vq_index_search_grouped_filtered", nq, k, mode, n_sel, exclude));
+    VQ_TRY(host_results(x, count * 12));
+    VQ_TRY(stage_queries(x, queries, nq));
+    VQ_TRY(search_grouped_filtered_dispatch(x, x->d_q, nq, k, mode, groups, n_sel, exclude, d_g, d_r, d_d));
+    VQ_HIP(hipMemcpyAsync(x->h_res, x->d_gout, (size_t)count * 12, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    std::memcpy(groups_out, x->h_res, (size_t)count * 4);
+    std::memcpy(rows, x->h_res + count * 4, (size_t)count * 4);
+    std::memcpy(dist, x->h_res + count * 8, (size_t)count * 4);
     return 0;
 }
 

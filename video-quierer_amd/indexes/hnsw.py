@@ -20,11 +20,11 @@ import os
 import pickle
 import threading
 import time
-from collections.abc import Mapping
+from collections.abc import Iterable, Mapping
 from concurrent.futures import ThreadPoolExecutor
 from itertools import compress
 from ctypes import POINTER, c_float, c_int32, c_int64, c_void_p
-from typing import Callable, Dict, Hashable, List, Optional, Sequence
+from typing import Callable, Dict, Hashable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -500,11 +500,14 @@ class HNSWIndex:
             gl.uploaded = n
         return gl
 
-    def _grouped_many(self, queries: Sequence[np.ndarray], k: int, group_of) -> List[List[Dict]]:
+    def _grouped_many(self, queries: Sequence[np.ndarray], k: int, group_of, flt=None) -> List[List[Dict]]:
+        filtered = flt is not None
+        if filtered:
+            fkeys, excl = flt
         unit = np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32)
         if unit.shape[1] != self.dimension:
             raise ValueError(f"query dimension {unit.shape[1]} != index dimension {self.dimension}")
-        if k <= 0 or not self._ids:
+        if k <= 0 or not self._ids or (filtered and not excl and not fkeys):
             return [[] for _ in queries]
         if not self._identity:
             self._sync_tie_order()
@@ -514,36 +517,138 @@ class HNSWIndex:
         groups = np.empty((nq, kk), dtype=np.int32)
         rows = np.empty((nq, kk), dtype=np.int32)
         dist = np.empty((nq, kk), dtype=np.float32)
-        _lib.check(_lib.load().vq_index_search_grouped(self._h, _lib.fptr(unit), nq, kk, int(self.search_mode),
-                                                       groups.ctypes.data_as(POINTER(c_int32)),
-                                                       rows.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist)))
+        if not filtered:
+            _lib.check(_lib.load().vq_index_search_grouped(self._h, _lib.fptr(unit), nq, kk, int(self.search_mode),
+                                                           groups.ctypes.data_as(POINTER(c_int32)),
+                                                           rows.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist)))
+        else:
+            labels = self._filter_labels(gl, fkeys)
+            if not excl and len(labels) == 0:
+                return [[] for _ in queries]
+            _lib.check(_lib.load().vq_index_search_grouped_filtered(
+                self._h, _lib.fptr(unit), nq, kk, int(self.search_mode), labels.ctypes.data_as(POINTER(c_int32)), len(labels),
+                int(excl), groups.ctypes.data_as(POINTER(c_int32)), rows.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist)))
         keys, names, identity = gl.keys, self._ids, self._identity
         return [[{"group": keys[g], "id": int(r) if identity else names[r], "distance": d, "score": np.float32(1.0) - d}
                  for g, r, d in zip(rg.tolist(), rr.tolist(), rd) if r >= 0]
                 for rg, rr, rd in zip(groups, rows, dist)]
 
     def search_grouped(self, query: np.ndarray, k: int = 5,
-                       group_of: Optional[Callable[[Hashable], Hashable]] = None) -> List[Dict]:
+                       group_of: Optional[Callable[[Hashable], Hashable]] = None, *,
+                       within: Optional[Iterable[Hashable]] = None, exclude: Optional[Iterable[Hashable]] = None) -> List[Dict]:
         """The k best GROUPS (videos) for one query, each with its best row: ``[{'group', 'id', 'distance', 'score'}]``.
         Exactly the plain search's exhaustive (distance, id) list with every row dropped whose group came earlier — what
         video_search_system.py:296-342 builds from ``search(q, k * 2)`` (it returns fewer than k videos once the top 2k
         frames span fewer than k of them; this never does while the index holds k groups).  ``group_of`` maps a node id to
         its group key (default ``video_of``: the caller's ``f"{video_id}_{i}"`` convention); a caller holding the metadata
-        passes ``lambda nid: meta[nid]['video_id']`` — keep passing the SAME callable, a different one relabels every row."""
+        passes ``lambda nid: meta[nid]['video_id']`` — keep passing the SAME callable, a different one relabels every row.
+        ``within`` / ``exclude`` (at most one, an iterable of group keys) restrict the search to those groups or to all the
+        others, exactly as ``search_filtered`` does."""
+        flt = self._filter_arg(within, exclude) if within is not None or exclude is not None else None
         if self.entry_point is None or self.element_count == 0:
             return []
         with self.lock:
-            return self._grouped_many([query], k, group_of)[0]
+            return self._grouped_many([query], k, group_of, flt)[0]
 
     def search_grouped_batch(self, queries: List[np.ndarray], k: int = 5,
-                             group_of: Optional[Callable[[Hashable], Hashable]] = None) -> List[List[Dict]]:
+                             group_of: Optional[Callable[[Hashable], Hashable]] = None, *,
+                             within: Optional[Iterable[Hashable]] = None,
+                             exclude: Optional[Iterable[Hashable]] = None) -> List[List[Dict]]:
         """``search_grouped`` for a batch of queries, one device pass."""
+        flt = self._filter_arg(within, exclude) if within is not None or exclude is not None else None
         if len(queries) == 0:
             return []
         if self.entry_point is None or self.element_count == 0:
             return [[] for _ in queries]
         with self.lock:
-            return self._grouped_many(queries, k, group_of)
+            return self._grouped_many(queries, k, group_of, flt)
+
+    # -- filtered query: the plain search within, or excluding, a set of groups (videos) -------------
+    @staticmethod
+    def _filter_arg(within, exclude) -> Tuple[List[Hashable], bool]:
+        """(group keys, exclude?) of a ``within`` / ``exclude`` pair: exactly one of them, an iterable of keys."""
+        if (within is None) == (exclude is None):
+            raise ValueError("give exactly one of `within` and `exclude` (an iterable of group keys)")
+        keys = within if within is not None else exclude
+        if isinstance(keys, (str, bytes)) or not isinstance(keys, Iterable):
+            raise ValueError("`within` / `exclude` take an iterable of group keys (a list of video ids), not one key")
+        return list(keys), exclude is not None
+
+    @staticmethod
+    def _filter_labels(gl: _GroupLabels, keys: List[Hashable]) -> np.ndarray:
+        """The dense labels of the keys the index holds, ascending; unknown keys hold no rows and are dropped."""
+        index = gl.index
+        return np.array(sorted({index[key] for key in keys if key in index}), dtype=np.int32)
+
+    def _filtered_many(self, queries: Sequence[np.ndarray], k: int, flt: Tuple[List[Hashable], bool], group_of) -> List[List[Dict]]:
+        keys, excl = flt
+        unit = np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32)
+        if unit.shape[1] != self.dimension:
+            raise ValueError(f"query dimension {unit.shape[1]} != index dimension {self.dimension}")
+        n = len(self._ids)
+        kk = min(int(k), n)
+        if kk <= 0 or (not excl and not keys):
+            return [[] for _ in queries]                 # nothing allowed: no device call
+        if not self._identity:
+            self._sync_tie_order()
+        gl = self._sync_groups(group_of)
+        labels = self._filter_labels(gl, keys)
+        if not excl and len(labels) == 0:
+            return [[] for _ in queries]
+        nq = unit.shape[0]
+
+        def run(fetch):
+            ids = np.empty((nq, fetch), dtype=np.int32)
+            dist = np.empty((nq, fetch), dtype=np.float32)
+            _lib.check(_lib.load().vq_index_search_filtered(
+                self._h, _lib.fptr(unit), nq, fetch, int(self.search_mode), labels.ctypes.data_as(POINTER(c_int32)), len(labels),
+                int(excl), ids.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist)))
+            return ids, dist
+
+        if self._identity or self._tie_order == "device":
+            ids, dist = run(kk)
+            names = None if self._identity else self._ids
+            return [[{"id": int(i) if names is None else names[i], "distance": d, "score": np.float32(1.0) - d}
+                     for i, d in zip(ri.tolist(), rd) if i >= 0] for ri, rd in zip(ids, dist)]
+        # ids without a common order: as _search_many, over-fetch until no tie group is cut at rank k, then re-sort
+        fetch = min(n, kk + 8)
+        while True:
+            ids, dist = run(fetch)
+            cut = fetch < n and np.any((dist[:, kk - 1] == dist[:, fetch - 1]) & np.isfinite(dist[:, kk - 1]))
+            if not cut:
+                break
+            fetch = min(n, fetch * 2)
+        out = []
+        for ri, rd in zip(ids, dist):
+            cand = sorted(((d, self._ids[i]) for i, d in zip(ri, rd) if i >= 0))[:kk]
+            out.append([{"id": i, "distance": d, "score": np.float32(1.0) - d} for d, i in cand])
+        return out
+
+    def search_filtered(self, query: np.ndarray, k: int = 5, *, within: Optional[Iterable[Hashable]] = None,
+                        exclude: Optional[Iterable[Hashable]] = None,
+                        group_of: Optional[Callable[[Hashable], Hashable]] = None) -> List[Dict]:
+        """``search`` restricted to the rows of some groups (videos): ``within=[video_id]`` searches inside one video,
+        ``exclude=[video_of(frame_id)]`` finds more like a frame from the other videos, ``within=collection`` searches a set.
+        Exactly one of ``within`` / ``exclude`` is given, as an iterable of group keys (``group_of`` as ``search_grouped``;
+        unknown keys hold no rows).  The result is what ``search`` returns on an index holding only the allowed rows: the same
+        dicts, distances and (distance, id) order, exact for any k however few rows the filter allows."""
+        flt = self._filter_arg(within, exclude)
+        if self.entry_point is None or self.element_count == 0:
+            return []
+        with self.lock:
+            return self._filtered_many([query], k, flt, group_of)[0]
+
+    def search_filtered_batch(self, queries: List[np.ndarray], k: int = 5, *, within: Optional[Iterable[Hashable]] = None,
+                              exclude: Optional[Iterable[Hashable]] = None,
+                              group_of: Optional[Callable[[Hashable], Hashable]] = None) -> List[List[Dict]]:
+        """``search_filtered`` for a batch of queries (one filter for all of them), one device pass."""
+        flt = self._filter_arg(within, exclude)
+        if len(queries) == 0:
+            return []
+        if self.entry_point is None or self.element_count == 0:
+            return [[] for _ in queries]
+        with self.lock:
+            return self._filtered_many(queries, k, flt, group_of)
 
     def synchronize(self) -> None:
         _lib.check(_lib.load().vq_index_synchronize(self._h))
