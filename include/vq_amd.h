@@ -300,6 +300,37 @@ int vq_index_search_grouped_filtered_device(vq_index* idx, const void* d_queries
                                             const int32_t* groups, int32_t n_sel, int exclude,
                                             void* d_groups_i32, void* d_rows_i32, void* d_dist_f32);
 
+/* Clip search: the k groups (videos) most similar to a SET of query frames q_0 .. q_{m-1} — "more like this video", "is this
+ * upload a cut or a re-encode of something indexed", several example frames that should all be found.
+ *   d(i, g) = the smallest distance of q_i to a row of group g (distance and tie rank as vq_index_search; the row that attains
+ *   it has the smallest (distance, tie rank));  D(g) = fp32((d(0,g) + d(1,g) + ... + d(m-1,g), added in fp64 in this order) /
+ *   m);  the answer is the first min(k, allowed groups) groups by (D, label) ascending, unused slots -1 / +inf.  It is
+ *   one-directional: every query frame looks for its best match in the video, the video's other frames cost nothing.  For
+ *   near-unit rows and queries the fp64 sum is exact, so the order of the frames does not change D.
+ *   match_rows [k][m] (or NULL): the row of result group j that attains d(i, group j), full-index row numbers; -1 in unused slots.
+ *   groups / n_sel / exclude: the filter of vq_index_search_filtered (host memory, duplicates allowed, a label outside
+ *   [0, n_groups) is VQ_ERR_INVALID; stale or missing labels and stale id ranks are refused before any work is queued).
+ *   n_sel = 0, exclude = 1 is the unfiltered call; n_sel = 0, exclude = 0 returns every slot empty.  A group's D does not
+ *   depend on other groups: the filtered answer is the unfiltered ranking with the disallowed groups struck out.
+ *   Limits: 1 <= m <= 4096, 1 <= k <= 1024 (else VQ_ERR_INVALID).
+ *   mode: 1 = exact (the plain path's distances per query chunk, group minima, per-group fp64 sums).  2 = fp16 with proof: one
+ *   pass of a 256-query MFMA tile scan per 256 query frames leaves each (frame, group) maximum, groups whose mean fp16 score is
+ *   within twice the mean error bound of the k-th are re-scored exactly over all their rows; dim 256, 512 or 768 and near-unit
+ *   rows, else VQ_ERR_INVALID before any work is queued.  A call it cannot prove (a query with |q|^2 outside [0.25, 4] or not
+ *   finite, more than 16 Mi candidate (group, frame) pairs) is redone by the exact path on the device.  0 = the plain search's
+ *   rule: fp16 where it exists, from 16,384 rows.
+ *   Scratch is bounded: the frames are processed in chunks that keep the per-(frame, group) tables within 256 MiB and the exact
+ *   distances within 512 MiB; the candidates' keys take at most 128 MiB; per-group arrays take 40 B per group.
+ *   The _device form takes device queries and results and is asynchronous on the index's stream; nothing is read back.
+ *   vq_index_last_search_stats afterwards: [0] 1 if the fp16 path proved the answer, [1] rows re-scored exactly (candidate rows
+ *   x m), [2] 1 if the exact path answered. */
+int vq_index_search_set(vq_index* idx, const float* queries /*[m][dim]*/, int m, int k, int mode,
+                        const int32_t* groups, int32_t n_sel, int exclude,
+                        int32_t* groups_out /*[k]*/, float* dist_out /*[k]*/, int32_t* match_rows /*[k][m] or NULL*/);
+int vq_index_search_set_device(vq_index* idx, const void* d_queries_f32, int m, int k, int mode,
+                               const int32_t* groups, int32_t n_sel, int exclude,
+                               void* d_groups_i32, void* d_dist_f32, void* d_match_rows_i32 /*or NULL*/);
+
 /* save / load support (hnsw.py:306-380): the stored (normalised) rows. */
 int vq_index_export(vq_index* idx, float* rows /*[size][dim]*/);
 /* Single stored rows (the reference reads `self.data[node_id]`, a dict lookup): out [n][dim] = rows row_numbers[0..n). */

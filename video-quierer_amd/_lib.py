@@ -118,6 +118,10 @@ SIGNATURES = {
                                                  POINTER(c_int32), POINTER(c_int32), POINTER(c_float)]),
     "vq_index_search_grouped_filtered_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_int32, c_int,
                                                         c_void_p, c_void_p, c_void_p]),
+    "vq_index_search_set": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, POINTER(c_int32), c_int32, c_int,
+                                    POINTER(c_int32), POINTER(c_float), POINTER(c_int32)]),
+    "vq_index_search_set_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_int32, c_int, c_void_p,
+                                           c_void_p, c_void_p]),
     "vq_index_synchronize": (c_int, [c_void_p]),
     "vq_index_set_stream": (c_int, [c_void_p, c_void_p]),
     "vq_index_export": (c_int, [c_void_p, POINTER(c_float)]),

@@ -11,6 +11,7 @@
 #include "knn_grouped.h"
 #include "knn_remove.h"
 #include "knn_filter.h"
+#include "knn_set.h"
 
 #include <algorithm>
 #include <atomic>
@@ -69,6 +70,14 @@ struct vq_index {
     unsigned long long* d_gcounters = nullptr; unsigned long long* h_gcounters = nullptr;
     int32_t* d_gout = nullptr; int64_t gout_cap = 0;                // vq_index_search_grouped: device results [3][nq][k]
     bool gstats_pending = false;
+    // clip-search scratch (knn_set.h): per-group sums [2][G], candidate list / positions [2][G] + count + flag, |q_i| [m],
+    // order keys [G] + the selection's block lists, candidate keys, result staging of the host form
+    double* d_ssum = nullptr; int64_t ssum_cap = 0;
+    int32_t* d_scand = nullptr; int64_t scand_cap = 0;
+    float* d_sqn = nullptr; int64_t sqn_cap = 0;
+    uint64_t* d_sekey = nullptr; int64_t sekey_cap = 0;
+    uint64_t* d_sckeys = nullptr; int64_t sckeys_cap = 0;
+    int32_t* d_sout = nullptr; int64_t sout_cap = 0;
     // fp16 scan scratch
     uint16_t* d_q16 = nullptr; int64_t q16_cap = 0;
     uint32_t* d_keys = nullptr; int64_t keys_cap = 0;
@@ -918,6 +927,156 @@ int host_results(vq_index* x, int64_t bytes) {          // h_res holds at least 
     return 0;
 }
 
+// ---- clip search (knn_set.h) ----
+bool set_fp16_ok(const vq_index* x) { return (x->dim == 256 || x->dim == 512 || x->dim == 768) && x->size >= 1 && x->near_unit; }
+
+// Everything that can refuse a clip search before any work is queued: the mode, stale ranks or labels, the filter's labels, and
+// mode 2 where the fp16 path does not exist.
+int set_precheck(vq_index* x, const char* fn, int mode, const int32_t* sel, int32_t n_sel) {
+    VQ_CHECK(mode >= 0 && mode <= 2, "%s: mode %d unknown", fn, mode);
+    VQ_CHECK(x->rank_n == 0 || x->rank_n == x->size, "%s: the id ranks cover %lld rows, the index holds %lld "
+             "(call vq_index_set_id_ranks again after adding rows, or clear them)", fn, (long long)x->rank_n, (long long)x->size);
+    VQ_CHECK(x->group_n == x->size && (int64_t)x->h_goff.size() == (int64_t)x->n_groups + 1, "%s: the group labels cover %lld rows, "
+             "the index holds %lld (call vq_index_set_groups after adding rows)", fn, (long long)x->group_n, (long long)x->size);
+    for (int32_t i = 0; i < n_sel; ++i)
+        VQ_CHECK(sel[i] >= 0 && sel[i] < x->n_groups, "%s: group %d outside [0, %d)", fn, (int)sel[i], (int)x->n_groups);
+    if (mode != 1) VQ_TRY(refresh_norm_range(x));
+    if (mode == 2) VQ_CHECK(set_fp16_ok(x), "%s: the fp16 path needs dim 256, 512 or 768 and near-unit rows (0.5 <= |row|^2 <= 2; rows "
+                                            "added with normalize=0 are measured); mode 1 takes any call", fn);
+    return 0;
+}
+
+// d_queries [m][dim], g_out / d_out [k], match [k][m] or null: all device memory.  Asynchronous on the index's stream.
+int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, int k, int mode, const int32_t* sel, int32_t n_sel,
+                   int exclude, int32_t* g_out, float* d_out, int32_t* match) {
+    FilterPlan p;
+    VQ_TRY(filter_prepare(x, fn, sel, n_sel, exclude, true, &p));
+    if (!p.all && p.m == 0) {                               // nothing allowed: every slot empty
+        if (match) VQ_HIP(hipMemsetAsync(match, 0xff, (size_t)k * m * 4, x->stream));
+        VQ_TRY(filter_fill_empty(x, 1, k, g_out, nullptr, d_out));
+        x->stats[2] = 1;
+        return 0;
+    }
+    const uint32_t* allow = p.all ? nullptr : p.bits;
+    const int64_t n = x->size, ld = round_up(n, 64);
+    const int G = x->n_groups, nA = p.all ? G : p.nA;
+    const int nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK), lpg = grouped_lpg(x);
+    const bool use_fp16 = mode == 2 || (mode == 0 && set_fp16_ok(x) && x->size >= 16384);     // the plain search's rule
+    VQ_TRY(reserve_buf(x->d_ssum, x->ssum_cap, 2 * (int64_t)G));
+    VQ_TRY(reserve_buf(x->d_scand, x->scand_cap, 2 * (int64_t)G + 2));
+    VQ_TRY(reserve_buf(x->d_sekey, x->sekey_cap, (int64_t)G + (int64_t)nblocks * kl));
+    double* sum16 = x->d_ssum; double* acc = sum16 + G;
+    int32_t* cand = x->d_scand; int32_t* candpos = cand + G; int32_t* cand_n = candpos + G; int32_t* flag = cand_n + 1;
+    uint64_t* ekey = x->d_sekey; uint64_t* partial = ekey + G;
+    const TieOrder tie = x->tie();
+
+    // the exact path; fl = null: the call's answer (distances from the tiled kernel), else the redo gated by the flag
+    auto run_exact = [&](const int32_t* fl) -> int {
+        const bool from_dist = fl == nullptr;
+        int64_t qs = std::max<int64_t>(1, std::min<int64_t>(m, ((int64_t)32 << 20) / G));                 // group minima: <= 256 MiB
+        if (from_dist) qs = std::max<int64_t>(1, std::min<int64_t>(qs, ((int64_t)128 << 20) / ld));         // distances: <= 512 MiB
+        VQ_TRY(reserve_buf(x->d_gkeys, x->gkeys_cap, qs * G));
+        if (from_dist) VQ_TRY(reserve_buf(x->d_dist, x->dist_cap, qs * ld));
+        auto gmin = from_dist ? (allow ? set_group_min_kernel<true, true> : set_group_min_kernel<true, false>)
+                              : (allow ? set_group_min_kernel<false, true> : set_group_min_kernel<false, false>);
+        for (int64_t q0 = 0; q0 < m; q0 += qs) {
+            const int cur = (int)std::min<int64_t>(qs, m - q0);
+            const float* qp = d_queries + q0 * x->dim;
+            if (from_dist) {
+                Prof pr(x, I_EXACT_DIST);
+                hipLaunchKernelGGL(exact_dist_kernel, dim3(cdiv(n, 64), cdiv(cur, 32)), dim3(256), 0, x->stream, x->rows, n, x->dim, qp, cur, x->d_dist, ld);
+            }
+            Prof pr(x, from_dist ? I_SELECT : I_EXACT_DIST);
+            hipLaunchKernelGGL(gmin, dim3(nblocks, cur), dim3(256), 0, x->stream, x->d_dist, ld, x->rows, x->dim, qp, x->d_goff, x->d_grows, G, lpg,
+                               x->d_gkeys, fl, tie, allow);
+            hipLaunchKernelGGL(set_accum_dist_kernel, dim3(nblocks), dim3(256), 0, x->stream, x->d_gkeys, cur, G, q0 == 0 ? 1 : 0, acc, fl);
+        }
+        hipLaunchKernelGGL(set_final_exact_kernel, dim3(nblocks), dim3(256), 0, x->stream, acc, G, m, allow, ekey, fl);
+        VQ_HIP(hipGetLastError());
+        return 0;
+    };
+
+    if (!use_fp16) {
+        VQ_TRY(run_exact(nullptr));
+    } else {
+        const int64_t streams = cdiv(n, SCAN_STREAM_ROWS);
+        int64_t qc = std::max<int64_t>(16, ((int64_t)64 << 20) / G / 16 * 16);          // gbest [qc][G]: <= 256 MiB
+        qc = std::min<int64_t>(qc, round_up(m, 16));
+        if (qc >= SCAN2_QT) qc = qc / SCAN2_QT * SCAN2_QT;                              // whole query tiles of the batch mainloop
+        VQ_TRY(reserve_buf(x->d_q16, x->q16_cap, round_up(qc, SCAN2_QT) * x->dim));
+        VQ_TRY(reserve_buf(x->d_gbest, x->gbest_cap, qc * G));
+        VQ_TRY(reserve_buf(x->d_sqn, x->sqn_cap, m));
+        VQ_TRY(reserve_buf(x->d_sckeys, x->sckeys_cap, std::min<int64_t>(SET_KEY_BUDGET, (int64_t)G * m)));
+        if (!x->d_gcounters) {
+            VQ_HIP(hipMalloc((void**)&x->d_gcounters, 3 * sizeof(unsigned long long)));
+            VQ_HIP(hipHostMalloc((void**)&x->h_gcounters, 3 * sizeof(unsigned long long)));
+        }
+        VQ_TRY(set_dyn_lds((const void*)set_group_max_kernel<false>, G2_LDS_BYTES));
+        VQ_TRY(set_dyn_lds((const void*)set_group_max_kernel<true>, G2_LDS_BYTES));
+        VQ_HIP(hipMemsetAsync(x->d_gcounters, 0, 3 * sizeof(unsigned long long), x->stream));
+        VQ_HIP(hipMemsetAsync(cand_n, 0, 8, x->stream));                                 // candidate count and the call's flag
+        hipLaunchKernelGGL(set_query_norm_kernel, dim3(m), dim3(64), 0, x->stream, d_queries, x->dim, x->d_sqn, flag);
+        const int ranges = cdiv(n, SCAN2_RANGE), range_groups = cdiv(ranges, 4);
+        for (int64_t q0 = 0; q0 < m; q0 += qc) {
+            const int cur = (int)std::min<int64_t>(qc, m - q0);
+            const bool small = cur <= 16;                   // the streaming group-max scan of the grouped search
+            const int64_t q_pad = round_up(cur, small ? 16 : SCAN2_QT);
+            {
+                Prof pr(x, I_TO_F16);
+                const int64_t total4 = q_pad * x->dim / 4;
+                hipLaunchKernelGGL(queries_to_f16_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 2048)), dim3(256), 0, x->stream,
+                                   d_queries + q0 * x->dim, x->d_q16, cur, q_pad, x->dim);
+            }
+            VQ_HIP(hipMemsetAsync(x->d_gbest, 0, (size_t)cur * G * 4, x->stream));
+            {
+                Prof pr(x, I_MFMA_SCAN);
+                if (small) {
+                    auto scan = x->dim == 768 ? scan3_group_max_kernel<24> : x->dim == 512 ? scan3_group_max_kernel<16> : scan3_group_max_kernel<8>;
+                    if (allow) scan = x->dim == 768 ? scan3_group_max_kernel<24, true> : x->dim == 512 ? scan3_group_max_kernel<16, true> : scan3_group_max_kernel<8, true>;
+                    hipLaunchKernelGGL(scan, dim3(cdiv(streams, 4), 1), dim3(256), 0, x->stream, x->d_q16, x->rows16, streams, x->d_group, x->d_sgroup,
+                                       cur, G, x->d_gbest, allow);
+                } else {
+                    const int q_tiles = (int)(q_pad / SCAN2_QT), q_groups = cdiv(q_tiles, 8);
+                    hipLaunchKernelGGL(allow ? set_group_max_kernel<true> : set_group_max_kernel<false>, dim3(range_groups * q_groups * 32), dim3(G2_THREADS),
+                                       G2_LDS_BYTES, x->stream, x->d_q16, x->rows16, x->dim, streams, q_tiles, ranges, range_groups, x->d_group, x->d_sgroup,
+                                       cur, G, x->d_gbest, allow);
+                }
+            }
+            Prof pr(x, I_RESCORE);
+            hipLaunchKernelGGL(set_accum_score_kernel, dim3(nblocks), dim3(256), 0, x->stream, x->d_gbest, cur, G, q0 == 0 ? 1 : 0, sum16);
+        }
+        {
+            Prof pr(x, I_RESCORE);
+            const int nsub = 256 / lpg;
+            hipLaunchKernelGGL(set_threshold_kernel, dim3(1), dim3(256), 0, x->stream, sum16, G, m, std::min(k, nA), nA, allow, x->d_sqn,
+                               scan_eps_unit(x->dim) * x->row_norm_max, x->d_goff, x->d_gbest, cand, candpos, cand_n, ekey, flag, x->d_gcounters);
+            hipLaunchKernelGGL(set_cand_keys_kernel, dim3(std::min(cdiv(G, nsub), 64), m), dim3(256), 0, x->stream, x->rows, x->dim, d_queries, m,
+                               x->d_goff, x->d_grows, cand, cand_n, lpg, x->d_sckeys, flag, tie);
+            hipLaunchKernelGGL(set_cand_sum_kernel, dim3(std::min(nblocks, 256)), dim3(256), 0, x->stream, x->d_sckeys, m, cand, cand_n, ekey, flag);
+        }
+        VQ_HIP(hipGetLastError());
+        VQ_TRY(run_exact(flag));                            // every kernel of it leaves at once unless the flag is 2
+    }
+    {
+        Prof pr(x, I_SELECT);
+        hipLaunchKernelGGL(set_select_block_kernel, dim3(nblocks), dim3(256), 0, x->stream, ekey, G, kl, partial);
+        hipLaunchKernelGGL(set_select_merge_kernel, dim3(1), dim3(256), 0, x->stream, partial, (int64_t)nblocks * kl, k, g_out, d_out,
+                           use_fp16 ? flag : nullptr, use_fp16 ? x->d_gcounters : nullptr);
+        if (match)
+            hipLaunchKernelGGL(set_match_rows_kernel, dim3(k, std::min(cdiv(m, 4), 64)), dim3(256), 0, x->stream, g_out, m, x->rows, x->dim, d_queries,
+                               x->d_goff, x->d_grows, candpos, x->d_sckeys, use_fp16 ? flag : nullptr, match, tie);
+    }
+    VQ_HIP(hipGetLastError());
+    if (use_fp16) {
+        VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+        x->stats_pending = false; x->gstats_pending = true;
+    } else {
+        x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = 1;
+        x->stats_pending = false; x->gstats_pending = false;
+    }
+    return 0;
+}
+
 }  // namespace
 
 // vq_comm.hip: this rank's part of a row-sharded search, on the index's stream (returned so that the exchange is
@@ -973,6 +1132,8 @@ int vq_index_destroy(vq_index* x) {
     if (x->h_q) (void)hipHostFree(x->h_q);
     if (x->h_res) (void)hipHostFree(x->h_res);
     (void)hipFree(x->d_norm_range); (void)hipFree(x->d_rank);
+    (void)hipFree(x->d_ssum); (void)hipFree(x->d_scand); (void)hipFree(x->d_sqn); (void)hipFree(x->d_sekey); (void)hipFree(x->d_sckeys);
+    (void)hipFree(x->d_sout);
     (void)hipFree(x->d_group); (void)hipFree(x->d_gbest); (void)hipFree(x->d_gcand); (void)hipFree(x->d_gkeys); (void)hipFree(x->d_gpart);
     (void)hipFree(x->d_gcounters); (void)hipFree(x->d_gout); (void)hipFree(x->d_flt); (void)hipFree(x->d_fcand); (void)hipFree(x->d_flist);
     for (int i = 0; i < vq_index::FLT_STAGE_SLOTS; ++i) {
@@ -1480,6 +1641,49 @@ int vq_index_search_grouped_filtered(vq_index* x, const float* queries, int nq, 
     std::memcpy(groups_out, x->h_res, (size_t)count * 4);
     std::memcpy(rows, x->h_res + count * 4, (size_t)count * 4);
     std::memcpy(dist, x->h_res + count * 8, (size_t)count * 4);
+    return 0;
+}
+
+int vq_index_search_set_device(vq_index* x, const void* d_queries, int m, int k, int mode, const int32_t* groups, int32_t n_sel,
+                               int exclude, void* d_groups_out, void* d_dist_out, void* d_match_rows) {
+    static const char* fn = "vq_index_search_set_device";
+    VQ_TRY(require_init());
+    VQ_CHECK(x && m >= 1 && m <= SET_MAX_M && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
+             d_queries && d_groups_out && d_dist_out, "%s: bad argument (1 <= m <= %d, 1 <= k <= 1024)", fn, SET_MAX_M);
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) {
+        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(k, 256)), dim3(256), 0, x->stream, (int32_t*)d_groups_out, (float*)d_dist_out, (int64_t)k);
+        if (d_match_rows) VQ_HIP(hipMemsetAsync(d_match_rows, 0xff, (size_t)k * m * 4, x->stream));
+        VQ_HIP(hipGetLastError());
+        return 0;
+    }
+    VQ_TRY(set_precheck(x, fn, mode, groups, n_sel));
+    return search_set_run(x, fn, (const float*)d_queries, m, k, mode, groups, n_sel, exclude, (int32_t*)d_groups_out, (float*)d_dist_out,
+                          (int32_t*)d_match_rows);
+}
+
+int vq_index_search_set(vq_index* x, const float* queries, int m, int k, int mode, const int32_t* groups, int32_t n_sel, int exclude,
+                        int32_t* groups_out, float* dist_out, int32_t* match_rows) {
+    static const char* fn = "vq_index_search_set";
+    VQ_TRY(require_init());
+    VQ_CHECK(x && m >= 1 && m <= SET_MAX_M && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
+             queries && groups_out && dist_out, "%s: bad argument (1 <= m <= %d, 1 <= k <= 1024)", fn, SET_MAX_M);
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t nm = match_rows ? (int64_t)k * m : 0;
+    if (x->size == 0) {
+        for (int j = 0; j < k; ++j) { groups_out[j] = -1; dist_out[j] = __builtin_inff(); }
+        for (int64_t i = 0; i < nm; ++i) match_rows[i] = -1;
+        return 0;
+    }
+    VQ_TRY(set_precheck(x, fn, mode, groups, n_sel));
+    VQ_TRY(reserve_buf(x->d_sout, x->sout_cap, 2 * (int64_t)k + nm));
+    int32_t* d_g = x->d_sout; float* d_d = (float*)(d_g + k); int32_t* d_m = match_rows ? d_g + 2 * k : nullptr;
+    VQ_TRY(stage_queries(x, queries, m));
+    VQ_TRY(search_set_run(x, fn, x->d_q, m, k, mode, groups, n_sel, exclude, d_g, d_d, d_m));
+    VQ_HIP(hipMemcpyAsync(groups_out, d_g, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(dist_out, d_d, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
+    if (match_rows) VQ_HIP(hipMemcpyAsync(match_rows, d_m, (size_t)nm * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
     return 0;
 }
 

@@ -650,6 +650,91 @@ class HNSWIndex:
         with self.lock:
             return self._filtered_many(queries, k, flt, group_of)
 
+    # -- clip query: the k groups (videos) most similar to a SET of frames -------------------------
+    SET_MAX_QUERIES = 4096        # vq_index_search_set: query frames per call
+
+    def _search_set_unit(self, unit: np.ndarray, k: int, flt, group_of, matches: bool) -> List[Dict]:
+        """unit: [m][dim] fp32 query frames, used as given.  flt: None or (group keys, exclude?)."""
+        m = unit.shape[0]
+        if m > self.SET_MAX_QUERIES:
+            raise ValueError(f"a clip query holds at most {self.SET_MAX_QUERIES} frames, got {m}")
+        if unit.shape[1] != self.dimension:
+            raise ValueError(f"query dimension {unit.shape[1]} != index dimension {self.dimension}")
+        if k <= 0 or not self._ids:
+            return []
+        keys_f, excl = flt if flt is not None else ([], True)
+        if not excl and not keys_f:
+            return []                                    # nothing allowed: no device call
+        if not self._identity:
+            self._sync_tie_order()
+        gl = self._sync_groups(group_of)
+        labels = self._filter_labels(gl, keys_f)
+        if not excl and len(labels) == 0:
+            return []
+        kk = min(int(k), len(gl.keys), 1024)
+        groups = np.empty(kk, dtype=np.int32)
+        dist = np.empty(kk, dtype=np.float32)
+        rows = np.empty((kk, m), dtype=np.int32) if matches else None
+        _lib.check(_lib.load().vq_index_search_set(
+            self._h, _lib.fptr(unit), m, kk, int(self.search_mode), labels.ctypes.data_as(POINTER(c_int32)), len(labels), int(excl),
+            groups.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist), rows.ctypes.data_as(POINTER(c_int32)) if matches else None))
+        keys, names, identity = gl.keys, self._ids, self._identity
+        out = []
+        for j, (g, d) in enumerate(zip(groups.tolist(), dist)):
+            if g < 0:
+                break
+            item = {"group": keys[g], "distance": d, "score": np.float32(1.0) - d}
+            if matches:
+                item["matches"] = [int(r) if identity else names[r] for r in rows[j].tolist()]
+            out.append(item)
+        return out
+
+    def search_set(self, queries: Sequence[np.ndarray], k: int = 5, *, within: Optional[Iterable[Hashable]] = None,
+                   exclude: Optional[Iterable[Hashable]] = None, group_of: Optional[Callable[[Hashable], Hashable]] = None,
+                   matches: bool = False) -> List[Dict]:
+        """The k GROUPS (videos) most similar to a set of query frames (a clip, several example frames, several prompts):
+        ``[{'group', 'distance', 'score'[, 'matches']}]``.  Every query frame (normalised as ``search`` does) takes its
+        smallest distance to a row of the group; ``distance`` is the mean of those over the frames (added in fp64 in the
+        frames' order, rounded once to float32), ``score = float32(1) - distance``; groups come back by (distance, order in
+        which the groups first appeared in the index).  One-directional: the video's other frames cost nothing, so a short
+        clip finds the long video it was cut from.  ``matches=True`` adds, per result, the node id of the matching row for
+        every query frame (ties inside a group by id, as ``search``).  ``within`` / ``exclude`` / ``group_of`` as
+        ``search_grouped``; giving neither searches every group.  At most 4,096 frames and 1,024 results."""
+        flt = self._filter_arg(within, exclude) if within is not None or exclude is not None else None
+        if len(queries) == 0:
+            raise ValueError("search_set needs at least one query frame")
+        if self.entry_point is None or self.element_count == 0 or k <= 0:
+            return []
+        with self.lock:
+            unit = np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32)
+            return self._search_set_unit(unit, k, flt, group_of, matches)
+
+    def similar_groups(self, group: Hashable, k: int = 5, *, within: Optional[Iterable[Hashable]] = None,
+                       group_of: Optional[Callable[[Hashable], Hashable]] = None, matches: bool = False) -> List[Dict]:
+        """"More like this video": ``search_set`` with the stored rows of ``group`` (in row order) as the query set and
+        ``group`` itself excluded; ``within`` restricts the answer to those groups.  ``KeyError`` for a group the index does
+        not hold, ``ValueError`` for a group of more than 4,096 rows."""
+        if within is not None:
+            within = self._filter_arg(within, None)[0]
+        with self.lock:
+            gl = self._group_labels(group_of)
+            gl.extend()
+            g = gl.index.get(group)
+            if g is None:
+                raise KeyError(group)
+            rn = np.flatnonzero(gl.labels == g).astype(np.int64)
+            if len(rn) > self.SET_MAX_QUERIES:
+                raise ValueError(f"group {group!r} holds {len(rn)} rows; a clip query holds at most {self.SET_MAX_QUERIES}")
+            if k <= 0:
+                return []
+            # one include list: `within` without the group itself; without `within`, one exclude list
+            flt = ([key for key in within if key != group], False) if within is not None else ([group], True)
+            if not flt[1] and not flt[0]:
+                return []
+            unit = np.empty((len(rn), self.dimension), dtype=np.float32)
+            _lib.check(_lib.load().vq_index_read_rows(self._h, rn.ctypes.data_as(POINTER(c_int64)), len(rn), _lib.fptr(unit)))
+            return self._search_set_unit(unit, k, flt, group_of, matches)
+
     def synchronize(self) -> None:
         _lib.check(_lib.load().vq_index_synchronize(self._h))
 

@@ -113,6 +113,25 @@ class SimpleVideoIndex:
             results.append(md)
         return results
 
+    def _video_of_row_id(self, node_id: int) -> str:
+        return self.metadata[-node_id]["video_name"]          # device ids are -position (see _sync_device)
+
+    def similar_videos(self, video_name: str, k: int = 5) -> List[Dict]:
+        """The k indexed videos most similar to ``video_name``, itself excluded: ``[{'video_name', 'score'}]``, best first.
+        Every stored frame of the video takes its best match in the other video; ``score`` is the mean of those cosine
+        scores (``HNSWIndex.similar_groups``: exact, a re-encode or a cut scores close to 1 where the reference's file-hash
+        comparison, video_search_overhaul.py:143-147, sees two different files).  ``KeyError`` for an unknown video."""
+        if not self.embeddings:
+            raise KeyError(video_name)
+        self._sync_device()
+        dev = self._dev
+        dev.search_mode = MODE_AUTO
+        fn = getattr(self, "_group_fn", None)
+        if fn is None:
+            fn = self._group_fn = self._video_of_row_id      # one callable for the index's life: the labels are kept
+        res = dev.similar_groups(video_name, k, group_of=fn)
+        return [{"video_name": r["group"], "score": float(r["score"])} for r in res]
+
     def save_to_disk(self, cache_path: Path):
         try:
             with open(cache_path, "wb") as f:
