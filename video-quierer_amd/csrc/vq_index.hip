@@ -14,11 +14,10 @@
 #include "knn_set.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <tuple>
+#include <utility>
 #include <vector>
 
 namespace vq {
@@ -30,74 +29,142 @@ static const char* kIdxClassNames[VQ_IDX_NCLASS] = {
 
 using namespace vq;
 
+namespace {
+
+// Device memory a handle owns: freed with the handle.  reserve() keeps no contents (free, then allocate); storage that grows by
+// other rules (the rows: with a copy; ranks and labels: behind a stream synchronise, under their own message) is allocated by the
+// code that grows it, straight into p.
+template <class T> struct DevBuf {
+    T* p = nullptr;
+    int64_t cap = 0;               // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    operator T*() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
+    int reserve(int64_t need) {
+        if (need <= cap) return 0;
+        release();
+        hipError_t e = hipMalloc((void**)&p, (size_t)need * sizeof(T));
+        if (e != hipSuccess) return fail(VQ_ERR_OOM, "index: scratch hipMalloc(%lld) failed: %s", (long long)(need * sizeof(T)), hipGetErrorString(e));
+        cap = need;
+        return 0;
+    }
+};
+
+// Pinned host memory a handle owns; a mapped one also has a device address (dev) that kernels write through.  Whoever replaces a
+// buffer the device may still be using waits for the stream first (host_results).
+template <class T> struct PinnedBuf {
+    T* p = nullptr;
+    T* dev = nullptr;              // mapped only
+    int64_t cap = 0;               // elements
+    const bool mapped;
+    explicit PinnedBuf(bool map = false) : mapped(map) {}
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { release(); }
+    operator T*() const { return p; }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; dev = nullptr; cap = 0; }
+    int reserve(int64_t need, int64_t at_least = 0) {          // no contents kept; a new buffer holds max(need, at_least)
+        if (need <= cap) return 0;
+        release();
+        const int64_t ncap = std::max(need, at_least);
+        VQ_HIP(hipHostMalloc((void**)&p, (size_t)ncap * sizeof(T), mapped ? hipHostMallocMapped : hipHostMallocDefault));
+        if (mapped) VQ_HIP(hipHostGetDevicePointer((void**)&dev, p, 0));
+        cap = ncap;
+        return 0;
+    }
+};
+
+// One slot of the filtered search's staging ring: pinned memory and the event of the copy that last read it.
+struct StageSlot {
+    PinnedBuf<int32_t> h;
+    hipEvent_t ev = nullptr;
+    ~StageSlot() { if (ev) (void)hipEventDestroy(ev); }
+};
+
+// Where the last search's statistics are (vq_index_last_search_stats).
+enum StatsAt {
+    STATS_HOST,        // in vq_index::stats
+    STATS_COUNTERS,    // on their way to h_counters behind the search
+    STATS_GCOUNTERS,   // on their way to h_gcounters behind the search
+    STATS_DEFERRED,    // a host-synchronous fp16 search: its kernels write h_counters; the caller (vq_index_search) reads them after its
+                       // one wait and launches the fallback itself when a query was flagged
+};
+
+}  // namespace
+
 struct vq_index {
     int dim = 0;
-    int64_t size = 0, cap = 0;
-    float* rows = nullptr;        // fp32 master [cap][dim] (normalised rows, what the reference keeps in .data)
-    uint16_t* rows16 = nullptr;   // fp16 scan copy [cap][dim]
+    int64_t size = 0, cap = 0;     // rows held / allocated
+    DevBuf<float> rows;            // fp32 master [cap][dim] (normalised rows, what the reference keeps in .data); `cap` above counts its rows
+    DevBuf<uint16_t> rows16;       // fp16 scan copy [cap][dim]
     hipStream_t stream = nullptr, own_stream = nullptr;
     std::mutex mu;
+    std::vector<std::pair<const void*, size_t>> dyn_lds;    // kernels whose dynamic-LDS limit this handle has raised (set_dyn_lds)
     // scratch
-    float* d_q = nullptr; int64_t q_cap = 0;          // queries [q_cap][dim]
-    float* d_dist = nullptr; int64_t dist_cap = 0;    // exact distances (elements)
-    uint64_t* d_partial = nullptr; int64_t partial_cap = 0;   // per-chunk top-k keys
-    int32_t* d_ids = nullptr; float* d_out = nullptr; int64_t out_cap = 0;
-    float* d_upd = nullptr; int64_t upd_cap = 0;      // vq_index_update_rows: staged rows [n][dim] + their row numbers behind them;
-                                                      // vq_index_remove_rows: one chunk of moved rows
-    int32_t* d_rmw = nullptr; int64_t rmw_cap = 0;    // vq_index_remove_rows: row maps, prefix sums, rebuilt ranks / labels (words)
-    // (distance, id) tie order (vq_index_set_id_ranks): rank of each row's id in the caller's id order + the inverse; rank_n = the
-    // number of rows they cover (0 = none set: ties come back in row order).  A search with rank_n != size is refused.
-    int32_t* d_rank = nullptr; int32_t* d_rank_inv = nullptr; int64_t rank_cap = 0, rank_n = 0;
+    DevBuf<float> d_q;             // queries [nq][dim]
+    DevBuf<float> d_dist;          // exact distances
+    DevBuf<uint64_t> d_partial;    // per-chunk top-k keys
+    DevBuf<int32_t> d_ids;         // host forms: device results
+    DevBuf<float> d_out;
+    DevBuf<float> d_upd;           // vq_index_update_rows: staged rows [n][dim] + their row numbers behind them;
+                                   // vq_index_remove_rows: one chunk of moved rows
+    DevBuf<int32_t> d_rmw;         // vq_index_remove_rows: row maps, prefix sums, rebuilt ranks / labels (words)
+    // (distance, id) tie order (vq_index_set_id_ranks): rank of each row's id in the caller's id order + the inverse behind it in one
+    // allocation; rank_n = the number of rows they cover (0 = none set: ties come back in row order).  A search with
+    // rank_n != size is refused.
+    DevBuf<int32_t> d_rank; int32_t* d_rank_inv = nullptr; int64_t rank_n = 0;      // d_rank.cap = 2 x the rows it holds (rank | inverse)
     TieOrder tie() const { return rank_n ? TieOrder{d_rank, d_rank_inv} : TieOrder{nullptr, nullptr}; }
-    // group labels (vq_index_set_groups): label per row, padded with -1 to whole 128-row streams; the by-group CSR row list
-    // (goff [n_groups + 1], grows [n]); per stream the label its 128 rows share, or -1.  group_n = the rows they cover (0 = none
-    // set); a grouped search with group_n != size is refused.
-    int32_t* d_group = nullptr; int32_t* d_goff = nullptr; int32_t* d_grows = nullptr; int32_t* d_sgroup = nullptr;
-    int64_t group_n = 0, group_cap = 0; int32_t n_groups = 0;
+    // group labels (vq_index_set_groups), one allocation: label per row, padded with -1 to whole 128-row streams; the by-group CSR
+    // row list (goff [n_groups + 1], grows [n]); per stream the label its 128 rows share, or -1.  group_n = the rows they cover
+    // (0 = none set); a grouped search with group_n != size is refused.
+    DevBuf<int32_t> d_group; int32_t* d_goff = nullptr; int32_t* d_grows = nullptr; int32_t* d_sgroup = nullptr;
+    int64_t group_n = 0; int32_t n_groups = 0;
     std::vector<int32_t> h_goff;    // host mirror of goff (kept by set_groups / remove_rows): a filtered search sizes itself from it
     // filtered-search scratch (knn_filter.h): allowed groups, their row offsets, the row list and its tie words or the allowed
     // groups' bitmap; the filter list goes up from a ring of pinned staging slots, each reused once its event (the copy) is done
-    int32_t* d_flt = nullptr; int64_t flt_cap = 0;
+    DevBuf<int32_t> d_flt;
     static constexpr int FLT_STAGE_SLOTS = 4;
-    int32_t* h_flt[FLT_STAGE_SLOTS] = {}; int64_t hflt_cap[FLT_STAGE_SLOTS] = {}; hipEvent_t flt_ev[FLT_STAGE_SLOTS] = {}; int flt_slot = 0;
-    int32_t* d_fcand = nullptr; int64_t fcand_cap = 0;             // masked fp16 path: candidate streams [nq][FLT_CAND] | n [nq] | listed [nq] | thr [nq]
-    uint64_t* d_flist = nullptr; int64_t flist_cap = 0;            // ... re-scored keys [nq][FLT_LIST]
+    StageSlot flt_stage[FLT_STAGE_SLOTS]; int flt_slot = 0;
+    DevBuf<int32_t> d_fcand;       // masked fp16 path: candidate streams [nq][FLT_CAND] | n [nq] | listed [nq] | thr [nq]
+    DevBuf<uint64_t> d_flist;      // ... re-scored keys [nq][FLT_LIST]
     // grouped-search scratch (knn_grouped.h) and its outcome counters (pinned copy read by last_search_stats)
-    uint32_t* d_gbest = nullptr; int64_t gbest_cap = 0;
-    int32_t* d_gcand = nullptr; int64_t gcand_cap = 0;              // cand [qc][CAND] | pref [qc][CAND + 1] | n [qc] | flags [qc] | thr [qc]
-    uint64_t* d_gkeys = nullptr; int64_t gkeys_cap = 0;             // best [qc][CAND] (fp16 path), per-block lists (exact path / redo)
-    uint64_t* d_gpart = nullptr; int64_t gpart_cap = 0;
-    unsigned long long* d_gcounters = nullptr; unsigned long long* h_gcounters = nullptr;
-    int32_t* d_gout = nullptr; int64_t gout_cap = 0;                // vq_index_search_grouped: device results [3][nq][k]
-    bool gstats_pending = false;
+    DevBuf<uint32_t> d_gbest;
+    DevBuf<int32_t> d_gcand;       // cand [qc][CAND] | pref [qc][CAND + 1] | n [qc] | flags [qc] | thr [qc]
+    DevBuf<uint64_t> d_gkeys;      // best [qc][CAND] (fp16 path), per-block lists (exact path / redo)
+    DevBuf<uint64_t> d_gpart;
+    DevBuf<unsigned long long> d_gcounters; PinnedBuf<unsigned long long> h_gcounters;
+    DevBuf<int32_t> d_gout;        // vq_index_search_grouped: device results [3][nq][k]
     // clip-search scratch (knn_set.h): per-group sums [2][G], candidate list / positions [2][G] + count + flag, |q_i| [m],
     // order keys [G] + the selection's block lists, candidate keys, result staging of the host form
-    double* d_ssum = nullptr; int64_t ssum_cap = 0;
-    int32_t* d_scand = nullptr; int64_t scand_cap = 0;
-    float* d_sqn = nullptr; int64_t sqn_cap = 0;
-    uint64_t* d_sekey = nullptr; int64_t sekey_cap = 0;
-    uint64_t* d_sckeys = nullptr; int64_t sckeys_cap = 0;
-    int32_t* d_sout = nullptr; int64_t sout_cap = 0;
+    DevBuf<double> d_ssum;
+    DevBuf<int32_t> d_scand;
+    DevBuf<float> d_sqn;
+    DevBuf<uint64_t> d_sekey;
+    DevBuf<uint64_t> d_sckeys;
+    DevBuf<int32_t> d_sout;
     // fp16 scan scratch
-    uint16_t* d_q16 = nullptr; int64_t q16_cap = 0;
-    uint32_t* d_keys = nullptr; int64_t keys_cap = 0;
-    int32_t* d_flags = nullptr; int64_t flags_cap = 0;
+    DevBuf<uint16_t> d_q16;
+    DevBuf<uint32_t> d_keys;
+    DevBuf<int32_t> d_flags;
     // device-side fallback (knn_fallback.h): flagged query numbers, counters {flagged, proven, rescanned, fallback},
-    // per-split top-k lists; the counters travel to pinned memory behind the search, read by last_search_stats
-    int32_t* d_slots = nullptr; int64_t slots_cap = 0;
-    int32_t* d_counters = nullptr; int32_t* h_counters = nullptr;
-    uint64_t* d_fb_partial = nullptr; int64_t fbp_cap = 0;
-    int32_t* d_counters_host = nullptr;   // the device's address of h_counters (pinned + mapped): a host-synchronous search lets its kernels write the counters there
-    // vq_index_search (host arrays in and out, the reference caller's call): pinned staging for the queries, and a pinned + MAPPED
-    // result buffer the kernels write straight into — no device-to-host copy command on the one-query path
-    float* h_q = nullptr; int64_t hq_cap = 0;
-    char* h_res = nullptr; char* d_res = nullptr; int64_t hres_cap = 0;
-    bool fb_deferred = false;      // a host-synchronous fp16 search left its fallback launches to the host (after it has read the flagged count)
-    bool stats_pending = false;    // the last search's counters are still on their way to h_counters
+    // per-split top-k lists; the counters travel to pinned memory behind the search, read by last_search_stats.  h_counters is
+    // mapped: a host-synchronous search lets its kernels write the counters there (h_counters.dev)
+    DevBuf<int32_t> d_slots;
+    DevBuf<int32_t> d_counters; PinnedBuf<int32_t> h_counters{true};
+    DevBuf<uint64_t> d_fb_partial;
+    // host forms: pinned staging for the queries, and a pinned + MAPPED result buffer.  vq_index_search (host arrays in and out, the
+    // reference caller's call) has its kernels write straight into it — no device-to-host copy command on the one-query path
+    PinnedBuf<float> h_q;
+    PinnedBuf<char> h_res{true};
+    StatsAt stats_at = STATS_HOST;
     int64_t stats[3] = {0, 0, 0};
     // |row|^2 range of rows added without normalisation (device: min/max fp32 bits); read back lazily by the first
     // search after such an add.  near_unit = the fp16 scan's error bound applies (knn_scan_f16.h scan_eps_unit).
-    uint32_t* d_norm_range = nullptr;
+    DevBuf<uint32_t> d_norm_range;
     bool norm_dirty = false, near_unit = true;
     float row_norm_max = 1.0f;
     int scan_version = 5;          // $VQ_AMD_SCAN: 5 = deep-prefetch mainloop with the fold spread behind the MFMA clusters (needs dim % 128 == 0), 4 = the same with
@@ -127,29 +194,45 @@ int reserve_rows(vq_index* x, int64_t need) {
     if (need <= x->cap) return 0;
     int64_t ncap = std::max<int64_t>(need, std::max<int64_t>(1024, x->cap * 2));
     ncap = round_up(ncap, SCAN2_RANGE);       // the fp16 scans walk whole 1024/2048-row ranges
-    float* nr = nullptr; uint16_t* nh = nullptr;
-    hipError_t e = hipMalloc((void**)&nr, (size_t)ncap * x->dim * 4);
+    DevBuf<float> nr; DevBuf<uint16_t> nh;                    // freed again if a step below fails
+    hipError_t e = hipMalloc((void**)&nr.p, (size_t)ncap * x->dim * 4);
     if (e != hipSuccess) return fail(VQ_ERR_OOM, "index: hipMalloc of %lld rows failed: %s", (long long)ncap, hipGetErrorString(e));
-    e = hipMalloc((void**)&nh, (size_t)ncap * x->dim * 2);
-    if (e != hipSuccess) { (void)hipFree(nr); return fail(VQ_ERR_OOM, "index: hipMalloc (fp16 copy) failed: %s", hipGetErrorString(e)); }
+    e = hipMalloc((void**)&nh.p, (size_t)ncap * x->dim * 2);
+    if (e != hipSuccess) return fail(VQ_ERR_OOM, "index: hipMalloc (fp16 copy) failed: %s", hipGetErrorString(e));
     VQ_HIP(hipMemsetAsync(nh, 0, (size_t)ncap * x->dim * 2, x->stream));   // pad rows of the scan copy stay finite
     if (x->size > 0) {
         VQ_HIP(hipMemcpyAsync(nr, x->rows, (size_t)x->size * x->dim * 4, hipMemcpyDeviceToDevice, x->stream));
         VQ_HIP(hipMemcpyAsync(nh, x->rows16, (size_t)x->size * x->dim * 2, hipMemcpyDeviceToDevice, x->stream));
     }
     VQ_HIP(hipStreamSynchronize(x->stream));
-    (void)hipFree(x->rows); (void)hipFree(x->rows16);
-    x->rows = nr; x->rows16 = nh; x->cap = ncap;
+    x->rows.swap(nr); x->rows16.swap(nh);                     // the old storage goes with nr / nh
+    x->cap = ncap;
     return 0;
 }
 
-template <class T> int reserve_buf(T*& p, int64_t& cap, int64_t need) {
-    if (need <= cap) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    hipError_t e = hipMalloc((void**)&p, (size_t)need * sizeof(T));
-    if (e != hipSuccess) return fail(VQ_ERR_OOM, "index: scratch hipMalloc(%lld) failed: %s", (long long)(need * sizeof(T)), hipGetErrorString(e));
-    cap = need;
+// at most 2048 workgroups of 256 threads for `count` items (grid-stride kernels)
+int grid_for(int64_t count) { return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(count, 256), 2048)); }
+
+// An asynchronous copy reads a buffer of the enclosing frame (or the caller's): whichever way that function is left (every VQ_HIP /
+// VQ_TRY returns early on error), the stream is drained before the buffer dies (declare the guard after it: destroyed first).
+struct StreamDrain { hipStream_t s; ~StreamDrain() { (void)hipStreamSynchronize(s); } };
+
+// The |row|^2 range starts at [1, 1].  Blocks on the stream (`init` is on this stack frame).
+int init_norm_range(vq_index* x) {
+    const uint32_t init[2] = {0x3f800000u, 0x3f800000u};            // 1.0f, 1.0f
+    VQ_HIP(hipMemcpyAsync(x->d_norm_range, init, 8, hipMemcpyHostToDevice, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// Rows the caller says are unit (HNSWIndex.load, SimpleVideoIndex) are measured instead of trusted.  The range only widens.
+int measure_norm_range(vq_index* x, const float* d_rows, int64_t n) {
+    if (!x->d_norm_range) {
+        VQ_TRY(x->d_norm_range.reserve(2));
+        VQ_TRY(init_norm_range(x));
+    }
+    hipLaunchKernelGGL(row_norm_range_kernel, dim3(cdiv(n, 4)), dim3(256), 0, x->stream, d_rows, n, x->dim, x->d_norm_range);
+    x->norm_dirty = true;
     return 0;
 }
 
@@ -158,25 +241,13 @@ int finish_add(vq_index* x, int64_t n, int normalize) {
     float* dst = x->rows + x->size * x->dim;
     {
         Prof p(x, I_NORMALIZE);
-        if (normalize) {
-            hipLaunchKernelGGL(normalize_rows_kernel, dim3(cdiv(n, NORM_ROWS)), dim3(NORM_ROWS), 0, x->stream, dst, n, x->dim);
-        } else {          // the caller says the rows are unit (HNSWIndex.load, SimpleVideoIndex): measure instead of trusting
-            if (!x->d_norm_range) {
-                VQ_HIP(hipMalloc((void**)&x->d_norm_range, 8));
-                const uint32_t init[2] = {0x3f800000u, 0x3f800000u};            // 1.0f, 1.0f
-                VQ_HIP(hipMemcpyAsync(x->d_norm_range, init, 8, hipMemcpyHostToDevice, x->stream));
-                VQ_HIP(hipStreamSynchronize(x->stream));                         // `init` is on this stack frame
-            }
-            hipLaunchKernelGGL(row_norm_range_kernel, dim3(cdiv(n, 4)), dim3(256), 0, x->stream, dst, n, x->dim, x->d_norm_range);
-            x->norm_dirty = true;
-        }
+        if (normalize) hipLaunchKernelGGL(normalize_rows_kernel, dim3(cdiv(n, NORM_ROWS)), dim3(NORM_ROWS), 0, x->stream, dst, n, x->dim);
+        else VQ_TRY(measure_norm_range(x, dst, n));
     }
     {
         Prof p(x, I_TO_F16);
         const int64_t count4 = n * x->dim / 4;
-        const int blocks = (int)std::min<int64_t>((count4 + 255) / 256, 256 * 8);
-        hipLaunchKernelGGL(rows_to_f16_kernel, dim3(blocks), dim3(256), 0, x->stream, dst,
-                           x->rows16 + x->size * x->dim, count4);
+        hipLaunchKernelGGL(rows_to_f16_kernel, dim3(grid_for(count4)), dim3(256), 0, x->stream, dst, x->rows16 + x->size * x->dim, count4);
     }
     VQ_HIP(hipGetLastError());
     x->size += n;
@@ -197,63 +268,161 @@ int refresh_norm_range(vq_index* x) {
     return 0;
 }
 
-// Exact scan: fp64-chain distances for a slice of queries into d_dist, then selection.
-int search_exact(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_ids, float* d_dist_out) {
+// ---- what the search families share ----
+
+// A kernel's dynamic-LDS limit (MaxDynamicSharedMemorySize) is set for the CURRENT device only.  A handle's memory and stream are one device's,
+// so what has been set is remembered per handle (under its lock): a search pays a look at a short list, no lock and no call.
+int set_dyn_lds(vq_index* x, const void* fn, size_t bytes) {
+    for (const auto& d : x->dyn_lds)
+        if (d.first == fn && d.second >= bytes) return 0;
+    VQ_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    x->dyn_lds.emplace_back(fn, bytes);
+    return 0;
+}
+
+// The one writer of where the last search's statistics are.  STATS_HOST carries the values {verified, rescanned, exact}: an exact
+// path passes (0, 0, queries), a reader of arrived counters what it read.
+void set_stats(vq_index* x, StatsAt at, int64_t verified = 0, int64_t rescanned = 0, int64_t exact = 0) {
+    x->stats_at = at;
+    if (at == STATS_HOST) { x->stats[0] = verified; x->stats[1] = rescanned; x->stats[2] = exact; }
+}
+void stats_from_counters(vq_index* x) {          // h_counters has arrived (the caller has waited for the stream)
+    set_stats(x, STATS_HOST, x->h_counters[1], x->h_counters[2], x->h_counters[3]);
+}
+
+// Refusals.  fn: the entry point's name.
+int check_mode(const char* fn, int mode) {
+    VQ_CHECK(mode >= 0 && mode <= 2, "%s: mode %d unknown", fn, mode);
+    return 0;
+}
+int check_ranks(const vq_index* x, const char* fn) {
+    VQ_CHECK(x->rank_n == 0 || x->rank_n == x->size, "%s: the id ranks cover %lld rows, the index holds %lld "
+             "(call vq_index_set_id_ranks again after adding rows, or clear them)", fn, (long long)x->rank_n, (long long)x->size);
+    return 0;
+}
+// (labels that cover a non-empty index always have their host mirror: set_groups and remove_rows write both)
+int check_labels(const vq_index* x, const char* fn) {
+    VQ_CHECK(x->group_n == x->size && (int64_t)x->h_goff.size() == (int64_t)x->n_groups + 1, "%s: the group labels cover %lld rows, "
+             "the index holds %lld (call vq_index_set_groups after adding rows)", fn, (long long)x->group_n, (long long)x->size);
+    return 0;
+}
+// mode 0 (auto): the fp16 scans pay once the matrix is large enough to amortise their fixed costs
+constexpr int64_t FP16_AUTO_MIN_ROWS = 16384;
+
+void fill_no_result(vq_index* x, int32_t* ids, float* dist, int64_t count) {
+    hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, ids, dist, count);
+}
+
+// a device form's answer with no result in any slot (b: the grouped forms' second id array, or null)
+int fill_empty(vq_index* x, int64_t count, int32_t* a, int32_t* b, float* dist) {
+    fill_no_result(x, a, dist, count);
+    if (b) fill_no_result(x, b, dist, count);
+    VQ_HIP(hipGetLastError());
+    return 0;
+}
+
+// queries [cur][dim] -> d_q16 [q_pad][dim], zero rows behind cur
+void queries_to_f16(vq_index* x, const float* d_queries, int cur, int64_t q_pad) {
+    Prof p(x, I_TO_F16);
+    hipLaunchKernelGGL(queries_to_f16_kernel, dim3(grid_for(q_pad * x->dim / 4)), dim3(256), 0, x->stream, d_queries, x->d_q16, cur, q_pad, x->dim);
+}
+
+// fp64-chain distances of `cur` queries to every row -> d_dist [cur][ld].  small: the one-launch kernel that keeps up to EDS_MAX_Q
+// queries in LDS (knn_kernels.h); it exists when exact_small_fits(), and each caller has its own rule for taking it.
+bool exact_small_fits(const vq_index* x) { return (size_t)EDS_MAX_Q * x->dim * 8 <= (size_t)96 << 10; }
+int exact_dist(vq_index* x, bool small, const float* qp, int cur, int64_t ld) {
     const int64_t n = x->size;
-    const int64_t ld = round_up(n, 64);
+    const size_t qbytes = (size_t)EDS_MAX_Q * x->dim * 8;
+    if (small) VQ_TRY(set_dyn_lds(x, (const void*)exact_dist_small_kernel, qbytes));
+    Prof p(x, I_EXACT_DIST);
+    if (small)
+        hipLaunchKernelGGL(exact_dist_small_kernel, dim3(cdiv(n, 64)), dim3(256), qbytes, x->stream, x->rows, n, x->dim, qp, cur, x->d_dist, ld);
+    else
+        hipLaunchKernelGGL(exact_dist_kernel, dim3(cdiv(n, 64), cdiv(cur, 32)), dim3(256), 0, x->stream, x->rows, n, x->dim, qp, cur, x->d_dist, ld);
+    return 0;
+}
+
+// The exact paths' selection: per slice of queries, `dist(q0, cur, ld)` queues the distances to m columns into d_dist [cur][ld],
+// then the k best columns of each query under `tie` -> ids / out.  one_wg: one workgroup per query (select_small_kernel, at most
+// SEL_SMALL_MAX_N columns) instead of chunks + merge.
+template <class Dist>
+int exact_topk(vq_index* x, int64_t m, int nq, int k, bool one_wg, const TieOrder tie, int32_t* ids, float* out, Dist dist) {
+    const int64_t ld = round_up(m, 64);
     const int64_t budget = (int64_t)128 << 20;                 // 512 MiB of fp32 distances per slice
-    int qslice = (int)std::max<int64_t>(32, std::min<int64_t>(nq, budget / ld) / 32 * 32);
-    VQ_TRY(reserve_buf(x->d_dist, x->dist_cap, (int64_t)std::min(qslice, (int)round_up(nq, 32)) * ld));
-    if (nq <= EDS_MAX_Q && n <= SEL_SMALL_MAX_N && x->dim % 4 == 0 && (size_t)EDS_MAX_Q * x->dim * 8 <= (size_t)96 << 10) {
-        // a handful of queries over a small index — the reference caller's one search at a time over a few thousand frames:
-        // two short launches (knn_kernels.h)
-        const size_t qbytes = (size_t)EDS_MAX_Q * x->dim * 8;
-        static std::atomic<size_t> attr_bytes{0};
-        if (qbytes > attr_bytes) {
-            VQ_HIP(hipFuncSetAttribute((const void*)exact_dist_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qbytes));
-            attr_bytes = qbytes;
-        }
-        {
-            Prof p(x, I_EXACT_DIST);
-            hipLaunchKernelGGL(exact_dist_small_kernel, dim3(cdiv(n, 64)), dim3(256), qbytes, x->stream, x->rows, n, x->dim, d_queries, nq,
-                               x->d_dist, ld);
-        }
-        {
-            Prof p(x, I_SELECT);
-            hipLaunchKernelGGL(select_small_kernel, dim3(nq), dim3(256), 0, x->stream, x->d_dist, ld, n, k, d_ids, d_dist_out, x->tie());
-        }
-        VQ_HIP(hipGetLastError());
-        x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = nq;
-        x->stats_pending = false;
-        return 0;
-    }
-    const int nchunks = cdiv(n, SEL_CHUNK);
-    VQ_TRY(reserve_buf(x->d_partial, x->partial_cap, (int64_t)std::min(qslice, nq) * nchunks * k));
+    const int qslice = (int)std::max<int64_t>(32, std::min<int64_t>(nq, budget / ld) / 32 * 32);
+    VQ_TRY(x->d_dist.reserve((int64_t)std::min(qslice, (int)round_up(nq, 32)) * ld));
+    const int nchunks = cdiv(m, SEL_CHUNK);
+    if (!one_wg) VQ_TRY(x->d_partial.reserve((int64_t)std::min(qslice, nq) * nchunks * k));
     for (int q0 = 0; q0 < nq; q0 += qslice) {
         const int cur = std::min(qslice, nq - q0);
-        {
-            Prof p(x, I_EXACT_DIST);
-            hipLaunchKernelGGL(exact_dist_kernel, dim3(cdiv(n, 64), cdiv(cur, 32)), dim3(256), 0, x->stream, x->rows, n,
-                               x->dim, d_queries + (int64_t)q0 * x->dim, cur, x->d_dist, ld);
-        }
-        {
-            Prof p(x, I_SELECT);
-            hipLaunchKernelGGL(select_chunk_kernel, dim3(cur, nchunks), dim3(256), 0, x->stream, x->d_dist, ld, n, k, nchunks,
-                               x->d_partial, x->tie());
-            hipLaunchKernelGGL(merge_topk_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_partial, nchunks, k,
-                               d_ids + (int64_t)q0 * k, d_dist_out + (int64_t)q0 * k, x->tie());
+        int32_t* ids0 = ids + (int64_t)q0 * k;
+        float* out0 = out + (int64_t)q0 * k;
+        VQ_TRY(dist(q0, cur, ld));
+        Prof p(x, I_SELECT);
+        if (one_wg) {
+            hipLaunchKernelGGL(select_small_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_dist, ld, m, k, ids0, out0, tie);
+        } else {
+            hipLaunchKernelGGL(select_chunk_kernel, dim3(cur, nchunks), dim3(256), 0, x->stream, x->d_dist, ld, m, k, nchunks, x->d_partial, tie);
+            hipLaunchKernelGGL(merge_topk_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_partial, nchunks, k, ids0, out0, tie);
         }
     }
     VQ_HIP(hipGetLastError());
-    x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = nq;
-    x->stats_pending = false;
+    set_stats(x, STATS_HOST, 0, 0, nq);
     return 0;
+}
+
+// Exact scan: fp64-chain distances for a slice of queries into d_dist, then selection.
+int search_exact(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_ids, float* d_dist_out) {
+    // a handful of queries over a small index — the reference caller's one search at a time over a few thousand frames:
+    // two short launches (knn_kernels.h)
+    const bool small = nq <= EDS_MAX_Q && x->size <= SEL_SMALL_MAX_N && x->dim % 4 == 0 && exact_small_fits(x);
+    return exact_topk(x, x->size, nq, k, small, x->tie(), d_ids, d_dist_out, [&](int q0, int cur, int64_t ld) {
+        return exact_dist(x, small, d_queries + (int64_t)q0 * x->dim, cur, ld);
+    });
 }
 
 // fp16 MFMA scan + exact re-score with proof; unproven queries go through search_exact.
 static bool large_qpw4() {          // $VQ_AMD_RESCORE_QPW4=1: the four-queries-per-workgroup kernel for small batches with k > 20 too (A/B switch)
     static const bool v = getenv("VQ_AMD_RESCORE_QPW4") && atoi(getenv("VQ_AMD_RESCORE_QPW4")) == 1;
     return v;
+}
+
+// Device-side fallback geometry (knn_fallback.h).  First round: the first FB_FAST_SLOTS flagged queries over fine row splits (many
+// short workgroups: the usual handful of unproven queries is back in ~0.1 ms); bulk rounds: the rest over coarse splits, as many
+// flagged queries per round as 64 MiB of per-split lists hold.  One scratch buffer (d_fb_partial) serves both.
+struct FallbackPlan {
+    int fast_splits, splits;       // row splits of the first round / of a bulk round
+    int64_t fast_rows, rows;       // rows per split
+    int64_t round_q;               // flagged queries per bulk round
+    int64_t partial;               // elements of d_fb_partial
+};
+FallbackPlan fallback_plan(int64_t n, int nq, int k) {
+    FallbackPlan f;
+    f.fast_splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_FAST_ROWS)));
+    f.fast_rows = round_up(cdiv(n, f.fast_splits), FB_TILE);
+    f.splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_SPLIT_ROWS)));
+    f.rows = round_up(cdiv(n, f.splits), FB_TILE);
+    f.round_q = std::max<int64_t>(FB_QG, std::min<int64_t>(round_up(nq, FB_QG), ((int64_t)64 << 20) / ((int64_t)f.splits * k * 8) / FB_QG * FB_QG));
+    f.partial = std::max<int64_t>(f.round_q * f.splits, (int64_t)FB_FAST_SLOTS * f.fast_splits) * k;
+    return f;
+}
+
+// the fp16 paths' outcome counters {flagged, proven, rescanned, fallback} and their pinned, mapped copy
+int ensure_counters(vq_index* x) {
+    VQ_TRY(x->d_counters.reserve(FB_NCOUNTERS));
+    return x->h_counters.reserve(FB_NCOUNTERS);
+}
+// the grouped and clip fp16 paths' counters and their pinned copy
+int ensure_gcounters(vq_index* x) {
+    VQ_TRY(x->d_gcounters.reserve(3));
+    return x->h_gcounters.reserve(3);
+}
+
+// what launch_fallback needs for nq queries: the flagged-query list, the counters, the per-split lists
+int reserve_fallback(vq_index* x, int nq, int k) {
+    VQ_TRY(x->d_slots.reserve(round_up(nq, 1024)));
+    VQ_TRY(ensure_counters(x));
+    return x->d_fb_partial.reserve(fallback_plan(x->size, nq, k).partial);
 }
 
 // The exact redo of the queries whose proof did not close (knn_fallback.h), sized from the device-side flagged count.
@@ -263,21 +432,17 @@ void launch_fallback(vq_index* x, const float* d_queries, int nq, int k, int32_t
     auto fb = mask ? exact_fallback_kernel<true> : exact_fallback_kernel<false>;
     const GroupMask gm = mask ? *mask : GroupMask{};
     const int64_t n = x->size;
-    const int fast_splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_FAST_ROWS)));
-    const int64_t fast_rows = round_up(cdiv(n, fast_splits), FB_TILE);
-    const int fb_splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_SPLIT_ROWS)));
-    const int64_t fb_rows = round_up(cdiv(n, fb_splits), FB_TILE);
-    const int64_t fb_cap = std::max<int64_t>(FB_QG, std::min<int64_t>(round_up(nq, FB_QG), ((int64_t)64 << 20) / ((int64_t)fb_splits * k * 8) / FB_QG * FB_QG));
+    const FallbackPlan f = fallback_plan(n, nq, k);
     Prof p(x, I_EXACT_DIST);
-    hipLaunchKernelGGL(fb, dim3(fast_splits, 1), dim3(FB_TILE), 0, x->stream, x->rows, n, x->dim,
-                       d_queries, x->d_slots, counters, 0, FB_FAST_SLOTS, k, fast_rows, x->d_fb_partial, x->tie(), gm);
-    hipLaunchKernelGGL(fallback_merge_kernel, dim3(FB_FAST_SLOTS), dim3(256), 0, x->stream, x->d_fb_partial, fast_splits, k, x->d_slots,
+    hipLaunchKernelGGL(fb, dim3(f.fast_splits, 1), dim3(FB_TILE), 0, x->stream, x->rows, n, x->dim,
+                       d_queries, x->d_slots, counters, 0, FB_FAST_SLOTS, k, f.fast_rows, x->d_fb_partial, x->tie(), gm);
+    hipLaunchKernelGGL(fallback_merge_kernel, dim3(FB_FAST_SLOTS), dim3(256), 0, x->stream, x->d_fb_partial, f.fast_splits, k, x->d_slots,
                        counters, 0, FB_FAST_SLOTS, d_ids, d_dist_out, x->tie());
-    for (int64_t base = FB_FAST_SLOTS; base < nq; base += fb_cap) {
-        hipLaunchKernelGGL(fb, dim3(fb_splits, FB_SLOT_LANES), dim3(FB_TILE), 0, x->stream, x->rows, n, x->dim,
-                           d_queries, x->d_slots, counters, (int)base, (int)fb_cap, k, fb_rows, x->d_fb_partial, x->tie(), gm);
-        hipLaunchKernelGGL(fallback_merge_kernel, dim3(64), dim3(256), 0, x->stream, x->d_fb_partial, fb_splits, k, x->d_slots,
-                           counters, (int)base, (int)fb_cap, d_ids, d_dist_out, x->tie());
+    for (int64_t base = FB_FAST_SLOTS; base < nq; base += f.round_q) {
+        hipLaunchKernelGGL(fb, dim3(f.splits, FB_SLOT_LANES), dim3(FB_TILE), 0, x->stream, x->rows, n, x->dim,
+                           d_queries, x->d_slots, counters, (int)base, (int)f.round_q, k, f.rows, x->d_fb_partial, x->tie(), gm);
+        hipLaunchKernelGGL(fallback_merge_kernel, dim3(64), dim3(256), 0, x->stream, x->d_fb_partial, f.splits, k, x->d_slots,
+                           counters, (int)base, (int)f.round_q, d_ids, d_dist_out, x->tie());
     }
 }
 
@@ -299,67 +464,34 @@ int search_fp16(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_i
     const int64_t key_budget = (int64_t)1 << 27;                       // 128 Mi (stream,query) pairs = 1 GiB of keys
     int64_t q_chunk = std::max<int64_t>(QT, key_budget / streams / QT * QT);
     q_chunk = std::min<int64_t>(q_chunk, round_up(nq, QT));
-    VQ_TRY(reserve_buf(x->d_q16, x->q16_cap, q_chunk * x->dim));
-    VQ_TRY(reserve_buf(x->d_keys, x->keys_cap, streams * q_chunk * 2));
-    VQ_TRY(reserve_buf(x->d_flags, x->flags_cap, round_up(nq, QT)));
-    VQ_TRY(reserve_buf(x->d_slots, x->slots_cap, round_up(nq, 1024)));
-    if (!x->d_counters) {
-        VQ_HIP(hipMalloc((void**)&x->d_counters, FB_NCOUNTERS * 4));
-        VQ_HIP(hipHostMalloc((void**)&x->h_counters, FB_NCOUNTERS * 4, hipHostMallocMapped));
-        VQ_HIP(hipHostGetDevicePointer((void**)&x->d_counters_host, x->h_counters, 0));
-    }
-    int32_t* const counters = host_sync ? x->d_counters_host : x->d_counters;
-    // Device-side fallback geometry.  First round: the first FB_FAST_SLOTS flagged queries over fine row splits (many
-    // short workgroups: the usual handful of unproven queries is back in ~0.1 ms); bulk rounds: the rest over coarse
-    // splits, as many flagged queries per round as 64 MiB of per-split lists hold.  One scratch buffer serves both.
-    const int fast_splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_FAST_ROWS)));
-    const int64_t fast_rows = round_up(cdiv(n, fast_splits), FB_TILE);
-    const int fb_splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_SPLIT_ROWS)));
-    const int64_t fb_rows = round_up(cdiv(n, fb_splits), FB_TILE);
-    const int64_t fb_cap = std::max<int64_t>(FB_QG, std::min<int64_t>(round_up(nq, FB_QG), ((int64_t)64 << 20) / ((int64_t)fb_splits * k * 8) / FB_QG * FB_QG));
-    (void)fast_rows; (void)fb_rows;                     // (launch_fallback derives the same geometry)
-    VQ_TRY(reserve_buf(x->d_fb_partial, x->fbp_cap, std::max<int64_t>(fb_cap * fb_splits, (int64_t)FB_FAST_SLOTS * fast_splits) * k));
+    VQ_TRY(x->d_q16.reserve(q_chunk * x->dim));
+    VQ_TRY(x->d_keys.reserve(streams * q_chunk * 2));
+    VQ_TRY(x->d_flags.reserve(round_up(nq, QT)));
+    VQ_TRY(reserve_fallback(x, nq, k));
+    int32_t* const counters = host_sync ? x->h_counters.dev : x->d_counters.p;
     const int ranges = (int)(n_pad / RANGE);
     // k in (20, 40] from the streaming scan (the caller's k * 2 for a user k of 11 .. 20): the 64-candidate form of the single-query kernel
     const bool small64 = ver == 3 && k > RV_K_SMALL && k <= RV_K_SMALL64 && x->dim <= 512 && !large_qpw4() && !(getenv("VQ_AMD_RESCORE_SMALL64") && atoi(getenv("VQ_AMD_RESCORE_SMALL64")) == 0);
     if (ver == 3) {
-        static std::atomic<bool> attr3_set{false};
-        if (!attr3_set) {
-            VQ_HIP(hipFuncSetAttribute((const void*)rescore_verify_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (RV_C * (768 + 4) + 768) * 4));
-            VQ_HIP(hipFuncSetAttribute((const void*)rescore_verify_small64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (64 * (512 + 4) + 512) * 4));
-            attr3_set = true;
-        }
+        VQ_TRY(set_dyn_lds(x, (const void*)rescore_verify_small_kernel, (RV_C * (768 + 4) + 768) * 4));
+        VQ_TRY(set_dyn_lds(x, (const void*)rescore_verify_small64_kernel, (64 * (512 + 4) + 512) * 4));
     }
     if (ver == 2 || deep) {
-        static std::atomic<bool> attr_set{false};
-        if (!attr_set) {
-            VQ_HIP(hipFuncSetAttribute((const void*)scan2_f16_top2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       G2_LDS_BYTES));
-            VQ_HIP(hipFuncSetAttribute((const void*)scan4_f16_top2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       SCAN4_LDS_BYTES));
-            VQ_HIP(hipFuncSetAttribute((const void*)scan5_f16_top2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       SCAN4_LDS_BYTES));
+        VQ_TRY(set_dyn_lds(x, (const void*)scan2_f16_top2_kernel, G2_LDS_BYTES));
+        VQ_TRY(set_dyn_lds(x, (const void*)scan4_f16_top2_kernel, SCAN4_LDS_BYTES));
+        VQ_TRY(set_dyn_lds(x, (const void*)scan5_f16_top2_kernel<0>, SCAN4_LDS_BYTES));
 #ifdef VQ_DIAG
-            VQ_HIP(hipFuncSetAttribute((const void*)scan5_f16_top2_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, SCAN4_LDS_BYTES));
-            VQ_HIP(hipFuncSetAttribute((const void*)scan5_f16_top2_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, SCAN4_LDS_BYTES));
-            VQ_HIP(hipFuncSetAttribute((const void*)scan5_f16_top2_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SCAN4_LDS_BYTES));
+        VQ_TRY(set_dyn_lds(x, (const void*)scan5_f16_top2_kernel<1>, SCAN4_LDS_BYTES));
+        VQ_TRY(set_dyn_lds(x, (const void*)scan5_f16_top2_kernel<2>, SCAN4_LDS_BYTES));
+        VQ_TRY(set_dyn_lds(x, (const void*)scan5_f16_top2_kernel<0, false>, SCAN4_LDS_BYTES));
 #endif
-            attr_set = true;
-        }
     }
     for (int64_t q0 = 0; q0 < nq; q0 += q_chunk) {
         const int cur = (int)std::min<int64_t>(q_chunk, nq - q0);
         const int64_t q_pad = round_up(cur, QT);
         const int q_tiles = (int)(q_pad / QT);
         const bool fused_q = ver == 3 && nq <= SCAN3_FUSED_MAX_Q;      // the streaming scan rounds the (one to four) queries itself
-        if (!fused_q) {
-            Prof p(x, I_TO_F16);
-            const int64_t total4 = q_pad * x->dim / 4;
-            hipLaunchKernelGGL(queries_to_f16_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 2048)), dim3(256), 0,
-                               x->stream, d_queries + q0 * x->dim, x->d_q16, cur, q_pad, x->dim);
-        }
+        if (!fused_q) queries_to_f16(x, d_queries + q0 * x->dim, cur, q_pad);
         {
             Prof p(x, I_MFMA_SCAN);
             if (ver == 3) {
@@ -406,7 +538,7 @@ int search_fp16(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_i
             if (small64)             // k in (20, 40] on the streaming scan's keys: the one-workgroup-per-query kernel with 64 candidates
                 hipLaunchKernelGGL(rescore_verify_small64_kernel, dim3(cur), dim3(256), (size_t)(64 * (x->dim + 4) + x->dim) * 4, x->stream, x->d_keys, streams, q_pad, x->rows, n,
                                    x->dim, d_queries + q0 * x->dim, cur, k, d_ids + q0 * k, d_dist_out + q0 * k, x->d_flags + q0,
-                                   scan_eps_unit(x->dim) * x->row_norm_max, nq == 1 ? x->d_slots : nullptr, nq == 1 ? counters : nullptr, x->tie());
+                                   scan_eps_unit(x->dim) * x->row_norm_max, nq == 1 ? x->d_slots.p : nullptr, nq == 1 ? counters : nullptr, x->tie());
             else if (large && ver == 3 && !large_qpw4())
                 hipLaunchKernelGGL(k > RV_K_MID ? rescore_verify_xlarge1_kernel : rescore_verify_large1_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_keys, streams,
                                    q_pad, x->rows, n, x->dim, d_queries + q0 * x->dim, cur, k, d_ids + q0 * k,
@@ -418,7 +550,7 @@ int search_fp16(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_i
             else if (ver == 3)
                 hipLaunchKernelGGL(rescore_verify_small_kernel, dim3(cur), dim3(256), (size_t)(RV_C * (x->dim + 4) + x->dim) * 4, x->stream, x->d_keys, streams, q_pad, x->rows, n,
                                    x->dim, d_queries + q0 * x->dim, cur, k, d_ids + q0 * k, d_dist_out + q0 * k, x->d_flags + q0,
-                                   scan_eps_unit(x->dim) * x->row_norm_max, nq == 1 ? x->d_slots : nullptr, nq == 1 ? counters : nullptr, x->tie());
+                                   scan_eps_unit(x->dim) * x->row_norm_max, nq == 1 ? x->d_slots.p : nullptr, nq == 1 ? counters : nullptr, x->tie());
             else
             hipLaunchKernelGGL(rescore_verify_kernel, dim3(cdiv(cur, RV_QPW)), dim3(256), 0, x->stream, x->d_keys, streams,
                                q_pad, x->rows, n, x->dim, d_queries + q0 * x->dim, cur, k, d_ids + q0 * k,
@@ -433,83 +565,71 @@ int search_fp16(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_i
     if (!(ver == 3 && nq == 1 && (k <= RV_K_SMALL || small64)))   // a single query's (small-k) re-score workgroup has written the list and the counters itself
         hipLaunchKernelGGL(collect_flags_kernel, dim3(1), dim3(1024), 0, x->stream, x->d_flags, nq, x->d_slots, counters);
     VQ_HIP(hipGetLastError());
-    if (host_sync) { x->fb_deferred = true; x->stats_pending = false; return 0; }
+    if (host_sync) { set_stats(x, STATS_DEFERRED); return 0; }
     launch_fallback(x, d_queries, nq, k, d_ids, d_dist_out, counters);
     VQ_HIP(hipGetLastError());
     VQ_HIP(hipMemcpyAsync(x->h_counters, x->d_counters, FB_NCOUNTERS * 4, hipMemcpyDeviceToHost, x->stream));
-    x->stats_pending = true;
+    set_stats(x, STATS_COUNTERS);
     return 0;
 }
 
 int search_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode, int32_t* d_ids, float* d_dist, bool host_sync = false) {
-    VQ_CHECK(mode >= 0 && mode <= 2, "vq_index_search: mode %d unknown", mode);
-    x->gstats_pending = false;
-    VQ_CHECK(x->rank_n == 0 || x->rank_n == x->size, "vq_index_search: the id ranks cover %lld rows, the index holds %lld "
-             "(call vq_index_set_id_ranks again after adding rows, or clear them)", (long long)x->rank_n, (long long)x->size);
+    static const char* fn = "vq_index_search";
+    VQ_TRY(check_mode(fn, mode));
+    VQ_TRY(check_ranks(x, fn));
     // rows were added un-normalised ON THE DEVICE since the last look (vq_index_add_device: the one add that does not block):
     // is the matrix still near-unit?  This is the only place a search waits for its stream.
     if (mode != 1) VQ_TRY(refresh_norm_range(x));
     const bool fp16_ok = x->dim % GEMM_BK == 0 && k <= RV_K_MAX && x->size >= 1 && x->near_unit;
     if (mode == 2) VQ_CHECK(fp16_ok, "vq_index_search: fp16 scan needs dim %% 64 == 0, k <= %d and near-unit rows "
                                      "(0.5 <= |row|^2 <= 2; rows added with normalize=0 are measured)", RV_K_MAX);
-    // auto: the MFMA scan pays once the matrix is large enough to amortise its fixed costs
-    const bool use_fp16 = mode == 2 || (mode == 0 && fp16_ok && x->size >= 16384);
+    const bool use_fp16 = mode == 2 || (mode == 0 && fp16_ok && x->size >= FP16_AUTO_MIN_ROWS);
     return use_fp16 ? search_fp16(x, d_queries, nq, k, d_ids, d_dist, host_sync) : search_exact(x, d_queries, nq, k, d_ids, d_dist);
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device only: remembered per (device, kernel).
-int set_dyn_lds(const void* fn, size_t bytes) {
-    static std::mutex mu;
-    static std::vector<std::tuple<int, const void*, size_t>> done;
-    int dev = 0;
-    VQ_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    for (const auto& t : done)
-        if (std::get<0>(t) == dev && std::get<1>(t) == fn && std::get<2>(t) >= bytes) return 0;
-    VQ_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    done.emplace_back(dev, fn, bytes);
-    return 0;
+// ---- grouped search (knn_grouped.h) ----
+// lanes per group in group_block_topk_kernel / set_group_min_kernel, from the mean group size
+int lanes_per_group(int64_t rows, int32_t groups) {
+    const int64_t mean = rows / std::max<int32_t>(1, groups);
+    return mean >= 256 ? 64 : mean >= 64 ? 16 : mean >= 8 ? 4 : 1;
 }
 
-// ---- grouped search (knn_grouped.h) ----
-int grouped_lpg(const vq_index* x) {                  // lanes per group in group_block_topk_kernel, from the mean group size
-    const int64_t mean = x->size / std::max<int32_t>(1, x->n_groups);
-    return mean >= 256 ? 64 : mean >= 64 ? 16 : mean >= 8 ? 4 : 1;
+// streaming group-max scan (fp16): the instance for the handle's dim (256, 512 or 768), masked by the allowed groups' bitmap or not
+auto group_max_scan(const vq_index* x, bool masked) -> decltype(&scan3_group_max_kernel<8>) {
+    if (masked) return x->dim == 768 ? scan3_group_max_kernel<24, true> : x->dim == 512 ? scan3_group_max_kernel<16, true> : scan3_group_max_kernel<8, true>;
+    return x->dim == 768 ? scan3_group_max_kernel<24> : x->dim == 512 ? scan3_group_max_kernel<16> : scan3_group_max_kernel<8>;
+}
+
+// The grouped exact paths' selection: per slice of queries, `dist(q0, cur, ld)` queues the distances to m columns into d_dist
+// [cur][ld]; block_topk takes the minimum of each of G groups (columns goff / grows) and each block's k best; then the merge.
+template <class Dist>
+int grouped_exact_topk(vq_index* x, decltype(&group_block_topk_kernel<true>) block_topk, int64_t m, int G, const int32_t* goff,
+                       const int32_t* grows, const TieOrder tie, int nq, int k, int32_t* groups, int32_t* rows_out, float* dist_out, Dist dist) {
+    const int64_t ld = round_up(m, 64);
+    const int nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK), lpg = lanes_per_group(m, G);
+    int64_t qslice = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)128 << 20) / ld));          // 512 MiB of distances per slice
+    qslice = std::max<int64_t>(1, std::min<int64_t>(qslice, ((int64_t)32 << 20) / ((int64_t)nblocks * kl)));   // 256 MiB of block lists
+    VQ_TRY(x->d_dist.reserve(qslice * ld));
+    VQ_TRY(x->d_gpart.reserve(qslice * nblocks * kl));
+    for (int64_t q0 = 0; q0 < nq; q0 += qslice) {
+        const int cur = (int)std::min<int64_t>(qslice, nq - q0);
+        VQ_TRY(dist(q0, cur, ld));
+        Prof p(x, I_SELECT);
+        hipLaunchKernelGGL(block_topk, dim3(nblocks, cur), dim3(256), 0, x->stream, x->d_dist, ld, nullptr, x->dim, nullptr, goff, grows, G, lpg, kl,
+                           nblocks, x->d_gpart, nullptr, tie, nullptr);
+        hipLaunchKernelGGL(group_merge_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gpart, nblocks * kl, k, x->d_group,
+                           groups + q0 * k, rows_out + q0 * k, dist_out + q0 * k, nullptr, tie);
+    }
+    VQ_HIP(hipGetLastError());
+    set_stats(x, STATS_HOST, 0, 0, nq);
+    return 0;
 }
 
 // Exact path: the plain path's fp64-chain distances for a slice of queries -> group minima and each block's k best -> merge.
 int search_grouped_exact(vq_index* x, const float* d_queries, int nq, int k, int32_t* groups, int32_t* rows_out, float* dist) {
-    const int64_t n = x->size, ld = round_up(n, 64);
-    const int G = x->n_groups, nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK);
-    int64_t qslice = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)128 << 20) / ld));          // 512 MiB of distances per slice
-    qslice = std::max<int64_t>(1, std::min<int64_t>(qslice, ((int64_t)32 << 20) / ((int64_t)nblocks * kl)));   // 256 MiB of block lists
-    VQ_TRY(reserve_buf(x->d_dist, x->dist_cap, qslice * ld));
-    VQ_TRY(reserve_buf(x->d_gpart, x->gpart_cap, qslice * nblocks * kl));
-    const size_t qbytes = (size_t)EDS_MAX_Q * x->dim * 8;
-    const bool small_ok = qbytes <= ((size_t)96 << 10);
-    if (small_ok && nq <= EDS_MAX_Q) VQ_TRY(set_dyn_lds((const void*)exact_dist_small_kernel, qbytes));
-    for (int64_t q0 = 0; q0 < nq; q0 += qslice) {
-        const int cur = (int)std::min<int64_t>(qslice, nq - q0);
-        const float* qp = d_queries + q0 * x->dim;
-        {
-            Prof p(x, I_EXACT_DIST);
-            if (small_ok && nq <= EDS_MAX_Q)
-                hipLaunchKernelGGL(exact_dist_small_kernel, dim3(cdiv(n, 64)), dim3(256), qbytes, x->stream, x->rows, n, x->dim, qp, cur, x->d_dist, ld);
-            else
-                hipLaunchKernelGGL(exact_dist_kernel, dim3(cdiv(n, 64), cdiv(cur, 32)), dim3(256), 0, x->stream, x->rows, n, x->dim, qp, cur, x->d_dist, ld);
-        }
-        {
-            Prof p(x, I_SELECT);
-            hipLaunchKernelGGL(group_block_topk_kernel<true>, dim3(nblocks, cur), dim3(256), 0, x->stream, x->d_dist, ld, nullptr, x->dim, nullptr,
-                               x->d_goff, x->d_grows, G, grouped_lpg(x), kl, nblocks, x->d_gpart, nullptr, x->tie(), nullptr);
-            hipLaunchKernelGGL(group_merge_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gpart, nblocks * kl, k, x->d_group,
-                               groups + q0 * k, rows_out + q0 * k, dist + q0 * k, nullptr, x->tie());
-        }
-    }
-    VQ_HIP(hipGetLastError());
-    x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = nq;
-    x->stats_pending = false; x->gstats_pending = false;
-    return 0;
+    const bool small = exact_small_fits(x) && nq <= EDS_MAX_Q;
+    return grouped_exact_topk(x, group_block_topk_kernel<true>, x->size, x->n_groups, x->d_goff, x->d_grows, x->tie(), nq, k, groups, rows_out, dist,
+                              [&](int64_t q0, int cur, int64_t ld) { return exact_dist(x, small, d_queries + q0 * x->dim, cur, ld); });
 }
 
 // fp16 path: group-max scan -> threshold + candidates -> exact re-score of the candidates' rows; flagged queries are redone
@@ -523,15 +643,12 @@ int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int3
     int64_t qc = std::max<int64_t>(16, ((int64_t)64 << 20) / G / 16 * 16);          // gbest [qc][G]: <= 256 MiB
     qc = std::min<int64_t>(std::min<int64_t>(qc, round_up(nq, 16)), 1024);
     while (qc > 16 && qc * nblocks * kl > ((int64_t)32 << 20)) qc -= 16;               // the redo's block lists: <= 256 MiB
-    VQ_TRY(reserve_buf(x->d_q16, x->q16_cap, qc * x->dim));
-    VQ_TRY(reserve_buf(x->d_gbest, x->gbest_cap, qc * G));
-    VQ_TRY(reserve_buf(x->d_gcand, x->gcand_cap, qc * CA + qc * (CA + 1) + 3 * qc));
-    VQ_TRY(reserve_buf(x->d_gkeys, x->gkeys_cap, qc * CA));
-    VQ_TRY(reserve_buf(x->d_gpart, x->gpart_cap, qc * nblocks * kl));
-    if (!x->d_gcounters) {
-        VQ_HIP(hipMalloc((void**)&x->d_gcounters, 3 * sizeof(unsigned long long)));
-        VQ_HIP(hipHostMalloc((void**)&x->h_gcounters, 3 * sizeof(unsigned long long)));
-    }
+    VQ_TRY(x->d_q16.reserve(qc * x->dim));
+    VQ_TRY(x->d_gbest.reserve(qc * G));
+    VQ_TRY(x->d_gcand.reserve(qc * CA + qc * (CA + 1) + 3 * qc));
+    VQ_TRY(x->d_gkeys.reserve(qc * CA));
+    VQ_TRY(x->d_gpart.reserve(qc * nblocks * kl));
+    VQ_TRY(ensure_gcounters(x));
     int32_t* cand = x->d_gcand;
     int32_t* pref = cand + qc * CA;
     int32_t* cn = pref + qc * (CA + 1);
@@ -539,8 +656,7 @@ int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int3
     float* thr = (float*)(flags + qc);
     VQ_HIP(hipMemsetAsync(x->d_gcounters, 0, 3 * sizeof(unsigned long long), x->stream));
     const float eps_rows = scan_eps_unit(x->dim) * x->row_norm_max;
-    auto scan = x->dim == 768 ? scan3_group_max_kernel<24> : x->dim == 512 ? scan3_group_max_kernel<16> : scan3_group_max_kernel<8>;
-    if (allow) scan = x->dim == 768 ? scan3_group_max_kernel<24, true> : x->dim == 512 ? scan3_group_max_kernel<16, true> : scan3_group_max_kernel<8, true>;
+    auto scan = group_max_scan(x, allow != nullptr);
     auto redo = allow ? group_block_topk_kernel<false, true> : group_block_topk_kernel<false>;
     // k among the allowed groups: the threshold is the k'-th largest gbest with k' = min(k, allowed) (a disallowed group's 0 is
     // below it), the finalize test asks for min(k, allowed) re-scored groups
@@ -549,12 +665,7 @@ int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int3
         const int cur = (int)std::min<int64_t>(qc, nq - q0);
         const int64_t q_pad = round_up(cur, 16);
         const float* qp = d_queries + q0 * x->dim;
-        {
-            Prof p(x, I_TO_F16);
-            const int64_t total4 = q_pad * x->dim / 4;
-            hipLaunchKernelGGL(queries_to_f16_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 2048)), dim3(256), 0, x->stream,
-                               qp, x->d_q16, cur, q_pad, x->dim);
-        }
+        queries_to_f16(x, qp, cur, q_pad);
         VQ_HIP(hipMemsetAsync(x->d_gbest, 0, (size_t)cur * G * 4, x->stream));
         {
             Prof p(x, I_MFMA_SCAN);
@@ -573,35 +684,32 @@ int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int3
         {
             Prof p(x, I_EXACT_DIST);                 // the exact redo of flagged queries (every workgroup of an unflagged query leaves at once)
             hipLaunchKernelGGL(redo, dim3(nblocks, cur), dim3(256), 0, x->stream, nullptr, 0, x->rows, x->dim, qp,
-                               x->d_goff, x->d_grows, G, grouped_lpg(x), kl, nblocks, x->d_gpart, flags, x->tie(), allow);
+                               x->d_goff, x->d_grows, G, lanes_per_group(n, G), kl, nblocks, x->d_gpart, flags, x->tie(), allow);
             hipLaunchKernelGGL(group_merge_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gpart, nblocks * kl, k, x->d_group,
                                groups + q0 * k, rows_out + q0 * k, dist + q0 * k, flags, x->tie());
         }
     }
     VQ_HIP(hipGetLastError());
     VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
-    x->stats_pending = false; x->gstats_pending = true;
+    set_stats(x, STATS_GCOUNTERS);
     return 0;
 }
 
 int search_grouped_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode, int32_t* groups, int32_t* rows_out, float* dist) {
-    VQ_CHECK(mode >= 0 && mode <= 2, "vq_index_search_grouped: mode %d unknown", mode);
-    VQ_CHECK(x->rank_n == 0 || x->rank_n == x->size, "vq_index_search_grouped: the id ranks cover %lld rows, the index holds %lld "
-             "(call vq_index_set_id_ranks again after adding rows, or clear them)", (long long)x->rank_n, (long long)x->size);
-    VQ_CHECK(x->group_n == x->size, "vq_index_search_grouped: the group labels cover %lld rows, the index holds %lld "
-             "(call vq_index_set_groups after adding rows)", (long long)x->group_n, (long long)x->size);
+    static const char* fn = "vq_index_search_grouped";
+    VQ_TRY(check_mode(fn, mode));
+    VQ_TRY(check_ranks(x, fn));
+    VQ_TRY(check_labels(x, fn));
     if (mode != 1) VQ_TRY(refresh_norm_range(x));
     const bool fp16_ok = (x->dim == 256 || x->dim == 512 || x->dim == 768) && k <= RV_K_MAX && x->size >= 1 && x->near_unit;
     if (mode == 2) VQ_CHECK(fp16_ok, "vq_index_search_grouped: the fp16 scan needs dim 256, 512 or 768, k <= %d and near-unit rows "
                                      "(0.5 <= |row|^2 <= 2; rows added with normalize=0 are measured)", RV_K_MAX);
-    const bool use_fp16 = mode == 2 || (mode == 0 && fp16_ok && x->size >= 16384);       // the plain search's rule
+    const bool use_fp16 = mode == 2 || (mode == 0 && fp16_ok && x->size >= FP16_AUTO_MIN_ROWS);       // the plain search's rule
     return use_fp16 ? search_grouped_fp16(x, d_queries, nq, k, groups, rows_out, dist)
                     : search_grouped_exact(x, d_queries, nq, k, groups, rows_out, dist);
 }
 
 // ---- vq_index_remove_rows (knn_remove.h) ----
-int grid_for(int64_t count) { return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(count, 256), 2048)); }
-
 // exclusive prefix sum of v[0..n) in place, v[n] = total; tiles holds cdiv(n, RM_SCAN_TILE) + 1 words
 int rm_exclusive_scan(vq_index* x, int32_t* v, int64_t n, int32_t* tiles) {
     const int64_t ntiles = std::max<int64_t>(1, cdiv(n, RM_SCAN_TILE));
@@ -637,7 +745,7 @@ bool filter_fp16_ok(const vq_index* x, int nq, int k) {
 
 // Everything that can refuse a filtered call before any work is queued: the mode, and mode 2 where the masked path does not exist.
 int filter_precheck(vq_index* x, const char* fn, int nq, int k, int mode, int32_t n_sel, int exclude) {
-    VQ_CHECK(mode >= 0 && mode <= 2, "%s: mode %d unknown", fn, mode);
+    VQ_TRY(check_mode(fn, mode));
     if (n_sel == 0 && exclude) return 0;                    // nothing excluded: the unfiltered search, under its own rules
     if (mode != 1) VQ_TRY(refresh_norm_range(x));
     if (mode == 2)
@@ -646,25 +754,43 @@ int filter_precheck(vq_index* x, const char* fn, int nq, int k, int mode, int32_
     return 0;
 }
 
-// Checks the labels and the filter and sizes S from the host mirror of goff.  Then, on the device, S's row list (gather path) or
-// the allowed groups' bitmap (fp16 path).  The list goes up from a ring of pinned staging slots: a slot is reused only after the
-// copy vq_index::FLT_STAGE_SLOTS calls back has completed, so back-to-back asynchronous calls do not wait for each other.
-int filter_prepare(vq_index* x, const char* fn, const int32_t* groups, int32_t n_sel, int exclude, bool fp16, FilterPlan* p) {
-    VQ_CHECK(x->rank_n == 0 || x->rank_n == x->size, "%s: the id ranks cover %lld rows, the index holds %lld "
-             "(call vq_index_set_id_ranks again after adding rows, or clear them)", fn, (long long)x->rank_n, (long long)x->size);
-    VQ_CHECK(x->group_n == x->size && (int64_t)x->h_goff.size() == (int64_t)x->n_groups + 1, "%s: the group labels cover %lld rows, "
-             "the index holds %lld (call vq_index_set_groups after adding rows)", fn, (long long)x->group_n, (long long)x->size);
+// A filter's labels, normalised once per call: sorted, a group named twice counted once; the rows they hold by the host mirror
+// of goff (before any device work: the mode-0 choice needs |S| to pick what filter_prepare builds); and the first label, in the
+// caller's order, that names no group.  Nothing is refused here: filter_prepare does that, behind the coverage checks.
+struct FilterLabels {
+    std::vector<int32_t> sel;
+    int64_t in_rows = 0;
+    bool bad = false; int32_t first_bad = 0;
+    int64_t allowed_rows(const vq_index* x, int exclude) const { return exclude ? x->size - in_rows : in_rows; }
+};
+FilterLabels filter_labels(const vq_index* x, const int32_t* groups, int32_t n_sel) {
+    FilterLabels f;
+    for (int32_t i = 0; i < n_sel && !f.bad; ++i)
+        if (groups[i] < 0 || groups[i] >= x->n_groups) { f.bad = true; f.first_bad = groups[i]; }
+    f.sel.assign(groups, groups + n_sel);
+    std::sort(f.sel.begin(), f.sel.end());
+    f.sel.erase(std::unique(f.sel.begin(), f.sel.end()), f.sel.end());           // a group named twice counts once
+    if (!f.bad && (int64_t)x->h_goff.size() == (int64_t)x->n_groups + 1)
+        for (int32_t g : f.sel) f.in_rows += x->h_goff[(size_t)g + 1] - x->h_goff[(size_t)g];
+    return f;
+}
+int check_label_range(const vq_index* x, const char* fn, const FilterLabels& f) {
+    VQ_CHECK(!f.bad, "%s: group %d outside [0, %d)", fn, (int)f.first_bad, (int)x->n_groups);
+    return 0;
+}
+
+// Checks the labels and the filter.  Then, on the device, S's row list (gather path) or the allowed groups' bitmap (fp16 path).
+// The list goes up from a ring of pinned staging slots: a slot is reused only after the copy vq_index::FLT_STAGE_SLOTS calls
+// back has completed, so back-to-back asynchronous calls do not wait for each other.
+int filter_prepare(vq_index* x, const char* fn, const FilterLabels& f, int exclude, bool fp16, FilterPlan* p) {
+    VQ_TRY(check_ranks(x, fn));
+    VQ_TRY(check_labels(x, fn));
+    VQ_TRY(check_label_range(x, fn, f));
     const int32_t G = x->n_groups;
-    std::vector<int32_t> sel(groups, groups + n_sel);
-    for (int32_t i = 0; i < n_sel; ++i)
-        VQ_CHECK(sel[(size_t)i] >= 0 && sel[(size_t)i] < G, "%s: group %d outside [0, %d)", fn, (int)sel[(size_t)i], (int)G);
-    std::sort(sel.begin(), sel.end());
-    sel.erase(std::unique(sel.begin(), sel.end()), sel.end());           // a group named twice counts once
+    const std::vector<int32_t>& sel = f.sel;
     const int32_t ns = (int32_t)sel.size();
     const int32_t* hg = x->h_goff.data();
-    int64_t in_rows = 0;
-    for (int32_t g : sel) in_rows += hg[g + 1] - hg[g];
-    p->m = exclude ? x->size - in_rows : in_rows;
+    p->m = f.allowed_rows(x, exclude);
     p->nA = exclude ? G - ns : ns;
     p->all = exclude && ns == 0;
     if (p->all || p->m == 0) return 0;
@@ -674,7 +800,7 @@ int filter_prepare(vq_index* x, const char* fn, const int32_t* groups, int32_t n
     const int64_t w_A = words(nA), w_soff = words((int64_t)nA + 1), w_K = exclude && list ? words((int64_t)G + 1) : 0,
                   w_tiles = exclude && list ? words(cdiv(G, RM_SCAN_TILE) + 2) : 0, w_E = exclude ? words(ns) : 0,
                   w_list = list ? words(p->m) : 0, w_bits = fp16 ? words(cdiv(G, 32)) : 0;
-    VQ_TRY(reserve_buf(x->d_flt, x->flt_cap, w_A + w_soff + w_K + w_tiles + w_E + 2 * w_list + w_bits));
+    VQ_TRY(x->d_flt.reserve(w_A + w_soff + w_K + w_tiles + w_E + 2 * w_list + w_bits));
     int32_t* A = x->d_flt;
     p->soff = A + w_A;
     int32_t* K = p->soff + w_soff;
@@ -684,19 +810,12 @@ int filter_prepare(vq_index* x, const char* fn, const int32_t* groups, int32_t n
     p->tie_w = list ? E + w_E + w_list : nullptr;
     p->bits = fp16 ? (uint32_t*)(E + w_E + 2 * w_list) : nullptr;
     // a staging slot of the ring
-    const int slot = x->flt_slot;
-    x->flt_slot = (slot + 1) % vq_index::FLT_STAGE_SLOTS;
-    if (x->flt_ev[slot]) VQ_HIP(hipEventSynchronize(x->flt_ev[slot]));
-    else VQ_HIP(hipEventCreateWithFlags(&x->flt_ev[slot], hipEventDisableTiming));
-    const int64_t stage = exclude ? ns : w_A + nA + 1;
-    if (stage > x->hflt_cap[slot]) {
-        if (x->h_flt[slot]) (void)hipHostFree(x->h_flt[slot]);
-        x->h_flt[slot] = nullptr; x->hflt_cap[slot] = 0;
-        const int64_t cap = std::max<int64_t>(stage, 16 << 10);
-        VQ_HIP(hipHostMalloc((void**)&x->h_flt[slot], (size_t)cap * 4));
-        x->hflt_cap[slot] = cap;
-    }
-    int32_t* h = x->h_flt[slot];
+    StageSlot& st = x->flt_stage[x->flt_slot];
+    x->flt_slot = (x->flt_slot + 1) % vq_index::FLT_STAGE_SLOTS;
+    if (st.ev) VQ_HIP(hipEventSynchronize(st.ev));
+    else VQ_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    VQ_TRY(st.h.reserve(exclude ? ns : w_A + nA + 1, 16 << 10));
+    int32_t* h = st.h;
     if (!exclude) {
         // the include list is the allowed groups: A and their offsets go up in one copy
         std::memcpy(h, sel.data(), (size_t)nA * 4);
@@ -709,7 +828,7 @@ int filter_prepare(vq_index* x, const char* fn, const int32_t* groups, int32_t n
         std::memcpy(h, sel.data(), (size_t)ns * 4);        // ns > 0: an empty exclude list is the unfiltered search
         VQ_HIP(hipMemcpyAsync(E, h, (size_t)ns * 4, hipMemcpyHostToDevice, x->stream));
     }
-    VQ_HIP(hipEventRecord(x->flt_ev[slot], x->stream));
+    VQ_HIP(hipEventRecord(st.ev, x->stream));
     if (fp16) {
         VQ_HIP(hipMemsetAsync(p->bits, exclude ? 0xff : 0, (size_t)w_bits * 4, x->stream));
         hipLaunchKernelGGL(filter_bitmap_kernel, dim3(grid_for(ns)), dim3(256), 0, x->stream, exclude ? E : A, ns, p->bits);
@@ -737,92 +856,40 @@ void filter_dist(vq_index* x, const FilterPlan& p, const float* qp, int cur, int
                            qp, cur, x->d_dist, ld);
 }
 
+// the gather paths' tie order: the list positions' tie words
+TieOrder list_tie(const vq_index* x, const FilterPlan& p) { return TieOrder{p.tie_w, x->rank_n ? x->d_rank_inv : nullptr}; }
+
 // Gather path, plain form: the plain exact path's selection over the list positions (knn_filter.h 4.)
 int search_filtered_gather(vq_index* x, const float* d_queries, int nq, int k, const FilterPlan& p, int32_t* d_ids, float* d_dist_out) {
-    const int64_t m = p.m, ld = round_up(m, 64);
-    const TieOrder ft{p.tie_w, x->rank_n ? x->d_rank_inv : nullptr};
-    const int64_t budget = (int64_t)128 << 20;                 // 512 MiB of fp32 distances per slice
-    const int qslice = (int)std::max<int64_t>(32, std::min<int64_t>(nq, budget / ld) / 32 * 32);
-    VQ_TRY(reserve_buf(x->d_dist, x->dist_cap, (int64_t)std::min(qslice, (int)round_up(nq, 32)) * ld));
-    const bool small_sel = m <= SEL_SMALL_MAX_N;
-    const int nchunks = cdiv(m, SEL_CHUNK);
-    if (!small_sel) VQ_TRY(reserve_buf(x->d_partial, x->partial_cap, (int64_t)std::min(qslice, nq) * nchunks * k));
-    for (int q0 = 0; q0 < nq; q0 += qslice) {
-        const int cur = std::min(qslice, nq - q0);
+    return exact_topk(x, p.m, nq, k, p.m <= SEL_SMALL_MAX_N, list_tie(x, p), d_ids, d_dist_out, [&](int q0, int cur, int64_t ld) {
         filter_dist(x, p, d_queries + (int64_t)q0 * x->dim, cur, ld);
-        Prof pr(x, I_SELECT);
-        if (small_sel) {
-            hipLaunchKernelGGL(select_small_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_dist, ld, m, k, d_ids + (int64_t)q0 * k,
-                               d_dist_out + (int64_t)q0 * k, ft);
-        } else {
-            hipLaunchKernelGGL(select_chunk_kernel, dim3(cur, nchunks), dim3(256), 0, x->stream, x->d_dist, ld, m, k, nchunks, x->d_partial, ft);
-            hipLaunchKernelGGL(merge_topk_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_partial, nchunks, k, d_ids + (int64_t)q0 * k,
-                               d_dist_out + (int64_t)q0 * k, ft);
-        }
-    }
-    VQ_HIP(hipGetLastError());
-    x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = nq;
-    x->stats_pending = false; x->gstats_pending = false;
-    return 0;
+        return 0;
+    });
 }
 
 // Gather path, grouped form: group minima over the allowed groups' list ranges -> block top-k -> group_merge_kernel
 int search_grouped_filtered_gather(vq_index* x, const float* d_queries, int nq, int k, const FilterPlan& p, int32_t* groups,
                                    int32_t* rows_out, float* dist) {
-    const int64_t m = p.m, ld = round_up(m, 64);
-    const TieOrder ft{p.tie_w, x->rank_n ? x->d_rank_inv : nullptr};
-    const int nblocks = cdiv(p.nA, GRP_BLOCK), kl = std::min(k, GRP_BLOCK);
-    int64_t qslice = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)128 << 20) / ld));              // 512 MiB of distances per slice
-    qslice = std::max<int64_t>(1, std::min<int64_t>(qslice, ((int64_t)32 << 20) / ((int64_t)nblocks * kl)));   // 256 MiB of block lists
-    VQ_TRY(reserve_buf(x->d_dist, x->dist_cap, qslice * ld));
-    VQ_TRY(reserve_buf(x->d_gpart, x->gpart_cap, qslice * nblocks * kl));
-    const int64_t mean = m / std::max<int32_t>(1, p.nA);
-    const int lpg = mean >= 256 ? 64 : mean >= 64 ? 16 : mean >= 8 ? 4 : 1;
-    for (int64_t q0 = 0; q0 < nq; q0 += qslice) {
-        const int cur = (int)std::min<int64_t>(qslice, nq - q0);
-        filter_dist(x, p, d_queries + q0 * x->dim, cur, ld);
-        Prof pr(x, I_SELECT);
-        hipLaunchKernelGGL((group_block_topk_kernel<true, false, true>),dim3(nblocks, cur), dim3(256), 0, x->stream, x->d_dist, ld, nullptr, x->dim,
-                           nullptr, p.soff, nullptr, p.nA, lpg, kl, nblocks, x->d_gpart, nullptr, ft, nullptr);
-        hipLaunchKernelGGL(group_merge_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gpart, nblocks * kl, k, x->d_group,
-                           groups + q0 * k, rows_out + q0 * k, dist + q0 * k, nullptr, ft);
-    }
-    VQ_HIP(hipGetLastError());
-    x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = nq;
-    x->stats_pending = false; x->gstats_pending = false;
-    return 0;
+    return grouped_exact_topk(x, group_block_topk_kernel<true, false, true>, p.m, p.nA, p.soff, nullptr, list_tie(x, p), nq, k, groups, rows_out, dist,
+                              [&](int64_t q0, int cur, int64_t ld) { filter_dist(x, p, d_queries + q0 * x->dim, cur, ld); return 0; });
 }
 
 // Masked fp16 path, plain form (knn_filter.h): masked stream scan -> stream threshold -> re-score of the candidate streams'
 // allowed rows -> top-k; flagged queries are redone by the masked exact fallback on the device, so nothing here waits.
 int search_filtered_fp16(vq_index* x, const float* d_queries, int nq, int k, const FilterPlan& p, int32_t* d_ids, float* d_dist_out) {
     const int64_t n = x->size, streams = round_up(n, SCAN_STREAM_ROWS) / SCAN_STREAM_ROWS, q_pad = round_up(nq, SCAN3_QB);
-    VQ_TRY(reserve_buf(x->d_q16, x->q16_cap, q_pad * x->dim));
-    VQ_TRY(reserve_buf(x->d_keys, x->keys_cap, streams * q_pad * 2));
-    VQ_TRY(reserve_buf(x->d_flags, x->flags_cap, q_pad));
-    VQ_TRY(reserve_buf(x->d_slots, x->slots_cap, round_up(nq, 1024)));
-    VQ_TRY(reserve_buf(x->d_fcand, x->fcand_cap, (int64_t)nq * FLT_CAND + 3 * (int64_t)nq));
-    VQ_TRY(reserve_buf(x->d_flist, x->flist_cap, (int64_t)nq * FLT_LIST));
-    if (!x->d_counters) {
-        VQ_HIP(hipMalloc((void**)&x->d_counters, FB_NCOUNTERS * 4));
-        VQ_HIP(hipHostMalloc((void**)&x->h_counters, FB_NCOUNTERS * 4, hipHostMallocMapped));
-        VQ_HIP(hipHostGetDevicePointer((void**)&x->d_counters_host, x->h_counters, 0));
-    }
-    const int fast_splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_FAST_ROWS)));
-    const int fb_splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_SPLIT_ROWS)));
-    const int64_t fb_cap = std::max<int64_t>(FB_QG, std::min<int64_t>(round_up(nq, FB_QG), ((int64_t)64 << 20) / ((int64_t)fb_splits * k * 8) / FB_QG * FB_QG));
-    VQ_TRY(reserve_buf(x->d_fb_partial, x->fbp_cap, std::max<int64_t>(fb_cap * fb_splits, (int64_t)FB_FAST_SLOTS * fast_splits) * k));
+    VQ_TRY(x->d_q16.reserve(q_pad * x->dim));
+    VQ_TRY(x->d_keys.reserve(streams * q_pad * 2));
+    VQ_TRY(x->d_flags.reserve(q_pad));
+    VQ_TRY(x->d_fcand.reserve((int64_t)nq * FLT_CAND + 3 * (int64_t)nq));
+    VQ_TRY(x->d_flist.reserve((int64_t)nq * FLT_LIST));
+    VQ_TRY(reserve_fallback(x, nq, k));
     int32_t* cand = x->d_fcand;
     int32_t* cn = cand + (int64_t)nq * FLT_CAND;
     int32_t* ln = cn + nq;
     float* thr = (float*)(ln + nq);
     const GroupMask gm{x->d_group, x->d_sgroup, p.bits};
-    {
-        Prof pr(x, I_TO_F16);
-        const int64_t total4 = q_pad * x->dim / 4;
-        hipLaunchKernelGGL(queries_to_f16_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 2048)), dim3(256), 0, x->stream,
-                           d_queries, x->d_q16, nq, q_pad, x->dim);
-    }
+    queries_to_f16(x, d_queries, nq, q_pad);
     {
         Prof pr(x, I_MFMA_SCAN);
         auto scan = x->dim == 768 ? scan3_f16_top2_kernel<24, 1, false, true> : x->dim == 512 ? scan3_f16_top2_kernel<16, 1, false, true>
@@ -844,36 +911,22 @@ int search_filtered_fp16(vq_index* x, const float* d_queries, int nq, int k, con
     launch_fallback(x, d_queries, nq, k, d_ids, d_dist_out, x->d_counters, &gm);
     VQ_HIP(hipGetLastError());
     VQ_HIP(hipMemcpyAsync(x->h_counters, x->d_counters, FB_NCOUNTERS * 4, hipMemcpyDeviceToHost, x->stream));
-    x->stats_pending = true; x->gstats_pending = false;
+    set_stats(x, STATS_COUNTERS);
     return 0;
 }
 
-// mode 0: the masked fp16 scan where it exists, the index is large enough for the plain rule (16,384 rows) and S is broad
+// mode 0: the masked fp16 scan where it exists, the index is large enough for the plain rule (FP16_AUTO_MIN_ROWS) and S is broad
 bool filter_use_fp16(const vq_index* x, int nq, int k, int mode, int64_t m) {
     if (mode != 0) return mode == 2;
     const int den = nq <= FLT_CROSS_FEW_Q ? FLT_CROSS_Q1_DEN : FLT_CROSS_QN_DEN;
-    return filter_fp16_ok(x, nq, k) && x->size >= 16384 && m * den >= x->size;
+    return filter_fp16_ok(x, nq, k) && x->size >= FP16_AUTO_MIN_ROWS && m * den >= x->size;
 }
 
+// S is empty: no result for any query
 int filter_fill_empty(vq_index* x, int nq, int k, int32_t* a, int32_t* b, float* dist) {
-    const int64_t count = (int64_t)nq * k;
-    hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, a, dist, count);
-    if (b) hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, b, dist, count);
-    VQ_HIP(hipGetLastError());
-    x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = nq;
-    x->stats_pending = false; x->gstats_pending = false;
+    VQ_TRY(fill_empty(x, (int64_t)nq * k, a, b, dist));
+    set_stats(x, STATS_HOST, 0, 0, nq);
     return 0;
-}
-
-// |S| before any device work: the host mirror of goff (the mode-0 choice needs it to pick what filter_prepare builds)
-int64_t filter_rows(const vq_index* x, const int32_t* sel, int32_t n_sel, int exclude) {
-    if ((int64_t)x->h_goff.size() != (int64_t)x->n_groups + 1) return 0;
-    std::vector<int32_t> s(sel, sel + n_sel);
-    std::sort(s.begin(), s.end());
-    s.erase(std::unique(s.begin(), s.end()), s.end());
-    int64_t in_rows = 0;
-    for (int32_t g : s) if (g >= 0 && g < x->n_groups) in_rows += x->h_goff[(size_t)g + 1] - x->h_goff[(size_t)g];
-    return exclude ? x->size - in_rows : in_rows;
 }
 
 int search_filtered_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode, const int32_t* sel, int32_t n_sel, int exclude,
@@ -881,9 +934,10 @@ int search_filtered_dispatch(vq_index* x, const float* d_queries, int nq, int k,
     static const char* fn = "vq_index_search_filtered";
     VQ_TRY(filter_precheck(x, fn, nq, k, mode, n_sel, exclude));
     if (n_sel == 0 && exclude) return search_dispatch(x, d_queries, nq, k, mode, d_ids, d_dist);       // nothing excluded: the plain search
-    const bool fp16 = filter_use_fp16(x, nq, k, mode, filter_rows(x, sel, n_sel, exclude));
+    const FilterLabels f = filter_labels(x, sel, n_sel);
+    const bool fp16 = filter_use_fp16(x, nq, k, mode, f.allowed_rows(x, exclude));
     FilterPlan p;
-    VQ_TRY(filter_prepare(x, fn, sel, n_sel, exclude, fp16, &p));
+    VQ_TRY(filter_prepare(x, fn, f, exclude, fp16, &p));
     if (p.m == 0) return filter_fill_empty(x, nq, k, d_ids, nullptr, d_dist);
     return fp16 ? search_filtered_fp16(x, d_queries, nq, k, p, d_ids, d_dist) : search_filtered_gather(x, d_queries, nq, k, p, d_ids, d_dist);
 }
@@ -893,38 +947,29 @@ int search_grouped_filtered_dispatch(vq_index* x, const float* d_queries, int nq
     static const char* fn = "vq_index_search_grouped_filtered";
     VQ_TRY(filter_precheck(x, fn, nq, k, mode, n_sel, exclude));
     if (n_sel == 0 && exclude) return search_grouped_dispatch(x, d_queries, nq, k, mode, groups, rows_out, dist);
-    const bool fp16 = filter_use_fp16(x, nq, k, mode, filter_rows(x, sel, n_sel, exclude));
+    const FilterLabels f = filter_labels(x, sel, n_sel);
+    const bool fp16 = filter_use_fp16(x, nq, k, mode, f.allowed_rows(x, exclude));
     FilterPlan p;
-    VQ_TRY(filter_prepare(x, fn, sel, n_sel, exclude, fp16, &p));
+    VQ_TRY(filter_prepare(x, fn, f, exclude, fp16, &p));
     if (p.m == 0) return filter_fill_empty(x, nq, k, groups, rows_out, dist);
     return fp16 ? search_grouped_fp16(x, d_queries, nq, k, groups, rows_out, dist, p.bits, p.nA)
                 : search_grouped_filtered_gather(x, d_queries, nq, k, p, groups, rows_out, dist);
 }
 
-// Host forms of the filtered searches: the queries go up from pinned staging, the results come back through it, one wait.
+// Host forms (vq_index_search's fast path, the filtered and clip searches): the queries go up from pinned staging; all but the clip search take their results through h_res.
 int stage_queries(vq_index* x, const float* queries, int nq) {
-    const int64_t q_bytes = (int64_t)nq * x->dim * 4;
-    VQ_TRY(reserve_buf(x->d_q, x->q_cap, (int64_t)nq * x->dim));
-    if (q_bytes > x->hq_cap) {
-        if (x->h_q) (void)hipHostFree(x->h_q);
-        x->h_q = nullptr; x->hq_cap = 0;
-        VQ_HIP(hipHostMalloc((void**)&x->h_q, (size_t)std::max<int64_t>(q_bytes, 64 << 10)));
-        x->hq_cap = std::max<int64_t>(q_bytes, 64 << 10);
-    }
-    std::memcpy(x->h_q, queries, (size_t)q_bytes);
-    VQ_HIP(hipMemcpyAsync(x->d_q, x->h_q, (size_t)q_bytes, hipMemcpyHostToDevice, x->stream));
+    const int64_t count = (int64_t)nq * x->dim;
+    VQ_TRY(x->d_q.reserve(count));
+    VQ_TRY(x->h_q.reserve(count, (64 << 10) / 4));
+    std::memcpy(x->h_q, queries, (size_t)count * 4);
+    VQ_HIP(hipMemcpyAsync(x->d_q, x->h_q, (size_t)count * 4, hipMemcpyHostToDevice, x->stream));
     return 0;
 }
 
-int host_results(vq_index* x, int64_t bytes) {          // h_res holds at least `bytes` (pinned; the stream is idle when it is replaced)
-    if (bytes <= x->hres_cap) return 0;
+int host_results(vq_index* x, int64_t bytes) {          // h_res holds at least `bytes` (pinned + mapped; the stream is idle when it is replaced)
+    if (bytes <= x->h_res.cap) return 0;
     VQ_HIP(hipStreamSynchronize(x->stream));
-    if (x->h_res) (void)hipHostFree(x->h_res);
-    x->h_res = nullptr; x->hres_cap = 0;
-    VQ_HIP(hipHostMalloc((void**)&x->h_res, (size_t)std::max<int64_t>(bytes, 64 << 10), hipHostMallocMapped));
-    VQ_HIP(hipHostGetDevicePointer((void**)&x->d_res, x->h_res, 0));
-    x->hres_cap = std::max<int64_t>(bytes, 64 << 10);
-    return 0;
+    return x->h_res.reserve(bytes, 64 << 10);
 }
 
 // ---- clip search (knn_set.h) ----
@@ -932,14 +977,11 @@ bool set_fp16_ok(const vq_index* x) { return (x->dim == 256 || x->dim == 512 || 
 
 // Everything that can refuse a clip search before any work is queued: the mode, stale ranks or labels, the filter's labels, and
 // mode 2 where the fp16 path does not exist.
-int set_precheck(vq_index* x, const char* fn, int mode, const int32_t* sel, int32_t n_sel) {
-    VQ_CHECK(mode >= 0 && mode <= 2, "%s: mode %d unknown", fn, mode);
-    VQ_CHECK(x->rank_n == 0 || x->rank_n == x->size, "%s: the id ranks cover %lld rows, the index holds %lld "
-             "(call vq_index_set_id_ranks again after adding rows, or clear them)", fn, (long long)x->rank_n, (long long)x->size);
-    VQ_CHECK(x->group_n == x->size && (int64_t)x->h_goff.size() == (int64_t)x->n_groups + 1, "%s: the group labels cover %lld rows, "
-             "the index holds %lld (call vq_index_set_groups after adding rows)", fn, (long long)x->group_n, (long long)x->size);
-    for (int32_t i = 0; i < n_sel; ++i)
-        VQ_CHECK(sel[i] >= 0 && sel[i] < x->n_groups, "%s: group %d outside [0, %d)", fn, (int)sel[i], (int)x->n_groups);
+int set_precheck(vq_index* x, const char* fn, int mode, const FilterLabels& f) {
+    VQ_TRY(check_mode(fn, mode));
+    VQ_TRY(check_ranks(x, fn));
+    VQ_TRY(check_labels(x, fn));
+    VQ_TRY(check_label_range(x, fn, f));
     if (mode != 1) VQ_TRY(refresh_norm_range(x));
     if (mode == 2) VQ_CHECK(set_fp16_ok(x), "%s: the fp16 path needs dim 256, 512 or 768 and near-unit rows (0.5 <= |row|^2 <= 2; rows "
                                             "added with normalize=0 are measured); mode 1 takes any call", fn);
@@ -947,24 +989,22 @@ int set_precheck(vq_index* x, const char* fn, int mode, const int32_t* sel, int3
 }
 
 // d_queries [m][dim], g_out / d_out [k], match [k][m] or null: all device memory.  Asynchronous on the index's stream.
-int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, int k, int mode, const int32_t* sel, int32_t n_sel,
-                   int exclude, int32_t* g_out, float* d_out, int32_t* match) {
+int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, int k, int mode, const FilterLabels& f, int exclude,
+                   int32_t* g_out, float* d_out, int32_t* match) {
     FilterPlan p;
-    VQ_TRY(filter_prepare(x, fn, sel, n_sel, exclude, true, &p));
+    VQ_TRY(filter_prepare(x, fn, f, exclude, true, &p));
     if (!p.all && p.m == 0) {                               // nothing allowed: every slot empty
         if (match) VQ_HIP(hipMemsetAsync(match, 0xff, (size_t)k * m * 4, x->stream));
-        VQ_TRY(filter_fill_empty(x, 1, k, g_out, nullptr, d_out));
-        x->stats[2] = 1;
-        return 0;
+        return filter_fill_empty(x, 1, k, g_out, nullptr, d_out);
     }
     const uint32_t* allow = p.all ? nullptr : p.bits;
     const int64_t n = x->size, ld = round_up(n, 64);
     const int G = x->n_groups, nA = p.all ? G : p.nA;
-    const int nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK), lpg = grouped_lpg(x);
-    const bool use_fp16 = mode == 2 || (mode == 0 && set_fp16_ok(x) && x->size >= 16384);     // the plain search's rule
-    VQ_TRY(reserve_buf(x->d_ssum, x->ssum_cap, 2 * (int64_t)G));
-    VQ_TRY(reserve_buf(x->d_scand, x->scand_cap, 2 * (int64_t)G + 2));
-    VQ_TRY(reserve_buf(x->d_sekey, x->sekey_cap, (int64_t)G + (int64_t)nblocks * kl));
+    const int nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK), lpg = lanes_per_group(n, G);
+    const bool use_fp16 = mode == 2 || (mode == 0 && set_fp16_ok(x) && x->size >= FP16_AUTO_MIN_ROWS);     // the plain search's rule
+    VQ_TRY(x->d_ssum.reserve(2 * (int64_t)G));
+    VQ_TRY(x->d_scand.reserve(2 * (int64_t)G + 2));
+    VQ_TRY(x->d_sekey.reserve((int64_t)G + (int64_t)nblocks * kl));
     double* sum16 = x->d_ssum; double* acc = sum16 + G;
     int32_t* cand = x->d_scand; int32_t* candpos = cand + G; int32_t* cand_n = candpos + G; int32_t* flag = cand_n + 1;
     uint64_t* ekey = x->d_sekey; uint64_t* partial = ekey + G;
@@ -975,17 +1015,14 @@ int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, i
         const bool from_dist = fl == nullptr;
         int64_t qs = std::max<int64_t>(1, std::min<int64_t>(m, ((int64_t)32 << 20) / G));                 // group minima: <= 256 MiB
         if (from_dist) qs = std::max<int64_t>(1, std::min<int64_t>(qs, ((int64_t)128 << 20) / ld));         // distances: <= 512 MiB
-        VQ_TRY(reserve_buf(x->d_gkeys, x->gkeys_cap, qs * G));
-        if (from_dist) VQ_TRY(reserve_buf(x->d_dist, x->dist_cap, qs * ld));
+        VQ_TRY(x->d_gkeys.reserve(qs * G));
+        if (from_dist) VQ_TRY(x->d_dist.reserve(qs * ld));
         auto gmin = from_dist ? (allow ? set_group_min_kernel<true, true> : set_group_min_kernel<true, false>)
                               : (allow ? set_group_min_kernel<false, true> : set_group_min_kernel<false, false>);
         for (int64_t q0 = 0; q0 < m; q0 += qs) {
             const int cur = (int)std::min<int64_t>(qs, m - q0);
             const float* qp = d_queries + q0 * x->dim;
-            if (from_dist) {
-                Prof pr(x, I_EXACT_DIST);
-                hipLaunchKernelGGL(exact_dist_kernel, dim3(cdiv(n, 64), cdiv(cur, 32)), dim3(256), 0, x->stream, x->rows, n, x->dim, qp, cur, x->d_dist, ld);
-            }
+            if (from_dist) VQ_TRY(exact_dist(x, false, qp, cur, ld));      // always the tiled kernel
             Prof pr(x, from_dist ? I_SELECT : I_EXACT_DIST);
             hipLaunchKernelGGL(gmin, dim3(nblocks, cur), dim3(256), 0, x->stream, x->d_dist, ld, x->rows, x->dim, qp, x->d_goff, x->d_grows, G, lpg,
                                x->d_gkeys, fl, tie, allow);
@@ -1003,16 +1040,13 @@ int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, i
         int64_t qc = std::max<int64_t>(16, ((int64_t)64 << 20) / G / 16 * 16);          // gbest [qc][G]: <= 256 MiB
         qc = std::min<int64_t>(qc, round_up(m, 16));
         if (qc >= SCAN2_QT) qc = qc / SCAN2_QT * SCAN2_QT;                              // whole query tiles of the batch mainloop
-        VQ_TRY(reserve_buf(x->d_q16, x->q16_cap, round_up(qc, SCAN2_QT) * x->dim));
-        VQ_TRY(reserve_buf(x->d_gbest, x->gbest_cap, qc * G));
-        VQ_TRY(reserve_buf(x->d_sqn, x->sqn_cap, m));
-        VQ_TRY(reserve_buf(x->d_sckeys, x->sckeys_cap, std::min<int64_t>(SET_KEY_BUDGET, (int64_t)G * m)));
-        if (!x->d_gcounters) {
-            VQ_HIP(hipMalloc((void**)&x->d_gcounters, 3 * sizeof(unsigned long long)));
-            VQ_HIP(hipHostMalloc((void**)&x->h_gcounters, 3 * sizeof(unsigned long long)));
-        }
-        VQ_TRY(set_dyn_lds((const void*)set_group_max_kernel<false>, G2_LDS_BYTES));
-        VQ_TRY(set_dyn_lds((const void*)set_group_max_kernel<true>, G2_LDS_BYTES));
+        VQ_TRY(x->d_q16.reserve(round_up(qc, SCAN2_QT) * x->dim));
+        VQ_TRY(x->d_gbest.reserve(qc * G));
+        VQ_TRY(x->d_sqn.reserve(m));
+        VQ_TRY(x->d_sckeys.reserve(std::min<int64_t>(SET_KEY_BUDGET, (int64_t)G * m)));
+        VQ_TRY(ensure_gcounters(x));
+        VQ_TRY(set_dyn_lds(x, (const void*)set_group_max_kernel<false>, G2_LDS_BYTES));
+        VQ_TRY(set_dyn_lds(x, (const void*)set_group_max_kernel<true>, G2_LDS_BYTES));
         VQ_HIP(hipMemsetAsync(x->d_gcounters, 0, 3 * sizeof(unsigned long long), x->stream));
         VQ_HIP(hipMemsetAsync(cand_n, 0, 8, x->stream));                                 // candidate count and the call's flag
         hipLaunchKernelGGL(set_query_norm_kernel, dim3(m), dim3(64), 0, x->stream, d_queries, x->dim, x->d_sqn, flag);
@@ -1021,18 +1055,12 @@ int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, i
             const int cur = (int)std::min<int64_t>(qc, m - q0);
             const bool small = cur <= 16;                   // the streaming group-max scan of the grouped search
             const int64_t q_pad = round_up(cur, small ? 16 : SCAN2_QT);
-            {
-                Prof pr(x, I_TO_F16);
-                const int64_t total4 = q_pad * x->dim / 4;
-                hipLaunchKernelGGL(queries_to_f16_kernel, dim3((int)std::min<int64_t>((total4 + 255) / 256, 2048)), dim3(256), 0, x->stream,
-                                   d_queries + q0 * x->dim, x->d_q16, cur, q_pad, x->dim);
-            }
+            queries_to_f16(x, d_queries + q0 * x->dim, cur, q_pad);
             VQ_HIP(hipMemsetAsync(x->d_gbest, 0, (size_t)cur * G * 4, x->stream));
             {
                 Prof pr(x, I_MFMA_SCAN);
                 if (small) {
-                    auto scan = x->dim == 768 ? scan3_group_max_kernel<24> : x->dim == 512 ? scan3_group_max_kernel<16> : scan3_group_max_kernel<8>;
-                    if (allow) scan = x->dim == 768 ? scan3_group_max_kernel<24, true> : x->dim == 512 ? scan3_group_max_kernel<16, true> : scan3_group_max_kernel<8, true>;
+                    auto scan = group_max_scan(x, allow != nullptr);
                     hipLaunchKernelGGL(scan, dim3(cdiv(streams, 4), 1), dim3(256), 0, x->stream, x->d_q16, x->rows16, streams, x->d_group, x->d_sgroup,
                                        cur, G, x->d_gbest, allow);
                 } else {
@@ -1061,7 +1089,7 @@ int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, i
         Prof pr(x, I_SELECT);
         hipLaunchKernelGGL(set_select_block_kernel, dim3(nblocks), dim3(256), 0, x->stream, ekey, G, kl, partial);
         hipLaunchKernelGGL(set_select_merge_kernel, dim3(1), dim3(256), 0, x->stream, partial, (int64_t)nblocks * kl, k, g_out, d_out,
-                           use_fp16 ? flag : nullptr, use_fp16 ? x->d_gcounters : nullptr);
+                           use_fp16 ? flag : nullptr, use_fp16 ? x->d_gcounters.p : nullptr);
         if (match)
             hipLaunchKernelGGL(set_match_rows_kernel, dim3(k, std::min(cdiv(m, 4), 64)), dim3(256), 0, x->stream, g_out, m, x->rows, x->dim, d_queries,
                                x->d_goff, x->d_grows, candpos, x->d_sckeys, use_fp16 ? flag : nullptr, match, tie);
@@ -1069,12 +1097,42 @@ int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, i
     VQ_HIP(hipGetLastError());
     if (use_fp16) {
         VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
-        x->stats_pending = false; x->gstats_pending = true;
+        set_stats(x, STATS_GCOUNTERS);
     } else {
-        x->stats[0] = 0; x->stats[1] = 0; x->stats[2] = 1;
-        x->stats_pending = false; x->gstats_pending = false;
+        set_stats(x, STATS_HOST, 0, 0, 1);
     }
     return 0;
+}
+
+// ---- what the search entry points share ----
+// One argument check per shape of call.  arrays: every array the call reads or writes is there.
+int check_batch_args(const char* fn, const vq_index* x, int nq, int k, bool arrays) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && (nq == 0 || arrays), "%s: bad argument", fn);
+    return 0;
+}
+int check_filtered_args(const char* fn, const vq_index* x, int nq, int k, const int32_t* groups, int32_t n_sel, int exclude, bool arrays) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) && (nq == 0 || arrays),
+             "%s: bad argument", fn);
+    return 0;
+}
+int check_set_args(const char* fn, const vq_index* x, int m, int k, const int32_t* groups, int32_t n_sel, int exclude, bool arrays) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && m >= 1 && m <= SET_MAX_M && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) && arrays,
+             "%s: bad argument (1 <= m <= %d, 1 <= k <= 1024)", fn, SET_MAX_M);
+    return 0;
+}
+
+// a host form's answer from an empty index: no candidates (hnsw.py:243-244 returns []); b: the grouped forms' second id array, or null
+void host_empty(int64_t count, int32_t* a, int32_t* b, float* dist) {
+    for (int64_t i = 0; i < count; ++i) { a[i] = -1; if (b) b[i] = -1; dist[i] = __builtin_inff(); }
+}
+
+// device results of the plain host forms: ids and distances [count] each
+int reserve_id_dist(vq_index* x, int64_t count) {
+    VQ_TRY(x->d_ids.reserve(count));
+    return x->d_out.reserve(count);
 }
 
 }  // namespace
@@ -1091,12 +1149,7 @@ int index_search_local(vq_index* x, const float* d_queries, int nq, int k, int m
     std::lock_guard<std::mutex> lk(x->mu);
     *stream_out = x->stream;
     *size_out = x->size;
-    if (x->size == 0) {
-        const int64_t count = (int64_t)nq * k;
-        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, d_ids, d_dist, count);
-        VQ_HIP(hipGetLastError());
-        return 0;
-    }
+    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, d_ids, nullptr, d_dist);
     return search_dispatch(x, d_queries, nq, k, mode, d_ids, d_dist);
 }
 }  // namespace vq
@@ -1124,23 +1177,6 @@ int vq_index_destroy(vq_index* x) {
     if (x->own_stream) (void)hipStreamDestroy(x->own_stream);
     for (auto& ev : x->events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto ev : x->pool) (void)hipEventDestroy(ev);
-    (void)hipFree(x->rows); (void)hipFree(x->rows16); (void)hipFree(x->d_q); (void)hipFree(x->d_dist);
-    (void)hipFree(x->d_ids); (void)hipFree(x->d_out); (void)hipFree(x->d_partial);
-    (void)hipFree(x->d_q16); (void)hipFree(x->d_keys); (void)hipFree(x->d_flags); (void)hipFree(x->d_slots);
-    (void)hipFree(x->d_counters); (void)hipFree(x->d_fb_partial); (void)hipFree(x->d_upd); (void)hipFree(x->d_rmw);
-    if (x->h_counters) (void)hipHostFree(x->h_counters);
-    if (x->h_q) (void)hipHostFree(x->h_q);
-    if (x->h_res) (void)hipHostFree(x->h_res);
-    (void)hipFree(x->d_norm_range); (void)hipFree(x->d_rank);
-    (void)hipFree(x->d_ssum); (void)hipFree(x->d_scand); (void)hipFree(x->d_sqn); (void)hipFree(x->d_sekey); (void)hipFree(x->d_sckeys);
-    (void)hipFree(x->d_sout);
-    (void)hipFree(x->d_group); (void)hipFree(x->d_gbest); (void)hipFree(x->d_gcand); (void)hipFree(x->d_gkeys); (void)hipFree(x->d_gpart);
-    (void)hipFree(x->d_gcounters); (void)hipFree(x->d_gout); (void)hipFree(x->d_flt); (void)hipFree(x->d_fcand); (void)hipFree(x->d_flist);
-    for (int i = 0; i < vq_index::FLT_STAGE_SLOTS; ++i) {
-        if (x->h_flt[i]) (void)hipHostFree(x->h_flt[i]);
-        if (x->flt_ev[i]) (void)hipEventDestroy(x->flt_ev[i]);
-    }
-    if (x->h_gcounters) (void)hipHostFree(x->h_gcounters);
     delete x;
     return 0;
 }
@@ -1155,11 +1191,7 @@ int vq_index_clear(vq_index* x) {
     VQ_CHECK(x, "vq_index_clear: null handle");
     std::lock_guard<std::mutex> lk(x->mu);
     x->size = 0;
-    if (x->d_norm_range) {
-        const uint32_t init[2] = {0x3f800000u, 0x3f800000u};
-        VQ_HIP(hipMemcpyAsync(x->d_norm_range, init, 8, hipMemcpyHostToDevice, x->stream));
-        VQ_HIP(hipStreamSynchronize(x->stream));
-    }
+    if (x->d_norm_range) VQ_TRY(init_norm_range(x));
     x->norm_dirty = false; x->near_unit = true; x->row_norm_max = 1.0f;
     x->rank_n = 0;
     x->group_n = 0; x->n_groups = 0; x->h_goff.clear();
@@ -1180,14 +1212,14 @@ int vq_index_set_id_ranks(vq_index* x, const int32_t* rank_of_row, int64_t n) {
                  "(row %lld holds %d)", (long long)n - 1, (long long)r, (int)t);
         inv[(size_t)t] = (int32_t)r;
     }
-    if (n > x->rank_cap) {
+    if (2 * n > x->d_rank.cap) {                                    // rank [cap] | rank_inv [cap]
         VQ_HIP(hipStreamSynchronize(x->stream));                   // a search in flight may still read the old arrays
-        (void)hipFree(x->d_rank); x->d_rank = nullptr; x->d_rank_inv = nullptr; x->rank_cap = 0; x->rank_n = 0;
+        x->d_rank.release(); x->d_rank_inv = nullptr; x->rank_n = 0;
         const int64_t cap = round_up(std::max<int64_t>(n, x->cap), 1024);
-        hipError_t e = hipMalloc((void**)&x->d_rank, (size_t)cap * 8);
+        hipError_t e = hipMalloc((void**)&x->d_rank.p, (size_t)cap * 8);
         if (e != hipSuccess) return fail(VQ_ERR_OOM, "vq_index_set_id_ranks: hipMalloc failed: %s", hipGetErrorString(e));
         x->d_rank_inv = x->d_rank + cap;
-        x->rank_cap = cap;
+        x->d_rank.cap = 2 * cap;
     }
     VQ_HIP(hipMemcpyAsync(x->d_rank, rank_of_row, (size_t)n * 4, hipMemcpyHostToDevice, x->stream));
     VQ_HIP(hipMemcpyAsync(x->d_rank_inv, inv.data(), (size_t)n * 4, hipMemcpyHostToDevice, x->stream));
@@ -1228,13 +1260,13 @@ int vq_index_set_groups(vq_index* x, const int32_t* group_of_row, int64_t n, int
         for (int i = 1; i < SCAN_STREAM_ROWS && same; ++i) same = l[i] == l[0];
         sg[s] = same ? l[0] : -1;
     }
-    if (total > x->group_cap) {
+    if (total > x->d_group.cap) {
         VQ_HIP(hipStreamSynchronize(x->stream));                   // a search in flight may still read the old arrays
-        (void)hipFree(x->d_group); x->d_group = nullptr; x->group_cap = 0; x->group_n = 0; x->n_groups = 0;
+        x->d_group.release(); x->group_n = 0; x->n_groups = 0;
         const int64_t cap = total + total / 4 + 1024;
-        hipError_t e = hipMalloc((void**)&x->d_group, (size_t)cap * 4);
+        hipError_t e = hipMalloc((void**)&x->d_group.p, (size_t)cap * 4);
         if (e != hipSuccess) return fail(VQ_ERR_OOM, "vq_index_set_groups: hipMalloc failed: %s", hipGetErrorString(e));
-        x->group_cap = cap;
+        x->d_group.cap = cap;
     }
     VQ_HIP(hipMemcpyAsync(x->d_group, h.data(), (size_t)total * 4, hipMemcpyHostToDevice, x->stream));
     VQ_HIP(hipStreamSynchronize(x->stream));                       // `h` is this frame's
@@ -1291,12 +1323,10 @@ int vq_index_update_rows(vq_index* x, const float* rows, const int64_t* row_numb
     }
     const int64_t m = (int64_t)keep.size();
     const int64_t row_bytes = (int64_t)x->dim * 4;
-    VQ_TRY(reserve_buf(x->d_upd, x->upd_cap, m * x->dim + m * 2 + 4));
+    VQ_TRY(x->d_upd.reserve(m * x->dim + m * 2 + 4));
     int64_t* d_rn = (int64_t*)(x->d_upd + round_up(m * x->dim, 2));       // 8-byte aligned behind the rows
     std::vector<int64_t> rn((size_t)m);
-    // `rn` and the caller's `rows` feed asynchronous copies: whichever way this function is left (every VQ_HIP / VQ_TRY below
-    // returns early on error), the stream is drained before `rn` dies (declared after it: destroyed first)
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{x->stream};
+    StreamDrain drain{x->stream};          // `rn` and the caller's `rows` feed asynchronous copies
     if (m == n) {
         VQ_HIP(hipMemcpyAsync(x->d_upd, rows, (size_t)(n * row_bytes), hipMemcpyHostToDevice, x->stream));
         for (int64_t i = 0; i < m; ++i) rn[(size_t)i] = row_numbers[i];
@@ -1309,24 +1339,14 @@ int vq_index_update_rows(vq_index* x, const float* rows, const int64_t* row_numb
     VQ_HIP(hipMemcpyAsync(d_rn, rn.data(), (size_t)m * 8, hipMemcpyHostToDevice, x->stream));
     {
         Prof p(x, I_NORMALIZE);
-        if (normalize) {
-            hipLaunchKernelGGL(normalize_rows_kernel, dim3(cdiv(m, NORM_ROWS)), dim3(NORM_ROWS), 0, x->stream, x->d_upd, m, x->dim);
-        } else {          // measured, not trusted (finish_add); the range only widens: a replaced row's old norm stays covered
-            if (!x->d_norm_range) {
-                VQ_HIP(hipMalloc((void**)&x->d_norm_range, 8));
-                const uint32_t init[2] = {0x3f800000u, 0x3f800000u};
-                VQ_HIP(hipMemcpyAsync(x->d_norm_range, init, 8, hipMemcpyHostToDevice, x->stream));
-                VQ_HIP(hipStreamSynchronize(x->stream));
-            }
-            hipLaunchKernelGGL(row_norm_range_kernel, dim3(cdiv(m, 4)), dim3(256), 0, x->stream, x->d_upd, m, x->dim, x->d_norm_range);
-            x->norm_dirty = true;
-        }
+        // not normalised: measured, not trusted (finish_add); the range only widens, so a replaced row's old norm stays covered
+        if (normalize) hipLaunchKernelGGL(normalize_rows_kernel, dim3(cdiv(m, NORM_ROWS)), dim3(NORM_ROWS), 0, x->stream, x->d_upd, m, x->dim);
+        else VQ_TRY(measure_norm_range(x, x->d_upd, m));
     }
     {
         Prof p(x, I_TO_F16);
         const int64_t count4 = m * x->dim / 4;
-        hipLaunchKernelGGL(scatter_rows_kernel, dim3((int)std::min<int64_t>((count4 + 255) / 256, 2048)), dim3(256), 0, x->stream,
-                           x->d_upd, d_rn, m, x->dim, x->rows, x->rows16);
+        hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for(count4)), dim3(256), 0, x->stream, x->d_upd, d_rn, m, x->dim, x->rows, x->rows16);
     }
     VQ_HIP(hipGetLastError());
     VQ_TRY(refresh_norm_range(x));
@@ -1356,8 +1376,8 @@ int vq_index_remove_rows(vq_index* x, const int64_t* row_numbers, int64_t n) {
     const int64_t w_rm = words(2 * m), w_map = words(size), w_src = words(moved), w_S = words(size + 1),
                   w_tiles = words(cdiv(size, RM_SCAN_TILE) + 2), w_K = words((int64_t)G + 1), w_rinv = ranks ? words(n_new) : 0,
                   w_grp = groups ? words(n_pad + G + 1 + size + streams) : 0;
-    VQ_TRY(reserve_buf(x->d_rmw, x->rmw_cap, w_rm + w_map + w_src + w_S + w_tiles + w_K + w_rinv + w_grp));
-    int64_t* d_rm = (int64_t*)x->d_rmw;
+    VQ_TRY(x->d_rmw.reserve(w_rm + w_map + w_src + w_S + w_tiles + w_K + w_rinv + w_grp));
+    int64_t* d_rm = (int64_t*)x->d_rmw.p;
     int32_t* newrow = x->d_rmw + w_rm;
     int32_t* src_of = newrow + w_map;
     int32_t* S = src_of + w_src;
@@ -1365,8 +1385,7 @@ int vq_index_remove_rows(vq_index* x, const int64_t* row_numbers, int64_t n) {
     int32_t* K = tiles + w_tiles;
     int32_t* rinv_new = K + w_K;
     int32_t* grp = rinv_new + w_rinv;
-    // `rm` feeds an asynchronous copy: whichever way this function is left, the stream is drained before `rm` dies
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{x->stream};
+    StreamDrain drain{x->stream};          // `rm` feeds an asynchronous copy
     VQ_HIP(hipMemcpyAsync(d_rm, rm.data(), (size_t)m * 8, hipMemcpyHostToDevice, x->stream));
     hipLaunchKernelGGL(remove_row_map_kernel, dim3(grid_for(size)), dim3(256), 0, x->stream, d_rm, m, size, r0, newrow, src_of);
     VQ_HIP(hipGetLastError());
@@ -1375,7 +1394,7 @@ int vq_index_remove_rows(vq_index* x, const int64_t* row_numbers, int64_t n) {
     // destinations lie below every later chunk's sources, so stream order alone makes this safe.
     if (moved > 0) {
         const int64_t chunk = std::min<int64_t>(moved, std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)x->dim * 4)));   // <= 256 MiB
-        VQ_TRY(reserve_buf(x->d_upd, x->upd_cap, chunk * x->dim));
+        VQ_TRY(x->d_upd.reserve(chunk * x->dim));
         for (int64_t d0 = 0; d0 < moved; d0 += chunk) {
             const int64_t cnt = std::min<int64_t>(chunk, moved - d0);
             const int64_t count4 = cnt * x->dim / 4, dst = (r0 + d0) * x->dim;
@@ -1439,111 +1458,69 @@ int vq_index_remove_rows(vq_index* x, const int64_t* row_numbers, int64_t n) {
 }
 
 int vq_index_search_device(vq_index* x, const void* d_queries, int nq, int k, int mode, void* d_ids, void* d_dist) {
-    VQ_TRY(require_init());
-    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && (nq == 0 || (d_queries && d_ids && d_dist)), "vq_index_search_device: bad argument");
+    VQ_TRY(check_batch_args("vq_index_search_device", x, nq, k, d_queries && d_ids && d_dist));
     if (nq == 0) return 0;
     std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {                       // empty index: no candidates, as vq_index_search reports it
-        const int64_t count = (int64_t)nq * k;
-        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, (int32_t*)d_ids, (float*)d_dist, count);
-        VQ_HIP(hipGetLastError());
-        return 0;
-    }
+    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_ids, nullptr, (float*)d_dist);      // as vq_index_search reports it
     return search_dispatch(x, (const float*)d_queries, nq, k, mode, (int32_t*)d_ids, (float*)d_dist);
 }
 
 int vq_index_search(vq_index* x, const float* queries, int nq, int k, int mode, int32_t* ids, float* dist) {
-    VQ_TRY(require_init());
-    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && (nq == 0 || (queries && ids && dist)), "vq_index_search: bad argument");
+    VQ_TRY(check_batch_args("vq_index_search", x, nq, k, queries && ids && dist));
     if (nq == 0) return 0;
     std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {                       // empty index: no candidates (hnsw.py:243-244 returns [])
-        for (int64_t i = 0; i < (int64_t)nq * k; ++i) { ids[i] = -1; dist[i] = __builtin_inff(); }
-        return 0;
-    }
-    VQ_TRY(reserve_buf(x->d_q, x->q_cap, (int64_t)nq * x->dim));
-    const int64_t q_bytes = (int64_t)nq * x->dim * 4, res_bytes = (int64_t)nq * k * 8;
+    const int64_t count = (int64_t)nq * k;
+    if (x->size == 0) { host_empty(count, ids, nullptr, dist); return 0; }
+    const int64_t q_bytes = (int64_t)nq * x->dim * 4, res_bytes = count * 8;
     static const bool host_fast = !(getenv("VQ_AMD_HOST_FAST") && atoi(getenv("VQ_AMD_HOST_FAST")) == 0);      // A/B switch
     if (host_fast && q_bytes <= ((int64_t)256 << 10) && res_bytes <= ((int64_t)16 << 10)) {      // (larger results: scattered 4-byte stores across PCIe lose to one copy)
         // The reference caller's call (one query, k * 2 results: video_search_system.py:297) and small batches: the query goes up
         // from pinned staging, the kernels write ids | distances straight into pinned, device-mapped host memory, and the ONE
         // wait below is the only host/device round trip — no copy-back commands, no fallback launches unless a query was flagged.
-        if (q_bytes > x->hq_cap) {
-            if (x->h_q) (void)hipHostFree(x->h_q);
-            x->h_q = nullptr; x->hq_cap = 0;
-            VQ_HIP(hipHostMalloc((void**)&x->h_q, (size_t)std::max<int64_t>(q_bytes, 64 << 10)));
-            x->hq_cap = std::max<int64_t>(q_bytes, 64 << 10);
-        }
-        if (res_bytes > x->hres_cap) {
-            VQ_HIP(hipStreamSynchronize(x->stream));
-            if (x->h_res) (void)hipHostFree(x->h_res);
-            x->h_res = nullptr; x->hres_cap = 0;
-            VQ_HIP(hipHostMalloc((void**)&x->h_res, (size_t)std::max<int64_t>(res_bytes, 64 << 10), hipHostMallocMapped));
-            VQ_HIP(hipHostGetDevicePointer((void**)&x->d_res, x->h_res, 0));
-            x->hres_cap = std::max<int64_t>(res_bytes, 64 << 10);
-        }
-        memcpy(x->h_q, queries, (size_t)q_bytes);
-        VQ_HIP(hipMemcpyAsync(x->d_q, x->h_q, (size_t)q_bytes, hipMemcpyHostToDevice, x->stream));
-        int32_t* r_ids = (int32_t*)x->d_res;
-        float* r_dist = (float*)(x->d_res + (size_t)nq * k * 4);
-        x->fb_deferred = false;
+        VQ_TRY(host_results(x, res_bytes));
+        VQ_TRY(stage_queries(x, queries, nq));
+        int32_t* r_ids = (int32_t*)x->h_res.dev;
+        float* r_dist = (float*)(x->h_res.dev + count * 4);
         VQ_TRY(search_dispatch(x, x->d_q, nq, k, mode, r_ids, r_dist, true));
         VQ_HIP(hipStreamSynchronize(x->stream));
-        if (x->fb_deferred) {
-            x->fb_deferred = false;
-            for (int i = 0; i < 3; ++i) x->stats[i] = x->h_counters[1 + i];
+        if (x->stats_at == STATS_DEFERRED) {
+            stats_from_counters(x);
             if (x->h_counters[0] > 0) {                      // some proof did not close: the exact redo, then one more wait
-                launch_fallback(x, x->d_q, nq, k, r_ids, r_dist, x->d_counters_host);
+                launch_fallback(x, x->d_q, nq, k, r_ids, r_dist, x->h_counters.dev);
                 VQ_HIP(hipGetLastError());
                 VQ_HIP(hipStreamSynchronize(x->stream));
             }
         }
-        memcpy(ids, x->h_res, (size_t)nq * k * 4);
-        memcpy(dist, x->h_res + (size_t)nq * k * 4, (size_t)nq * k * 4);
+        std::memcpy(ids, x->h_res, (size_t)count * 4);
+        std::memcpy(dist, x->h_res + count * 4, (size_t)count * 4);
         return 0;
     }
-    if ((int64_t)nq * k > x->out_cap) {
-        int64_t c1 = x->out_cap, c2 = x->out_cap;
-        VQ_TRY(reserve_buf(x->d_ids, c1, (int64_t)nq * k));
-        VQ_TRY(reserve_buf(x->d_out, c2, (int64_t)nq * k));
-        x->out_cap = (int64_t)nq * k;
-    }
-    VQ_HIP(hipMemcpyAsync(x->d_q, queries, (size_t)nq * x->dim * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_TRY(x->d_q.reserve((int64_t)nq * x->dim));
+    VQ_TRY(reserve_id_dist(x, count));
+    VQ_HIP(hipMemcpyAsync(x->d_q, queries, (size_t)q_bytes, hipMemcpyHostToDevice, x->stream));
     VQ_TRY(search_dispatch(x, x->d_q, nq, k, mode, x->d_ids, x->d_out));
-    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)nq * k * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)nq * k * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
     VQ_HIP(hipStreamSynchronize(x->stream));
     return 0;
 }
 
 int vq_index_search_grouped_device(vq_index* x, const void* d_queries, int nq, int k, int mode, void* d_groups, void* d_rows, void* d_dist) {
-    VQ_TRY(require_init());
-    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && (nq == 0 || (d_queries && d_groups && d_rows && d_dist)),
-             "vq_index_search_grouped_device: bad argument");
+    VQ_TRY(check_batch_args("vq_index_search_grouped_device", x, nq, k, d_queries && d_groups && d_rows && d_dist));
     if (nq == 0) return 0;
     std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {
-        const int64_t count = (int64_t)nq * k;
-        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, (int32_t*)d_groups, (float*)d_dist, count);
-        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, (int32_t*)d_rows, (float*)d_dist, count);
-        VQ_HIP(hipGetLastError());
-        return 0;
-    }
+    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_groups, (int32_t*)d_rows, (float*)d_dist);
     return search_grouped_dispatch(x, (const float*)d_queries, nq, k, mode, (int32_t*)d_groups, (int32_t*)d_rows, (float*)d_dist);
 }
 
 int vq_index_search_grouped(vq_index* x, const float* queries, int nq, int k, int mode, int32_t* groups, int32_t* rows, float* dist) {
-    VQ_TRY(require_init());
-    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && (nq == 0 || (queries && groups && rows && dist)), "vq_index_search_grouped: bad argument");
+    VQ_TRY(check_batch_args("vq_index_search_grouped", x, nq, k, queries && groups && rows && dist));
     if (nq == 0) return 0;
     std::lock_guard<std::mutex> lk(x->mu);
     const int64_t count = (int64_t)nq * k;
-    if (x->size == 0) {
-        for (int64_t i = 0; i < count; ++i) { groups[i] = -1; rows[i] = -1; dist[i] = __builtin_inff(); }
-        return 0;
-    }
-    VQ_TRY(reserve_buf(x->d_q, x->q_cap, (int64_t)nq * x->dim));
-    VQ_TRY(reserve_buf(x->d_gout, x->gout_cap, 3 * count));
+    if (x->size == 0) { host_empty(count, groups, rows, dist); return 0; }
+    VQ_TRY(x->d_q.reserve((int64_t)nq * x->dim));
+    VQ_TRY(x->d_gout.reserve(3 * count));
     int32_t* d_g = x->d_gout; int32_t* d_r = d_g + count; float* d_d = (float*)(d_r + count);
     VQ_HIP(hipMemcpyAsync(x->d_q, queries, (size_t)nq * x->dim * 4, hipMemcpyHostToDevice, x->stream));
     VQ_TRY(search_grouped_dispatch(x, x->d_q, nq, k, mode, d_g, d_r, d_d));
@@ -1556,39 +1533,23 @@ int vq_index_search_grouped(vq_index* x, const float* queries, int nq, int k, in
 
 int vq_index_search_filtered_device(vq_index* x, const void* d_queries, int nq, int k, int mode, const int32_t* groups, int32_t n_sel,
                                     int exclude, void* d_ids, void* d_dist) {
-    VQ_TRY(require_init());
-    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
-             (nq == 0 || (d_queries && d_ids && d_dist)), "vq_index_search_filtered_device: bad argument");
+    VQ_TRY(check_filtered_args("vq_index_search_filtered_device", x, nq, k, groups, n_sel, exclude, d_queries && d_ids && d_dist));
     if (nq == 0) return 0;
     std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {
-        const int64_t count = (int64_t)nq * k;
-        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, (int32_t*)d_ids, (float*)d_dist, count);
-        VQ_HIP(hipGetLastError());
-        return 0;
-    }
+    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_ids, nullptr, (float*)d_dist);
     return search_filtered_dispatch(x, (const float*)d_queries, nq, k, mode, groups, n_sel, exclude, (int32_t*)d_ids, (float*)d_dist);
 }
 
 int vq_index_search_filtered(vq_index* x, const float* queries, int nq, int k, int mode, const int32_t* groups, int32_t n_sel, int exclude,
                              int32_t* ids, float* dist) {
-    VQ_TRY(require_init());
-    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
-             (nq == 0 || (queries && ids && dist)), "vq_index_search_filtered: bad argument");
+    static const char* fn = "vq_index_search_filtered";
+    VQ_TRY(check_filtered_args(fn, x, nq, k, groups, n_sel, exclude, queries && ids && dist));
     if (nq == 0) return 0;
     std::lock_guard<std::mutex> lk(x->mu);
     const int64_t count = (int64_t)nq * k;
-    if (x->size == 0) {
-        for (int64_t i = 0; i < count; ++i) { ids[i] = -1; dist[i] = __builtin_inff(); }
-        return 0;
-    }
-    if (count > x->out_cap) {
-        int64_t c1 = x->out_cap, c2 = x->out_cap;
-        VQ_TRY(reserve_buf(x->d_ids, c1, count));
-        VQ_TRY(reserve_buf(x->d_out, c2, count));
-        x->out_cap = count;
-    }
-    VQ_TRY(filter_precheck(x, "vq_index_search_filtered", nq, k, mode, n_sel, exclude));      // refuse before staging anything
+    if (x->size == 0) { host_empty(count, ids, nullptr, dist); return 0; }
+    VQ_TRY(reserve_id_dist(x, count));
+    VQ_TRY(filter_precheck(x, fn, nq, k, mode, n_sel, exclude));      // refuse before staging anything
     VQ_TRY(host_results(x, count * 8));
     VQ_TRY(stage_queries(x, queries, nq));
     VQ_TRY(search_filtered_dispatch(x, x->d_q, nq, k, mode, groups, n_sel, exclude, x->d_ids, x->d_out));
@@ -1602,37 +1563,26 @@ int vq_index_search_filtered(vq_index* x, const float* queries, int nq, int k, i
 
 int vq_index_search_grouped_filtered_device(vq_index* x, const void* d_queries, int nq, int k, int mode, const int32_t* groups,
                                             int32_t n_sel, int exclude, void* d_groups, void* d_rows, void* d_dist) {
-    VQ_TRY(require_init());
-    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
-             (nq == 0 || (d_queries && d_groups && d_rows && d_dist)), "vq_index_search_grouped_filtered_device: bad argument");
+    VQ_TRY(check_filtered_args("vq_index_search_grouped_filtered_device", x, nq, k, groups, n_sel, exclude,
+                               d_queries && d_groups && d_rows && d_dist));
     if (nq == 0) return 0;
     std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {
-        const int64_t count = (int64_t)nq * k;
-        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, (int32_t*)d_groups, (float*)d_dist, count);
-        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, (int32_t*)d_rows, (float*)d_dist, count);
-        VQ_HIP(hipGetLastError());
-        return 0;
-    }
+    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_groups, (int32_t*)d_rows, (float*)d_dist);
     return search_grouped_filtered_dispatch(x, (const float*)d_queries, nq, k, mode, groups, n_sel, exclude, (int32_t*)d_groups,
                                             (int32_t*)d_rows, (float*)d_dist);
 }
 
 int vq_index_search_grouped_filtered(vq_index* x, const float* queries, int nq, int k, int mode, const int32_t* groups, int32_t n_sel,
                                      int exclude, int32_t* groups_out, int32_t* rows, float* dist) {
-    VQ_TRY(require_init());
-    VQ_CHECK(x && nq >= 0 && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
-             (nq == 0 || (queries && groups_out && rows && dist)), "vq_index_search_grouped_filtered: bad argument");
+    static const char* fn = "vq_index_search_grouped_filtered";
+    VQ_TRY(check_filtered_args(fn, x, nq, k, groups, n_sel, exclude, queries && groups_out && rows && dist));
     if (nq == 0) return 0;
     std::lock_guard<std::mutex> lk(x->mu);
     const int64_t count = (int64_t)nq * k;
-    if (x->size == 0) {
-        for (int64_t i = 0; i < count; ++i) { groups_out[i] = -1; rows[i] = -1; dist[i] = __builtin_inff(); }
-        return 0;
-    }
-    VQ_TRY(reserve_buf(x->d_gout, x->gout_cap, 3 * count));
+    if (x->size == 0) { host_empty(count, groups_out, rows, dist); return 0; }
+    VQ_TRY(x->d_gout.reserve(3 * count));
     int32_t* d_g = x->d_gout; int32_t* d_r = d_g + count; float* d_d = (float*)(d_r + count);
-    VQ_TRY(filter_precheck(x, "vq_index_search_grouped_filtered", nq, k, mode, n_sel, exclude));
+    VQ_TRY(filter_precheck(x, fn, nq, k, mode, n_sel, exclude));      // refuse before staging anything
     VQ_TRY(host_results(x, count * 12));
     VQ_TRY(stage_queries(x, queries, nq));
     VQ_TRY(search_grouped_filtered_dispatch(x, x->d_q, nq, k, mode, groups, n_sel, exclude, d_g, d_r, d_d));
@@ -1647,39 +1597,37 @@ int vq_index_search_grouped_filtered(vq_index* x, const float* queries, int nq, 
 int vq_index_search_set_device(vq_index* x, const void* d_queries, int m, int k, int mode, const int32_t* groups, int32_t n_sel,
                                int exclude, void* d_groups_out, void* d_dist_out, void* d_match_rows) {
     static const char* fn = "vq_index_search_set_device";
-    VQ_TRY(require_init());
-    VQ_CHECK(x && m >= 1 && m <= SET_MAX_M && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
-             d_queries && d_groups_out && d_dist_out, "%s: bad argument (1 <= m <= %d, 1 <= k <= 1024)", fn, SET_MAX_M);
+    VQ_TRY(check_set_args(fn, x, m, k, groups, n_sel, exclude, d_queries && d_groups_out && d_dist_out));
     std::lock_guard<std::mutex> lk(x->mu);
     if (x->size == 0) {
-        hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(k, 256)), dim3(256), 0, x->stream, (int32_t*)d_groups_out, (float*)d_dist_out, (int64_t)k);
+        fill_no_result(x, (int32_t*)d_groups_out, (float*)d_dist_out, k);
         if (d_match_rows) VQ_HIP(hipMemsetAsync(d_match_rows, 0xff, (size_t)k * m * 4, x->stream));
         VQ_HIP(hipGetLastError());
         return 0;
     }
-    VQ_TRY(set_precheck(x, fn, mode, groups, n_sel));
-    return search_set_run(x, fn, (const float*)d_queries, m, k, mode, groups, n_sel, exclude, (int32_t*)d_groups_out, (float*)d_dist_out,
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(set_precheck(x, fn, mode, f));
+    return search_set_run(x, fn, (const float*)d_queries, m, k, mode, f, exclude, (int32_t*)d_groups_out, (float*)d_dist_out,
                           (int32_t*)d_match_rows);
 }
 
 int vq_index_search_set(vq_index* x, const float* queries, int m, int k, int mode, const int32_t* groups, int32_t n_sel, int exclude,
                         int32_t* groups_out, float* dist_out, int32_t* match_rows) {
     static const char* fn = "vq_index_search_set";
-    VQ_TRY(require_init());
-    VQ_CHECK(x && m >= 1 && m <= SET_MAX_M && k > 0 && k <= 1024 && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) &&
-             queries && groups_out && dist_out, "%s: bad argument (1 <= m <= %d, 1 <= k <= 1024)", fn, SET_MAX_M);
+    VQ_TRY(check_set_args(fn, x, m, k, groups, n_sel, exclude, queries && groups_out && dist_out));
     std::lock_guard<std::mutex> lk(x->mu);
     const int64_t nm = match_rows ? (int64_t)k * m : 0;
     if (x->size == 0) {
-        for (int j = 0; j < k; ++j) { groups_out[j] = -1; dist_out[j] = __builtin_inff(); }
-        for (int64_t i = 0; i < nm; ++i) match_rows[i] = -1;
+        host_empty(k, groups_out, nullptr, dist_out);
+        std::fill(match_rows, match_rows + nm, -1);
         return 0;
     }
-    VQ_TRY(set_precheck(x, fn, mode, groups, n_sel));
-    VQ_TRY(reserve_buf(x->d_sout, x->sout_cap, 2 * (int64_t)k + nm));
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(set_precheck(x, fn, mode, f));
+    VQ_TRY(x->d_sout.reserve(2 * (int64_t)k + nm));
     int32_t* d_g = x->d_sout; float* d_d = (float*)(d_g + k); int32_t* d_m = match_rows ? d_g + 2 * k : nullptr;
     VQ_TRY(stage_queries(x, queries, m));
-    VQ_TRY(search_set_run(x, fn, x->d_q, m, k, mode, groups, n_sel, exclude, d_g, d_d, d_m));
+    VQ_TRY(search_set_run(x, fn, x->d_q, m, k, mode, f, exclude, d_g, d_d, d_m));
     VQ_HIP(hipMemcpyAsync(groups_out, d_g, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
     VQ_HIP(hipMemcpyAsync(dist_out, d_d, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
     if (match_rows) VQ_HIP(hipMemcpyAsync(match_rows, d_m, (size_t)nm * 4, hipMemcpyDeviceToHost, x->stream));
@@ -1757,15 +1705,12 @@ const char* vq_index_profile_class_name(int cls) {
 int vq_index_last_search_stats(vq_index* x, int64_t* stats) {
     VQ_CHECK(x && stats, "vq_index_last_search_stats: null argument");
     std::lock_guard<std::mutex> lk(x->mu);
-    if (x->stats_pending) {                    // the fp16 path's counters follow the search on its stream
+    if (x->stats_at == STATS_COUNTERS) {           // the fp16 path's counters follow the search on its stream
         VQ_HIP(hipStreamSynchronize(x->stream));
-        for (int i = 0; i < 3; ++i) x->stats[i] = x->h_counters[1 + i];
-        x->stats_pending = false;
-    }
-    if (x->gstats_pending) {                   // ... and so do the grouped fp16 path's
+        stats_from_counters(x);
+    } else if (x->stats_at == STATS_GCOUNTERS) {   // ... and so do the grouped fp16 path's
         VQ_HIP(hipStreamSynchronize(x->stream));
-        for (int i = 0; i < 3; ++i) x->stats[i] = (int64_t)x->h_gcounters[i];
-        x->gstats_pending = false;
+        set_stats(x, STATS_HOST, (int64_t)x->h_gcounters[0], (int64_t)x->h_gcounters[1], (int64_t)x->h_gcounters[2]);
     }
     for (int i = 0; i < 3; ++i) stats[i] = x->stats[i];
     return 0;
