@@ -48,6 +48,17 @@ class TextEncoder:
                                                               _lib.fptr(out)))
         return out
 
+    # -- test hooks (a text handle is a vq_encoder: the image tower's debug entry points apply) --
+    def debug_set_layers(self, layers: int) -> None:
+        _lib.check(_lib.load().vq_encoder_debug_set_layers(self._h, int(layers)))
+
+    def debug_read(self, name: str, rows: int) -> np.ndarray:
+        cols = {"x": self.cfg.hidden, "h": self.cfg.hidden, "qkv": 3 * self.cfg.hidden, "att": self.cfg.hidden,
+                "mlp": self.cfg.mlp}[name]
+        out = np.empty((rows, cols), dtype=np.float32)
+        _lib.check(_lib.load().vq_encoder_debug_read(self._h, name.encode(), int(rows), _lib.fptr(out)))
+        return out
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             _lib.load().vq_text_encoder_destroy(self._h)
