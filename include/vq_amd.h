@@ -145,9 +145,17 @@ int vq_encoder_debug_read(vq_encoder* enc, const char* name, int rows, float* ou
 
 /* C[M][N] = A[M][K] * W[N][K]^T through the production MFMA mainloops (inputs
  * rounded from the given fp32, fp32 accumulate) — unit-test hook.
- * flags: bit 0 = fp16 inputs (else bf16); bits 1-4 = kernel (0 auto, 1 = 128x128
- * two-phase, 2 = 256x256 phased). */
+ * flags: bit 0 = fp16 inputs (else bf16); bits 1-5 = kernel (the GemmKernel ids of
+ * csrc/gemm_dispatch.h: 0 auto, 1 = 128x128 two-phase, 2 = 256x256 phased, ...). */
 int vq_debug_gemm(const float* A, const float* W, int M, int N, int K, int flags, float* C);
+
+/* What the GEMM dispatch (csrc/gemm_dispatch.h) would launch for C[M][N] with leading dimensions lda / ldw in this
+ * build and with this process's environment switches: n_steps (1 or 2) launches of `kernel` (a GemmKernel id) on
+ * `rows` rows from row `row0`, `tiles_per_wg` tiles per workgroup.  row_in: the epilogue consumes LayerNorm row
+ * statistics (q|k|v, fc1).  force: the kernel id of $VQ_AMD_GEMM.  Pure host arithmetic: needs neither vq_init nor
+ * a device.  An id that this build does not carry returns VQ_ERR_INVALID. */
+int vq_debug_gemm_plan(int M, int N, int K, int lda, int ldw, int row_in, int force, int* n_steps,
+                       int* kernel /*[2]*/, int* rows /*[2]*/, int* row0 /*[2]*/, int* tiles_per_wg /*[2]*/);
 
 /* ---- text tower: FeatureExtractor.extract_text_features (feature_extractor.py:218-234) ------------ */
 /* CLIPTextModel + text_projection on token ids (the tokenizer stays on the host).  weights: host fp32

@@ -39,7 +39,7 @@ int vq_debug_gemm_stamps_deep(int M, int N, int K, int reps, unsigned long long*
  * >= 2 entries that receive the median clock inside the K loop in MHz and the median K-loop cycles per workgroup), 20 = persistent out-of-phase 128x256 (two workgroups per CU), 12 = the
  * non-persistent 128x256 experiment (EXPERIMENTS builds).  epi: 0 = fp32 store, 1 = bias + residual + 16-bit copy +
  * LayerNorm row partials, 2 = LayerNorm-consuming quick-GELU 16-bit store, 3 = the same without GELU.
- * mode / dephase_cycles / grid: kernel 20 only (csrc/gemm_mfma128x256p.h).  census: null or [grid][4] =
+ * mode / dephase_cycles / grid: kernel 20 only (csrc/experiments/gemm_mfma128x256p.h).  census: null or [grid][4] =
  * {HW_ID, XCC_ID, s_memtime at start, at end} per workgroup of the LAST launch. */
 int vq_debug_gemm_bench(int M, int N, int K, int kernel, int mode, int dephase_cycles, int epi, int reps, int grid,
                         float* ms_avg, unsigned long long* census);

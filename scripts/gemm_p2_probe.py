@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B in ONE process, interleaved rounds: the 256x256 deep-prefetch kernel (8) against the persistent out-of-phase
-128x256 kernel (20; two workgroups per CU, gemm_mfma128x256p.h) with the tower's own epilogues, on the tower's shapes and
+128x256 kernel (20; two workgroups per CU, experiments/gemm_mfma128x256p.h) with the tower's own epilogues, on the tower's shapes and
 on 4x-row versions of the N = 768 pair (steady state: every CU holds its pair for many tiles).  Needs a DIAG build:
     make -C video-quierer_amd/csrc DIAG=1 EXPERIMENTS=1 OUT=../lib/libvq_amd_diag.so OBJDIR=../lib/obj_diag
     VQ_AMD_LIB=video-quierer_amd/lib/libvq_amd_diag.so python scripts/gemm_p2_probe.py"""

@@ -95,6 +95,7 @@ SIGNATURES = {
     "vq_text_encoder_encode_ids": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, POINTER(c_float)]),
     "vq_text_encoder_destroy": (c_int, [c_void_p]),
     "vq_debug_gemm": (c_int, [POINTER(c_float), POINTER(c_float), c_int, c_int, c_int, c_int, POINTER(c_float)]),
+    "vq_debug_gemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "vq_index_create": (c_int, [c_int, POINTER(c_void_p)]),
     "vq_index_destroy": (c_int, [c_void_p]),
     "vq_index_add": (c_int, [c_void_p, POINTER(c_float), c_int64, c_int]),

@@ -20,8 +20,8 @@
 // W rows are private to the wave that stages them (wave w stages and reads W rows 64w..64w+63); A is shared.
 // Requirements: M % 128 == 0, N % 256 == 0, K % 64 == 0, K >= 128, lda/ldw % 8 == 0.
 #pragma once
-#include "vq_common.h"
-#include "gemm_mfma.h"
+#include "../vq_common.h"
+#include "../gemm_mfma.h"
 
 namespace vq {
 

@@ -20,8 +20,8 @@
 // LDS-DMA / statistics write — one barrier behind the epilogue.
 // Requirements: M % 128 == 0, N % 256 == 0, K % 64 == 0, K >= 128, lda/ldw % 8 == 0.
 #pragma once
-#include "vq_common.h"
-#include "gemm_mfma.h"
+#include "../vq_common.h"
+#include "../gemm_mfma.h"
 #include <cstdlib>
 
 namespace vq {

@@ -22,10 +22,10 @@
 //               first read in iteration p+1.
 // Requirements: M % 256 == 0, N % 256 == 0, K % 128 == 0.
 #pragma once
-#include "vq_common.h"
-#include "gemm_mfma.h"
-#include "gemm_mfma256.h"
-#include "gemm_mfma256d.h"
+#include "../vq_common.h"
+#include "../gemm_mfma.h"
+#include "../gemm_mfma256.h"
+#include "../gemm_mfma256d.h"
 
 namespace vq {
 

@@ -18,21 +18,10 @@
 //   - tile order: an XCD's 32 concurrent workgroups take a 4 (m) x 8 (n) block of tiles per round when
 //     tiles_n >= 8 (else (32/tiles_n) x tiles_n), so operand panels are shared in that XCD's L2.
 #pragma once
-#include "vq_common.h"
-#include <cstring>
-#include "gemm_mfma.h"
-#include "gemm_mfma256.h"
-#include "gemm_mfma160.h"
-#include "gemm_mfma256w4.h"
-#include "gemm_mfma256d.h"
-#include "gemm_mfma128x256.h"
-#ifdef VQ_GEMM_EXPERIMENTS
-#include "gemm_mfma128x256p.h"
-#endif
-#include "gemm_mfma256f.h"
-#ifdef VQ_DIAG       // the hand-scheduled four-wave kernel (id 24) changed nothing in frames/s (DESIGN.md section 4 "Round 3" (5)): diagnostic builds only
-#include "gemm_asm256.h"
-#endif
+#include "../vq_common.h"
+#include "../gemm_mfma.h"
+#include "../gemm_mfma256.h"
+#include <algorithm>
 
 namespace vq {
 
@@ -276,162 +265,6 @@ static int launch_gemm_tn256p(hipStream_t st, const uint16_t* A, int lda, const 
                        A, lda, W, ldw, K, tiles_m, tiles_n, slots, epi);
     VQ_HIP(hipGetLastError());
     return 0;
-}
-
-// Dispatch: the phased 256x256 kernel when the problem tiles by it and yields enough
-// workgroups to occupy the chip, else the 128x128 kernel.  force: 1 = 128x128, 2 = four-phase, 8 = four-phase with the deep prefetch and buffer_load..lds staging (gemm_mfma256d.h, the default 256x256 mainloop), 11 = the same with global_load_lds staging, 3 = ring,
-// 4 = persistent four-phase, 5 = 160x256 ring, 6 = auto without the 160-row tiles, 7 = four-wave 256x256.  Auto picks the 160-row tiles when they put one workgroup on
-// more CUs than 256-row tiles would (VQ_AMD_GEMM160=0 disables that).
-static inline int gemm_use_deep() {           // $VQ_AMD_GEMM256=4phase: auto picks the second-generation mainloop (A/B switch)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VQ_AMD_GEMM256"); v = (e && !strcmp(e, "4phase")) ? 0 : 1; }
-    return v;
-}
-template <bool IS_F16, class Epi>
-static int launch_gemm_tn256_best(hipStream_t st, const uint16_t* A, int lda, const uint16_t* W, int ldw,
-                                  int M, int N, int K, const Epi& epi) {
-    return gemm_use_deep() ? launch_gemm_tn256d<IS_F16>(st, A, lda, W, ldw, M, N, K, epi)
-                           : launch_gemm_tn256<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-}
-
-static inline int gemm_multi_min_wgs() {        // $VQ_AMD_GEMM_MULTI_MIN: fewest workgroups a three-tile launch may leave.  Default 128 [r03]: with
-    static int v = -1;                           // three batches in flight qkv (450 tiles -> 150 workgroups) gains 0.6-0.9 % frames/s too (192 kept it on single tiles)
-    if (v < 0) { const char* e = getenv("VQ_AMD_GEMM_MULTI_MIN"); v = e ? atoi(e) : 128; }
-    return v;
-}
-
-static inline bool gemm_use_multi() {          // $VQ_AMD_GEMM_MULTI=0: one tile per workgroup everywhere
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VQ_AMD_GEMM_MULTI"); v = (e && atoi(e) == 0) ? 0 : 1; }
-    return v != 0;
-}
-
-static inline bool gemm_use_tail_split() {     // $VQ_AMD_GEMM_TAIL=0 keeps one launch per GEMM
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VQ_AMD_GEMM_TAIL"); v = (e && atoi(e) == 0) ? 0 : 1; }
-    return v != 0;
-}
-
-template <bool IS_F16, class Epi>
-static int launch_gemm_auto(hipStream_t st, const uint16_t* A, int lda, const uint16_t* W, int ldw,
-                            int M, int N, int K, const Epi& epi, int force = 0) {
-    // 24: the hand-scheduled four-wave 256x256 mainloop (gemm_asm256.h) on every shape that tiles
-    if (force == 24) {
-#ifdef VQ_DIAG
-        if (M % G2_BM == 0 && N % G2_BN == 0 && K % (2 * G2_BK) == 0) return launch_gemm_tn256a<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-        force = 6;
-#else
-        return fail(VQ_ERR_INVALID, "gemm kernel 24 (hand-scheduled four-wave loop) is built into diagnostic libraries only: `make DIAG=1 OUT=... OBJDIR=...`");
-#endif
-    }
-    // 20 / 21: persistent out-of-phase 128x256 tiles, two workgroups per CU (gemm_mfma128x256p.h), on every shape that tiles
-    // (20: the second workgroup of a CU starts half a tile late; 21: no lag — the in-step control of the A/B)
-#ifdef VQ_GEMM_EXPERIMENTS
-    if ((force == 20 || force == 21) && M % GP_BM == 0 && N % GP_BN == 0 && K % (2 * GP_SUB_K) == 0 && K >= 4 * GP_SUB_K)
-        return launch_gemm_tn128x256p<IS_F16>(st, A, lda, W, ldw, M, N, K, epi, force == 20 ? 1 : 0, gp_dephase_cycles(K));
-    if (force == 20 || force == 21) force = 6;
-#else       // measured and rejected (DESIGN.md §4 "Round 3"): not part of the product library
-    if (force == 20 || force == 21)
-        return fail(VQ_ERR_INVALID, "gemm kernel %d is an experiment: rebuild with `make EXPERIMENTS=1`", force);
-#endif
-    // 12: 128x256 tiles, two workgroups per CU, wherever the 256x256 kernel would run (13: on every shape that tiles)
-#ifdef VQ_GEMM_EXPERIMENTS
-    if ((force == 12 || force == 13) && M % G12_BM == 0 && N % G12_BN == 0 && K % (2 * G12_SUB_K) == 0 && K >= 4 * G12_SUB_K &&
-        (force == 13 || (int64_t)(M / G12_BM) * (N / G12_BN) >= 256))
-        return launch_gemm_tn128x256<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-    if (force == 12 || force == 13) force = 6;
-#else       // measured and rejected mainloops are not part of the product library
-    if (force == 9 || force == 12 || force == 13)
-        return fail(VQ_ERR_INVALID, "gemm kernel %d is an experiment: rebuild with `make EXPERIMENTS=1`", force);
-#endif
-    if constexpr (epi_row_in<Epi>::value) {
-        // epilogues that consume per-row LayerNorm statistics need the kernels with the row-stat prologue
-        const bool fits = M % G2_BM == 0 && N % G2_BN == 0 && K % (2 * G2_BK) == 0;
-        const int64_t tiles = (int64_t)(M / G2_BM) * (N / G2_BN);
-        if (fits && force != 1 && (force == 8 || tiles >= 128)) {
-            const int rem = (int)(tiles % 256);
-            if (force == 0 && gemm_use_tail_split() && tiles > 256 && rem > 0 && rem < 128) {      // thin last round -> 128x128 tiles
-                const int m_main = (int)((tiles - rem) / (N / G2_BN)) * G2_BM;
-                if (m_main > 0 && m_main < M) {
-                    VQ_TRY((launch_gemm_tn256d<IS_F16>(st, A, lda, W, ldw, m_main, N, K, epi)));
-                    return launch_gemm_tn<IS_F16>(st, A, lda, W, ldw, M - m_main, N, K, epi, m_main);
-                }
-            }
-#ifdef VQ_GEMM_EXPERIMENTS
-            if (force == 9 && lda % 64 == 0 && ldw % 64 == 0) return launch_gemm_tn256e<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-#endif
-            // Three tiles of a tile row per workgroup where that still leaves >= 128 workgroups (fc1 and, since round 3, qkv at batch
-            // 256): the second and third tile's first operands land under the previous epilogue (fc1 -3.5 % with one batch in flight,
-            // +0.5 % frames/s with three; qkv drops to 150 workgroups: -29 % alone, +0.6-0.9 % frames/s with three batches in flight —
-            // the idle CUs belong to the other batches then).  Concurrent handles only: a lone batch keeps the
-            // tail-split dispatch below.  $VQ_AMD_GEMM_MULTI=0 switches it off, VQ_AMD_GEMM=15 forces it everywhere.
-            if ((((force == 6 || force == 14) && gemm_use_multi() && tiles / 3 >= gemm_multi_min_wgs()) || force == 15) && lda % 64 == 0 && ldw % 64 == 0 && (N / G2_BN) % 3 == 0) {
-                // [r04] FOUR tiles per workgroup where that fills the chip's 256 CUs better than three: ViT-L/14@336's q|k|v GEMM is 73 x 12
-                // tiles = 292 workgroups of three (two rounds, the second 14 % full) or 219 of four (one round, 86 % full).  $VQ_AMD_GEMM_TPW forces.
-                static const int tpw_env = [] { const char* e = getenv("VQ_AMD_GEMM_TPW"); return e ? atoi(e) : 0; }();
-                auto fill = [&](int t) { const int64_t w = tiles / t; return (double)w / (double)(((w + 255) / 256) * 256); };
-                int tpw = 3;
-                if ((N / G2_BN) % 4 == 0 && tiles / 4 >= gemm_multi_min_wgs() && fill(4) > fill(3) + 0.05) tpw = 4;
-                if (tpw_env >= 1 && (N / G2_BN) % tpw_env == 0) tpw = tpw_env;
-                return launch_gemm_tn256dm<IS_F16>(st, A, lda, W, ldw, M, N, K, epi, tpw);
-            }
-            return launch_gemm_tn256d<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-        }
-        return launch_gemm_tn<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-    } else {
-    const bool allow160 = force != 6 && force != 14 && force != 15;
-    if (force == 6) force = 0;
-    if (force == 5 || (force == 0 && allow160 && gemm_use160() && prefer_tn160(M, N, K)))
-        return launch_gemm_tn160_ring<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-#ifdef VQ_GEMM_EXPERIMENTS
-    if (force == 7) return launch_gemm_tn256w4<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-#else
-    if (force == 3 || force == 4 || force == 7)
-        return fail(VQ_ERR_INVALID, "gemm kernel %d is an experiment: rebuild with `make EXPERIMENTS=1`", force);
-#endif
-    const bool fits256 = M % G2_BM == 0 && N % G2_BN == 0 && K % (2 * G2_BK) == 0;
-    if (force == 8) return launch_gemm_tn256d<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-    if (force == 11) return launch_gemm_tn256d<IS_F16, Epi, false>(st, A, lda, W, ldw, M, N, K, epi);
-#ifdef VQ_GEMM_EXPERIMENTS
-    if (force == 9 && fits256 && lda % 64 == 0 && ldw % 64 == 0) return launch_gemm_tn256e<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-#endif
-    if (force == 15 && fits256 && lda % 64 == 0 && ldw % 64 == 0 && (N / G2_BN) % 3 == 0 && (int64_t)(M / G2_BM) * (N / G2_BN) >= 128)
-        return launch_gemm_tn256dm<IS_F16>(st, A, lda, W, ldw, M, N, K, epi, 3);
-    if (force == 16 && fits256 && lda % 64 == 0 && ldw % 64 == 0)          // tests: the multi-tile kernel on any shape that tiles
-        return launch_gemm_tn256dm<IS_F16>(st, A, lda, W, ldw, M, N, K, epi, (N / G2_BN) % 3 == 0 ? 3 : (N / G2_BN) % 4 == 0 ? 4 : (N / G2_BN) % 2 == 0 ? 2 : 1);
-    if (force == 14 || force == 15 || force == 16) force = 0;
-#ifdef VQ_GEMM_EXPERIMENTS
-    if (force == 10) return launch_gemm_tn256f<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-#else
-    if (force == 10)
-        return fail(VQ_ERR_INVALID, "gemm kernel %d is an experiment: rebuild with `make EXPERIMENTS=1`", force);
-#endif
-    if (force == 2) return launch_gemm_tn256<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-    const bool want256 = force >= 2 || (force == 0 && (int64_t)(M / G2_BM) * (N / G2_BN) >= 128);
-#ifdef VQ_GEMM_EXPERIMENTS
-    if (fits256 && want256 && force == 4) return launch_gemm_tn256p<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-    if (fits256 && want256 && force == 3) return launch_gemm_tn256_ring<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-#endif
-    if (fits256 && want256 && force == 0 && allow160 && gemm_use_tail_split()) {
-        // Tile quantisation: T tiles over 256 CUs run ceil(T/256) rounds.  When the last round is less than half
-        // full, its tiles' rows go to the 128x128 kernel instead (4x the workgroups, two per CU: one short round)
-        // — same K order per output element, so the results are bit-identical.  Not for concurrent handles:
-        // other streams fill the idle CUs of a thin round.
-        const int tiles_n = N / G2_BN, tiles_m = M / G2_BM;
-        const int64_t tiles = (int64_t)tiles_m * tiles_n;
-        const int rem = (int)(tiles % 256);
-        if (tiles > 256 && rem > 0 && rem < 128) {
-            const int main_rows_tiles = (int)((tiles - rem) / tiles_n);          // whole tile rows inside the full rounds
-            const int m_main = main_rows_tiles * G2_BM;
-            if (m_main > 0 && m_main < M) {
-                VQ_TRY((launch_gemm_tn256_best<IS_F16>(st, A, lda, W, ldw, m_main, N, K, epi)));
-                return launch_gemm_tn<IS_F16>(st, A, lda, W, ldw, M - m_main, N, K, epi, m_main);
-            }
-        }
-    }
-    if (fits256 && want256 && force != 1) return launch_gemm_tn256_best<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-    return launch_gemm_tn<IS_F16>(st, A, lda, W, ldw, M, N, K, epi);
-    }
 }
 
 }  // namespace vq

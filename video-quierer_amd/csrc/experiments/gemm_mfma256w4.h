@@ -8,11 +8,12 @@
 // read into a second register set while the 64 MFMAs of step p run: no MFMA ever waits on LDS.  One barrier per
 // k-step hands slots over; LDS-DMA runs NSLOT k-steps ahead.
 //
-// LDS image, swizzle and DMA pieces are those of gemm_tn256_ring_kernel (gemm_mfma256.h): a slot is one 32-wide
+// LDS image, swizzle and DMA pieces are those of gemm_tn256_ring_kernel (gemm_mfma256_ring.h): a slot is one 32-wide
 // sub-tile = 256 A rows + 256 W rows of 64 B; a 1-KiB piece = 16 rows; waves 0-1 bring the A pieces, waves 2-3 the
 // W pieces (8 each per sub-tile).
 #pragma once
-#include "gemm_mfma256.h"
+#include "../gemm_mfma256.h"
+#include "gemm_mfma256_ring.h"
 #include <type_traits>
 
 namespace vq {

@@ -1,4 +1,4 @@
-// C[M,N] = A[M,K] * W[N,K]^T with 160x256 output tiles — the ring mainloop of gemm_mfma256.h re-cut for the
+// C[M,N] = A[M,K] * W[N,K]^T with 160x256 output tiles — the ring mainloop of experiments/gemm_mfma256_ring.h re-cut for the
 // N = 768 GEMMs of the B/32 tower (out_proj, fc2).  At 12,800 rows those have 50 x 3 = 150 tiles of 256x256,
 // one wave of workgroups on 150 of the 256 CUs; 160-row tiles give 80 x 3 = 240 workgroups, one per CU on 240
 // CUs, each with 0.625 of the work.
@@ -8,7 +8,8 @@
 // 160 A rows + 256 W rows of 64 B (26 KiB, 130 KiB in all).  A sub-tile is 26 LDS-DMA pieces of 16 rows x 64 B;
 // wave w issues pieces w, w+8, w+16 (and w+24 for w < 2), so waves 0-1 count 4 loads per sub-tile and the
 // others 3 — the vmcnt a wave waits on follows its own count.  Swizzle, stagger between the two row groups and
-// the two barriers per phase are those of gemm_tn256_ring_kernel.
+// the two barriers per phase are those of gemm_tn256_ring_kernel (experiments/gemm_mfma256_ring.h).
+// Which shapes get these tiles: gemm_dispatch.h (prefer_tn160).
 #pragma once
 #include "gemm_mfma256.h"
 
@@ -148,20 +149,6 @@ static int launch_gemm_tn160_ring(hipStream_t st, const uint16_t* A, int lda, co
                        G5_LDS_BYTES, st, A, lda, W, ldw, K, N / G5_BN, epi);
     VQ_HIP(hipGetLastError());
     return 0;
-}
-
-static inline bool gemm_use160() {            // $VQ_AMD_GEMM160=0 keeps the 256x256 kernel for every shape
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VQ_AMD_GEMM160"); v = (e && atoi(e) == 0) ? 0 : 1; }
-    return v != 0;
-}
-
-// True when 160-row tiles fill more CUs than 256-row tiles in a single wave of workgroups.
-static inline bool prefer_tn160(int M, int N, int K) {
-    if (M % G5_BM || N % G5_BN || K % G3_SUB_K || K < (G5_NSLOT - 1) * G3_SUB_K) return false;
-    const int64_t t160 = (int64_t)(M / G5_BM) * (N / G5_BN);
-    const int64_t t256 = (int64_t)((M + G2_BM - 1) / G2_BM) * (N / G2_BN);
-    return t160 <= 256 && t256 < 200 && t160 > t256;
 }
 
 }  // namespace vq

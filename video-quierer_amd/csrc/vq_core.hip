@@ -2,9 +2,7 @@
 // GEMM unit-test hook.
 #include "../../include/vq_amd.h"
 #include "vq_common.h"
-#include "gemm_mfma.h"
-#include "gemm_mfma256.h"
-#include "gemm_mfma256p.h"
+#include "gemm_dispatch.h"
 
 #include <algorithm>
 #include <cstring>
@@ -79,7 +77,7 @@ int vq_init(int device_ordinal) {
 int vq_debug_gemm(const float* A, const float* W, int M, int N, int K, int flags, float* C) {
     VQ_TRY(require_init());
     VQ_CHECK(A && W && C, "vq_debug_gemm: null argument");
-    const int use_f16 = flags & 1, force = (flags >> 1) & 31;    // force: launch_gemm_auto's kernel ids (0 auto, 1 = 128x128, 2 = four-phase, 5 = 160x256 ring, 8 / 11 deep prefetch, 16 multi-tile, ...)
+    const int use_f16 = flags & 1, force = (flags >> 1) & 31;    // force: a GemmKernel id (gemm_dispatch.h)
     std::vector<uint16_t> a16((size_t)M * K), w16((size_t)N * K);
     for (size_t i = 0; i < a16.size(); ++i)
         a16[i] = use_f16 ? __builtin_bit_cast(uint16_t, (_Float16)A[i]) : f32_to_bf16_rne(A[i]);
@@ -100,6 +98,19 @@ int vq_debug_gemm(const float* A, const float* W, int M, int N, int K, int flags
     }
     (void)hipFree(dA); (void)hipFree(dW); (void)hipFree(dC);
     return rc;
+}
+
+// What launch_gemm_auto would launch for this shape in this build with this process's environment; needs no device.
+int vq_debug_gemm_plan(int M, int N, int K, int lda, int ldw, int row_in, int force, int* n_steps,
+                       int* kernel /*[2]*/, int* rows /*[2]*/, int* row0 /*[2]*/, int* tiles_per_wg /*[2]*/) {
+    VQ_CHECK(n_steps && kernel && rows && row0 && tiles_per_wg, "vq_debug_gemm_plan: null argument");
+    const GemmPlan plan = plan_gemm(M, N, K, lda, ldw, row_in != 0, force, GEMM_DIAG_BUILD, GEMM_EXPERIMENTS_BUILD, gemm_options());
+    if (plan.err) return fail(plan.err, "%s", plan.msg);
+    *n_steps = plan.n_steps;
+    for (int i = 0; i < plan.n_steps; ++i) {
+        kernel[i] = plan.step[i].kernel; rows[i] = plan.step[i].rows; row0[i] = plan.step[i].row0; tiles_per_wg[i] = plan.step[i].tiles_per_wg;
+    }
+    return 0;
 }
 
 }  // extern "C"

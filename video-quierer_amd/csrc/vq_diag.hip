@@ -5,10 +5,8 @@
 #include "../../include/vq_amd.h"
 #include "../../include/vq_amd_diag.h"
 #include "vq_common.h"
-#include "gemm_mfma.h"
-#include "gemm_mfma256.h"
-#include "gemm_mfma256p.h"
-#include "gemm_mfma128x256p.h"
+#include "gemm_dispatch.h"
+#include "experiments/gemm_mfma128x256p.h"     // vq_debug_gemm_bench times kernel 20 in every diagnostic build
 #include "encoder_kernels.h"
 
 #include <algorithm>

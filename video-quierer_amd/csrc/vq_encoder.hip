@@ -4,9 +4,7 @@
 // transformers CLIP vision tower it calls.
 #include "../../include/vq_amd.h"
 #include "vq_common.h"
-#include "gemm_mfma.h"
-#include "gemm_mfma256.h"
-#include "gemm_mfma256p.h"
+#include "gemm_dispatch.h"
 #include "encoder_kernels.h"
 
 #include <cmath>
@@ -95,7 +93,7 @@ struct vq_encoder {
     int gemm24_mask = 0;     // $VQ_AMD_GEMM24: which full-batch GEMMs run the hand-scheduled four-wave kernel (gemm_asm256.h): 1 qkv, 2 out_proj, 4 fc1, 8 fc2, 16 patch
                              // embedding.  Default none: 16 % fewer cycles per K-tile, and the chip answers with a 14 % lower clock - frames/s equal within 1 %
                              // with three batches in flight, +1.3 % for fc2 on a lone handle, -1 % on ViT-L/14 (DESIGN.md §4 "Round 3" (5))
-    int gemm_force = 0;      // $VQ_AMD_GEMM: 0 auto, 1 = 128x128 kernel only, 2 = 256x256 wherever it tiles, 6 = auto without 160-row tiles
+    int gemm_force = GK_AUTO; // $VQ_AMD_GEMM: a GemmKernel id (gemm_dispatch.h); concurrent handles: GK_AUTO_NO160
     // profiling
     bool profiling = false;
     struct Ev { int cls; hipEvent_t a, b; };
@@ -236,15 +234,15 @@ int run_forward(vq_encoder* e, const uint8_t* d_frames, int n, int swap_rb, floa
     // per-GEMM row count: 160-row tiles where they occupy more CUs than 256-row tiles (gemm_mfma160.h)
     // the hand-scheduled four-wave kernel (gemm_asm256.h) for the GEMMs $VQ_AMD_GEMM24 names, where 256-row tiles fill half the chip
     auto use24 = [&](int bit, int M, int N, int K) {
-        return (e->gemm24_mask & bit) && (e->gemm_force == 0 || e->gemm_force == 6) && M % G2_BM == 0 && N % G2_BN == 0 && K % (2 * G2_BK) == 0 &&
+        return (e->gemm24_mask & bit) && (e->gemm_force == GK_AUTO || e->gemm_force == GK_AUTO_NO160) && M % G2_BM == 0 && N % G2_BN == 0 && K % (2 * G2_BK) == 0 &&
                (int64_t)(M / G2_BM) * (N / G2_BN) >= 128;
     };
     auto gemm_rows = [&](int N, int K, int bit = 0) {
         if (use24(bit, rows_gemm, N, K)) return rows_gemm;
         const int r160 = (int)round_up(rows, G5_BM);
-        return (e->gemm_force == 0 && gemm_use160() && r160 <= e->rows_pad && prefer_tn160(r160, N, K)) ? r160 : rows_gemm;
+        return (e->gemm_force == GK_AUTO && gemm_use160() && r160 <= e->rows_pad && prefer_tn160(r160, N, K)) ? r160 : rows_gemm;
     };
-    auto gf = [&](int bit, int M, int N, int K) { return use24(bit, M, N, K) ? 24 : e->gemm_force; };
+    auto gf = [&](int bit, int M, int N, int K) { return use24(bit, M, N, K) ? (int)GK_ASM256 : e->gemm_force; };
     const int prows = n * e->patches;
     const int prows_gemm = pad_rows(prows);
     const LnPartials part{e->ps, e->rows_pad};
@@ -381,7 +379,7 @@ int run_forward(vq_encoder* e, const uint8_t* d_frames, int n, int swap_rb, floa
                 // live in the (now free) q|k|v buffer, summed in slice order by the reduce kernel
                 Prof p(e, C_LAST_CLS);
                 const int splits = (c.mlp % (8 * GEMM_BK) == 0 && (size_t)8 * crows * H * 2 <= (size_t)e->rows_pad * 3 * H) ? 8 : 0;
-                if (splits && crows % GEMM_BM == 0 && e->gemm_force != 2 && e->gemm_force != 8) {
+                if (splits && crows % GEMM_BM == 0 && e->gemm_force != GK_PHASE4 && e->gemm_force != GK_DEEP) {
                     float* part = (float*)e->qkv;
                     const int64_t plane = (int64_t)crows * H;
                     VQ_TRY(by_f16(f2, [&](auto F) {
@@ -476,6 +474,28 @@ int dtype_mask_from(int flags) {
     return mask;
 }
 
+// What a new handle takes from its create flags and the environment.  A shared handle (`parent`) takes the attention
+// and prune switches and the operand types from the handle whose weights it uses (they are already stored in those
+// types); the text tower (e->is_text, set before the call) has no concurrent mode and no attention or prune switches.
+void apply_create_options(vq_encoder* e, int flags, const vq_encoder* parent) {
+    if (!e->is_text && (flags & VQ_ENC_CONCURRENT)) e->gemm_force = GK_AUTO_NO160;
+    if (const char* gf = getenv("VQ_AMD_GEMM")) e->gemm_force = atoi(gf);
+    if (const char* rs = getenv("VQ_AMD_RESID")) e->split_resid = strcmp(rs, "f32") != 0;
+#ifdef VQ_DIAG
+    if (const char* gm = getenv("VQ_AMD_GEMM24")) e->gemm24_mask = atoi(gm);
+#endif
+    if (parent) {
+        e->attn_simple = parent->attn_simple; e->attn_q64 = parent->attn_q64; e->attn_t64 = parent->attn_t64; e->prune_last = parent->prune_last;
+        e->f16_mask = parent->f16_mask;
+        return;
+    }
+    if (!e->is_text) {
+        if (const char* at = getenv("VQ_AMD_ATTN")) { e->attn_simple = !strcmp(at, "simple"); e->attn_q64 = !strcmp(at, "q64"); e->attn_t64 = !strcmp(at, "t64"); }
+        if (const char* fl = getenv("VQ_AMD_FULL_LAST_LAYER")) e->prune_last = atoi(fl) == 0;
+    }
+    e->f16_mask = dtype_mask_from(flags);
+}
+
 }  // namespace
 
 extern "C" {
@@ -505,15 +525,7 @@ int vq_encoder_create_ex(const vq_vit_config* cfg, const float* const* weights, 
     const int patch_k = (int)round_up(patch_k_raw, 2 * G2_BK);     // zero-padded K (ViT-L/14: 588 -> 640)
 
     vq_encoder* e = new vq_encoder();
-    if (flags & VQ_ENC_CONCURRENT) e->gemm_force = 6;        // auto, without the 160-row tiles
-    if (const char* gf = getenv("VQ_AMD_GEMM")) e->gemm_force = atoi(gf);
-    if (const char* rs = getenv("VQ_AMD_RESID")) e->split_resid = strcmp(rs, "f32") != 0;
-    #ifdef VQ_DIAG
-    if (const char* gm = getenv("VQ_AMD_GEMM24")) e->gemm24_mask = atoi(gm);
-#endif
-    if (const char* at = getenv("VQ_AMD_ATTN")) { e->attn_simple = !strcmp(at, "simple"); e->attn_q64 = !strcmp(at, "q64"); e->attn_t64 = !strcmp(at, "t64"); }
-    if (const char* fl = getenv("VQ_AMD_FULL_LAST_LAYER")) e->prune_last = atoi(fl) == 0;
-    e->f16_mask = dtype_mask_from(flags);
+    apply_create_options(e, flags, nullptr);
     e->cfg = c; e->tokens = tokens; e->patches = patches; e->grid = grid; e->patch_k = patch_k; e->max_batch = max_batch;
     e->rows_pad = round_up((int64_t)max_batch * tokens + (G5_BM - 1), 256);     // room for 256- and 160-row padding
     e->prow_pad = round_up((int64_t)max_batch * patches, 256);
@@ -617,15 +629,8 @@ int vq_encoder_create_shared(vq_encoder* parent, int max_batch, int flags, vq_en
     vq_encoder* e = new vq_encoder();
     e->cfg = c; e->tokens = parent->tokens; e->patches = parent->patches; e->grid = parent->grid; e->patch_k = parent->patch_k;
     e->max_batch = max_batch;
-    e->f16_mask = parent->f16_mask;                          // the weights are already stored in these types
     e->patch_unscale = parent->patch_unscale;
-    e->gemm_force = (flags & VQ_ENC_CONCURRENT) ? 6 : 0;
-    if (const char* gf = getenv("VQ_AMD_GEMM")) e->gemm_force = atoi(gf);
-    if (const char* rs = getenv("VQ_AMD_RESID")) e->split_resid = strcmp(rs, "f32") != 0;
-    #ifdef VQ_DIAG
-    if (const char* gm = getenv("VQ_AMD_GEMM24")) e->gemm24_mask = atoi(gm);
-#endif
-    e->attn_simple = parent->attn_simple; e->attn_q64 = parent->attn_q64; e->attn_t64 = parent->attn_t64; e->prune_last = parent->prune_last;
+    apply_create_options(e, flags, parent);
     e->rows_pad = round_up((int64_t)max_batch * e->tokens + (G5_BM - 1), 256);
     e->prow_pad = round_up((int64_t)max_batch * e->patches, 256);
     e->weights_owner = parent->weights_owner ? parent->weights_owner : parent->arena_owner;   // a clone of a clone still pins the original weights
@@ -687,12 +692,7 @@ int vq_text_encoder_create(const vq_text_config* cfg, const float* const* weight
     e->vocab = t.vocab; e->eos_id = t.eos_token_id;
     e->rows_pad = round_up((int64_t)max_batch * e->tokens + (G5_BM - 1), 256);
     e->prow_pad = 0;
-    if (const char* gf = getenv("VQ_AMD_GEMM")) e->gemm_force = atoi(gf);
-    if (const char* rs = getenv("VQ_AMD_RESID")) e->split_resid = strcmp(rs, "f32") != 0;
-    #ifdef VQ_DIAG
-    if (const char* gm = getenv("VQ_AMD_GEMM24")) e->gemm24_mask = atoi(gm);
-#endif
-    e->f16_mask = dtype_mask_from(flags);
+    apply_create_options(e, flags, nullptr);
     auto cleanup = [&](int rc) { vq_encoder_destroy(e); return rc; };
 
     const size_t H = t.hidden, M = t.mlp, T = e->tokens;
