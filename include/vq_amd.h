@@ -139,8 +139,16 @@ int vq_encoder_profile_bracket_overhead(vq_encoder* enc, float* ms);
 
 /* Test hooks: run only the first `layers` transformer blocks (<0: all), and copy
  * an internal activation to the host as fp32: "x" [n*T][hidden] residual stream,
- * "h" LN output, "qkv", "att", "mlp" (bf16 widened). */
+ * "h" LN output, "qkv", "att", "mlp" (bf16 widened); "xl" [n*T][hidden]: the low half of the split residual
+ * stream as its raw bytes 0..255 (fp8 e4m3 of (x - xh) * 512; the reader decodes).
+ * vq_encoder_debug_keep_stream(on): a layer-limited pass runs its blocks exactly as the full pass runs them
+ * (the split 16 + 8-bit stream and the epilogue modes follow the model's depth and the CLS-only last block,
+ * not the limit) and leaves x, xh, xl as they are at that point; its pooled output is meaningless.  Off
+ * (the default): layer-limited passes keep the fp32 stream.  vq_encoder_debug_stream_is_split: whether the
+ * last pass left the stream as the pair xh + xl (1) or as the fp32 x (0). */
 int vq_encoder_debug_set_layers(vq_encoder* enc, int layers);
+int vq_encoder_debug_keep_stream(vq_encoder* enc, int on);
+int vq_encoder_debug_stream_is_split(vq_encoder* enc, int* split);
 int vq_encoder_debug_read(vq_encoder* enc, const char* name, int rows, float* out);
 
 /* C[M][N] = A[M][K] * W[N][K]^T through the production MFMA mainloops (inputs

@@ -155,6 +155,130 @@ def test_cls_row_from_the_wrong_image_leaves_the_bound(dt):
     assert r > 1.0
 
 
+# ------------------------------------------------------------------- the split residual stream (fp16 + one fp8 byte)
+SPLIT_GEOMETRIES = {      # the smallest depths at which the default pass uses all four epilogue modes
+    "image_t50_3_blocks": ("image", VitConfig(image_size=224, patch_size=32, layers=3), 3),
+    "text_t77_2_blocks": ("text", TextConfig(vocab=520, eos_token_id=519, bos_token_id=518, layers=2), 4),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def split_chain(geo, kind, mutant=None):
+    tower, cfg, n = SPLIT_GEOMETRIES[geo]
+    tw = R.Tower(tower, cfg, R.make_weights(tower, cfg, kind), "fp16")
+    inp = R.make_input(tower, cfg, n)
+    return tw, n, inp, R.emu_chain_split(tw, n, inp, mutant)
+
+
+def test_fp8_codec_against_torch():
+    import torch
+    codes = np.arange(256, dtype=np.uint8)
+    want = torch.from_numpy(codes).view(torch.float8_e4m3fn).float().numpy().astype(np.float64)
+    assert np.array_equal(np.isnan(want), np.isnan(R.FP8_VALUE)) and np.array_equal(want[~np.isnan(want)], R.FP8_VALUE[~np.isnan(want)])
+    rng = np.random.default_rng(3)
+    t = np.concatenate([rng.uniform(-448, 448, 20000), rng.uniform(-2.0 ** -5, 2.0 ** -5, 20000), R.FP8_VALUE[:127],
+                        (R.FP8_VALUE[:126] + R.FP8_VALUE[1:127]) / 2]).astype(np.float32)      # the last: every tie
+    mine = R.fp8_encode(t)
+    theirs = torch.from_numpy(t).to(torch.float8_e4m3fn).view(torch.uint8).numpy()
+    zero = t == 0
+    assert np.array_equal(mine[~zero], theirs[~zero]) and np.all((mine[zero] & 0x7F) == 0)
+    assert np.array_equal(R.fp8_encode(np.array([449.0, -1e9, np.nan])) & 0x7F, [0x7F] * 3)
+
+
+def test_pair_bound_is_met_and_attained_in_every_binade():
+    """Sound: no fp32 x leaves pair_bound.  Not slack: in every fp16 binade from 2^-14 to 2^15 some x comes within 1 % of it.
+    Per binade [2^e, 2^(e+1)) and sign: EVERY fp32 value of four fp16 steps in the middle of the binade, of the two steps at its
+    top (where xh is 2^(e+1)) and of the two at its bottom, so every position of x between two fp16 values occurs, ties included."""
+    worst = {}
+    for e in range(-14, 16):
+        step32 = 2.0 ** (e - 23)
+        k = np.arange(4 * 8192 + 1, dtype=np.float64)
+        x = np.concatenate([2.0 ** e * 1.5 + k * step32, 2.0 ** (e + 1) - k[:2 * 8192 + 1] * step32, 2.0 ** e + k[:2 * 8192 + 1] * step32])
+        x = x[x <= 65504.0]
+        x = np.concatenate([x, -x]).astype(np.float32)
+        assert np.all(np.abs(x.astype(np.float64)) >= 2.0 ** e) and np.all(np.abs(x.astype(np.float64)) <= 2.0 ** (e + 1))
+        h, code = R.split16_8(x)
+        err = np.abs(R.pair_value(h, code) - x.astype(np.float64))
+        inside = np.abs(x.astype(np.float64)) < 2.0 ** (e + 1)
+        bound = R.pair_bound(x.astype(np.float64))
+        assert np.all(err <= bound), (e, float((err / bound).max()))
+        assert len(np.unique(bound[inside])) == 1
+        worst[e] = float(err[inside].max() / bound[inside][0])
+        assert worst[e] >= 0.99, (e, worst[e])
+        # the exact properties the device is held to
+        assert np.all(np.abs(R.fp8_decode(code)) / R.XL_SCALE <= R.half_ulp16(h, "fp16")) and not np.any((code & 0x7F) == 0x7F)
+    print("max error / pair_bound per binade:", {e: round(r, 4) for e, r in worst.items()})
+    # the statements of csrc/encoder_kernels.h: relative to |x|, and where the clamp begins
+    assert R.pair_bound(2047.9) == 2.0 ** -6 and R.pair_bound(2048.0) == 0.125
+    for e in range(-3, 11):
+        assert R.pair_bound(2.0 ** e) == 2.0 ** (e - 16)
+    assert all(R.pair_bound(2.0 ** e) == 2.0 ** -19 for e in range(-7, -3)) and R.pair_bound(2.0 ** -8) == 2.0 ** -19
+    # fp16's own subnormals: the low byte is zero and the pair is xh
+    x = np.linspace(-2.0 ** -14, 2.0 ** -14, 40001).astype(np.float32)
+    h, code = R.split16_8(x)
+    assert np.all(np.abs(R.pair_value(h, code) - x.astype(np.float64)) <= R.pair_bound(x.astype(np.float64)))
+
+
+@pytest.mark.parametrize("geo", list(SPLIT_GEOMETRIES))
+def test_passthrough_fixture_has_the_promised_properties(geo):
+    tw, n, inp, runs = split_chain(geo, "passthrough")
+    assert [r["split"] for r in runs] == R.split_forms(tw)[:len(runs)]
+    for l in range(tw.layers):                             # zero accumulators: the residual bound is the pair's error + four adds
+        o = tw.ops(l)
+        assert not o["w_out"].any() and not o["w_fc2"].any()
+    pr = R.passthrough_properties(runs)
+    print(geo, pr)
+    assert min(pr.values()) >= 100, pr
+    y = np.abs(np.asarray(runs[1]["y_mid"], np.float64))
+    for lo in (2048.0, 8192.0):
+        for sign in (1, -1):
+            sel = (y >= lo) & (y < 2 * lo) & (np.sign(runs[1]["y_mid"]) == sign)
+            assert np.count_nonzero(sel) >= 100, (lo, sign)
+
+
+@pytest.mark.parametrize("kind", ("passthrough", "stress", "seeded"))
+@pytest.mark.parametrize("geo", list(SPLIT_GEOMETRIES))
+def test_split_emulation_stays_within_every_bound(geo, kind):
+    tw, n, inp, runs = split_chain(geo, kind)
+    ratios = R.check_chain(tw, n, inp, runs, split=True)
+    amb = ratios.pop(("ambiguous", 0))
+    if tw.is_text:
+        rows = runs[-1]["x"][R.eos_rows(inp, tw.cfg)]
+        ratios[("pool", tw.layers - 1)] = R.check_pool(tw, rows, R.emu_pool(tw, rows))
+    else:
+        prod, emb = R.emu_product_image(tw, n, runs[-1])
+        ratios.update(R.check_product_image(tw, n, runs[-1], prod, emb))
+    show(f"split {geo} {kind} (ambiguous fc1 operand elements: {amb})", ratios)
+    worst = max(ratios, key=ratios.get)
+    assert ratios[worst] <= 1.0, f"emulation leaves the bound at {worst}: {ratios[worst]}"
+    if kind == "passthrough":                              # the pair leads the bound, and the emulation comes close to it
+        assert max(r for (s, l), r in ratios.items() if s == "resid") > 0.5, ratios
+
+
+@pytest.mark.parametrize("mutant", R.SPLIT_MUTANTS)
+@pytest.mark.parametrize("geo", list(SPLIT_GEOMETRIES))
+def test_low_half_mutants_leave_the_residual_bound(geo, mutant):
+    tw, n, inp, runs = split_chain(geo, "passthrough", mutant)
+    ratios = R.check_chain(tw, n, inp, runs, split=True, exact=False)
+    resid = {k: r for k, r in ratios.items() if k[0] == "resid"}
+    print(f"{geo} {mutant}:", "  ".join(f"resid{l}={r:.3g}" for (s, l), r in resid.items()))
+    assert max(resid.values()) > 1.0, f"mutant {mutant} stays within the residual bound ({resid})"
+    if mutant == "no_clamp":                               # the exact properties see this one as well
+        with pytest.raises(AssertionError, match="NaN code"):
+            R.check_chain(tw, n, inp, runs, split=True)
+
+
+@pytest.mark.parametrize("kind", ("passthrough", "stress"))
+@pytest.mark.parametrize("geo", list(SPLIT_GEOMETRIES))
+def test_row_partials_missing_an_8_column_piece_leave_the_bound(geo, kind):
+    tw, n, inp, runs = split_chain(geo, kind, R.STATS_MUTANT)
+    ratios = R.check_chain(tw, n, inp, runs, split=True, exact=False)
+    seen = {k: r for k, r in ratios.items() if k[0] in ("qkv", "mlp")}
+    print(f"{geo} {kind} {R.STATS_MUTANT}:", "  ".join(f"{s}{l}={r:.3g}" for (s, l), r in seen.items()))
+    assert ratios[("qkv", 0)] <= 1.0                       # block 0's q|k|v has the embedding kernel's partials
+    assert ratios[("mlp", 0)] > 1.0 and ratios[("qkv", 1)] > 1.0, seen
+
+
 def test_rounding_helpers():
     a = np.array([1.0, 1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11, 65504.0, 2.0 ** -25, 3.0e-39], np.float32)
     assert np.array_equal(R.round16(a, "fp16")[:3], np.array([1.0, 1.0, 1.0 + 2.0 ** -9], np.float32))     # ties to even

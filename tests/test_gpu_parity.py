@@ -217,6 +217,8 @@ def test_encoder_split_residual_stream(gpu_lib, b32_weights, golden_encoder, mon
             monkeypatch.setenv("VQ_AMD_RESID", mode)
             enc = VitEncoder(VIT_B_32, W, max_batch=64)
             out[mode] = enc.encode(frames)
+            if mode == "split":                                            # the low half is in use: its bytes are not all zero
+                assert enc.debug_read("xl", 64 * 50).any()
             enc.close()
         monkeypatch.delenv("VQ_AMD_RESID")
         d = float(np.abs(out["split"] - out["f32"]).max())

@@ -90,6 +90,8 @@ SIGNATURES = {
     "vq_encoder_profile_class_name": (c_char_p, [c_int]),
     "vq_encoder_profile_bracket_overhead": (c_int, [c_void_p, POINTER(c_float)]),
     "vq_encoder_debug_set_layers": (c_int, [c_void_p, c_int]),
+    "vq_encoder_debug_keep_stream": (c_int, [c_void_p, c_int]),
+    "vq_encoder_debug_stream_is_split": (c_int, [c_void_p, POINTER(c_int)]),
     "vq_encoder_debug_read": (c_int, [c_void_p, c_char_p, c_int, POINTER(c_float)]),
     "vq_text_encoder_create": (c_int, [POINTER(TextConfigC), POINTER(POINTER(c_float)), c_int, c_int, c_int, POINTER(c_void_p)]),
     "vq_text_encoder_encode_ids": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, POINTER(c_float)]),

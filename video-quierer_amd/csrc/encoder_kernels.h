@@ -137,8 +137,11 @@ __device__ __forceinline__ void st8_maybe_nt(uint16_t* p, uint2 v) {
 enum : int { RS_IN_SPLIT = 1, RS_OUT_SPLIT = 2, RS_OUT_F32 = 4, RS_F32 = RS_OUT_F32 };
 // [r04, second session] The low half as ONE byte: xl is stored as fp8 (OCP e4m3 of xl * 512, clamped to the format's +-448 - an
 // out-of-range conversion is a NaN) instead of fp16: 3 bytes per element in and 3 out of a residual epilogue instead of 4 + 4.  |xl| is
-// at most half an fp16 ulp of x, so xl * 512 <= |x| / 4: nothing clamps below |x| = 1,792, and the pair carries x to ~15 bits
-// (|error| <= 2^-15 |x| for |x| >= 2^-6; below that xl flushes to zero and the error is <= 2^-17).  That is 16 times finer than the
+// at most half an fp16 ulp of x: 0.5 in [1024, 2048), so nothing clamps below |x| = 2048 (from there on up to half an ulp - 448 / 512 is
+// lost: 0.125 below 4096).  Under the clamp the pair's error is e4m3's on xl * 512: at most 2^-16 * 2^floor(log2 |x|) for |x| >= 2^-3 (half
+// a step of three mantissa bits, 1 / 32 of xh's own rounding error), and at most 2^-19 absolute below that, where xl * 512 is an fp8
+// SUBNORMAL of step 2^-9 (relative to |x| that is up to 2^-14 in [2^-5, 2^-4) and 2^-13 in [2^-6, 2^-5)); below |x| = 2^-7 xl is zero and
+// the pair is xh.  Swept over every fp16 binade in tests/test_encoder_stages_cpu.py (pair_bound).  That is finer than the
 // rounding of xh that every GEMM applies to its operand anyway: against the fp32 stream the embeddings move by 7.5e-5 (the 16 + 16-bit
 // pair: 7e-5) and the score error against the fp32 pipeline is unchanged (7.2e-5 / 7.4e-5).  103.7k -> 105.7k frames/s with three
 // batches in flight, same box (profiles/r04_ab_resid_xl8.txt).  VQ_RESID_XL8=0 builds the 16 + 16-bit form (A/B switch).

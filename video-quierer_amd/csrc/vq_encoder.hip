@@ -80,6 +80,8 @@ struct vq_encoder {
     hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_fwd[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
     int slot_n[2] = {0, 0};                     // frames in flight per slot (0 = idle)
     int run_layers = -1;
+    bool keep_stream = false;                  // debug: a layer-limited pass keeps the residual stream in the form the full pass holds it in (vq_encoder_debug_keep_stream)
+    bool stream_split = false;                 // what the last pass left: the pair xh + xl (true) or the fp32 x
     int last_n = 0;
     bool is_text = false;       // CLIP text tower (vq_text_encoder_*): token embedding, causal attention, EOS pooling
     float* tok_emb = nullptr; int* d_ids = nullptr; int* d_rowidx = nullptr; int vocab = 0, eos_id = 0;
@@ -296,8 +298,12 @@ int run_forward(vq_encoder* e, const uint8_t* d_frames, int n, int swap_rb, floa
     // [r04] the residual stream at 16 + 16 bits between the residual epilogues (encoder_kernels.h): fp16 operands in every group
     // that writes xh, and not in layer-limited debug runs (vq_encoder_debug_read reads the fp32 x).  The first residual epilogue
     // reads the embedding kernel's fp32 x; the last one in front of a reader of x (pooling head / the CLS-only last block) writes it.
-    const bool cls_last = !e->is_text && e->prune_last && e->run_layers < 0;
-    const bool split = e->split_resid && fQ && f1 && e->run_layers < 0;
+    // With keep_stream a layer-limited run is the full pass cut short: every block it runs has the full pass's form and modes
+    // (decided by cfg.layers and prune_last, not by the limit), and x, xh, xl stay as that block left them.
+    const bool as_full = e->run_layers < 0 || e->keep_stream;
+    const int last_l = as_full ? c.layers - 1 : nl - 1;        // the block in front of the pooling head
+    const bool cls_last = !e->is_text && e->prune_last && as_full;
+    const bool split = e->split_resid && fQ && f1 && as_full;
     bool stream_split = false;                                 // what the residual stream is held as right now
     auto resid_mode = [&](bool wants_f32_after) {
         if (!split) return (int)RS_F32;
@@ -351,7 +357,7 @@ int run_forward(vq_encoder* e, const uint8_t* d_frames, int n, int swap_rb, floa
         // Only the CLS token of the last block is consumed (E8): its out_proj / LN2 / MLP run on the
         // n CLS rows instead of n*T rows (292.8 MMAC of 4408.8 per frame).  K/V and the
         // attention itself still cover every token.  $VQ_AMD_FULL_LAST_LAYER=1 disables the pruning.
-        const bool cls_only = !e->is_text && e->prune_last && e->run_layers < 0 && l == c.layers - 1;   // debug runs keep every row
+        const bool cls_only = cls_last && l == c.layers - 1;   // layer-limited runs keep every row (unless they keep the full pass's stream)
         if (cls_only) {
             const int crows = pad_rows(n);
             {   // attention rows of the CLS tokens -> compact operand (the q|k|v buffer is free now); x, xh (compact) out
@@ -425,7 +431,7 @@ int run_forward(vq_encoder* e, const uint8_t* d_frames, int n, int swap_rb, floa
         {   // fc2 + residual; writes xh and the row partials for the next block's folded LN1
             Prof p(e, C_GEMM_FC2);
             // the fp32 x is wanted behind this epilogue when the pooling head comes next, or the CLS-only last block
-            const int mode = resid_mode(l == nl - 1 || (cls_last && l == c.layers - 2));
+            const int mode = resid_mode(l == last_l || (cls_last && l == c.layers - 2));
             VQ_TRY(by_f16(f2, [&](auto F) {
                 return by_f16(fQ, [&](auto FO) {
                     auto go = [&](auto epi) { return launch_gemm_auto<VQ_F16(F)>(st, e->mlp, c.mlp, L.w_fc2, c.mlp, gemm_rows(H, c.mlp, 8), H, c.mlp, epi, gf(8, rows_gemm, H, c.mlp)); };
@@ -448,6 +454,7 @@ int run_forward(vq_encoder* e, const uint8_t* d_frames, int n, int swap_rb, floa
     }
     VQ_HIP(hipGetLastError());
     e->last_n = n;
+    e->stream_split = stream_split;
     return 0;
 }
 
@@ -1003,6 +1010,18 @@ int vq_encoder_debug_set_layers(vq_encoder* e, int layers) {
     return 0;
 }
 
+int vq_encoder_debug_keep_stream(vq_encoder* e, int on) {
+    VQ_CHECK(e, "vq_encoder_debug_keep_stream: null handle");
+    e->keep_stream = on != 0;
+    return 0;
+}
+
+int vq_encoder_debug_stream_is_split(vq_encoder* e, int* split) {
+    VQ_CHECK(e && split, "vq_encoder_debug_stream_is_split: null argument");
+    *split = e->stream_split ? 1 : 0;
+    return 0;
+}
+
 int vq_encoder_debug_read(vq_encoder* e, const char* name, int rows, float* out) {
     VQ_CHECK(e && name && out, "vq_encoder_debug_read: null argument");
     VQ_CHECK(rows > 0 && rows <= e->rows_pad, "vq_encoder_debug_read: rows out of range");
@@ -1011,6 +1030,13 @@ int vq_encoder_debug_read(vq_encoder* e, const char* name, int rows, float* out)
     const size_t H = e->cfg.hidden;
     if (!strcmp(name, "x")) {
         VQ_HIP(hipMemcpy(out, e->x, (size_t)rows * H * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    if (!strcmp(name, "xl")) {                             // the raw bytes; decoding them is the reader's business
+        VQ_CHECK(VQ_RESID_XL8, "vq_encoder_debug_read: 'xl' is read as bytes, and this build holds it as fp16");
+        std::vector<uint8_t> bytes((size_t)rows * H);
+        VQ_HIP(hipMemcpy(bytes.data(), e->xl, bytes.size(), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < bytes.size(); ++i) out[i] = (float)bytes[i];
         return 0;
     }
     const uint16_t* src = nullptr; size_t cols = 0; bool f16 = false;

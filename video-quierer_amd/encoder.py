@@ -163,9 +163,20 @@ class VitEncoder:
     def debug_set_layers(self, layers: int) -> None:
         _lib.check(_lib.load().vq_encoder_debug_set_layers(self._h, int(layers)))
 
+    def debug_keep_stream(self, on: bool) -> None:
+        """A layer-limited pass runs its blocks as the full pass does (split residual stream, epilogue modes) and leaves
+        x, h and xl as they are at that point; its pooled output means nothing."""
+        _lib.check(_lib.load().vq_encoder_debug_keep_stream(self._h, int(bool(on))))
+
+    def debug_stream_is_split(self) -> bool:
+        """Whether the last pass left the residual stream as the pair h + xl (else as the fp32 x)."""
+        split = ctypes.c_int(0)
+        _lib.check(_lib.load().vq_encoder_debug_stream_is_split(self._h, ctypes.byref(split)))
+        return bool(split.value)
+
     def debug_read(self, name: str, rows: int) -> np.ndarray:
         cols = {"x": self.cfg.hidden, "h": self.cfg.hidden, "qkv": 3 * self.cfg.hidden, "att": self.cfg.hidden,
-                "mlp": self.cfg.mlp}[name]
+                "mlp": self.cfg.mlp, "xl": self.cfg.hidden}[name]
         out = np.empty((rows, cols), dtype=np.float32)
         _lib.check(_lib.load().vq_encoder_debug_read(self._h, name.encode(), int(rows), _lib.fptr(out)))
         return out
