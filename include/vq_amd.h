@@ -189,6 +189,25 @@ int vq_text_encoder_create(const vq_text_config* cfg, const float* const* weight
 int vq_text_encoder_encode_ids(vq_text_encoder* enc, const int32_t* ids, int n, int seq_len, float* out);
 int vq_text_encoder_destroy(vq_text_encoder* enc);
 
+/* What a forward pass of n inputs would launch, and where a handle's buffers would lie (csrc/encoder_plan.h), for a
+ * handle that is never made: one of `vit` / `text` (the other NULL), max_batch, the create flags, `shared` (the handle
+ * of vq_encoder_create_shared: workspace only), the two debug switches, this process's environment.  Row counts of the
+ * GEMMs (qkv and fc1 / out_proj / fc2 / patch embedding / the CLS-only block), the kernel id each hands to the GEMM
+ * dispatch, the patchify kernel (0 none, 1 8-pixel, 2 generic) and the attention kernel (0 causal workgroup, 1 T = 50
+ * tile, 2 T <= 64 tile, 3 per-wave stream, 4 32-row workgroup, 5 64-row workgroup), the residual stream's form, and
+ * byte offsets from the arena's base.  resid_modes (optional) [2 * layers]: the mode bits (1 reads xh + xl, 2 writes
+ * xl, 4 writes the fp32 x) of each block's out_proj and fc2 epilogue, -1 where the pass runs neither on every row.
+ * Pure host arithmetic: needs neither vq_init nor a device. */
+typedef struct vq_encoder_plan {
+    int64_t rows, rows_gemm, rows_out, rows_fc2, prows, prows_gemm, rows_cls;
+    int64_t k_patch, k_qkv, k_out, k_fc1, k_fc2, k_cls;
+    int64_t patchify, attention, layers_run, cls_only_last, fc2_splits, split, stream_left_split;
+    int64_t rows_pad, prow_pad, arena_bytes, workspace_end;      /* workspace_end: where mlp, the last buffer, ends */
+    int64_t off_input, off_rowidx, off_ps, off_x, off_out, off_h, off_xl, off_qkv, off_att, off_mlp;   /* input: frames or ids; rowidx: -1 for images */
+} vq_encoder_plan;
+int vq_debug_encoder_plan(const vq_vit_config* vit, const vq_text_config* text, int max_batch, int n, int flags, int shared,
+                          int run_layers, int keep_stream, vq_encoder_plan* out, int* resid_modes);
+
 /* Mainloop stamps / ablations / clock probes are not product entry points: include/vq_amd_diag.h (`make DIAG=1`). */
 
 /* ---- index: HNSWIndex.add / search / size / save / load --------------------- */

@@ -131,8 +131,9 @@ SPLIT_TEXT = {"text512": TEXT_GEOMETRIES["text512"][0]}     # two blocks reach a
 def _split_cases():
     """(geometry, kind, batch, concurrent, $VQ_AMD_GEMM, $VQ_AMD_RESID, GEMM rows of out_proj / fc2, their kernel).
 
-    The rows are the encoder's padding rule by hand (run_forward: 160-row tiles where prefer_tn160 holds for a lone handle, else
-    128 or 256); the kernel for them is asked of vq_debug_gemm_plan.  t50: 50 and 250 rows -> 128 and 256 rows of the 128x128
+    The rows are the encoder's padding rule (plan_forward: 160-row tiles where prefer_tn160 holds for a lone handle, else 128 or
+    256), pinned here and compared with vq_debug_encoder_plan's out_proj and fc2 rows in the test; the kernel for them is asked
+    of vq_debug_gemm_plan.  t50: 50 and 250 rows -> 128 and 256 rows of the 128x128
     kernel; 300 rows pad to 384 of the same kernel (two 160-row tiles would be no more workgroups than two 256-row tiles), so
     350 rows (n = 7: three 160-row tiles, the odd-MI tail) are the smallest batch on the ring; 6400 rows are on the ring too.
     The deep 256x256 kernel comes by $VQ_AMD_GEMM=8 at 256 rows: the text tower at n = 3 (231 rows) start to end, the image
@@ -148,6 +149,20 @@ def _split_cases():
             ("t50", "seeded", 5, False, None, None, 256, TILE128),
             ("t50", "passthrough", 5, False, None, "f32", 256, TILE128), ("text512", "passthrough", 4, False, None, "f32", 384, TILE128)]
     return out
+
+
+def _plan_resid_rows(lib, cfg, n, concurrent):
+    """(out_proj rows, fc2 rows) of a handle with max_batch = n under this process's environment (vq_debug_encoder_plan)."""
+    from video_quierer_amd import _lib
+    out = _lib.EncoderPlanC()
+    if isinstance(cfg, TextConfig):
+        c = _lib.TextConfigC(cfg.vocab, cfg.max_positions, cfg.hidden, cfg.mlp, cfg.layers, cfg.heads, cfg.proj_dim, cfg.eos_token_id, cfg.ln_eps)
+        args = (None, ctypes.byref(c))
+    else:
+        c = _lib.VitConfigC(cfg.image_size, cfg.patch_size, cfg.hidden, cfg.mlp, cfg.layers, cfg.heads, cfg.proj_dim, cfg.ln_eps)
+        args = (ctypes.byref(c), None)
+    assert lib.vq_debug_encoder_plan(*args, n, n, 1 | (2 if concurrent else 0), 0, -1, 0, ctypes.byref(out), None) == 0
+    return out.rows_out, out.rows_fc2
 
 
 def _plan_kernels(lib, M, N, K, force):
@@ -175,6 +190,7 @@ def test_every_stage_of_the_split_stream_against_fp64(gpu_lib, monkeypatch, geo,
         monkeypatch.setenv("VQ_AMD_GEMM", str(force))
     rows = n * tw.T
     assert gemm_rows >= rows
+    assert _plan_resid_rows(_lib.load(), cfg, n, concurrent) == (gemm_rows, gemm_rows), (geo, n)
     plan_force = force or (6 if concurrent else 0)          # a concurrent handle plans as GK_AUTO_NO160
     for K in (cfg.hidden, cfg.mlp):                         # out_proj, fc2: the GEMMs that carry the wide residual epilogue
         assert _plan_kernels(_lib.load(), gemm_rows, cfg.hidden, K, plan_force) == [(kernel, gemm_rows)], (geo, n, K)

@@ -299,6 +299,55 @@ def test_encoder_batch_shapes_and_paths(encoder, b32_weights):
         encoder.encode(np.zeros((1, 200, 224, 3), np.uint8))
 
 
+@pytest.mark.parametrize("tower,n,full_last", [("image", 5, False), ("image", 5, True), ("text", 3, False)])
+def test_encoder_runs_what_its_plan_says(gpu_lib, monkeypatch, tower, n, full_last):
+    """One profiled pass: the event brackets per kernel class are the counts that follow from vq_debug_encoder_plan's scalars
+    (one bracket per full-row GEMM per block, three for a CLS-only last block), for a 3-block T = 50 image tower - with and
+    without the CLS-only last block - and the 2-block text tower."""
+    import ctypes
+    import encoder_stage_ref as R
+    from video_quierer_amd.encoder import VitEncoder
+    from video_quierer_amd.text_encoder import TextEncoder
+    from video_quierer_amd.weights import TextConfig, VitConfig
+    for name in ("VQ_AMD_GEMM", "VQ_AMD_RESID", "VQ_AMD_ATTN", "VQ_AMD_FULL_LAST_LAYER", "VQ_AMD_DTYPE"):
+        monkeypatch.delenv(name, raising=False)
+    if full_last:
+        monkeypatch.setenv("VQ_AMD_FULL_LAST_LAYER", "1")
+    lib = gpu_lib.load()
+    plan = gpu_lib.EncoderPlanC()
+    if tower == "text":
+        cfg = TextConfig(vocab=520, eos_token_id=519, bos_token_id=518, layers=2)
+        c = gpu_lib.TextConfigC(cfg.vocab, cfg.max_positions, cfg.hidden, cfg.mlp, cfg.layers, cfg.heads, cfg.proj_dim, cfg.eos_token_id, cfg.ln_eps)
+        assert lib.vq_debug_encoder_plan(None, ctypes.byref(c), n, n, 1, 0, -1, 0, ctypes.byref(plan), None) == 0
+        enc = TextEncoder(cfg, R.make_weights(tower, cfg, "seeded"), max_batch=n, compute_dtype="fp16")
+        run = enc.encode_ids
+    else:
+        cfg = VitConfig(layers=3)
+        c = gpu_lib.VitConfigC(cfg.image_size, cfg.patch_size, cfg.hidden, cfg.mlp, cfg.layers, cfg.heads, cfg.proj_dim, cfg.ln_eps)
+        assert lib.vq_debug_encoder_plan(ctypes.byref(c), None, n, n, 1, 0, -1, 0, ctypes.byref(plan), None) == 0
+        enc = VitEncoder(cfg, R.make_weights(tower, cfg, "seeded"), max_batch=n, compute_dtype="fp16")
+        run = enc.encode
+    assert (plan.layers_run, plan.cls_only_last) == (cfg.layers, int(tower == "image" and not full_last))
+    full = plan.layers_run - plan.cls_only_last             # blocks that run on every row
+    image = int(tower == "image")
+    want = {"patchify_u8": image, "gemm_patch_embed": image, "embed_finish_ln": 1, "layernorm_bf16": 0, "gemm_qkv": plan.layers_run,
+            "attention": plan.layers_run, "gemm_out_proj_residual": full, "gemm_fc1_quickgelu": full, "gemm_fc2_residual": full,
+            "pool_project": 1, "last_block_cls_rows": 3 * plan.cls_only_last}
+    ms, cnt = (ctypes.c_float * gpu_lib.ENC_NCLASS)(), (ctypes.c_int * gpu_lib.ENC_NCLASS)()
+    try:
+        inp = R.make_input(tower, cfg, n)
+        plain = run(inp)
+        gpu_lib.check(lib.vq_encoder_profile_begin(enc._h))
+        emb = run(inp)
+        gpu_lib.check(lib.vq_encoder_profile_end(enc._h, ms, cnt))
+    finally:
+        enc.close()
+    got = {lib.vq_encoder_profile_class_name(i).decode(): cnt[i] for i in range(gpu_lib.ENC_NCLASS)}
+    assert got == want
+    assert all(ms[i] > 0.0 for i in range(gpu_lib.ENC_NCLASS) if cnt[i])
+    assert np.array_equal(emb, plain) and np.all(np.isfinite(emb))      # the brackets change nothing
+
+
 def test_feature_extractor_api(gpu_lib, b32_weights):
     from video_quierer_amd.core.feature_extractor import FeatureExtractor
     fx = FeatureExtractor(model_name="seed:1234", batch_size=32, device_batch=64)

@@ -68,6 +68,14 @@ class VitConfigC(ctypes.Structure):
                 ("layers", c_int32), ("heads", c_int32), ("proj_dim", c_int32), ("ln_eps", c_float)]
 
 
+class EncoderPlanC(ctypes.Structure):
+    """vq_encoder_plan: int64 fields, in the header's order."""
+    _fields_ = [(name, c_int64) for name in (
+        "rows rows_gemm rows_out rows_fc2 prows prows_gemm rows_cls k_patch k_qkv k_out k_fc1 k_fc2 k_cls "
+        "patchify attention layers_run cls_only_last fc2_splits split stream_left_split rows_pad prow_pad arena_bytes workspace_end "
+        "off_input off_rowidx off_ps off_x off_out off_h off_xl off_qkv off_att off_mlp").split()]
+
+
 # name -> (restype, argtypes); every symbol include/vq_amd.h declares
 SIGNATURES = {
     "vq_init": (c_int, [c_int]),
@@ -96,6 +104,7 @@ SIGNATURES = {
     "vq_text_encoder_create": (c_int, [POINTER(TextConfigC), POINTER(POINTER(c_float)), c_int, c_int, c_int, POINTER(c_void_p)]),
     "vq_text_encoder_encode_ids": (c_int, [c_void_p, POINTER(c_int32), c_int, c_int, POINTER(c_float)]),
     "vq_text_encoder_destroy": (c_int, [c_void_p]),
+    "vq_debug_encoder_plan": (c_int, [POINTER(VitConfigC), POINTER(TextConfigC), c_int, c_int, c_int, c_int, c_int, c_int, POINTER(EncoderPlanC), POINTER(c_int)]),
     "vq_debug_gemm": (c_int, [POINTER(c_float), POINTER(c_float), c_int, c_int, c_int, c_int, POINTER(c_float)]),
     "vq_debug_gemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "vq_index_create": (c_int, [c_int, POINTER(c_void_p)]),
