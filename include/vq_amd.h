@@ -424,6 +424,23 @@ const char* vq_index_profile_class_name(int cls);
  * queries answered by the exact path. */
 int vq_index_last_search_stats(vq_index* idx, int64_t* stats /*[3]*/);
 
+/* What an fp16 search (mode 2) of nq queries for k results over n rows of dimension dim would launch (csrc/scan_plan.h), in
+ * this build and with this process's environment switches; force_scan != 0 takes the place of $VQ_AMD_SCAN.
+ * scan: 1 the 128 x 1024 MFMA tile, 3 the streaming scan of small batches, 5 the 256 x 2048 batch scan (2, 4: its superseded
+ * predecessors, `make EXPERIMENTS=1`; 51-53: diagnostic forms of 5, `make DIAG=1`).  qt / range: queries / rows per scan
+ * workgroup; streams = n_pad / 128 keys pairs per query; q_chunk queries per chunk (1 GiB of keys), `chunks` of them.
+ * nqg, fused_q: the streaming scan's groups of 16 queries per pass, and whether it rounds the queries itself (no
+ * conversion launch).  rescore: 0 BATCH8, 1 LARGE4, 2 XLARGE4, 3 LARGE1, 4 XLARGE1, 5 SMALL32, 6 SMALL64, with its queries
+ * per workgroup, dynamic LDS and the key layout it is told (1, 2, 3); rescore_files_flags: its workgroup writes the flagged
+ * list and the counters itself (no collect_flags_kernel).  q_pad .. rescore_grid: the launch of the first (largest) chunk.
+ * Pure host arithmetic: needs neither vq_init nor a device.  A scan this build does not carry returns VQ_ERR_INVALID. */
+typedef struct vq_scan_plan {
+    int64_t scan, qt, range, n_pad, streams, ranges, q_chunk, chunks, nqg, fused_q, rb, scan_lds;
+    int64_t rescore, rescore_qpw, rescore_lds, layout, rescore_files_flags;
+    int64_t q_pad, q_tiles, scan_grid_x, scan_grid_y, rescore_grid;
+} vq_scan_plan;
+int vq_debug_scan_plan(int dim, int64_t n, int nq, int k, int force_scan, vq_scan_plan* out);
+
 /* ------------------------------------------------------------------ frame preprocessing
  * The resize in front of the encoder, bit-identical to Pillow's 8-bit separable resample
  * (Pillow src/libImaging/Resample.c), which is what the reference runs in two places:

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """A/B of the batch scan kernels on one box: per-kernel device time of a top-10 search over N x 512 at Q queries.
-usage: scan_ab.py [N] [Q] [k] [dim]   (env VQ_AMD_SCAN = 2 four-phase | 4 deep prefetch)"""
+usage: scan_ab.py [N] [Q] [k] [dim]   (env VQ_AMD_SCAN = 1 128x128 tile | 5 the product's scan, the default;
+2 four-phase | 4 deep prefetch: the superseded mainloops, which only a `make EXPERIMENTS=1` library carries - point VQ_AMD_LIB
+at one; 51 | 52 | 53: diagnostic forms of 5, `make DIAG=1`.  A library that does not carry the kind refuses to create the index.)"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""fp16 scan vs the C oracle on a few shapes (debug helper).  usage: VQ_AMD_SCAN=2 scan_check.py"""
+"""fp16 scan vs the C oracle on a few shapes (debug helper).  usage: VQ_AMD_SCAN=1 scan_check.py
+(VQ_AMD_SCAN=2|4 need VQ_AMD_LIB=<a `make EXPERIMENTS=1` library>, 51-53 a `make DIAG=1` one)"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

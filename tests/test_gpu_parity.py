@@ -792,6 +792,42 @@ def test_fp16_scan_random_matches_oracle_bit_exact(gpu_lib):
     _scan_vs_oracle(vecs[:16500], qs[:17], 1)
     for k in (21, 32, 40, 64):                                         # the caller's k * 2 (video_search_system.py:297): wide candidate pool, MFMA-tile scan
         _scan_vs_oracle(vecs, qs, k)
+    # dim % 128 != 0: the 128 x 1024 MFMA tile and key layout 1 (16.1 ranges of 1024, 1.02 query tiles of 128)
+    vecs192 = rng.standard_normal((16500, 192)).astype(np.float32)
+    qs192 = rng.standard_normal((130, 192)).astype(np.float32)
+    for k in (10, 32):
+        _scan_vs_oracle(vecs192, qs192, k)
+
+
+@pytest.mark.parametrize("dim,n,nq,k", [(512, 20001, 130, 10), (512, 20001, 3, 10), (192, 16500, 130, 10)])
+def test_search_runs_what_its_plan_says(gpu_lib, monkeypatch, dim, n, nq, k):
+    """One profiled fp16 search: the scan, re-score and query-conversion brackets are the counts that follow from
+    vq_debug_scan_plan's scalars (one scan and one re-score per chunk, no conversion where the streaming scan rounds the queries
+    itself) for the batch scan, the fused streaming scan and the 128 x 1024 tile; the brackets change nothing in the answer."""
+    import ctypes
+    from video_quierer_amd.indexes.hnsw import MODE_FP16, OptimizedHNSWIndex
+    for name in ("VQ_AMD_SCAN", "VQ_AMD_SCAN_SMALL", "VQ_AMD_SCAN_RB", "VQ_AMD_RESCORE_QPW4", "VQ_AMD_RESCORE_SMALL64"):
+        monkeypatch.delenv(name, raising=False)
+    plan = gpu_lib.ScanPlanC()
+    assert gpu_lib.load().vq_debug_scan_plan(dim, n, nq, k, 0, ctypes.byref(plan)) == 0
+    assert (plan.scan, plan.fused_q, plan.chunks) == ({130: 5 if dim == 512 else 1, 3: 3}[nq], int(nq == 3), 1)
+    rng = np.random.default_rng(47)
+    vecs = rng.standard_normal((n, dim)).astype(np.float32)
+    qs = rng.standard_normal((nq, dim)).astype(np.float32)
+    idx = OptimizedHNSWIndex(dimension=dim)
+    try:
+        idx.add_batch(list(vecs), list(range(n)))
+        idx.search_mode = MODE_FP16
+        plain = idx.search_batch(list(qs), k)
+        idx.profile_begin()
+        res = idx.search_batch(list(qs), k)
+        prof = idx.profile_end()
+    finally:
+        idx.close()
+    got = {name: prof[name]["launches"] for name in ("scan_f16_mfma_top2", "rescore_verify", "rows_to_f16")}
+    assert got == {"scan_f16_mfma_top2": plan.chunks, "rescore_verify": plan.chunks, "rows_to_f16": 0 if plan.fused_q else plan.chunks}
+    assert prof["scan_f16_mfma_top2"]["ms"] > 0.0 and prof["rescore_verify"]["ms"] > 0.0
+    assert res == plain and all(len(r) == k for r in res)
 
 
 def test_small_batch_streaming_scan_matches_oracle_bit_exact(gpu_lib):

@@ -76,6 +76,13 @@ class EncoderPlanC(ctypes.Structure):
         "off_input off_rowidx off_ps off_x off_out off_h off_xl off_qkv off_att off_mlp").split()]
 
 
+class ScanPlanC(ctypes.Structure):
+    """vq_scan_plan: int64 fields, in the header's order."""
+    _fields_ = [(name, c_int64) for name in (
+        "scan qt range n_pad streams ranges q_chunk chunks nqg fused_q rb scan_lds rescore rescore_qpw rescore_lds layout "
+        "rescore_files_flags q_pad q_tiles scan_grid_x scan_grid_y rescore_grid").split()]
+
+
 # name -> (restype, argtypes); every symbol include/vq_amd.h declares
 SIGNATURES = {
     "vq_init": (c_int, [c_int]),
@@ -142,6 +149,7 @@ SIGNATURES = {
     "vq_index_profile_end": (c_int, [c_void_p, POINTER(c_float), POINTER(c_int)]),
     "vq_index_profile_class_name": (c_char_p, [c_int]),
     "vq_index_last_search_stats": (c_int, [c_void_p, POINTER(c_int64)]),
+    "vq_debug_scan_plan": (c_int, [c_int, c_int64, c_int, c_int, c_int, POINTER(ScanPlanC)]),
     "vq_encoder_stage_frames": (c_int, [c_void_p, c_int, POINTER(c_void_p), c_int, c_int]),
     "vq_encoder_submit_staged": (c_int, [c_void_p, c_int, c_int, c_int]),
     "vq_encoder_wait_staged": (c_int, [c_void_p, c_int, POINTER(c_float)]),

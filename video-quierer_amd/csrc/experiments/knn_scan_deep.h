@@ -1,5 +1,6 @@
-// Third-generation batch scan: scan2_f16_top2_kernel (knn_scan_f16.h) on the deep-prefetch mainloop of
-// gemm_mfma256d.h — same 256 queries x 2048 rows per workgroup, same LDS image, same streams and key layout
+// Third-generation batch scan, superseded by scan5_f16_top2_kernel (knn_scan_fold.h: 9.79-9.83 ms against 9.53-9.55) and kept
+// for A/B runs behind VQ_AMD_SCAN=4, `make EXPERIMENTS=1` only: scan2_f16_top2_kernel (knn_scan_phase4.h) on the deep-prefetch
+// mainloop of gemm_mfma256d.h — same 256 queries x 2048 rows per workgroup, same LDS image, same streams and key layout
 // (rescore layout 2), same fold of a finished quadrant in the read half of the following phase.  What changes is the
 // staging: units are the LDS rows ONE phase reads (A0/A1 = 64-row halves of each wave's query rows, W0/W1 = 32-row
 // halves of each wave's matrix rows), each re-issued 2-3 phases after its last read, i.e. 5-6 phases (1.25 K-tiles)
@@ -7,14 +8,14 @@
 // offset in an SGPR).  See gemm_mfma256d.h for the schedule table and the RAW / WAR argument; the flattened K-tile
 // index runs over the 8 row tiles of the workgroup's range, so the DMA stream never stops at a row-tile boundary.
 #pragma once
-#include "vq_common.h"
-#include "gemm_mfma.h"
-#include "gemm_mfma256.h"
-#include "knn_scan_f16.h"
+#include "../vq_common.h"
+#include "../gemm_mfma.h"
+#include "../gemm_mfma256.h"
+#include "../knn_scan_f16.h"
 
 namespace vq {
 
-constexpr int SCAN4_LDS_BYTES = G2_LDS_BYTES + 8 * 8 * 64 * 8;      // + the running keys: 160 KiB, the whole LDS of a CU
+constexpr int SCAN4_LDS_BYTES = G2_LDS_BYTES + 8 * 8 * 64 * 8;      // + the running keys: 160 KiB, the whole LDS of a CU (= SCAN5_LDS_BYTES)
 
 __global__ __launch_bounds__(G2_THREADS, 2)
 void scan4_f16_top2_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __restrict__ X16,

@@ -1,5 +1,15 @@
-// Fourth-generation batch scan: scan4_f16_top2_kernel (knn_scan_deep.h) with the top-2 fold taken OUT of the row-tile
-// boundary and spread behind the MFMA clusters that follow it.
+// The batch scan: 256 queries x 2048 matrix rows per workgroup (geometry, streams, key layout 2: knn_scan_f16.h) on the
+// deep-prefetch mainloop of gemm_mfma256d.h, with the top-2 fold taken OUT of the row-tile boundary and spread behind the MFMA
+// clusters that follow it.  Fourth generation; its predecessor scan4_f16_top2_kernel, which folds at the row-tile boundary, is
+// parked in experiments/knn_scan_deep.h (`make EXPERIMENTS=1`).
+//
+// Staging: units are the LDS rows ONE phase reads (A0/A1 = 64-row halves of each wave's query rows, W0/W1 = 32-row halves of
+// each wave's matrix rows), each re-issued 2-3 phases after its last read, i.e. 5-6 phases (1.25 K-tiles) before its first
+// read, as `buffer_load ... lds` (one descriptor per operand, a 32-bit lane offset, the K / row-tile offset in an SGPR); see
+// gemm_mfma256d.h for the schedule table and the RAW / WAR argument.  The flattened K-tile index runs over the 8 row tiles of
+// the workgroup's range, so the DMA stream never stops at a row-tile boundary.  The running (best, second) keys of a lane's 8
+// query columns live in the 32 KiB of LDS behind the two K-tile buffers (SCAN5_LDS_BYTES), [wave][column][lane] float2: as 16
+// registers they pushed the kernel over its 256-register budget.
 //
 // What the fold costs (measured, profiles/r03_scan_fold_ab.txt — NOT the "third of the kernel" round 2 inferred from two
 // geometries): scan4, which folds in two bursts per row tile (behind phase 4 of its last K-tile and phase 1 of the next one,
@@ -32,7 +42,7 @@
 // one wave: no cross-wave hazard).  The last row tile of the range is folded after the loop.  Ragged tiles (the matrix's last
 // range only) take the same schedule with the row mask compiled in, behind a wave-uniform branch.
 //
-// Staging, LDS image, key layout, streams: scan4's.  Results are bit-identical to scan4's keys.
+// Results are bit-identical to the keys of the two parked mainloops.
 #pragma once
 #ifndef VQ_SCAN_NT_KEYS
 #define VQ_SCAN_NT_KEYS 0
@@ -41,9 +51,10 @@
 #include "gemm_mfma.h"
 #include "gemm_mfma256.h"
 #include "knn_scan_f16.h"
-#include "knn_scan_deep.h"
 
 namespace vq {
+
+constexpr int SCAN5_LDS_BYTES = G2_LDS_BYTES + 8 * 8 * 64 * 8;      // + the running keys: 160 KiB, the whole LDS of a CU
 
 // fold blocks dealt to one cluster: N of {query column mi (0..7), matrix-column half hn (0..1)}
 template <int N_, int M0 = 0, int H0 = 0, int M1 = 0, int H1 = 0, int M2 = 0, int H2 = 0>
@@ -79,7 +90,7 @@ void scan5_f16_top2_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __r
     const int m0 = qtile * SCAN2_QT;
     const int64_t n0 = (int64_t)range * SCAN2_RANGE;
 
-    // ---- LDS-DMA (scan4): 4 lane-offset registers, unit / piece / K / row-tile offsets scalar ----
+    // ---- LDS-DMA: 4 lane-offset registers, unit / piece / K / row-tile offsets scalar ----
     const int srow = lane >> 3, sslot = lane & 7;
     const int arow_w = (wave >> 2) * 128 + (wave & 3) * 16, wrow_w = (wave >> 1) * 64 + (wave & 1) * 16;
     const int ar = arow_w + srow, wrw = wrow_w + srow;

@@ -1,7 +1,7 @@
 // Small-batch scan: the reference's own call pattern is ONE query at a time, k*2 results
 // (src/video_search_system.py:297 `index.search(query_vector, k * 2)`), i.e. a matrix-vector product: every
 // fp16 row is read once from HBM per pass and does 2*Q FLOP per element — HBM-bound for Q below ~300
-// (SURVEY.md §8d).  The 256-query MFMA tile of scan2_f16_top2_kernel wastes 255/256 of its matrix work there.
+// (SURVEY.md §8d).  The 256-query MFMA tile of the batch scan wastes 255/256 of its matrix work there.
 //
 // This kernel streams the fp16 matrix straight into MFMA operand registers, no LDS:
 //   one wave = one stream of 128 consecutive rows = 8 blocks of 16 rows; per block 16 wave-wide 16-byte loads

@@ -17,8 +17,8 @@
 //
 // fp16 path (mode 2):
 //   1. set_group_max_kernel: gbest[i][g] = the order-preserving key of the largest fp16 score of query i over group g, for a
-//      whole tile of 256 queries per pass over the matrix — the 256 x 256 four-phase LDS-DMA mainloop of scan2_f16_top2_kernel
-//      (knn_scan_f16.h) with a group-max epilogue instead of the top-2 fold.  Wave (wr, wc) owns 64 rows of every 256-row tile,
+//      whole tile of 256 queries per pass over the matrix — the 256 x 256 four-phase LDS-DMA mainloop of gemm_mfma256.h over
+//      2048-row ranges (geometry: knn_scan_f16.h) with a group-max epilogue where a batch scan folds its top-2.  Wave (wr, wc) owns 64 rows of every 256-row tile,
 //      all inside one 128-row stream: when stream_group says those rows share a label, the epilogue is a register maximum per
 //      query column and ONE atomicMax per (wave, row tile, query); otherwise it reads the 8 row labels of its quadrant and
 //      issues at most one atomicMax per (query, run of equal labels); where a lane's 8 rows hold more than two runs (scattered
@@ -61,8 +61,9 @@ constexpr int SET_MAX_M = 4096;                       // query frames per call
 constexpr int64_t SET_KEY_BUDGET = (int64_t)16 << 20; // candidate (group, query) keys on the fp16 path (more: exact redo)
 constexpr float SET_SLACK = 1.0f / 524288;            // 2^-19 >= 5 * 2^-22 (derivation above)
 
-// ---- fp16 pass 1: group-max over a 256-query tile.  Geometry, staging, phases and waits are scan2_f16_top2_kernel's; the
-// fold of a finished quadrant (4 query blocks x 2 row blocks of 16) is replaced.  stream_group / group_of cover
+// ---- fp16 pass 1: group-max over a 256-query tile.  A workgroup covers 256 queries x 2048 rows (SCAN2_QT, SCAN2_RANGE: 8 row
+// tiles, one continuous K loop); staging, phases and waits are gemm_tn256_kernel's (gemm_mfma256.h); a finished quadrant (4 query
+// blocks x 2 row blocks of 16) is folded into group maxima.  stream_group / group_of cover
 // `streams` = cdiv(n, 128) streams; row tiles past them score nothing.  MASK: disallowed groups never reach gbest. ----
 template <bool MASK>
 __global__ __launch_bounds__(G2_THREADS, 2)
@@ -259,7 +260,7 @@ void set_group_max_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __re
     };
 
     int sg_cur = -2, sg_prev = -2;
-    // One K-tile: the four phases, hazards and waits of scan2_f16_top2_kernel.  `last` = final K-tile of a row tile: each
+    // One K-tile: the four phases, hazards and waits of gemm_tn256_kernel.  `last` = final K-tile of a row tile: each
     // quadrant is folded in the read half of the phase after its last MFMAs; the fourth quadrant's fold lands in phase 1 of
     // the next K-tile (`fold_prev`).
     auto tile = [&](int kt, int bufi, bool last, bool fold_prev, int t) __attribute__((always_inline)) {

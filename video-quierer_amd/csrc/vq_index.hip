@@ -6,12 +6,15 @@
 #include "knn_kernels.h"
 #include "knn_scan_f16.h"
 #include "knn_fallback.h"
-#include "knn_scan_deep.h"
 #include "knn_scan_fold.h"
 #include "knn_grouped.h"
 #include "knn_remove.h"
 #include "knn_filter.h"
 #include "knn_set.h"
+#include "scan_plan.h"
+#ifdef VQ_SCAN_EXPERIMENTS      // `make EXPERIMENTS=1`: the two superseded batch mainloops behind VQ_AMD_SCAN=2|4
+#include "experiments/scan_experiments.h"
+#endif
 
 #include <algorithm>
 #include <cstdlib>
@@ -25,6 +28,23 @@ int require_init();
 enum IdxClass { I_NORMALIZE = 0, I_TO_F16, I_EXACT_DIST, I_SELECT, I_MFMA_SCAN, I_RESCORE };
 static const char* kIdxClassNames[VQ_IDX_NCLASS] = {
     "normalize_rows", "rows_to_f16", "exact_dist_f64chain", "select_topk", "scan_f16_mfma_top2", "rescore_verify"};
+#ifdef VQ_DIAG
+constexpr bool SCAN_DIAG_BUILD = true;
+#else
+constexpr bool SCAN_DIAG_BUILD = false;
+#endif
+#ifdef VQ_SCAN_EXPERIMENTS
+constexpr bool SCAN_EXPERIMENTS_BUILD = true;
+#else
+constexpr bool SCAN_EXPERIMENTS_BUILD = false;
+#endif
+// plan_scan (scan_plan.h, no HIP in it) computes with the kernels' geometry
+static_assert(SP_STREAM_ROWS == SCAN_STREAM_ROWS && SP_TILE128_QT == SCAN_QT && SP_TILE128_RANGE == SCAN_RANGE && SP_BATCH_QT == SCAN2_QT &&
+              SP_BATCH_RANGE == SCAN2_RANGE && SP_STREAM_QB == SCAN3_QB && SP_STREAM_FUSED_MAX_Q == SCAN3_FUSED_MAX_Q && SP_STREAM_MAX_Q == SCAN3_MAX_Q,
+              "scan_plan.h: scan geometry");
+static_assert(SP_PHASE4_LDS == G2_LDS_BYTES && SP_FOLD_LDS == SCAN5_LDS_BYTES, "scan_plan.h: scan LDS bytes");
+static_assert(SP_K_SMALL == RV_K_SMALL && SP_K_SMALL64 == RV_K_SMALL64 && SP_K_MID == RV_K_MID && SP_BATCH8_QPW == RV_QPW && SP_LARGE_QPW == RVL_QPW &&
+              SP_LARGE_QPW == RVX_QPW && SP_SMALL32_C == RV_C && SP_SMALL64_C == 64, "scan_plan.h: re-score geometry");
 }  // namespace vq
 
 using namespace vq;
@@ -167,9 +187,7 @@ struct vq_index {
     DevBuf<uint32_t> d_norm_range;
     bool norm_dirty = false, near_unit = true;
     float row_norm_max = 1.0f;
-    int scan_version = 5;          // $VQ_AMD_SCAN: 5 = deep-prefetch mainloop with the fold spread behind the MFMA clusters (needs dim % 128 == 0), 4 = the same with
-                                   // the fold at the row-tile boundary, 2 = 256x256 four-phase, 1 = 128x128; diagnostic builds: 51 / 52 = scan5 without fold / fold not interleaved
-    bool no_small_scan = false;    // $VQ_AMD_SCAN_SMALL=0: batches of <= SCAN3_MAX_Q queries also take the MFMA-tile scan (A/B switch)
+    ScanSwitches scan_switches;    // the fp16 search's A/B switches (scan_plan.h), read from the environment at create
     bool profiling = false;
     struct Ev { int cls; hipEvent_t a, b; };
     std::vector<Ev> events;
@@ -381,12 +399,6 @@ int search_exact(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_
     });
 }
 
-// fp16 MFMA scan + exact re-score with proof; unproven queries go through search_exact.
-static bool large_qpw4() {          // $VQ_AMD_RESCORE_QPW4=1: the four-queries-per-workgroup kernel for small batches with k > 20 too (A/B switch)
-    static const bool v = getenv("VQ_AMD_RESCORE_QPW4") && atoi(getenv("VQ_AMD_RESCORE_QPW4")) == 1;
-    return v;
-}
-
 // Device-side fallback geometry (knn_fallback.h).  First round: the first FB_FAST_SLOTS flagged queries over fine row splits (many
 // short workgroups: the usual handful of unproven queries is back in ~0.1 ms); bulk rounds: the rest over coarse splits, as many
 // flagged queries per round as 64 MiB of per-split lists hold.  One scratch buffer (d_fb_partial) serves both.
@@ -446,123 +458,126 @@ void launch_fallback(vq_index* x, const float* d_queries, int nq, int k, int32_t
     }
 }
 
+// ---- fp16 MFMA scan + exact re-score with proof (scan_plan.h decides, these launch); unproven queries go through the fallback ----
+// the streaming scan's instance for the handle's dim (256, 512 or 768) and the groups of 16 queries it holds per pass (two: the
+// plain form at dim <= 512).  FUSED: fp32 queries, rounded by the scan; MASK: the filtered search's
+template <bool FUSED, bool MASK>
+auto scan3_instance(int dim, int nqg) -> decltype(&scan3_f16_top2_kernel<8, 1, FUSED, MASK>) {
+    if constexpr (!FUSED && !MASK)
+        if (nqg == 2 && dim != 768) return dim == 512 ? scan3_f16_top2_kernel<16, 2> : scan3_f16_top2_kernel<8, 2>;
+    return dim == 768 ? scan3_f16_top2_kernel<24, 1, FUSED, MASK> : dim == 512 ? scan3_f16_top2_kernel<16, 1, FUSED, MASK>
+                                                                              : scan3_f16_top2_kernel<8, 1, FUSED, MASK>;
+}
+// streaming group-max scan (grouped and clip search): the instance for the handle's dim, masked by the allowed groups' bitmap or not
+template <bool MASK>
+auto scan3_group_max_instance(int dim) -> decltype(&scan3_group_max_kernel<8, MASK>) {
+    return dim == 768 ? scan3_group_max_kernel<24, MASK> : dim == 512 ? scan3_group_max_kernel<16, MASK> : scan3_group_max_kernel<8, MASK>;
+}
+auto scan3_group_max(int dim, bool masked) -> decltype(&scan3_group_max_kernel<8>) {
+    return masked ? scan3_group_max_instance<true>(dim) : scan3_group_max_instance<false>(dim);
+}
+
+// One chunk's scan: `cur` queries -> d_keys.  qp: the chunk's fp32 queries, which only the fused streaming scan reads; every other
+// scan reads d_q16 (queries_to_f16).
+int launch_scan(vq_index* x, const ScanPlan& p, const float* qp, int cur) {
+    const int64_t n = x->size, qpad = q_pad(p, cur);
+    const int qt = q_tiles(p, cur);
+    const ScanGrid g = scan_grid(p, cur);
+    auto fold = scan5_f16_top2_kernel<0>;
+    switch (p.scan) {
+        case SCAN_STREAM: {
+            Prof pr(x, I_MFMA_SCAN);
+            if (p.fused_q)
+                hipLaunchKernelGGL((scan3_instance<true, false>(x->dim, 1)), dim3(g.x, g.y), dim3(256), 0, x->stream, (const uint16_t*)qp, x->rows16, n,
+                                   p.streams, qpad, x->d_keys, cur, GroupMask{});
+            else
+                hipLaunchKernelGGL((scan3_instance<false, false>(x->dim, p.nqg)), dim3(g.x, g.y), dim3(256), 0, x->stream, x->d_q16, x->rows16, n,
+                                   p.streams, qpad, x->d_keys, 0, GroupMask{});
+            return 0;
+        }
+        case SCAN_TILE128: {
+            Prof pr(x, I_MFMA_SCAN);
+            hipLaunchKernelGGL(scan_f16_top2_kernel, dim3(g.x), dim3(GEMM_THREADS), 0, x->stream, x->d_q16, x->rows16, x->dim, n, qt, qpad, x->d_keys);
+            return 0;
+        }
+        case SCAN_FOLD: break;
+#ifdef VQ_DIAG
+        case SCAN_FOLD_NONE: fold = scan5_f16_top2_kernel<1>; break;
+        case SCAN_FOLD_AFTER: fold = scan5_f16_top2_kernel<2>; break;
+        case SCAN_FOLD_CLEAR: fold = scan5_f16_top2_kernel<0, false>; break;
+#endif
+        default:
+#ifdef VQ_SCAN_EXPERIMENTS
+            if (const void* fn = scan_experiment_kernel(p.scan)) {
+                VQ_TRY(set_dyn_lds(x, fn, p.scan_lds));
+                Prof pr(x, I_MFMA_SCAN);
+                launch_scan_experiment(p.scan, g.x, p.scan_lds, x->stream, x->d_q16, x->rows16, x->dim, n, qt, p.ranges, range_groups(p), qpad, x->d_keys);
+                return 0;
+            }
+#endif
+            return fail(VQ_ERR_STATE, "scan plan names kind %d, which this build does not carry", p.scan);
+    }
+    VQ_TRY(set_dyn_lds(x, (const void*)fold, p.scan_lds));
+    Prof pr(x, I_MFMA_SCAN);
+    hipLaunchKernelGGL(fold, dim3(g.x), dim3(G2_THREADS), p.scan_lds, x->stream, x->d_q16, x->rows16, x->dim, n, qt, p.ranges, range_groups(p), qpad,
+                       x->d_keys, x->dim, p.rb);
+    return 0;
+}
+
+// One chunk's re-score: d_keys -> the exact top-k of `cur` queries (ids, dist) and their outcome (flags).  counters: where a
+// re-score workgroup that files its own flag writes the outcome counters (plan.rescore_files_flags).
+int launch_rescore(vq_index* x, const ScanPlan& p, const float* qp, int cur, int k, int32_t* ids, float* dist, int32_t* flags, int32_t* counters) {
+    const int64_t n = x->size, qpad = q_pad(p, cur);
+    const float eps_rows = scan_eps_unit(x->dim) * x->row_norm_max;
+    const dim3 grid(rescore_grid(p, cur));
+    auto batch = rescore_verify_kernel;                 // several queries per workgroup, or one: told the key layout
+    auto one = rescore_verify_small_kernel;             // one query per workgroup, its candidate rows in LDS: the streaming scan's keys only
+    size_t one_lds_max = 0;                             // ... the limit is raised to what the largest dim takes: it is the kernel's, not this handle's
+    switch (p.rescore) {
+        case RESCORE_BATCH8: break;
+        case RESCORE_LARGE4: batch = rescore_verify_large_kernel; break;
+        case RESCORE_XLARGE4: batch = rescore_verify_xlarge_kernel; break;
+        case RESCORE_LARGE1: batch = rescore_verify_large1_kernel; break;
+        case RESCORE_XLARGE1: batch = rescore_verify_xlarge1_kernel; break;
+        case RESCORE_SMALL32: one_lds_max = (RV_C * (768 + 4) + 768) * 4; break;
+        case RESCORE_SMALL64: one = rescore_verify_small64_kernel; one_lds_max = (64 * (512 + 4) + 512) * 4; break;
+        default: return fail(VQ_ERR_STATE, "scan plan names re-score kind %d", p.rescore);
+    }
+    if (one_lds_max) VQ_TRY(set_dyn_lds(x, (const void*)one, one_lds_max));
+    Prof pr(x, I_RESCORE);
+    if (one_lds_max)
+        hipLaunchKernelGGL(one, grid, dim3(256), (size_t)p.rescore_lds, x->stream, x->d_keys, p.streams, qpad, x->rows, n, x->dim, qp, cur, k, ids, dist, flags,
+                           eps_rows, p.rescore_files_flags ? x->d_slots.p : nullptr, p.rescore_files_flags ? counters : nullptr, x->tie());
+    else
+        hipLaunchKernelGGL(batch, grid, dim3(256), 0, x->stream, x->d_keys, p.streams, qpad, x->rows, n, x->dim, qp, cur, k, ids, dist, flags, p.layout,
+                           eps_rows, x->tie());
+    return 0;
+}
+
 // host_sync: the caller (vq_index_search) waits for the stream anyway, so the outcome counters are written by the kernels into
 // host-visible memory and the fallback launches are left to it — it reads the flagged count after its one wait and launches
 // them only when there is something to redo (normally nothing: two launches and a copy command fewer per search).
 int search_fp16(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_ids, float* d_dist_out, bool host_sync = false) {
-    const int64_t n = x->size;
-    // small batches (the reference's one-query-at-a-time search, video_search_system.py:297) take the HBM-bound
-    // streaming scan; the 256-query MFMA tile is for batches
-    const bool small = nq <= SCAN3_MAX_Q && (x->dim == 512 || x->dim == 256 || x->dim == 768) && !x->no_small_scan;
-    const int ver = small ? 3 : x->scan_version;                       // 3: streaming, 2: 256x256 phased mainloop, 1: 128x128
-    const int nqg3 = nq > SCAN3_QB && x->dim <= 512 ? 2 : 1;           // query groups the streaming scan holds per pass (768-d: 96 + 96 VGPRs for one)
-    const int QT = ver == 3 ? SCAN3_QB * nqg3 : ver >= 2 ? SCAN2_QT : SCAN_QT;
-    const bool deep = ver == 4 || ver >= 5;                            // the 2048-row-range kernels that share scan2's key layout
-    const int RANGE = ver == 3 ? SCAN_STREAM_ROWS : ver >= 2 ? SCAN2_RANGE : SCAN_RANGE;
-    const int64_t n_pad = round_up(n, RANGE);
-    const int64_t streams = n_pad / SCAN_STREAM_ROWS;
-    const int64_t key_budget = (int64_t)1 << 27;                       // 128 Mi (stream,query) pairs = 1 GiB of keys
-    int64_t q_chunk = std::max<int64_t>(QT, key_budget / streams / QT * QT);
-    q_chunk = std::min<int64_t>(q_chunk, round_up(nq, QT));
-    VQ_TRY(x->d_q16.reserve(q_chunk * x->dim));
-    VQ_TRY(x->d_keys.reserve(streams * q_chunk * 2));
-    VQ_TRY(x->d_flags.reserve(round_up(nq, QT)));
+    const ScanPlan p = plan_scan(x->dim, x->size, nq, k, x->scan_switches, SCAN_DIAG_BUILD, SCAN_EXPERIMENTS_BUILD);
+    if (p.err) return fail(p.err, "%s", p.msg);
+    VQ_TRY(x->d_q16.reserve(p.q_chunk * x->dim));
+    VQ_TRY(x->d_keys.reserve(p.streams * p.q_chunk * 2));
+    VQ_TRY(x->d_flags.reserve(q_pad(p, nq)));
     VQ_TRY(reserve_fallback(x, nq, k));
     int32_t* const counters = host_sync ? x->h_counters.dev : x->d_counters.p;
-    const int ranges = (int)(n_pad / RANGE);
-    // k in (20, 40] from the streaming scan (the caller's k * 2 for a user k of 11 .. 20): the 64-candidate form of the single-query kernel
-    const bool small64 = ver == 3 && k > RV_K_SMALL && k <= RV_K_SMALL64 && x->dim <= 512 && !large_qpw4() && !(getenv("VQ_AMD_RESCORE_SMALL64") && atoi(getenv("VQ_AMD_RESCORE_SMALL64")) == 0);
-    if (ver == 3) {
-        VQ_TRY(set_dyn_lds(x, (const void*)rescore_verify_small_kernel, (RV_C * (768 + 4) + 768) * 4));
-        VQ_TRY(set_dyn_lds(x, (const void*)rescore_verify_small64_kernel, (64 * (512 + 4) + 512) * 4));
-    }
-    if (ver == 2 || deep) {
-        VQ_TRY(set_dyn_lds(x, (const void*)scan2_f16_top2_kernel, G2_LDS_BYTES));
-        VQ_TRY(set_dyn_lds(x, (const void*)scan4_f16_top2_kernel, SCAN4_LDS_BYTES));
-        VQ_TRY(set_dyn_lds(x, (const void*)scan5_f16_top2_kernel<0>, SCAN4_LDS_BYTES));
-#ifdef VQ_DIAG
-        VQ_TRY(set_dyn_lds(x, (const void*)scan5_f16_top2_kernel<1>, SCAN4_LDS_BYTES));
-        VQ_TRY(set_dyn_lds(x, (const void*)scan5_f16_top2_kernel<2>, SCAN4_LDS_BYTES));
-        VQ_TRY(set_dyn_lds(x, (const void*)scan5_f16_top2_kernel<0, false>, SCAN4_LDS_BYTES));
-#endif
-    }
-    for (int64_t q0 = 0; q0 < nq; q0 += q_chunk) {
-        const int cur = (int)std::min<int64_t>(q_chunk, nq - q0);
-        const int64_t q_pad = round_up(cur, QT);
-        const int q_tiles = (int)(q_pad / QT);
-        const bool fused_q = ver == 3 && nq <= SCAN3_FUSED_MAX_Q;      // the streaming scan rounds the (one to four) queries itself
-        if (!fused_q) queries_to_f16(x, d_queries + q0 * x->dim, cur, q_pad);
-        {
-            Prof p(x, I_MFMA_SCAN);
-            if (ver == 3) {
-                const dim3 grid(cdiv(streams, 4), q_tiles);
-                auto scan3 = x->dim == 768 ? scan3_f16_top2_kernel<24, 1>
-                           : x->dim == 512 ? (nqg3 == 2 ? scan3_f16_top2_kernel<16, 2> : scan3_f16_top2_kernel<16, 1>)
-                                           : (nqg3 == 2 ? scan3_f16_top2_kernel<8, 2> : scan3_f16_top2_kernel<8, 1>);
-                if (fused_q) {
-                    auto scan3f = x->dim == 768 ? scan3_f16_top2_kernel<24, 1, true> : x->dim == 512 ? scan3_f16_top2_kernel<16, 1, true>
-                                                                                                      : scan3_f16_top2_kernel<8, 1, true>;
-                    hipLaunchKernelGGL(scan3f, grid, dim3(256), 0, x->stream, (const uint16_t*)(d_queries + q0 * x->dim), x->rows16, n, streams,
-                                       q_pad, x->d_keys, cur, GroupMask{});
-                } else
-                hipLaunchKernelGGL(scan3, grid, dim3(256), 0, x->stream, x->d_q16, x->rows16, n, streams, q_pad, x->d_keys, 0, GroupMask{});
-            } else if (ver == 2 || deep) {
-                const int range_groups = cdiv(ranges, 4), q_groups = cdiv(q_tiles, 8);
-                if (ver >= 5) {
-                    auto k5 = scan5_f16_top2_kernel<0>;
-#ifdef VQ_DIAG
-                    if (ver == 51) k5 = scan5_f16_top2_kernel<1>;
-                    if (ver == 52) k5 = scan5_f16_top2_kernel<2>;
-                    if (ver == 53) k5 = scan5_f16_top2_kernel<0, false>;      // the fold clears its accumulators (no C = 0 MFMAs)
-#endif
-                    // workgroup -> (row range, query tile) blocking inside an XCD's 32 concurrent workgroups: $VQ_AMD_SCAN_RB = log2 of the
-                    // ranges per block (default 2: 4 ranges x 8 query tiles)
-                    static const int rb = [] { const char* e = getenv("VQ_AMD_SCAN_RB"); return e ? std::min(5, std::max(0, atoi(e))) : 2; }();   // (thread-safe: searches of different handles run concurrently)
-                    const int rg5 = cdiv(ranges, 1 << rb), qg5 = cdiv(q_tiles, 32 >> rb);
-                    hipLaunchKernelGGL(k5, dim3(rg5 * qg5 * 32), dim3(G2_THREADS), SCAN4_LDS_BYTES,
-                                       x->stream, x->d_q16, x->rows16, x->dim, n, q_tiles, ranges, rg5, q_pad, x->d_keys, x->dim, rb);
-                } else if (ver == 4)
-                    hipLaunchKernelGGL(scan4_f16_top2_kernel, dim3(range_groups * q_groups * 32), dim3(G2_THREADS), SCAN4_LDS_BYTES,
-                                       x->stream, x->d_q16, x->rows16, x->dim, n, q_tiles, ranges, range_groups, q_pad, x->d_keys);
-                else
-                    hipLaunchKernelGGL(scan2_f16_top2_kernel, dim3(range_groups * q_groups * 32), dim3(G2_THREADS), G2_LDS_BYTES,
-                                       x->stream, x->d_q16, x->rows16, x->dim, n, q_tiles, ranges, range_groups, q_pad, x->d_keys);
-            }
-            else
-                hipLaunchKernelGGL(scan_f16_top2_kernel, dim3(q_tiles * ranges), dim3(GEMM_THREADS), 0, x->stream, x->d_q16,
-                                   x->rows16, x->dim, n, q_tiles, q_pad, x->d_keys);
-        }
-        {
-            Prof p(x, I_RESCORE);
-            const bool large = k > RV_K_SMALL;                  // k in (20, 64]: the wide candidate pool, whatever scan produced the keys
-            if (small64)             // k in (20, 40] on the streaming scan's keys: the one-workgroup-per-query kernel with 64 candidates
-                hipLaunchKernelGGL(rescore_verify_small64_kernel, dim3(cur), dim3(256), (size_t)(64 * (x->dim + 4) + x->dim) * 4, x->stream, x->d_keys, streams, q_pad, x->rows, n,
-                                   x->dim, d_queries + q0 * x->dim, cur, k, d_ids + q0 * k, d_dist_out + q0 * k, x->d_flags + q0,
-                                   scan_eps_unit(x->dim) * x->row_norm_max, nq == 1 ? x->d_slots.p : nullptr, nq == 1 ? counters : nullptr, x->tie());
-            else if (large && ver == 3 && !large_qpw4())
-                hipLaunchKernelGGL(k > RV_K_MID ? rescore_verify_xlarge1_kernel : rescore_verify_large1_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_keys, streams,
-                                   q_pad, x->rows, n, x->dim, d_queries + q0 * x->dim, cur, k, d_ids + q0 * k,
-                                   d_dist_out + q0 * k, x->d_flags + q0, 3, scan_eps_unit(x->dim) * x->row_norm_max, x->tie());
-            else if (large)
-                hipLaunchKernelGGL(k > RV_K_MID ? rescore_verify_xlarge_kernel : rescore_verify_large_kernel, dim3(cdiv(cur, RVL_QPW)), dim3(256), 0, x->stream, x->d_keys, streams,
-                                   q_pad, x->rows, n, x->dim, d_queries + q0 * x->dim, cur, k, d_ids + q0 * k,
-                                   d_dist_out + q0 * k, x->d_flags + q0, ver == 3 ? 3 : deep ? 2 : ver, scan_eps_unit(x->dim) * x->row_norm_max, x->tie());
-            else if (ver == 3)
-                hipLaunchKernelGGL(rescore_verify_small_kernel, dim3(cur), dim3(256), (size_t)(RV_C * (x->dim + 4) + x->dim) * 4, x->stream, x->d_keys, streams, q_pad, x->rows, n,
-                                   x->dim, d_queries + q0 * x->dim, cur, k, d_ids + q0 * k, d_dist_out + q0 * k, x->d_flags + q0,
-                                   scan_eps_unit(x->dim) * x->row_norm_max, nq == 1 ? x->d_slots.p : nullptr, nq == 1 ? counters : nullptr, x->tie());
-            else
-            hipLaunchKernelGGL(rescore_verify_kernel, dim3(cdiv(cur, RV_QPW)), dim3(256), 0, x->stream, x->d_keys, streams,
-                               q_pad, x->rows, n, x->dim, d_queries + q0 * x->dim, cur, k, d_ids + q0 * k,
-                               d_dist_out + q0 * k, x->d_flags + q0, deep ? 2 : ver, scan_eps_unit(x->dim) * x->row_norm_max, x->tie());
-        }
+    for (int64_t q0 = 0; q0 < nq; q0 += p.q_chunk) {
+        const int cur = (int)std::min<int64_t>(p.q_chunk, nq - q0);
+        const float* qp = d_queries + q0 * x->dim;
+        if (!p.fused_q) queries_to_f16(x, qp, cur, q_pad(p, cur));
+        VQ_TRY(launch_scan(x, p, qp, cur));
+        VQ_TRY(launch_rescore(x, p, qp, cur, k, d_ids + q0 * k, d_dist_out + q0 * k, x->d_flags + q0, counters));
     }
     VQ_HIP(hipGetLastError());
     // Queries the proof could not close are redone by the exact scan, on the device: the flags are compacted into a
     // list and the fallback kernels size themselves from its length (all of them leave at once when it is empty), so
     // nothing here waits for the stream.  Rounds beyond the first exist only when more queries could be flagged than
     // one round's scratch holds.
-    if (!(ver == 3 && nq == 1 && (k <= RV_K_SMALL || small64)))   // a single query's (small-k) re-score workgroup has written the list and the counters itself
+    if (!p.rescore_files_flags)
         hipLaunchKernelGGL(collect_flags_kernel, dim3(1), dim3(1024), 0, x->stream, x->d_flags, nq, x->d_slots, counters);
     VQ_HIP(hipGetLastError());
     if (host_sync) { set_stats(x, STATS_DEFERRED); return 0; }
@@ -592,12 +607,6 @@ int search_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode
 int lanes_per_group(int64_t rows, int32_t groups) {
     const int64_t mean = rows / std::max<int32_t>(1, groups);
     return mean >= 256 ? 64 : mean >= 64 ? 16 : mean >= 8 ? 4 : 1;
-}
-
-// streaming group-max scan (fp16): the instance for the handle's dim (256, 512 or 768), masked by the allowed groups' bitmap or not
-auto group_max_scan(const vq_index* x, bool masked) -> decltype(&scan3_group_max_kernel<8>) {
-    if (masked) return x->dim == 768 ? scan3_group_max_kernel<24, true> : x->dim == 512 ? scan3_group_max_kernel<16, true> : scan3_group_max_kernel<8, true>;
-    return x->dim == 768 ? scan3_group_max_kernel<24> : x->dim == 512 ? scan3_group_max_kernel<16> : scan3_group_max_kernel<8>;
 }
 
 // The grouped exact paths' selection: per slice of queries, `dist(q0, cur, ld)` queues the distances to m columns into d_dist
@@ -656,7 +665,7 @@ int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int3
     float* thr = (float*)(flags + qc);
     VQ_HIP(hipMemsetAsync(x->d_gcounters, 0, 3 * sizeof(unsigned long long), x->stream));
     const float eps_rows = scan_eps_unit(x->dim) * x->row_norm_max;
-    auto scan = group_max_scan(x, allow != nullptr);
+    auto scan = scan3_group_max(x->dim, allow != nullptr);
     auto redo = allow ? group_block_topk_kernel<false, true> : group_block_topk_kernel<false>;
     // k among the allowed groups: the threshold is the k'-th largest gbest with k' = min(k, allowed) (a disallowed group's 0 is
     // below it), the finalize test asks for min(k, allowed) re-scored groups
@@ -892,9 +901,7 @@ int search_filtered_fp16(vq_index* x, const float* d_queries, int nq, int k, con
     queries_to_f16(x, d_queries, nq, q_pad);
     {
         Prof pr(x, I_MFMA_SCAN);
-        auto scan = x->dim == 768 ? scan3_f16_top2_kernel<24, 1, false, true> : x->dim == 512 ? scan3_f16_top2_kernel<16, 1, false, true>
-                                                                                              : scan3_f16_top2_kernel<8, 1, false, true>;
-        hipLaunchKernelGGL(scan, dim3(cdiv(streams, 4), (int)(q_pad / SCAN3_QB)), dim3(256), 0, x->stream, x->d_q16, x->rows16, n, streams, q_pad,
+        hipLaunchKernelGGL((scan3_instance<false, true>(x->dim, 1)), dim3(cdiv(streams, 4), (int)(q_pad / SCAN3_QB)), dim3(256), 0, x->stream, x->d_q16, x->rows16, n, streams, q_pad,
                            x->d_keys, 0, gm);
     }
     {
@@ -1060,7 +1067,7 @@ int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, i
             {
                 Prof pr(x, I_MFMA_SCAN);
                 if (small) {
-                    auto scan = group_max_scan(x, allow != nullptr);
+                    auto scan = scan3_group_max(x->dim, allow != nullptr);
                     hipLaunchKernelGGL(scan, dim3(cdiv(streams, 4), 1), dim3(256), 0, x->stream, x->d_q16, x->rows16, streams, x->d_group, x->d_sgroup,
                                        cur, G, x->d_gbest, allow);
                 } else {
@@ -1161,13 +1168,30 @@ int vq_index_create(int dim, vq_index** out) {
     VQ_CHECK(out && dim > 0 && dim % 4 == 0 && dim <= 4096, "vq_index_create: dim %d must be a positive multiple of 4", dim);
     vq_index* x = new vq_index();
     x->dim = dim;
-    if (const char* sv = getenv("VQ_AMD_SCAN")) { const int v = atoi(sv); x->scan_version = (v == 1 || v == 2 || v == 4 || v == 51 || v == 52 || v == 53) ? v : 5; }
-    if (dim % 128 != 0) x->scan_version = 1;
-    if (const char* ss = getenv("VQ_AMD_SCAN_SMALL")) x->no_small_scan = atoi(ss) == 0;
+    x->scan_switches = scan_switches_from_env();
+    // a scan kind this build does not carry is refused here, not at the first search (an A/B run against the wrong library)
+    const ScanPlan probe = plan_scan(dim, 1, 1, 1, x->scan_switches, SCAN_DIAG_BUILD, SCAN_EXPERIMENTS_BUILD);
+    if (probe.err) { delete x; return fail(probe.err, "vq_index_create: %s", probe.msg); }
     hipError_t e = hipStreamCreateWithFlags(&x->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete x; return fail(VQ_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e)); }
     x->stream = x->own_stream;
     *out = x;
+    return 0;
+}
+
+// plan_scan's answer for this build and this process's environment; needs no device
+int vq_debug_scan_plan(int dim, int64_t n, int nq, int k, int force_scan, vq_scan_plan* out) {
+    VQ_CHECK(out && dim > 0 && dim % GEMM_BK == 0 && n >= 1 && n < ((int64_t)1 << 31) && nq >= 1 && k >= 1 && k <= RV_K_MAX,
+             "vq_debug_scan_plan: the fp16 search takes dim %% %d == 0, 1 <= n < 2^31, nq >= 1, 1 <= k <= %d", GEMM_BK, RV_K_MAX);
+    ScanSwitches sw = scan_switches_from_env();
+    if (force_scan) sw.scan = (force_scan == 1 || force_scan == 2 || force_scan == 4 || (force_scan >= 51 && force_scan <= 53)) ? force_scan : SCAN_FOLD;
+    const ScanPlan p = plan_scan(dim, n, nq, k, sw, SCAN_DIAG_BUILD, SCAN_EXPERIMENTS_BUILD);
+    if (p.err) return fail(p.err, "%s", p.msg);
+    const int cur = (int)std::min<int64_t>(p.q_chunk, nq);
+    const ScanGrid g = scan_grid(p, cur);
+    *out = vq_scan_plan{p.scan, p.QT, p.RANGE, p.n_pad, p.streams, p.ranges, p.q_chunk, n_chunks(p, nq), p.nqg, p.fused_q, p.rb, p.scan_lds,
+                        p.rescore, p.rescore_qpw, p.rescore_lds, p.layout, p.rescore_files_flags, q_pad(p, cur), q_tiles(p, cur), g.x, g.y,
+                        rescore_grid(p, cur)};
     return 0;
 }
 
