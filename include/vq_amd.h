@@ -484,6 +484,22 @@ int vq_clip_processor_geometry(int h, int w, int size, int crop, int* resized_h,
  * restates its published fixed-point grey conversion and 4-neighbour stencil; parity unpinned.) */
 int vq_frame_quality_u8(vq_resampler* r, const uint8_t* frames, int n, int h, int w, int on_device,
                         double* mean_brightness, double* laplacian_var);
+/* AdaptiveFrameSampler._calculate_frame_difference (frame_extractor.py:168-186) for every consecutive pair of
+ * BGR uint8 frames [n][h][w][3]: score[i] compares frames[i-1] (earlier) with frames[i]; score[0] compares
+ * prev_frame (ONE h x w x 3 frame of the same residency as `frames`) with frames[0], or is 0.0 when prev_frame
+ * is NULL (the reference's first frame carries scene_change_score 0.0).  mse / hist_diff (optional, may be
+ * NULL) receive the two terms.  on_device != 0: frames and prev_frame are device pointers of any alignment.
+ * Results are host doubles; returns when they are complete.
+ *   mse       = np.mean((grey_a.astype(float) - grey_b.astype(float)) ** 2): an exact integer sum, one division;
+ *   hist_diff = cv2.compareHist(hist_a, hist_b, HISTCMP_CHISQR): sum over ascending bins with hist_a != 0 of
+ *               (hist_a - hist_b)^2 / hist_a in fp64, the earlier frame supplying the denominators;
+ *   score     = mse + hist_diff * 0.01.
+ * h * w <= 2^24 (histogram counts stay exact in OpenCV's float32 bins), n <= 65535; n == 0 is a no-op.  Host
+ * frames go up in slices of at most 512 MiB ($VQ_AMD_SCENE_SLICE_BYTES, read per call, overrides the budget).
+ * Grey is the fixed-point BGR2GRAY restated for vq_frame_quality_u8 (parity with OpenCV unpinned, as there);
+ * OpenCV does not fix the order of compareHist's sum, so its hist_diff may differ from this one in the last bits. */
+int vq_frame_scene_scores_u8(vq_resampler* r, const uint8_t* frames, int n, int h, int w, int on_device,
+                             const uint8_t* prev_frame, double* score, double* mse, double* hist_diff);
 
 #ifdef __cplusplus
 }

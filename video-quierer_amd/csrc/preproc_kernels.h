@@ -347,9 +347,10 @@ void cv_resize_half_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict_
 // per frame: sum of all bytes (np.mean(frame)), and over the grey image g = BGR2GRAY(frame) the sums of
 // L and L^2 where L = cv2.Laplacian(g, CV_64F) (aperture 1: the 4-neighbour stencil, BORDER_REFLECT_101).
 // Grey conversion: OpenCV 4.x fixed point, (B*3735 + G*19235 + R*9798 + 2^14) >> 15.
-__device__ __forceinline__ int gray_bgr(const uint8_t* p) {
-    return (p[0] * 3735 + p[1] * 19235 + p[2] * 9798 + (1 << 14)) >> 15;
+__device__ __forceinline__ int gray_bgr(int b, int g, int r) {
+    return (b * 3735 + g * 19235 + r * 9798 + (1 << 14)) >> 15;
 }
+__device__ __forceinline__ int gray_bgr(const uint8_t* p) { return gray_bgr(p[0], p[1], p[2]); }
 __device__ __forceinline__ int reflect101(int i, int n) {
     if (n == 1) return 0;
     if (i < 0) return -i;
@@ -383,6 +384,201 @@ void frame_quality_kernel(const uint8_t* __restrict__ frames, long long* __restr
         atomicAdd((unsigned long long*)&acc[img * 3 + 0], (unsigned long long)sb);
         atomicAdd((unsigned long long*)&acc[img * 3 + 1], (unsigned long long)sl);
         atomicAdd((unsigned long long*)&acc[img * 3 + 2], (unsigned long long)sl2);
+    }
+}
+
+// ---- scene-change score (reference frame_extractor.py:168-186) -------------------------------------------
+// AdaptiveFrameSampler._calculate_frame_difference for every consecutive pair (earlier a, later b) of a batch:
+//   mse = mean((grey_a - grey_b)^2), chi = cv2.compareHist(hist_a, hist_b, HISTCMP_CHISQR), score = mse + chi * 0.01.
+// Two kernels.  scene_partials_kernel streams the frames once and leaves exact integer partials per (frame, pixel
+// tile); scene_finalise_kernel sums them and does the few hundred fp64 operations of a pair in a fixed order.
+//
+// scene_partials_kernel: grid (pixel tiles, frame chunks).  A workgroup owns SC_TILE pixels (SC_PPT per thread) and
+// walks SC_CHUNK_FRAMES consecutive frames in order, keeping the previous frame's grey values of its own pixels packed
+// four to a register, so the squared difference of a pair needs no second read.  The frame before a chunk's first one
+// (the caller's `prev` for chunk 0) is read for its grey values only: a 1/SC_CHUNK_FRAMES share of re-read, and its
+// histogram belongs to the chunk before (to chunk 0 for `prev`, which nobody else reads).
+// Histogram: one private 256-bin copy per wave in LDS, non-returning ds_add_u32; combined per frame after a barrier and
+// stored plainly to hist[slot][tile][256] (slot 0 = prev, slot k + 1 = frame k) — no global atomics: a 1080p frame
+// would send its ~250 workgroups to the same 257 words.  1 KiB of partials per 24 KiB of tile read.
+// Counts are uint32 (a constant tile puts SC_TILE pixels into one bin); a tile's squared-difference sum is at most
+// SC_TILE * 255^2 < 2^32.
+constexpr int SC_PPT = 32;                                   // pixels per thread: two groups of 16 (48 bytes = three 16-byte loads)
+constexpr int SC_TILE = RS_THREADS * SC_PPT;                 // 8192 pixels per workgroup
+constexpr int SC_CHUNK_FRAMES = 8;                           // frames a workgroup walks (plus the one before them, grey only)
+static_assert((long long)SC_TILE * 255 * 255 < (1ll << 32), "a tile's squared-difference sum must fit uint32");
+
+// grey values of this thread's SC_PPT pixels of one frame, packed four to a dword.
+//   WIDE (frame base and h*w*3 multiples of 16): pixels [first + 16*(tid + 256*j), +16), j = 0, 1; a group of 16 is
+//   all inside the frame or all outside it, since h*w is then a multiple of 16.
+//   bytes: pixels first + tid + 256*k, k = 0..31 (consecutive lanes on consecutive pixels), each bounds-checked.
+// Pixels outside the frame pack as 0 and are skipped by `valid` (bit per pixel, the same for every frame).
+template <bool WIDE>
+__device__ __forceinline__ void sc_load_grey(const uint8_t* __restrict__ f, int first, int npix, uint32_t (&g)[SC_PPT / 4]) {
+    if constexpr (WIDE) {
+#pragma unroll
+        for (int j = 0; j < SC_PPT / 16; ++j) {
+            const int p0 = first + 16 * ((int)threadIdx.x + RS_THREADS * j);
+            uint32_t d[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) d[i] = 0;
+            if (p0 < npix) {
+                const uint4* q = (const uint4*)(f + (size_t)p0 * 3);
+                const uint4 a = q[0], b = q[1], c = q[2];
+                d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
+                d[8] = c.x; d[9] = c.y; d[10] = c.z; d[11] = c.w;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int k = 3 * i;
+                const int bb = (d[k >> 2] >> (8 * (k & 3))) & 255, gg = (d[(k + 1) >> 2] >> (8 * ((k + 1) & 3))) & 255,
+                          rr = (d[(k + 2) >> 2] >> (8 * ((k + 2) & 3))) & 255;
+                const uint32_t v = (uint32_t)gray_bgr(bb, gg, rr);
+                if ((i & 3) == 0) g[4 * j + (i >> 2)] = v; else g[4 * j + (i >> 2)] |= v << (8 * (i & 3));
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < SC_PPT; ++k) {
+            const int p = first + (int)threadIdx.x + RS_THREADS * k;
+            const uint32_t v = p < npix ? (uint32_t)gray_bgr(f + (size_t)p * 3) : 0u;
+            if ((k & 3) == 0) g[k >> 2] = v; else g[k >> 2] |= v << (8 * (k & 3));
+        }
+    }
+}
+
+template <bool WIDE>
+__device__ __forceinline__ uint32_t sc_valid_mask(int first, int npix) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < SC_PPT; ++k) {
+        const int p = WIDE ? first + 16 * ((int)threadIdx.x + RS_THREADS * (k >> 4)) + (k & 15) : first + (int)threadIdx.x + RS_THREADS * k;
+        m |= (uint32_t)(p < npix) << k;
+    }
+    return m;
+}
+
+//   frames [m][npix][3]; prev: one frame or null
+//   hist   [m + 1][tiles][256] uint32: slot 0 is written only when prev is given
+//   ssd    [m][tiles] uint32: pair i = (frame i - 1 or prev, frame i); pair 0 is written only when prev is given
+template <bool WIDE>
+__global__ __launch_bounds__(RS_THREADS)
+void scene_partials_kernel(const uint8_t* __restrict__ frames, const uint8_t* __restrict__ prev,
+                           uint32_t* __restrict__ hist, uint32_t* __restrict__ ssd, int m, int npix) {
+    __shared__ uint32_t lh[4][256];                                  // one histogram copy per wave
+    __shared__ uint32_t ls[4];
+    const int tile = blockIdx.x, tiles = gridDim.x;
+    const int first = tile * SC_TILE;
+    const int k0 = blockIdx.y * SC_CHUNK_FRAMES, k1 = min(m, k0 + SC_CHUNK_FRAMES);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const size_t frame_bytes = (size_t)npix * 3;
+    const uint32_t valid = sc_valid_mask<WIDE>(first, npix);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) lh[c][threadIdx.x] = 0;
+    __syncthreads();
+
+    uint32_t pg[SC_PPT / 4];
+    bool have_pg = false;
+    // k = k0 - 1 is the frame before the chunk: grey only, except prev (k = -1), whose histogram is this chunk's too
+    for (int k = (k0 > 0 || prev) ? k0 - 1 : k0; k < k1; ++k) {
+        const uint8_t* f = k < 0 ? prev : frames + (size_t)k * frame_bytes;
+        const bool want_hist = k >= k0 || k < 0;
+        uint32_t g[SC_PPT / 4];
+        sc_load_grey<WIDE>(f, first, npix, g);
+        uint32_t s = 0;
+#pragma unroll
+        for (int j = 0; j < SC_PPT / 16; ++j) {
+            if (WIDE && !((valid >> (16 * j)) & 1)) continue;        // a wide group is inside the frame or outside it as a whole
+            bool add_each = want_hist;
+            if constexpr (WIDE) {
+                // Flat picture areas (a constant frame, letterbox bars): when all 16 pixels of every active lane hold one grey
+                // value, the wave's 1,024 consecutive pixels go to the bin in ONE add.  Lane by lane they would be 64 adds to
+                // the same LDS word per instruction, which serialise (measured: constant 1080p frames 3.6x slower than noise).
+                if (want_hist) {
+                    const uint32_t c = __builtin_amdgcn_readfirstlane(g[4 * j]);
+                    const uint32_t odd = (g[4 * j] ^ c) | (g[4 * j + 1] ^ c) | (g[4 * j + 2] ^ c) | (g[4 * j + 3] ^ c);
+                    if (c == (c & 255u) * 0x01010101u && __builtin_amdgcn_ballot_w64(odd != 0) == 0) {
+                        const unsigned long long active = __builtin_amdgcn_ballot_w64(true);
+                        if (lane == __builtin_ctzll(active))
+                            __hip_atomic_fetch_add(&lh[wave][c & 255u], 16u * (uint32_t)__builtin_popcountll(active), __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+                        add_each = false;
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 16 * j; i < 16 * j + 16; ++i) {
+                if (!WIDE && !((valid >> i) & 1)) continue;
+                const int v = (g[i >> 2] >> (8 * (i & 3))) & 255;
+                if (add_each) __hip_atomic_fetch_add(&lh[wave][v], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (have_pg) {
+                    const int dlt = v - (int)((pg[i >> 2] >> (8 * (i & 3))) & 255);
+                    s += (uint32_t)(dlt * dlt);
+                }
+            }
+        }
+        if (have_pg) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+            if (lane == 0) ls[wave] = s;
+        }
+        __syncthreads();                                             // every wave's adds of this frame are in LDS
+        if (want_hist) {
+            const uint32_t c = lh[0][threadIdx.x] + lh[1][threadIdx.x] + lh[2][threadIdx.x] + lh[3][threadIdx.x];
+            hist[((size_t)(k + 1) * tiles + tile) * 256 + threadIdx.x] = c;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) lh[w][threadIdx.x] = 0;
+        }
+        if (have_pg && threadIdx.x == 0) ssd[(size_t)k * tiles + tile] = ls[0] + ls[1] + ls[2] + ls[3];
+        __syncthreads();                                             // copies are zero and ls is free before the next frame
+#pragma unroll
+        for (int i = 0; i < SC_PPT / 4; ++i) pg[i] = g[i];
+        have_pg = true;
+    }
+}
+
+// One 256-thread workgroup per pair.  Thread b sums bin b of the earlier (slot pair) and the later (slot pair + 1)
+// frame over the tiles, as integers, and forms its chi-square term; the squared-difference partials are summed as
+// integers; thread 0 adds the 256 terms in ascending bin order (a bin with H_a == 0 contributes +0.0, which leaves
+// the running non-negative sum unchanged, so this is OpenCV's "skip when the denominator is zero").
+// Every fp64 step is one correctly rounded operation: no contraction into FMAs here.
+//   res [m][3] = {mse, chi, score}; pair 0 without a predecessor is {0, 0, 0}
+__global__ __launch_bounds__(256)
+void scene_finalise_kernel(const uint32_t* __restrict__ hist, const uint32_t* __restrict__ ssd, double* __restrict__ res,
+                           int tiles, int npix, int has_prev) {
+#pragma clang fp contract(off)
+    __shared__ double term[256];
+    __shared__ unsigned long long part[256];
+    const int pair = blockIdx.x, b = threadIdx.x;
+    if (pair == 0 && !has_prev) {
+        if (b < 3) res[b] = 0.0;
+        return;
+    }
+    const uint32_t* ha = hist + (size_t)pair * tiles * 256 + b;
+    const uint32_t* hb = ha + (size_t)tiles * 256;
+    long long ca = 0, cb = 0;
+    unsigned long long s = 0;
+    for (int t = 0; t < tiles; ++t) { ca += ha[(size_t)t * 256]; cb += hb[(size_t)t * 256]; }
+    for (int t = b; t < tiles; t += 256) s += ssd[(size_t)pair * tiles + t];
+    double tm = 0.0;
+    if (ca != 0) {
+        const double d = (double)(ca - cb);
+        const double dd = d * d;
+        tm = dd / (double)ca;
+    }
+    term[b] = tm;
+    part[b] = s;
+    __syncthreads();
+    if (b == 0) {
+        double chi = 0.0;
+        unsigned long long S = 0;
+        for (int i = 0; i < 256; ++i) { chi += term[i]; S += part[i]; }
+        const double mse = (double)S / (double)npix;
+        const double scaled = chi * 0.01;
+        res[(size_t)pair * 3 + 0] = mse;
+        res[(size_t)pair * 3 + 1] = chi;
+        res[(size_t)pair * 3 + 2] = mse + scaled;
     }
 }
 

@@ -285,6 +285,42 @@ int run_device(vq_resampler* r, const uint8_t* d_src, int n, int h, int w, int f
     return 0;
 }
 
+// Scene-change partials + finalise for m device-resident frames; d_res gets [m][3] = {mse, chi, score} per pair
+// (pair i = (frame i - 1, frame i); pair 0 = (d_prev, frame 0), or zeros when d_prev is null).  Frames go through in
+// batches whose histogram partials fit SCENE_SCRATCH_BYTES: a batch's predecessor is the frame before it, so a batch
+// boundary is one more use of `prev`.  Everything is queued on the handle's stream; r->tmp holds the partials.
+// $VQ_AMD_SCENE_SCRATCH_BYTES (read per call) overrides the budget, so a test can force batches of SC_CHUNK_FRAMES.
+constexpr size_t SCENE_SCRATCH_BYTES = (size_t)256 << 20;
+
+int scene_run_device(vq_resampler* r, const uint8_t* d_frames, int m, int h, int w, const uint8_t* d_prev, double* d_res) {
+    const int npix = h * w, tiles = cdiv(npix, SC_TILE);
+    const size_t frame_bytes = (size_t)npix * 3;
+    const size_t slot_bytes = (size_t)tiles * 256 * sizeof(uint32_t);
+    size_t budget = SCENE_SCRATCH_BYTES;
+    if (const char* e = getenv("VQ_AMD_SCENE_SCRATCH_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+    const int batch = (int)std::min<size_t>((size_t)m, std::max<size_t>(SC_CHUNK_FRAMES, budget / slot_bytes / SC_CHUNK_FRAMES * SC_CHUNK_FRAMES));
+    const size_t hist_bytes = (size_t)(batch + 1) * slot_bytes, ssd_bytes = (size_t)batch * tiles * sizeof(uint32_t);
+    if (hist_bytes + ssd_bytes > r->tmp.cap) VQ_HIP(hipStreamSynchronize(r->stream));     // queued passes still use the old workspace
+    VQ_TRY(r->tmp.reserve(hist_bytes + ssd_bytes));
+    uint32_t* d_hist = (uint32_t*)r->tmp.p;
+    uint32_t* d_ssd = (uint32_t*)((uint8_t*)r->tmp.p + hist_bytes);
+    // 16-byte loads need every frame to start on a 16-byte boundary; anything else takes the byte-load kernel
+    const bool wide = frame_bytes % 16 == 0 && ((uintptr_t)d_frames & 15) == 0 && ((uintptr_t)d_prev & 15) == 0;
+    for (int i = 0; i < m; i += batch) {
+        const int mm = std::min(batch, m - i);
+        const uint8_t* f = d_frames + (size_t)i * frame_bytes;
+        const uint8_t* pv = i == 0 ? d_prev : f - frame_bytes;
+        const dim3 grid(tiles, cdiv(mm, SC_CHUNK_FRAMES));
+        if (wide) hipLaunchKernelGGL(scene_partials_kernel<true>, grid, dim3(RS_THREADS), 0, r->stream, f, pv, d_hist, d_ssd, mm, npix);
+        else hipLaunchKernelGGL(scene_partials_kernel<false>, grid, dim3(RS_THREADS), 0, r->stream, f, pv, d_hist, d_ssd, mm, npix);
+        VQ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(scene_finalise_kernel, dim3(mm), dim3(256), 0, r->stream, (const uint32_t*)d_hist, (const uint32_t*)d_ssd,
+                           d_res + (size_t)i * 3, tiles, npix, pv ? 1 : 0);
+        VQ_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -446,6 +482,52 @@ int vq_frame_quality_u8(vq_resampler* r, const uint8_t* frames, int n, int h, in
         // var = E[L^2] - E[L]^2 from exact integer sums: (N*S2 - S1^2) / N^2
         const __int128 num = (__int128)((int64_t)h * w) * acc[3 * i + 2] - (__int128)acc[3 * i + 1] * acc[3 * i + 1];
         laplacian_var[i] = (double)((long double)num / ((long double)npix * (long double)npix));
+    }
+    return 0;
+}
+
+int vq_frame_scene_scores_u8(vq_resampler* r, const uint8_t* frames, int n, int h, int w, int on_device,
+                             const uint8_t* prev_frame, double* score, double* mse, double* hist_diff) {
+    VQ_TRY(require_init());
+    VQ_CHECK(r && n >= 0 && h > 0 && w > 0 && (n == 0 || (frames && score)), "vq_frame_scene_scores_u8: bad argument");
+    VQ_CHECK((int64_t)h * w <= (int64_t)1 << 24, "vq_frame_scene_scores_u8: frame of %dx%d pixels is too large (at most 2^24 pixels: "
+             "histogram counts must stay exact in float32)", h, w);
+    VQ_CHECK(n <= 65535, "vq_frame_scene_scores_u8: at most 65535 frames per call");
+    if (n == 0) return 0;
+    std::lock_guard<std::mutex> lk(r->mu);
+    const size_t frame_bytes = (size_t)h * w * 3;
+    VQ_HIP(hipStreamSynchronize(r->stream));
+    VQ_TRY(r->acc.reserve((size_t)n * 3 * sizeof(double)));
+    double* d_res = (double*)r->acc.p;
+    if (on_device) {
+        VQ_TRY(scene_run_device(r, frames, n, h, w, prev_frame, d_res));
+    } else {
+        // host frames go up in slices; slot 0 of the staging buffer holds the frame before the slice (the caller's
+        // prev_frame, then each slice's last frame), which the device form takes as its prev
+        size_t budget = (size_t)512 << 20;
+        if (const char* e = getenv("VQ_AMD_SCENE_SLICE_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+        const int slice = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / frame_bytes));
+        VQ_TRY(r->src.reserve((size_t)(slice + 1) * frame_bytes));
+        uint8_t* stage = (uint8_t*)r->src.p;
+        bool have_prev = prev_frame != nullptr;
+        if (have_prev) VQ_HIP(hipMemcpyAsync(stage, prev_frame, frame_bytes, hipMemcpyHostToDevice, r->stream));
+        for (int i = 0; i < n; i += slice) {
+            const int m = std::min(slice, n - i);
+            VQ_HIP(hipMemcpyAsync(stage + frame_bytes, frames + (size_t)i * frame_bytes, (size_t)m * frame_bytes, hipMemcpyHostToDevice, r->stream));
+            VQ_TRY(scene_run_device(r, stage + frame_bytes, m, h, w, have_prev ? stage : nullptr, d_res + (size_t)i * 3));
+            if (i + m < n) {
+                VQ_HIP(hipMemcpyAsync(stage, stage + (size_t)m * frame_bytes, frame_bytes, hipMemcpyDeviceToDevice, r->stream));
+                have_prev = true;
+            }
+        }
+    }
+    std::vector<double> res((size_t)n * 3);
+    VQ_HIP(hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(double), hipMemcpyDeviceToHost, r->stream));
+    VQ_HIP(hipStreamSynchronize(r->stream));
+    for (int i = 0; i < n; ++i) {
+        if (mse) mse[i] = res[3 * (size_t)i];
+        if (hist_diff) hist_diff[i] = res[3 * (size_t)i + 1];
+        score[i] = res[3 * (size_t)i + 2];
     }
     return 0;
 }

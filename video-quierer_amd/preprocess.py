@@ -8,7 +8,10 @@ frame-quality statistics of the reference's frame extractor, over ``vq_resampler
   * :meth:`FramePreprocessor.cv_resize` — ``cv2.resize(frame, frame_size)`` of reference
     src/core/frame_extractor.py:283-284 (OpenCV INTER_LINEAR; parity unpinned);
   * :meth:`FramePreprocessor.quality` / :meth:`is_low_quality` — reference
-    src/core/frame_extractor.py:301-316.
+    src/core/frame_extractor.py:301-316;
+  * :meth:`FramePreprocessor.scene_change_scores` — ``AdaptiveFrameSampler._calculate_frame_difference`` of
+    reference src/core/frame_extractor.py:168-186 for every consecutive pair of a batch (the samplers on top of
+    it: :mod:`video_quierer_amd.core.frame_extractor`).
 """
 import ctypes
 from ctypes import c_double, c_int, c_int64, c_void_p
@@ -20,6 +23,9 @@ from . import _lib
 
 BILINEAR, BICUBIC = 2, 3            # PIL.Image.Resampling values (VQ_RESAMPLE_*)
 CV_LINEAR = 100                     # cv2.resize's default INTER_LINEAR (VQ_RESAMPLE_CV_LINEAR)
+# geometry of the scene-change pass (csrc/preproc_kernels.h SC_CHUNK_FRAMES / SC_TILE; tests read both and compare)
+SCENE_CHUNK_FRAMES = 8              # frames one workgroup walks
+SCENE_TILE_PIXELS = 8192            # pixels one workgroup owns
 
 
 def clip_processor_geometry(h: int, w: int, size: int = 224, crop: int = 224) -> Tuple[int, int, int, int]:
@@ -147,3 +153,29 @@ class FramePreprocessor:
         blurry (Laplacian variance < 100)."""
         mean, var = self.quality(frames)
         return (mean < 20) | (mean > 235) | (var < 100)
+
+    # -- scene-change score ---------------------------------------------------
+    def scene_change_scores(self, frames, prev=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """→ (score[n], mse[n], hist_diff[n]) float64 of BGR uint8 frames: entry i compares frame i - 1 with frame i
+        (reference frame_extractor.py:168-186); entry 0 compares ``prev`` (one frame of the same size) with frame 0,
+        or is 0.0 without one, like the reference's first frame."""
+        a = _frames(frames)
+        n, h, w = a.shape[:3]
+        p = None
+        if prev is not None:
+            p = _frames(prev)
+            if p.shape != (1, h, w, 3):
+                raise ValueError(f"prev must be one frame of shape ({h}, {w}, 3), got {p.shape[1:] if p.shape[0] == 1 else p.shape}")
+        return self._scene(a.ctypes.data_as(c_void_p), n, h, w, 0, p.ctypes.data_as(c_void_p) if p is not None else None)
+
+    def scene_change_scores_device(self, ptr: int, n: int, h: int, w: int, prev_ptr: Optional[int] = None):
+        """:meth:`scene_change_scores` over device-resident frames [n, h, w, 3] at ``ptr`` (any alignment) and an
+        optional device-resident predecessor frame at ``prev_ptr``.  Results are host arrays."""
+        return self._scene(c_void_p(ptr), int(n), int(h), int(w), 1, c_void_p(prev_ptr) if prev_ptr else None)
+
+    def _scene(self, frames_p, n, h, w, on_device, prev_p):
+        score, mse, hist = (np.empty(n, np.float64) for _ in range(3))
+        dp = ctypes.POINTER(c_double)
+        _lib.check(_lib.load().vq_frame_scene_scores_u8(self._h, frames_p, n, h, w, on_device, prev_p, score.ctypes.data_as(dp),
+                                                        mse.ctypes.data_as(dp), hist.ctypes.data_as(dp)))
+        return score, mse, hist
