@@ -501,6 +501,37 @@ int vq_frame_quality_u8(vq_resampler* r, const uint8_t* frames, int n, int h, in
 int vq_frame_scene_scores_u8(vq_resampler* r, const uint8_t* frames, int n, int h, int w, int on_device,
                              const uint8_t* prev_frame, double* score, double* mse, double* hist_diff);
 
+/* OptimizedFrameExtractor.extract_frames' per-frame work (frame_extractor.py:279-293) for a batch of BGR uint8 frames
+ * [n][h][w][3] in one device pass: cv2.resize to out_w x out_h (VQ_RESAMPLE_CV_LINEAR, bit-identical to
+ * vq_resampler_run_u8 with that filter), the three integer sums behind _is_low_quality taken from on-chip memory
+ * while the resized frame is written, the keep / drop verdict on the device, and the survivors compacted in input order.
+ *   out_h == out_w == 0: no resize (frame_size=None): the statistics are those of the frames as given.
+ *   quality_filter == 0: every frame is kept; the sums are computed only when `sums` is given.
+ *   keep [n]: 1 = kept.  sums [n][3] (may be NULL) = {sum of all bytes, sum L, sum L^2}, L the 4-neighbour Laplacian
+ *     (BORDER_REFLECT_101) of the fixed-point BGR2GRAY image, as for vq_frame_quality_u8.
+ *   A frame is dropped when, with N = out_h * out_w:  sum_bytes < 20 * 3 * N,  or  sum_bytes > 235 * 3 * N,  or
+ *     N * sumL2 - sumL^2 < 100 * N^2  — mean brightness < 20 or > 235, Laplacian variance < 100, decided in exact
+ *     integers.  out_h * out_w <= 2^21 keeps every term inside int64; larger outputs are VQ_ERR_INVALID.
+ *   out: host memory for n frames, of which the first *n_kept are written.  out == NULL: the result stays on the
+ *     device; vq_resampler_device_output returns its address, it is *n_kept frames long and valid until the next
+ *     call on the handle.
+ * on_device != 0: `frames` is a device pointer of any alignment.  n <= 65535; n == 0 is a no-op with *n_kept = 0.
+ * All forms return when the result is complete.  Host frames go up in slices of at most 512 MiB
+ * ($VQ_AMD_POSTPROC_SLICE_BYTES, read per call, overrides the budget); survivors of later slices follow those of
+ * earlier ones.  (OpenCV parity unpinned, as for the resize and the quality statistics.) */
+int vq_frame_postprocess_u8(vq_resampler* r, const uint8_t* frames, int n, int h, int w, int on_device,
+                            int out_h, int out_w, int quality_filter,
+                            uint8_t* out, int64_t* n_kept, uint8_t* keep /*[n]*/, int64_t* sums /*[n][3], may be NULL*/);
+/* Same for n separately allocated host frames of one size. */
+int vq_frame_postprocess_u8_list(vq_resampler* r, const uint8_t* const* frames, int n, int h, int w,
+                                 int out_h, int out_w, int quality_filter,
+                                 uint8_t* out, int64_t* n_kept, uint8_t* keep, int64_t* sums);
+/* How the pass above splits an out_h x out_w output: rows per workgroup band, bands per frame, and whether a band
+ * fits the on-chip budget (fused = 1 for every out_w <= 1024 at least).  fused = 0: the existing resize and
+ * quality kernels run back to back on the device instead, one band per frame.  Pure host arithmetic: needs neither
+ * vq_init nor a device. */
+int vq_frame_postprocess_plan(int out_h, int out_w, int* band_rows, int* n_bands, int* fused);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@ hand-written gfx950 HIP kernels (csrc/, include/vq_amd.h).
 
 Drop-in classes (same names/signatures as the reference):
   core.feature_extractor.FeatureExtractor / BatchProcessor / CachedFeatureExtractor
+  core.frame_extractor.OptimizedFrameExtractor (+ the three samplers, choose_optimal_strategy)
   indexes.hnsw.HNSWIndex / OptimizedHNSWIndex
 Also: overhaul_index.SimpleVideoIndex (the live path's brute-force index), preprocess.FramePreprocessor
 (Pillow-exact / cv2-style resize and the frame-quality filter on the GPU), text_encoder.TextEncoder.
@@ -18,19 +19,23 @@ __version__ = "0.1.0"
 
 
 def install_dropin() -> None:
-    """Make ``from core.feature_extractor import FeatureExtractor, BatchProcessor`` and
+    """Make ``from core.feature_extractor import FeatureExtractor, BatchProcessor``,
+    ``from core.frame_extractor import OptimizedFrameExtractor`` and
     ``from indexes.hnsw import OptimizedHNSWIndex`` (reference
-    src/video_search_system.py:18-19) resolve to this build, whatever sys.path says."""
+    src/video_search_system.py:17-19) resolve to this build, whatever sys.path says."""
     for short in ("core", "indexes"):
         pkg = _importlib.import_module(f"video_quierer_amd.{short}")
         _sys.modules[short] = pkg
     _sys.modules["core.feature_extractor"] = _importlib.import_module("video_quierer_amd.core.feature_extractor")
+    _sys.modules["core.frame_extractor"] = _importlib.import_module("video_quierer_amd.core.frame_extractor")
     _sys.modules["indexes.hnsw"] = _importlib.import_module("video_quierer_amd.indexes.hnsw")
 
 
 def __getattr__(name):  # lazy: keep `import video_quierer_amd` free of ctypes/GPU work
     if name in ("FeatureExtractor", "BatchProcessor", "CachedFeatureExtractor"):
         return getattr(_importlib.import_module("video_quierer_amd.core.feature_extractor"), name)
+    if name in ("OptimizedFrameExtractor", "choose_optimal_strategy"):
+        return getattr(_importlib.import_module("video_quierer_amd.core.frame_extractor"), name)
     if name in ("HNSWIndex", "OptimizedHNSWIndex"):
         return getattr(_importlib.import_module("video_quierer_amd.indexes.hnsw"), name)
     if name == "FramePreprocessor":

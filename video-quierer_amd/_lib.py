@@ -174,6 +174,11 @@ SIGNATURES = {
     "vq_frame_quality_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
     "vq_frame_scene_scores_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, POINTER(c_double), POINTER(c_double),
                                          POINTER(c_double)]),
+    "vq_frame_postprocess_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, POINTER(c_int64),
+                                        c_void_p, c_void_p]),
+    "vq_frame_postprocess_u8_list": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                             POINTER(c_int64), c_void_p, c_void_p]),
+    "vq_frame_postprocess_plan": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
 }
 
 # include/vq_amd_diag.h: present only in a `make DIAG=1` build (scripts/ point $VQ_AMD_LIB at one); bound when found

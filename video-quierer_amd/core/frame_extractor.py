@@ -1,5 +1,6 @@
-"""Frame samplers of the reference's ``core.frame_extractor`` (reference src/core/frame_extractor.py:23-237) over
-decoded frames: which frames of a video go on to the resize, the quality filter and the encoder.
+"""The reference's ``core.frame_extractor`` (reference src/core/frame_extractor.py) over decoded frames: the samplers
+(:23-237) choose which frames of a video go on, :class:`OptimizedFrameExtractor` (:240-362) resizes them, drops the
+low-quality ones and hands the rest to the encoder.
 
   * :class:`UniformFrameSampler` — every ``interval``-th frame (index arithmetic only);
   * :class:`AdaptiveFrameSampler` — a frame is kept when its scene-change score against the frame before it exceeds
@@ -8,14 +9,22 @@ decoded frames: which frames of a video go on to the resize, the quality filter 
     (:func:`select_scene_changes`) is host code;
   * :class:`HybridFrameSampler` — both, merged by timestamp.
 
-The samplers take frames (``sample``), an iterable of frame chunks of one video (``sample_chunks``) or, for the
-reference's call shape, a path plus a ``reader`` that decodes it (``extract_frames``).  Records are the reference's
-dicts.  Importing this module needs neither OpenCV nor a GPU; the default scorer binds the GPU when first used.
-This module is not part of ``install_dropin()``.
+  * :class:`OptimizedFrameExtractor` — a sampler plus the post-processing of its records: resize to ``frame_size``,
+    quality verdict and compaction, one GPU pass per chunk of a video (``FramePreprocessor.postprocess_list``);
+  * :func:`choose_optimal_strategy` — the reference's duration heuristic.
+
+The samplers take frames (``sample``), an iterable of frame chunks of one video (``sample_chunks``, or chunk by chunk
+``iter_chunks``) or, for the reference's call shape, a path plus a ``reader`` that decodes it (``extract_frames``).
+Records are the reference's dicts.  Importing this module needs neither OpenCV, torch nor a GPU; the default scorer and
+the default preprocessor bind the GPU when first used.  ``install_dropin()`` registers it as ``core.frame_extractor``.
 """
-from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
+import logging
+import time
+from typing import Any, Callable, Dict, Iterable, Iterator, List, Optional, Tuple
 
 import numpy as np
+
+logger = logging.getLogger(__name__)
 
 Record = Dict[str, Any]
 Reader = Callable[[str], Tuple[float, Iterable[np.ndarray]]]
@@ -98,14 +107,22 @@ class _ChunkedSampler:
     def sample_chunks(self, chunks: Iterable, fps: float, video_path: Optional[str] = None, _copy: bool = True) -> List[Record]:
         """:meth:`sample` of one video that arrives as consecutive chunks of frames; the same records as in one piece
         (their ``'frame'`` is a copy, so a record does not keep its whole chunk alive)."""
-        run, out = self._start(fps), []
+        out: List[Record] = []
+        for recs in self.iter_chunks(chunks, fps, video_path, _copy):
+            out.extend(recs)
+        return out
+
+    def iter_chunks(self, chunks: Iterable, fps: float, video_path: Optional[str] = None, _copy: bool = True) -> Iterator[List[Record]]:
+        """:meth:`sample_chunks` chunk by chunk: yields the records of each chunk as soon as it has been fed, so a
+        caller can post-process them and let the chunk's full-size frames go.  Concatenated, the lists are
+        ``sample_chunks``'s records.  With ``_copy=False`` a record's ``'frame'`` is a view into its chunk."""
+        run = self._start(fps)
         for chunk in chunks:
             a = _batch(chunk)
             if len(a):
-                out.extend(self._feed(run, a, fps, video_path, _copy))
+                yield self._feed(run, a, fps, video_path, _copy)
             if run["taken"] >= self.max_frames:
                 break                                    # the reference stops decoding here
-        return out
 
     def extract_frames(self, video_path: str, reader: Optional[Reader] = None) -> List[Record]:
         """The reference's call shape.  ``reader(video_path) -> (fps, iterable of frame chunks)``; the default decodes
@@ -213,3 +230,148 @@ class HybridFrameSampler(_ChunkedSampler):
                 rec["sampling_method"] = "adaptive"
                 merged[rec["timestamp"]] = rec
         return sorted(merged.values(), key=lambda rec: rec["timestamp"])
+
+    def iter_chunks(self, chunks: Iterable, fps: float, video_path: Optional[str] = None, _copy: bool = True) -> Iterator[List[Record]]:
+        """The merge of :meth:`sample_chunks` chunk by chunk.  Two records share a timestamp only when they are the
+        same frame, hence in the same chunk, and timestamps grow from chunk to chunk: merging inside each chunk and
+        concatenating gives the records ``sample_chunks`` gives."""
+        samplers = (self.uniform_sampler, self.adaptive_sampler)
+        runs = [s._start(fps) for s in samplers]
+        for chunk in chunks:
+            a = _batch(chunk)
+            live = [i for i, s in enumerate(samplers) if runs[i]["taken"] < s.max_frames]
+            if not live:
+                break
+            if not len(a):
+                continue
+            merged: Dict[float, Record] = {}
+            for i in live:
+                for rec in samplers[i]._feed(runs[i], a, fps, video_path, _copy):
+                    if rec["timestamp"] not in merged:      # live is in (uniform, adaptive) order: uniform wins
+                        rec["sampling_method"] = ("uniform", "adaptive")[i]
+                        merged[rec["timestamp"]] = rec
+            yield sorted(merged.values(), key=lambda rec: rec["timestamp"])
+
+
+class OptimizedFrameExtractor:
+    """The reference's main frame extraction class (:240-362): a sampler chosen by ``strategy`` plus the
+    post-processing of its records — resize to ``frame_size``, quality filter — done per chunk of the video in one GPU
+    pass (``preprocessor.postprocess_list``; the default :class:`~video_quierer_amd.preprocess.FramePreprocessor` is
+    created when first needed).  ``frame_size`` keeps the reference's quirk: a frame is resized unless
+    ``frame.shape[:2] == frame_size``, and then to width ``frame_size[0]``, height ``frame_size[1]``."""
+
+    def __init__(self, sample_rate: float = 1.0, strategy: str = "uniform", max_frames_per_video: int = 3600,
+                 frame_size: Optional[tuple] = (224, 224), quality_filter: bool = True, preprocessor=None):
+        self.sample_rate = sample_rate
+        self.max_frames_per_video = max_frames_per_video
+        self.frame_size = frame_size
+        self.quality_filter = quality_filter
+        self._preprocessor = preprocessor
+        if strategy == "uniform":
+            self.sampler = UniformFrameSampler(sample_rate, max_frames_per_video)
+        elif strategy == "adaptive":
+            self.sampler = AdaptiveFrameSampler(max_frames=max_frames_per_video)
+        elif strategy == "hybrid":
+            self.sampler = HybridFrameSampler(sample_rate * 0.7, max_frames=max_frames_per_video)
+        else:
+            raise ValueError(f"Unknown strategy: {strategy}")
+
+    @property
+    def preprocessor(self):
+        if self._preprocessor is None:
+            from ..preprocess import FramePreprocessor
+            self._preprocessor = FramePreprocessor()
+        return self._preprocessor
+
+    def _post(self, records: List[Record], start: Optional[float], always_resize: bool = False) -> List[Record]:
+        """Post-process records in runs of equal frame shape, order preserved; survivors get the resized frame and,
+        with ``start``, the seconds since ``start`` at which their batch finished as ``'processing_time'``."""
+        out: List[Record] = []
+        a = 0
+        while a < len(records):
+            shape = np.asarray(records[a]["frame"]).shape
+            b = a + 1
+            while b < len(records) and np.asarray(records[b]["frame"]).shape == shape:
+                b += 1
+            kept, keep, _ = self.preprocessor.postprocess_list([rec["frame"] for rec in records[a:b]], self.frame_size or None,
+                                                               bool(self.quality_filter), always_resize=always_resize)
+            done = None if start is None else time.perf_counter() - start
+            j = 0
+            for rec, ok in zip(records[a:b], keep):
+                if ok:
+                    rec["frame"] = np.array(kept[j])        # its own memory: a record does not keep its batch alive
+                    if done is not None:
+                        rec["processing_time"] = done
+                    out.append(rec)
+                    j += 1
+            a = b
+        return out
+
+    def process_records(self, records: List[Record]) -> List[Record]:
+        """The post-processing of :meth:`extract_frames` for records a caller already has (any sampler's): low-quality
+        ones are dropped, ``'frame'`` becomes the resized frame.  Runs of equal frame shape go through together."""
+        return self._post(list(records), None)
+
+    def extract_frames(self, video_path: str, reader: Optional[Reader] = None) -> List[Record]:
+        """Extract and preprocess frames from a video (reference :268-299).  Each chunk's records are post-processed as
+        they appear, so at most one chunk of full-size frames is held (the reference holds every sampled frame of the
+        video at full size: 3,600 frames of 1080p are 22 GB).  ``'processing_time'`` is the time since the call began
+        at which the record's chunk was finished; it does not decrease along the list."""
+        start = time.perf_counter()
+        fps, chunks = (reader or cv2_reader)(video_path)
+        out: List[Record] = []
+        for recs in self.sampler.iter_chunks(chunks, fps, video_path, _copy=False):
+            out.extend(self._post(recs, start))
+        total = time.perf_counter() - start
+        logger.info("Frame extraction completed: %d frames in %.2fs (%.1f fps)", len(out), total, len(out) / total if total > 0 else 0.0)
+        return out
+
+    def extract_frames_generator(self, video_path: str, reader: Optional[Reader] = None) -> Iterator[Record]:
+        """Memory-efficient extraction (reference :318-362): frames 0, interval, 2 * interval, ... with
+        ``interval = max(1, int(fps / sample_rate))``, always resized when ``frame_size`` is set; a low-quality frame
+        is skipped without counting towards ``max_frames_per_video``.  Records carry no ``'processing_time'``."""
+        fps, chunks = (reader or cv2_reader)(video_path)
+        interval = max(1, int(fps / self.sample_rate))
+        seen = count = 0
+        for chunk in chunks:
+            if count >= self.max_frames_per_video:
+                break
+            a = _batch(chunk)
+            recs = [_record(a, local, seen + local, fps, video_path, False) for local in range(-seen % interval, len(a), interval)]
+            seen += len(a)
+            for rec in self._post(recs, None, always_resize=True):
+                if count >= self.max_frames_per_video:
+                    break
+                count += 1
+                yield rec
+
+
+def cv2_probe(video_path: str) -> Optional[Tuple[float, int]]:
+    """Default ``probe`` of :func:`choose_optimal_strategy`: (fps, frame_count) from ``cv2.VideoCapture``, or None
+    when the file does not open."""
+    try:
+        import cv2
+    except ImportError as e:
+        raise ImportError("probing a video file needs OpenCV (cv2), which is not installed: pass probe=") from e
+    video = cv2.VideoCapture(video_path)
+    if not video.isOpened():
+        return None
+    try:
+        return video.get(cv2.CAP_PROP_FPS), int(video.get(cv2.CAP_PROP_FRAME_COUNT))
+    finally:
+        video.release()
+
+
+def choose_optimal_strategy(video_path: str, probe: Optional[Callable] = None) -> str:
+    """The reference's heuristic (:365-388): 'uniform' under 5 minutes (and for a file that does not open), 'adaptive'
+    over an hour, 'hybrid' between.  ``probe(video_path) -> (fps, frame_count)`` or None; the default uses OpenCV."""
+    got = (probe or cv2_probe)(video_path)
+    if got is None:
+        return "uniform"
+    fps, frame_count = got
+    duration = int(frame_count) / fps if fps > 0 else 0
+    if duration < 300:
+        return "uniform"
+    if duration > 3600:
+        return "adaptive"
+    return "hybrid"

@@ -387,6 +387,239 @@ void frame_quality_kernel(const uint8_t* __restrict__ frames, long long* __restr
     }
 }
 
+// ---- fused frame post-processing (reference frame_extractor.py:279-293) -----------------------------------
+// OptimizedFrameExtractor.extract_frames per sampled frame: cv2.resize to frame_size, _is_low_quality, keep or drop.
+// One device pass instead of resize -> download -> upload -> frame_quality_kernel -> host verdict:
+//
+// postproc_fused_kernel: grid (bands of output rows, frames).  A workgroup produces its band of the resized frame
+// into LDS — the arithmetic of cv_resize_linear_kernel / cv_resize_half_kernel / a copy, byte for byte — plus the two
+// halo rows reflect101(y0 - 1, out_h) and reflect101(y1 + 1, out_h) (y0 / y1: its first / last owned row), computed
+// like any other row whichever row they turn out to be.  Each pixel is converted to grey once, into an LDS grey plane.
+// The owned rows go to global memory from LDS (16-byte stores when the row bytes and the destination allow, else
+// 4-byte, else bytes); the sum of the owned bytes and the sums of L and L^2 of the 4-neighbour Laplacian over the
+// owned pixels (BORDER_REFLECT_101: the halo rows vertically, reflect101 on the column horizontally) come from LDS.
+// They are frame_quality_kernel's three sums, stored per workgroup (no global atomics; integers, so the order of
+// the later sum does not matter).
+//   LDS: pix [lrows][pitch] bytes (row 0 / rows + 1 the halos, pitch = row bytes rounded up to 16), grey
+//   [lrows][gpitch], then PP_RED_BYTES of reduction scratch; lrows = min(band_rows, out_h) + 2.  The host plan
+//   (pp_plan) picks band_rows so that all of it stays within PP_LDS_BUDGET.
+//   A thread handles at most lrows * (out_w / 256 + 1) <= 64 + 34 pixels (lrows * out_w * 4 <= the budget), so its
+//   three sums fit 32 bits: 98 * 1020^2 < 2^27.
+//
+// postproc_verdict_kernel: one workgroup over n <= 65535 frames sums each frame's partials and decides in integers,
+// with N = out_h * out_w, S1 = sum L, S2 = sum L^2:
+//   low quality  <=>  sum_bytes < 20 * 3 * N  ||  sum_bytes > 235 * 3 * N  ||  N * S2 - S1^2 < 100 * N^2.
+// N <= 2^21 keeps every term inside int64 (N^2 * 1020^2 < 2^63).  These are the verdicts of
+// FramePreprocessor.is_low_quality, which compares the rounded quotients sum_bytes / (3 N) and (N S2 - S1^2) / N^2
+// with 20, 235 and 100: a quotient that does not equal its threshold lies at least 1 / (3 N) resp. 1 / N^2 >= 2^-42
+// away from it — relative to a threshold of at most 235 that is above 2^-50, several ulps of a double — so rounding
+// the quotient cannot carry it onto or across the threshold, and a quotient that equals the threshold is exact.
+// It then leaves keep[i], the exclusive prefix sum of keep and the total (kept bits in LDS, popcounts).
+//
+// postproc_gather_kernel: kept frame i -> slot prefix[i] of the result buffer.
+constexpr int PP_LDS_BUDGET = 65536;                         // bytes of dynamic LDS a fused workgroup may ask for
+constexpr int PP_MAX_BAND_ROWS = 32;                         // 224 x 224: 7 bands of 32 rows, 6 % of halo rows
+constexpr int PP_RED_BYTES = 128;                            // 4 waves x 3 int64, rounded up
+constexpr int PP_MAX_PIXELS = 1 << 21;                       // out_h * out_w the integer verdict is proven for
+constexpr int PP_COPY = 0, PP_HALF = 1, PP_LINEAR = 2;
+
+__host__ __device__ inline int pp_pitch(int out_w) { return (out_w * 3 + 15) & ~15; }
+__host__ __device__ inline int pp_gpitch(int out_w) { return (out_w + 15) & ~15; }
+// LDS bytes of a fused workgroup whose bands have `rows` rows
+__host__ __device__ inline long long pp_lds_bytes(int rows, int out_w) {
+    return (long long)(rows + 2) * (pp_pitch(out_w) + pp_gpitch(out_w)) + PP_RED_BYTES;
+}
+// band_rows: the most rows (at most PP_MAX_BAND_ROWS) whose band fits the budget; fused = 0 when not even one does
+inline void pp_plan(int out_h, int out_w, int* band_rows, int* n_bands, int* fused) {
+    const long long per_row = pp_pitch(out_w) + pp_gpitch(out_w);
+    long long rows = (PP_LDS_BUDGET - PP_RED_BYTES) / per_row - 2;
+    if (rows > PP_MAX_BAND_ROWS) rows = PP_MAX_BAND_ROWS;
+    *fused = rows >= 1;
+    *band_rows = rows >= 1 ? (int)rows : out_h;              // unfused: the whole frame is one "band" (one partial)
+    *n_bands = (out_h + *band_rows - 1) / *band_rows;
+}
+
+// one output pixel (dy, dx) of the resized frame, exactly as cv_resize_linear_kernel / cv_resize_half_kernel / a copy
+template <int MODE>
+__device__ __forceinline__ void pp_pixel(const uint8_t* __restrict__ f, const int* __restrict__ xofs, const int* __restrict__ wx,
+                                         const int* __restrict__ yofs, const int* __restrict__ wy, int h, int w, int dy, int dx,
+                                         int (&v)[3]) {
+    const size_t pitch = (size_t)w * 3;
+    if constexpr (MODE == PP_COPY) {
+        const uint8_t* p = f + (size_t)dy * pitch + (size_t)dx * 3;
+        v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
+    } else if constexpr (MODE == PP_HALF) {
+        const uint8_t* p = f + (size_t)(2 * dy) * pitch + (size_t)(2 * dx) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = (p[c] + p[3 + c] + p[pitch + c] + p[pitch + 3 + c] + 2) >> 2;
+    } else {
+        const int sx = xofs[dx], sx1 = min(sx + 1, w - 1);
+        const int a0 = wx[2 * dx], a1 = wx[2 * dx + 1];
+        const int sy = yofs[dy];
+        const int y0 = min(max(sy, 0), h - 1), y1 = min(max(sy + 1, 0), h - 1);
+        const int b0 = wy[2 * dy], b1 = wy[2 * dy + 1];
+        const uint8_t* r0 = f + (size_t)y0 * pitch;
+        const uint8_t* r1 = f + (size_t)y1 * pitch;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int d0 = r0[sx * 3 + c] * a0 + r0[sx1 * 3 + c] * a1;
+            const int d1 = r1[sx * 3 + c] * a0 + r1[sx1 * 3 + c] * a1;
+            v[c] = (int)(uint8_t)((((b0 * (d0 >> 4)) >> 16) + ((b1 * (d1 >> 4)) >> 16) + 2) >> 2);
+        }
+    }
+}
+
+//   src [n][h][w][3]; dst [n][out_h][out_w][3]; partials [n][gridDim.x][3] int64 = {sum bytes, sum L, sum L^2}
+//   WIDE_SRC (PP_COPY only): rows are 16-byte aligned multiples of 16 bytes, staged with 16-byte loads
+//   store_vec: 16, 4 or 1 bytes per store of the owned rows
+template <int MODE, bool WIDE_SRC>
+__global__ __launch_bounds__(RS_THREADS)
+void postproc_fused_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long* __restrict__ partials,
+                           const int* __restrict__ xofs, const int* __restrict__ wx, const int* __restrict__ yofs,
+                           const int* __restrict__ wy, int h, int w, int out_h, int out_w, int band_rows, int lrows, int store_vec) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t pp_lds[];
+    const int pitch = pp_pitch(out_w), gpitch = pp_gpitch(out_w);
+    uint8_t* pix = pp_lds;                                           // [lrows][pitch]
+    uint8_t* grey = pix + (size_t)lrows * pitch;                     // [lrows][gpitch]
+    long long* red = (long long*)(grey + (size_t)lrows * gpitch);    // [4][3]
+    const int band = blockIdx.x, img = blockIdx.y;
+    const int y0 = band * band_rows, rows = min(band_rows, out_h - y0), y1 = y0 + rows - 1;
+    const int row_bytes = out_w * 3;
+    const uint8_t* f = src + (size_t)img * h * w * 3;
+    auto out_row = [&](int r) { return r == 0 ? reflect101(y0 - 1, out_h) : (r == rows + 1 ? reflect101(y1 + 1, out_h) : y0 + r - 1); };
+    int sb = 0;
+
+    // ---- the band and its halo rows -> pix, grey ----
+    if constexpr (MODE == PP_COPY && WIDE_SRC) {
+        const int cpr = row_bytes >> 4;                              // row_bytes == pitch here
+        for (int i = threadIdx.x; i < (rows + 2) * cpr; i += RS_THREADS) {
+            const int r = i / cpr, c = i - r * cpr;
+            *(uint4*)(pix + (size_t)r * pitch + 16 * c) = *(const uint4*)(f + (size_t)out_row(r) * row_bytes + 16 * c);
+        }
+        __syncthreads();
+        for (int r = 0; r < rows + 2; ++r) {
+            const bool owned = r >= 1 && r <= rows;
+            for (int x = threadIdx.x; x < out_w; x += RS_THREADS) {
+                const uint8_t* p = pix + (size_t)r * pitch + 3 * x;
+                const int b = p[0], g = p[1], rr = p[2];
+                grey[(size_t)r * gpitch + x] = (uint8_t)gray_bgr(b, g, rr);
+                if (owned) sb += b + g + rr;
+            }
+        }
+    } else {
+        for (int r = 0; r < rows + 2; ++r) {
+            const int dy = out_row(r);
+            const bool owned = r >= 1 && r <= rows;
+            for (int x = threadIdx.x; x < out_w; x += RS_THREADS) {
+                int v[3];
+                pp_pixel<MODE>(f, xofs, wx, yofs, wy, h, w, dy, x, v);
+                uint8_t* p = pix + (size_t)r * pitch + 3 * x;
+                p[0] = (uint8_t)v[0]; p[1] = (uint8_t)v[1]; p[2] = (uint8_t)v[2];
+                grey[(size_t)r * gpitch + x] = (uint8_t)gray_bgr(v[0], v[1], v[2]);
+                if (owned) sb += v[0] + v[1] + v[2];
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- owned rows -> global: rows y0 .. y1 are contiguous there ----
+    uint8_t* o = dst + ((size_t)img * out_h + y0) * row_bytes;
+    if (store_vec == 16) {
+        const int cpr = row_bytes >> 4;
+        for (int i = threadIdx.x; i < rows * cpr; i += RS_THREADS) {
+            const int r = i / cpr, c = i - r * cpr;
+            *(uint4*)(o + (size_t)r * row_bytes + 16 * c) = *(const uint4*)(pix + (size_t)(r + 1) * pitch + 16 * c);
+        }
+    } else if (store_vec == 4) {
+        const int cpr = row_bytes >> 2;
+        for (int i = threadIdx.x; i < rows * cpr; i += RS_THREADS) {
+            const int r = i / cpr, c = i - r * cpr;
+            *(uint32_t*)(o + (size_t)r * row_bytes + 4 * c) = *(const uint32_t*)(pix + (size_t)(r + 1) * pitch + 4 * c);
+        }
+    } else {
+        for (int r = 0; r < rows; ++r)
+            for (int j = threadIdx.x; j < row_bytes; j += RS_THREADS) o[(size_t)r * row_bytes + j] = pix[(size_t)(r + 1) * pitch + j];
+    }
+
+    // ---- Laplacian sums over the owned pixels, from the grey plane ----
+    int sl = 0, sl2 = 0;
+    for (int r = 1; r <= rows; ++r) {
+        const uint8_t* g = grey + (size_t)r * gpitch;
+        for (int x = threadIdx.x; x < out_w; x += RS_THREADS) {
+            const int lap = (int)g[x - gpitch] + (int)g[x + gpitch] + (int)g[reflect101(x - 1, out_w)] + (int)g[reflect101(x + 1, out_w)] -
+                            4 * (int)g[x];
+            sl += lap; sl2 += lap * lap;
+        }
+    }
+    long long a = sb, b = sl, c = sl2;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); c += __shfl_down(c, off); }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[wave * 3] = a; red[wave * 3 + 1] = b; red[wave * 3 + 2] = c; }
+    __syncthreads();
+    if (threadIdx.x < 3)
+        partials[((size_t)img * gridDim.x + band) * 3 + threadIdx.x] =
+            red[threadIdx.x] + red[3 + threadIdx.x] + red[6 + threadIdx.x] + red[9 + threadIdx.x];
+}
+
+//   partials [n][nb][3]; res: [0] = frames kept, then sums [n][3]; keep [n] bytes; prefix [n]: kept frames before frame i
+//   filter == 0: every frame is kept (the sums are still formed)
+__global__ __launch_bounds__(RS_THREADS)
+void postproc_verdict_kernel(const long long* __restrict__ partials, int n, int nb, long long N, int filter,
+                             long long* __restrict__ res, uint8_t* __restrict__ keep, int* __restrict__ prefix) {
+    __shared__ uint32_t bits[2048];                                  // bit i: frame i is kept (n <= 65535)
+    __shared__ uint32_t wpre[2048];                                  // kept frames before word j's first frame
+    __shared__ uint32_t tsum[RS_THREADS];
+    const int t = threadIdx.x;
+    for (int i = t; i < 2048; i += RS_THREADS) bits[i] = 0;
+    __syncthreads();
+    for (int i = t; i < n; i += RS_THREADS) {
+        const long long* p = partials + (size_t)i * nb * 3;
+        long long sb = 0, s1 = 0, s2 = 0;
+        for (int b = 0; b < nb; ++b) { sb += p[3 * b]; s1 += p[3 * b + 1]; s2 += p[3 * b + 2]; }
+        res[1 + 3 * (size_t)i] = sb; res[2 + 3 * (size_t)i] = s1; res[3 + 3 * (size_t)i] = s2;
+        const bool low = filter && (sb < 20 * 3 * N || sb > 235 * 3 * N || N * s2 - s1 * s1 < 100 * N * N);
+        keep[i] = low ? 0 : 1;
+        if (!low) atomicOr(&bits[i >> 5], 1u << (i & 31));
+    }
+    __syncthreads();
+    uint32_t mine = 0;                                               // thread t owns words 8t .. 8t + 7
+#pragma unroll
+    for (int k = 0; k < 8; ++k) mine += __popc(bits[8 * t + k]);
+    tsum[t] = mine;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t run = 0;
+        for (int i = 0; i < RS_THREADS; ++i) { const uint32_t v = tsum[i]; tsum[i] = run; run += v; }
+        res[0] = run;
+    }
+    __syncthreads();
+    uint32_t run = tsum[t];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { wpre[8 * t + k] = run; run += __popc(bits[8 * t + k]); }
+    __syncthreads();
+    for (int i = t; i < n; i += RS_THREADS) prefix[i] = (int)(wpre[i >> 5] + __popc(bits[i >> 5] & ((1u << (i & 31)) - 1u)));
+}
+static_assert(RS_THREADS * 8 * 32 >= 65536, "the verdict's bit set must hold 65535 frames");
+
+// grid (x, n).  WIDE: frame_bytes is a multiple of 16 and both buffers are 16-byte aligned -> 16-byte copies
+template <bool WIDE>
+__global__ __launch_bounds__(RS_THREADS)
+void postproc_gather_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const uint8_t* __restrict__ keep,
+                            const int* __restrict__ prefix, size_t frame_bytes) {
+    const int i = blockIdx.y;
+    if (!keep[i]) return;
+    const uint8_t* s = src + (size_t)i * frame_bytes;
+    uint8_t* d = dst + (size_t)prefix[i] * frame_bytes;
+    const size_t step = (size_t)gridDim.x * RS_THREADS;
+    if constexpr (WIDE) {
+        const size_t n16 = frame_bytes >> 4;
+        for (size_t j = (size_t)blockIdx.x * RS_THREADS + threadIdx.x; j < n16; j += step) ((uint4*)d)[j] = ((const uint4*)s)[j];
+    } else {
+        for (size_t j = (size_t)blockIdx.x * RS_THREADS + threadIdx.x; j < frame_bytes; j += step) d[j] = s[j];
+    }
+}
+
 // ---- scene-change score (reference frame_extractor.py:168-186) -------------------------------------------
 // AdaptiveFrameSampler._calculate_frame_difference for every consecutive pair (earlier a, later b) of a batch:
 //   mse = mean((grey_a - grey_b)^2), chi = cv2.compareHist(hist_a, hist_b, HISTCMP_CHISQR), score = mse + chi * 0.01.

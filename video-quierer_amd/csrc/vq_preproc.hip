@@ -112,12 +112,13 @@ using namespace vq;
 struct vq_resampler {
     std::mutex mu;
     hipStream_t stream = nullptr, own_stream = nullptr;
-    DevBuf src, tmp, dst, coef, acc;
+    DevBuf src, tmp, dst, coef, acc, post;
     // plan cache: coefficient tables on the device for the last geometry
     int p_h = 0, p_w = 0, p_filter = 0, p_out_h = 0, p_out_w = 0;
     Coeffs ch, cv;
     int *d_bh = nullptr, *d_kh = nullptr, *d_bv = nullptr, *d_kv = nullptr;
     int64_t out_bytes = 0;
+    void* out_ptr = nullptr;     // what vq_resampler_device_output hands out: dst, or post after a compaction
 };
 
 namespace {
@@ -152,6 +153,24 @@ int check_geometry(const char* who, int n, int h, int w, int filter, int out_h, 
     return 0;
 }
 
+// OpenCV's INTER_LINEAR tables of the geometry on the device: d_bh = xofs, d_kh = wx, d_bv = yofs, d_kv = wy
+int plan_cv(vq_resampler* r, int h, int w, int out_h, int out_w) {
+    if (r->p_h == h && r->p_w == w && r->p_filter == VQ_RESAMPLE_CV_LINEAR && r->p_out_h == out_h && r->p_out_w == out_w) return 0;
+    VQ_HIP(hipStreamSynchronize(r->stream));
+    std::vector<int> xo, wx, yo, wy;
+    cv_linear_coeffs(w, out_w, true, xo, wx);
+    cv_linear_coeffs(h, out_h, false, yo, wy);
+    const size_t total = xo.size() + wx.size() + yo.size() + wy.size();
+    VQ_TRY(r->coef.reserve(total * sizeof(int)));
+    r->d_bh = (int*)r->coef.p; r->d_kh = r->d_bh + xo.size(); r->d_bv = r->d_kh + wx.size(); r->d_kv = r->d_bv + yo.size();
+    VQ_HIP(hipMemcpy(r->d_bh, xo.data(), xo.size() * 4, hipMemcpyHostToDevice));
+    VQ_HIP(hipMemcpy(r->d_kh, wx.data(), wx.size() * 4, hipMemcpyHostToDevice));
+    VQ_HIP(hipMemcpy(r->d_bv, yo.data(), yo.size() * 4, hipMemcpyHostToDevice));
+    VQ_HIP(hipMemcpy(r->d_kv, wy.data(), wy.size() * 4, hipMemcpyHostToDevice));
+    r->p_h = h; r->p_w = w; r->p_filter = VQ_RESAMPLE_CV_LINEAR; r->p_out_h = out_h; r->p_out_w = out_w;
+    return 0;
+}
+
 // both passes for n device-resident frames; d_dst gets [n][crop_h][crop_w][3]
 // cv2.resize(frame, (out_w, out_h)) — INTER_LINEAR
 int run_device_cv(vq_resampler* r, const uint8_t* d_src, int n, int h, int w, int out_h, int out_w,
@@ -167,20 +186,7 @@ int run_device_cv(vq_resampler* r, const uint8_t* d_src, int n, int h, int w, in
         VQ_HIP(hipGetLastError());
         return 0;
     }
-    if (!(r->p_h == h && r->p_w == w && r->p_filter == VQ_RESAMPLE_CV_LINEAR && r->p_out_h == out_h && r->p_out_w == out_w)) {
-        VQ_HIP(hipStreamSynchronize(r->stream));
-        std::vector<int> xo, wx, yo, wy;
-        cv_linear_coeffs(w, out_w, true, xo, wx);
-        cv_linear_coeffs(h, out_h, false, yo, wy);
-        const size_t total = xo.size() + wx.size() + yo.size() + wy.size();
-        VQ_TRY(r->coef.reserve(total * sizeof(int)));
-        r->d_bh = (int*)r->coef.p; r->d_kh = r->d_bh + xo.size(); r->d_bv = r->d_kh + wx.size(); r->d_kv = r->d_bv + yo.size();
-        VQ_HIP(hipMemcpy(r->d_bh, xo.data(), xo.size() * 4, hipMemcpyHostToDevice));
-        VQ_HIP(hipMemcpy(r->d_kh, wx.data(), wx.size() * 4, hipMemcpyHostToDevice));
-        VQ_HIP(hipMemcpy(r->d_bv, yo.data(), yo.size() * 4, hipMemcpyHostToDevice));
-        VQ_HIP(hipMemcpy(r->d_kv, wy.data(), wy.size() * 4, hipMemcpyHostToDevice));
-        r->p_h = h; r->p_w = w; r->p_filter = VQ_RESAMPLE_CV_LINEAR; r->p_out_h = out_h; r->p_out_w = out_w;
-    }
+    VQ_TRY(plan_cv(r, h, w, out_h, out_w));
     hipLaunchKernelGGL(cv_resize_linear_kernel, grid, dim3(RS_THREADS), 0, r->stream, d_src, d_dst, r->d_bh, r->d_kh, r->d_bv,
                        r->d_kv, h, w, crop_top, crop_left, crop_h, crop_w);
     VQ_HIP(hipGetLastError());
@@ -321,6 +327,160 @@ int scene_run_device(vq_resampler* r, const uint8_t* d_frames, int m, int h, int
     return 0;
 }
 
+// ---- fused post-processing (preproc_kernels.h "fused frame post-processing") ------------------------------
+// m device-resident frames -> d_dst [m][out_h][out_w][3] and, in r->acc, the verdict's results:
+//   partials [m][n_bands][3] int64 | res: kept, sums [m][3] int64 | prefix [m] int32 | keep [m] bytes
+struct PostLayout {
+    size_t partials, res, prefix, keep, total;
+    PostLayout(int m, int nb) {
+        partials = 0;
+        res = partials + (size_t)m * nb * 3 * sizeof(long long);
+        prefix = res + (1 + (size_t)m * 3) * sizeof(long long);
+        keep = prefix + (size_t)round_up((int64_t)m * 4, 8);
+        total = keep + (size_t)round_up(m, 8);
+    }
+};
+
+template <int MODE>
+void launch_fused(vq_resampler* r, bool wide_src, const dim3 grid, size_t lds, const uint8_t* d_src, uint8_t* d_dst, long long* d_part,
+                  int h, int w, int out_h, int out_w, int band_rows, int lrows, int store_vec) {
+    if constexpr (MODE == PP_COPY) if (wide_src) {
+        hipLaunchKernelGGL((postproc_fused_kernel<MODE, true>), grid, dim3(RS_THREADS), lds, r->stream, d_src, d_dst, d_part,
+                           (const int*)r->d_bh, (const int*)r->d_kh, (const int*)r->d_bv, (const int*)r->d_kv, h, w, out_h, out_w,
+                           band_rows, lrows, store_vec);
+        return;
+    }
+    hipLaunchKernelGGL((postproc_fused_kernel<MODE, false>), grid, dim3(RS_THREADS), lds, r->stream, d_src, d_dst, d_part,
+                       (const int*)r->d_bh, (const int*)r->d_kh, (const int*)r->d_bv, (const int*)r->d_kv, h, w, out_h, out_w,
+                       band_rows, lrows, store_vec);
+}
+
+int post_run_device(vq_resampler* r, const uint8_t* d_src, int m, int h, int w, int out_h, int out_w, int quality_filter,
+                    uint8_t* d_dst, const PostLayout& lay, int band_rows, int n_bands, int fused) {
+    uint8_t* acc = (uint8_t*)r->acc.p;
+    long long* d_part = (long long*)(acc + lay.partials);
+    if (fused) {
+        const int mode = (out_h == h && out_w == w) ? PP_COPY : (h == 2 * out_h && w == 2 * out_w) ? PP_HALF : PP_LINEAR;
+        if (mode == PP_LINEAR) VQ_TRY(plan_cv(r, h, w, out_h, out_w));
+        const int row_bytes = out_w * 3;
+        const int lrows = std::min(band_rows, out_h) + 2;
+        const size_t lds = (size_t)pp_lds_bytes(lrows - 2, out_w);
+        const bool wide_src = row_bytes % 16 == 0 && ((uintptr_t)d_src & 15) == 0;
+        const int store_vec = (row_bytes % 16 == 0 && ((uintptr_t)d_dst & 15) == 0) ? 16 : (row_bytes % 4 == 0 && ((uintptr_t)d_dst & 3) == 0) ? 4 : 1;
+        const dim3 grid(n_bands, m);
+        if (mode == PP_COPY) launch_fused<PP_COPY>(r, wide_src, grid, lds, d_src, d_dst, d_part, h, w, out_h, out_w, band_rows, lrows, store_vec);
+        else if (mode == PP_HALF) launch_fused<PP_HALF>(r, false, grid, lds, d_src, d_dst, d_part, h, w, out_h, out_w, band_rows, lrows, store_vec);
+        else launch_fused<PP_LINEAR>(r, false, grid, lds, d_src, d_dst, d_part, h, w, out_h, out_w, band_rows, lrows, store_vec);
+        VQ_HIP(hipGetLastError());
+    } else {
+        // a row too wide for the LDS plan: the resize kernel, then frame_quality_kernel over the device buffer (one partial per frame)
+        VQ_TRY(run_device_cv(r, d_src, m, h, w, out_h, out_w, 0, 0, out_h, out_w, d_dst));
+        VQ_HIP(hipMemsetAsync(d_part, 0, (size_t)m * 3 * sizeof(long long), r->stream));
+        const int wgs = std::min(cdiv((int64_t)out_h * out_w, RS_THREADS), 1024);
+        hipLaunchKernelGGL(frame_quality_kernel, dim3(wgs, m), dim3(RS_THREADS), 0, r->stream, (const uint8_t*)d_dst, d_part, out_h, out_w);
+        VQ_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(postproc_verdict_kernel, dim3(1), dim3(RS_THREADS), 0, r->stream, (const long long*)d_part, m, n_bands,
+                       (long long)out_h * out_w, quality_filter, (long long*)(acc + lay.res), acc + lay.keep, (int*)(acc + lay.prefix));
+    VQ_HIP(hipGetLastError());
+    return 0;
+}
+
+// `list` (n host frames) or `d_frames` (n contiguous device frames): exactly one of them
+int postprocess(const char* who, vq_resampler* r, const uint8_t* const* list, const uint8_t* d_frames, int n, int h, int w,
+                int out_h, int out_w, int quality_filter, uint8_t* out, int64_t* n_kept, uint8_t* keep, int64_t* sums) {
+    VQ_TRY(require_init());
+    VQ_CHECK(r && n >= 0 && h > 0 && w > 0 && out_h >= 0 && out_w >= 0 && (out_h == 0) == (out_w == 0) && n_kept &&
+             (n == 0 || ((list || d_frames) && keep)), "%s: bad argument", who);
+    if (out_h == 0) { out_h = h; out_w = w; }
+    VQ_CHECK((int64_t)h * w < (int64_t)1 << 30, "%s: frame of %dx%d pixels is too large", who, h, w);
+    VQ_CHECK((int64_t)out_h * out_w <= PP_MAX_PIXELS, "%s: output of %dx%d pixels is too large (at most 2^21 pixels: the integer "
+             "verdict must stay inside int64)", who, out_h, out_w);
+    VQ_CHECK(n <= 65535, "%s: at most 65535 frames per call", who);
+    VQ_TRY(check_geometry(who, n, h, w, VQ_RESAMPLE_CV_LINEAR, out_h, out_w, 0, 0, out_h, out_w));
+    *n_kept = 0;
+    if (n == 0) return 0;
+    if (list) for (int i = 0; i < n; ++i) VQ_CHECK(list[i], "%s: frame %d is null", who, i);
+    std::lock_guard<std::mutex> lk(r->mu);
+    const size_t frame_bytes = (size_t)h * w * 3, ob = (size_t)out_h * out_w * 3;
+    int band_rows, n_bands, fused;
+    pp_plan(out_h, out_w, &band_rows, &n_bands, &fused);
+    const bool need_stats = quality_filter || sums;
+    int slice = n;
+    if (list) {
+        size_t budget = (size_t)512 << 20;
+        if (const char* e = getenv("VQ_AMD_POSTPROC_SLICE_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+        slice = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / frame_bytes));
+    }
+    const bool single = slice >= n;
+    VQ_HIP(hipStreamSynchronize(r->stream));                 // the buffers below may move; an earlier result may still be read
+    r->out_ptr = nullptr;                                    // a call that fails half way leaves no result behind
+    r->out_bytes = 0;
+    if (list) VQ_TRY(r->src.reserve((size_t)slice * frame_bytes));
+    VQ_TRY(r->dst.reserve((size_t)slice * ob));
+    if (!single) VQ_TRY(r->post.reserve((size_t)n * ob));
+    const PostLayout lay(slice, n_bands);
+    if (need_stats) VQ_TRY(r->acc.reserve(lay.total));
+    std::vector<long long> res(1 + (size_t)slice * 3);
+    int64_t kept_total = 0;
+    void* result = r->dst.p;
+    for (int i = 0; i < n; i += slice) {
+        const int m = std::min(slice, n - i);
+        const uint8_t* d_src = d_frames;
+        if (list) {
+            for (int a = 0; a < m;) {                        // consecutive frames that are contiguous in host memory go up in one copy
+                int b = a + 1;
+                while (b < m && list[i + b] == list[i + b - 1] + frame_bytes) ++b;
+                VQ_HIP(hipMemcpyAsync((uint8_t*)r->src.p + (size_t)a * frame_bytes, list[i + a], (size_t)(b - a) * frame_bytes,
+                                      hipMemcpyHostToDevice, r->stream));
+                a = b;
+            }
+            d_src = (const uint8_t*)r->src.p;
+        }
+        int64_t kept = m;
+        if (!need_stats) {                                   // nothing to decide: the resize alone, straight into its final place
+            uint8_t* target = single ? (uint8_t*)r->dst.p : (uint8_t*)r->post.p + (size_t)i * ob;
+            VQ_TRY(run_device_cv(r, d_src, m, h, w, out_h, out_w, 0, 0, out_h, out_w, target));
+            memset(keep + i, 1, (size_t)m);
+            result = single ? r->dst.p : r->post.p;
+        } else {
+            VQ_TRY(post_run_device(r, d_src, m, h, w, out_h, out_w, quality_filter, (uint8_t*)r->dst.p, lay, band_rows, n_bands, fused));
+            const uint8_t* acc = (const uint8_t*)r->acc.p;
+            VQ_HIP(hipMemcpyAsync(res.data(), acc + lay.res, (1 + (size_t)m * 3) * sizeof(long long), hipMemcpyDeviceToHost, r->stream));
+            VQ_HIP(hipMemcpyAsync(keep + i, acc + lay.keep, (size_t)m, hipMemcpyDeviceToHost, r->stream));
+            VQ_HIP(hipStreamSynchronize(r->stream));         // the host needs the count to place the next slice's survivors
+            kept = res[0];
+            if (sums) memcpy(sums + (size_t)i * 3, res.data() + 1, (size_t)m * 3 * sizeof(long long));
+            if (single && kept == m) {
+                result = r->dst.p;                           // everything kept: the resized buffer is the result
+            } else {
+                if (single) VQ_TRY(r->post.reserve((size_t)kept * ob));
+                result = r->post.p;
+                if (kept > 0) {
+                    uint8_t* target = (uint8_t*)r->post.p + (size_t)kept_total * ob;
+                    const bool wide = ob % 16 == 0;          // hipMalloc'd bases are 16-byte aligned, and so is every frame slot then
+                    const dim3 grid(std::max(1, std::min(cdiv((int64_t)(wide ? ob / 16 : ob), RS_THREADS), 64)), m);
+                    if (wide) hipLaunchKernelGGL(postproc_gather_kernel<true>, grid, dim3(RS_THREADS), 0, r->stream, (const uint8_t*)r->dst.p,
+                                                 target, acc + lay.keep, (const int*)(acc + lay.prefix), ob);
+                    else hipLaunchKernelGGL(postproc_gather_kernel<false>, grid, dim3(RS_THREADS), 0, r->stream, (const uint8_t*)r->dst.p,
+                                            target, acc + lay.keep, (const int*)(acc + lay.prefix), ob);
+                    VQ_HIP(hipGetLastError());
+                }
+            }
+        }
+        kept_total += kept;
+        VQ_HIP(hipStreamSynchronize(r->stream));             // the source slice and the resized slice are reused
+    }
+    r->out_ptr = result;
+    r->out_bytes = (int64_t)((size_t)kept_total * ob);
+    if (out && kept_total > 0) {
+        VQ_HIP(hipMemcpyAsync(out, result, (size_t)kept_total * ob, hipMemcpyDeviceToHost, r->stream));
+        VQ_HIP(hipStreamSynchronize(r->stream));
+    }
+    *n_kept = kept_total;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -339,7 +499,7 @@ int vq_resampler_create(vq_resampler** out) {
 int vq_resampler_destroy(vq_resampler* r) {
     if (!r) return 0;
     (void)hipStreamSynchronize(r->stream);
-    r->src.release(); r->tmp.release(); r->dst.release(); r->coef.release(); r->acc.release();
+    r->src.release(); r->tmp.release(); r->dst.release(); r->coef.release(); r->acc.release(); r->post.release();
     if (r->own_stream) (void)hipStreamDestroy(r->own_stream);
     delete r;
     return 0;
@@ -372,6 +532,7 @@ int vq_resampler_run_u8_device(vq_resampler* r, const uint8_t* d_frames, int n, 
         VQ_TRY(r->dst.reserve(ob));
         d_out = (uint8_t*)r->dst.p;
         r->out_bytes = (int64_t)ob;
+        r->out_ptr = r->dst.p;
     }
     return run_device(r, d_frames, n, h, w, filter, out_h, out_w, crop_top, crop_left, crop_h, crop_w, d_out);
 }
@@ -388,6 +549,7 @@ int vq_resampler_run_u8_list(vq_resampler* r, const uint8_t* const* frames, int 
     VQ_HIP(hipStreamSynchronize(r->stream));
     VQ_TRY(r->dst.reserve((size_t)n * ob_frame));
     r->out_bytes = (int64_t)((size_t)n * ob_frame);
+    r->out_ptr = r->dst.p;
     // frames go up in slices of <= 512 MiB so the source workspace stays bounded
     int slice = (int)std::max<size_t>(1, ((size_t)512 << 20) / frame_bytes);
     if (slice > n) slice = n;
@@ -424,7 +586,7 @@ int vq_resampler_run_u8(vq_resampler* r, const uint8_t* frames, int n, int h, in
 int vq_resampler_device_output(vq_resampler* r, void** d_ptr, int64_t* bytes) {
     VQ_CHECK(r && d_ptr, "vq_resampler_device_output: null argument");
     std::lock_guard<std::mutex> lk(r->mu);
-    *d_ptr = r->dst.p;
+    *d_ptr = r->out_ptr ? r->out_ptr : r->dst.p;
     if (bytes) *bytes = r->out_bytes;
     return 0;
 }
@@ -530,6 +692,28 @@ int vq_frame_scene_scores_u8(vq_resampler* r, const uint8_t* frames, int n, int 
         score[i] = res[3 * (size_t)i + 2];
     }
     return 0;
+}
+
+int vq_frame_postprocess_plan(int out_h, int out_w, int* band_rows, int* n_bands, int* fused) {
+    VQ_CHECK(out_h > 0 && out_w > 0 && band_rows && n_bands && fused, "vq_frame_postprocess_plan: bad argument");
+    VQ_CHECK((int64_t)out_h * out_w <= PP_MAX_PIXELS, "vq_frame_postprocess_plan: output of %dx%d pixels is too large (at most 2^21)", out_h, out_w);
+    pp_plan(out_h, out_w, band_rows, n_bands, fused);
+    return 0;
+}
+
+int vq_frame_postprocess_u8_list(vq_resampler* r, const uint8_t* const* frames, int n, int h, int w, int out_h, int out_w,
+                                 int quality_filter, uint8_t* out, int64_t* n_kept, uint8_t* keep, int64_t* sums) {
+    return postprocess("vq_frame_postprocess_u8_list", r, frames, nullptr, n, h, w, out_h, out_w, quality_filter, out, n_kept, keep, sums);
+}
+
+int vq_frame_postprocess_u8(vq_resampler* r, const uint8_t* frames, int n, int h, int w, int on_device, int out_h, int out_w,
+                            int quality_filter, uint8_t* out, int64_t* n_kept, uint8_t* keep, int64_t* sums) {
+    if (on_device)
+        return postprocess("vq_frame_postprocess_u8", r, nullptr, frames, n, h, w, out_h, out_w, quality_filter, out, n_kept, keep, sums);
+    VQ_CHECK(n >= 0 && n <= 65535 && h > 0 && w > 0 && (n == 0 || frames), "vq_frame_postprocess_u8: bad argument (at most 65535 frames per call)");
+    std::vector<const uint8_t*> ptrs((size_t)n);
+    for (int i = 0; i < n; ++i) ptrs[i] = frames + (size_t)i * h * w * 3;
+    return postprocess("vq_frame_postprocess_u8", r, n ? ptrs.data() : nullptr, nullptr, n, h, w, out_h, out_w, quality_filter, out, n_kept, keep, sums);
 }
 
 }  // extern "C"

@@ -9,6 +9,8 @@ frame-quality statistics of the reference's frame extractor, over ``vq_resampler
     src/core/frame_extractor.py:283-284 (OpenCV INTER_LINEAR; parity unpinned);
   * :meth:`FramePreprocessor.quality` / :meth:`is_low_quality` — reference
     src/core/frame_extractor.py:301-316;
+  * :meth:`FramePreprocessor.postprocess` — resize, quality verdict and compaction of a batch in one device pass
+    (``vq_frame_postprocess_u8``): the per-frame loop of reference src/core/frame_extractor.py:279-293;
   * :meth:`FramePreprocessor.scene_change_scores` — ``AdaptiveFrameSampler._calculate_frame_difference`` of
     reference src/core/frame_extractor.py:168-186 for every consecutive pair of a batch (the samplers on top of
     it: :mod:`video_quierer_amd.core.frame_extractor`).
@@ -26,6 +28,7 @@ CV_LINEAR = 100                     # cv2.resize's default INTER_LINEAR (VQ_RESA
 # geometry of the scene-change pass (csrc/preproc_kernels.h SC_CHUNK_FRAMES / SC_TILE; tests read both and compare)
 SCENE_CHUNK_FRAMES = 8              # frames one workgroup walks
 SCENE_TILE_PIXELS = 8192            # pixels one workgroup owns
+POSTPROCESS_MAX_PIXELS = 1 << 21    # out_h * out_w the integer quality verdict is proven for (PP_MAX_PIXELS)
 
 
 def clip_processor_geometry(h: int, w: int, size: int = 224, crop: int = 224) -> Tuple[int, int, int, int]:
@@ -34,6 +37,29 @@ def clip_processor_geometry(h: int, w: int, size: int = 224, crop: int = 224) ->
     _lib.check(_lib.load().vq_clip_processor_geometry(int(h), int(w), int(size), int(crop), ctypes.byref(rh),
                                                       ctypes.byref(rw), ctypes.byref(top), ctypes.byref(left)))
     return rh.value, rw.value, top.value, left.value
+
+
+def postprocess_plan(out_h: int, out_w: int) -> Tuple[int, int, bool]:
+    """(band_rows, n_bands, fused) of the post-processing pass for an out_h x out_w output; needs no device."""
+    rows, bands, fused = c_int(), c_int(), c_int()
+    _lib.check(_lib.load().vq_frame_postprocess_plan(int(out_h), int(out_w), ctypes.byref(rows), ctypes.byref(bands),
+                                                     ctypes.byref(fused)))
+    return rows.value, bands.value, bool(fused.value)
+
+
+def postprocess_size(h: int, w: int, frame_size, always_resize: bool = False) -> Tuple[int, int]:
+    """(out_h, out_w) of the reference's resize step for an h x w frame (frame_extractor.py:283-284): no resize for
+    ``frame_size`` None or — the reference's quirk — when ``(h, w) == tuple(frame_size)``; otherwise
+    ``cv2.resize(frame, frame_size)``, whose dsize is (WIDTH, HEIGHT).  ``always_resize``: the generator's form
+    (:342-343), which resizes whenever ``frame_size`` is set."""
+    if frame_size is None or not tuple(frame_size):
+        return int(h), int(w)
+    fw, fh = int(frame_size[0]), int(frame_size[1])
+    if fw <= 0 or fh <= 0:
+        raise ValueError(f"frame_size must be positive, got {tuple(frame_size)}")
+    if not always_resize and (int(h), int(w)) == (fw, fh):
+        return int(h), int(w)
+    return fh, fw
 
 
 def _frames(frames) -> np.ndarray:
@@ -153,6 +179,58 @@ class FramePreprocessor:
         blurry (Laplacian variance < 100)."""
         mean, var = self.quality(frames)
         return (mean < 20) | (mean > 235) | (var < 100)
+
+    # -- resize + quality filter + compaction in one pass ----------------------
+    def postprocess(self, frames, frame_size=(224, 224), quality_filter: bool = True, keep_on_device: bool = False,
+                    always_resize: bool = False):
+        """What ``OptimizedFrameExtractor.extract_frames`` does to each sampled frame (reference
+        frame_extractor.py:279-293), for a batch of BGR uint8 frames [n, h, w, 3] in one device pass: the resize of
+        :func:`postprocess_size`, the low-quality verdict of :meth:`is_low_quality` on the resized frame, survivors
+        compacted in input order.  → (kept frames uint8 [n_kept, out_h, out_w, 3], keep bool[n], sums int64[n, 3] =
+        {sum of bytes, sum L, sum L^2} of each resized frame).  With ``keep_on_device`` the first element is the
+        device address of the kept frames instead (valid until the next call on this object)."""
+        a = _frames(frames)
+        n, h, w = a.shape[:3]
+        return self._post(lambda lib, *rest: lib.vq_frame_postprocess_u8(self._h, a.ctypes.data_as(c_void_p), n, h, w, 0, *rest),
+                          n, h, w, frame_size, quality_filter, keep_on_device, always_resize)
+
+    def postprocess_list(self, frames, frame_size=(224, 224), quality_filter: bool = True, keep_on_device: bool = False,
+                         always_resize: bool = False):
+        """:meth:`postprocess` for a list of separately allocated uint8 [h, w, 3] frames of one size (what sampler
+        records hold; no stacking copy)."""
+        arrs = [np.ascontiguousarray(f) for f in frames]
+        if not arrs:
+            return np.empty((0, 0, 0, 3), np.uint8), np.zeros(0, bool), np.zeros((0, 3), np.int64)
+        h, w = arrs[0].shape[:2]
+        for f in arrs:
+            if f.dtype != np.uint8 or f.shape != (h, w, 3):
+                raise ValueError(f"expected uint8 frames of one shape ({h}, {w}, 3), got {f.dtype} {f.shape}")
+        ptrs = (c_void_p * len(arrs))(*[f.ctypes.data for f in arrs])
+        return self._post(lambda lib, *rest: lib.vq_frame_postprocess_u8_list(self._h, ptrs, len(arrs), h, w, *rest),
+                          len(arrs), h, w, frame_size, quality_filter, keep_on_device, always_resize)
+
+    def postprocess_device(self, ptr: int, n: int, h: int, w: int, frame_size=(224, 224), quality_filter: bool = True,
+                           keep_on_device: bool = True, always_resize: bool = False):
+        """:meth:`postprocess` over device-resident frames [n, h, w, 3] at ``ptr`` (any alignment)."""
+        n, h, w = int(n), int(h), int(w)
+        return self._post(lambda lib, *rest: lib.vq_frame_postprocess_u8(self._h, c_void_p(ptr), n, h, w, 1, *rest),
+                          n, h, w, frame_size, quality_filter, keep_on_device, always_resize)
+
+    def _post(self, call, n, h, w, frame_size, quality_filter, keep_on_device, always_resize):
+        if h <= 0 or w <= 0:
+            raise ValueError(f"frames must not be empty, got {h} x {w}")
+        out_h, out_w = postprocess_size(h, w, frame_size, always_resize)
+        resized = frame_size is not None and bool(tuple(frame_size))      # None: out 0 x 0, "the frames as given"
+        out = None if keep_on_device else np.empty((n, out_h, out_w, 3), np.uint8)
+        keep, sums, kept = np.zeros(n, np.uint8), np.zeros((n, 3), np.int64), c_int64(0)
+        _lib.check(call(_lib.load(), out_h if resized else 0, out_w if resized else 0, 1 if quality_filter else 0,
+                        out.ctypes.data_as(c_void_p) if out is not None else None, ctypes.byref(kept),
+                        keep.ctypes.data_as(c_void_p), sums.ctypes.data_as(c_void_p)))
+        if out is not None:
+            return out[:kept.value], keep.astype(bool), sums
+        ptr = c_void_p()
+        _lib.check(_lib.load().vq_resampler_device_output(self._h, ctypes.byref(ptr), None))
+        return ptr.value, keep.astype(bool), sums
 
     # -- scene-change score ---------------------------------------------------
     def scene_change_scores(self, frames, prev=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
