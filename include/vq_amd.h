@@ -366,6 +366,41 @@ int vq_index_search_set_device(vq_index* idx, const void* d_queries_f32, int m, 
                                const int32_t* groups, int32_t n_sel, int exclude,
                                void* d_groups_i32, void* d_dist_f32, void* d_match_rows_i32 /*or NULL*/);
 
+/* Distinct-moment search: the k best rows such that two results of the same group (video) lie at least min_gap positions
+ * apart — "the three places in this lecture where the whiteboard is shown".  Between the plain search (one moment k times)
+ * and the grouped search (one row per video).
+ *   vq_index_set_positions: pos_of_row [n], one int32 per row of the caller's choosing (a frame ordinal, a timestamp in ms); it
+ *   need not be monotone in row order and may repeat.  n = the current size; n = 0 clears the positions.  Lifetime: after
+ *   vq_index_add* a distinct search is refused (VQ_ERR_INVALID) until the positions are set again; vq_index_update_rows keeps
+ *   them; vq_index_clear drops them; vq_index_remove_rows DROPS them too (they are not compacted: set them again).
+ *   Synchronous.
+ *   vq_index_search_distinct: let L be the exhaustive list of all rows in vq_index_search's order ((dist, row), or (dist, id
+ *   rank) once ranks are set).  Walk L and keep a row unless an already kept row of the SAME group (vq_index_set_groups) lies
+ *   at |position difference| < min_gap (min_gap >= 0; the difference is taken in 64-bit).  ids / dist [nq][k] are the first k
+ *   kept rows (row numbers) and their distances in L's order; unused slots are -1 / +inf.  min_gap = 0 is exactly
+ *   vq_index_search; a min_gap above every position difference gives the rows and distances of vq_index_search_grouped.
+ *   Limits: 1 <= k <= 1024, min_gap >= 0.  Stale or missing labels, positions or id ranks are refused before any work is queued.
+ *   How it runs: the plain search fetches a prefix of L of depth D per query and one wave per query walks it; greedy over a
+ *   prefix keeps exactly the kept rows among it, so k kept rows (or D = size) prove the answer.  Queries left short are redone
+ *   exactly on the device: fp64-chain distances to all rows, a per-(query, group) greedy walk that gives +inf to every row of
+ *   the group it does not keep, then the exact path's selection; sliced so that the distances stay within 512 MiB.  The
+ *   launches queued depend on the shapes only.
+ *   Depth rule: D = max(64, 4 k), capped by the size and by the producer's k limit (fp16 scan: 100, exact selection: 1024);
+ *   D = k when min_gap = 0 or k = 1.  $VQ_AMD_DISTINCT_DEPTH (tests only, read per call) replaces the rule, under the same caps.
+ *   mode is vq_index_search's and chooses only the producer of the prefix (0: the fp16 scan from 16,384 rows); the answer is
+ *   bit-identical in every mode.  The _device form takes device pointers, is asynchronous on the index's stream and reads
+ *   nothing back.  vq_index_last_search_stats afterwards: [0] queries proven on the prefix, [1] prefix entries walked (summed
+ *   over queries), [2] queries answered by the exact path.
+ *   vq_debug_distinct_plan (host only, as vq_debug_scan_plan): the depth D a call of this shape fetches, the producer (0 exact
+ *   distances + selection, 1 fp16 scan) and the number of redo slices it queues. */
+int vq_index_set_positions(vq_index* idx, const int32_t* pos_of_row, int64_t n);
+int vq_index_search_distinct(vq_index* idx, const float* queries, int nq, int k, int mode, int64_t min_gap,
+                             int32_t* ids, float* dist);
+int vq_index_search_distinct_device(vq_index* idx, const void* d_queries_f32, int nq, int k, int mode, int64_t min_gap,
+                                    void* d_ids_i32, void* d_dist_f32);
+int vq_debug_distinct_plan(int64_t n, int nq, int k, int64_t min_gap, int mode,
+                           int64_t* depth, int* producer, int* redo_slices);
+
 /* save / load support (hnsw.py:306-380): the stored (normalised) rows. */
 int vq_index_export(vq_index* idx, float* rows /*[size][dim]*/);
 /* Single stored rows (the reference reads `self.data[node_id]`, a dict lookup): out [n][dim] = rows row_numbers[0..n). */

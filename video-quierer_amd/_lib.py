@@ -129,6 +129,10 @@ SIGNATURES = {
     "vq_index_search_grouped": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32),
                                         POINTER(c_float)]),
     "vq_index_search_grouped_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vq_index_set_positions": (c_int, [c_void_p, POINTER(c_int32), c_int64]),
+    "vq_index_search_distinct": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, c_int64, POINTER(c_int32), POINTER(c_float)]),
+    "vq_index_search_distinct_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p]),
+    "vq_debug_distinct_plan": (c_int, [c_int64, c_int, c_int, c_int64, c_int, POINTER(c_int64), POINTER(c_int), POINTER(c_int)]),
     "vq_index_search_filtered": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, POINTER(c_int32), c_int32, c_int,
                                          POINTER(c_int32), POINTER(c_float)]),
     "vq_index_search_filtered_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_int32, c_int, c_void_p,

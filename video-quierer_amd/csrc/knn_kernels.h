@@ -266,7 +266,9 @@ constexpr int SEL_SMALL_MAX_N = 32768;
 constexpr int SEL_SMALL_LIST = 1024;
 __global__ __launch_bounds__(256)
 void select_small_kernel(const float* __restrict__ dist, int64_t ld, int64_t n, int k,
-                         int32_t* __restrict__ ids, float* __restrict__ out_dist, const TieOrder tie) {
+                         int32_t* __restrict__ ids, float* __restrict__ out_dist, const TieOrder tie,
+                         const unsigned long long* __restrict__ live = nullptr, int live_base = 0) {
+    if (live && (int)blockIdx.x + live_base >= (int)*live) return;        // distinct search: the slot is not filed (knn_distinct.h)
     __shared__ uint64_t mins[256];
     __shared__ uint64_t list[SEL_SMALL_LIST];
     __shared__ uint64_t red[4];
@@ -364,7 +366,9 @@ void select_small_kernel(const float* __restrict__ dist, int64_t ld, int64_t n, 
 
 __global__ __launch_bounds__(256)
 void select_chunk_kernel(const float* __restrict__ dist, int64_t ld, int64_t n, int k, int nchunks,
-                         uint64_t* __restrict__ partial /*[q][nchunks][k]*/, const TieOrder tie) {
+                         uint64_t* __restrict__ partial /*[q][nchunks][k]*/, const TieOrder tie,
+                         const unsigned long long* __restrict__ live = nullptr, int live_base = 0) {
+    if (live && (int)blockIdx.x + live_base >= (int)*live) return;        // distinct search: the slot is not filed (knn_distinct.h)
     __shared__ uint64_t red[4];
     const int q = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x;
     const float* d = dist + (int64_t)q * ld;
@@ -394,7 +398,9 @@ void select_chunk_kernel(const float* __restrict__ dist, int64_t ld, int64_t n, 
 
 __global__ __launch_bounds__(256)
 void merge_topk_kernel(const uint64_t* __restrict__ partial, int nchunks, int k,
-                       int32_t* __restrict__ ids, float* __restrict__ out_dist, const TieOrder tie) {
+                       int32_t* __restrict__ ids, float* __restrict__ out_dist, const TieOrder tie,
+                       const unsigned long long* __restrict__ live = nullptr, int live_base = 0) {
+    if (live && (int)blockIdx.x + live_base >= (int)*live) return;        // distinct search: the slot is not filed (knn_distinct.h)
     __shared__ uint64_t red[4];
     const int q = blockIdx.x, tid = threadIdx.x;
     const uint64_t* p = partial + (int64_t)q * nchunks * k;

@@ -11,6 +11,7 @@
 #include "knn_remove.h"
 #include "knn_filter.h"
 #include "knn_set.h"
+#include "knn_distinct.h"
 #include "scan_plan.h"
 #ifdef VQ_SCAN_EXPERIMENTS      // `make EXPERIMENTS=1`: the two superseded batch mainloops behind VQ_AMD_SCAN=2|4
 #include "experiments/scan_experiments.h"
@@ -42,6 +43,7 @@ constexpr bool SCAN_EXPERIMENTS_BUILD = false;
 static_assert(SP_STREAM_ROWS == SCAN_STREAM_ROWS && SP_TILE128_QT == SCAN_QT && SP_TILE128_RANGE == SCAN_RANGE && SP_BATCH_QT == SCAN2_QT &&
               SP_BATCH_RANGE == SCAN2_RANGE && SP_STREAM_QB == SCAN3_QB && SP_STREAM_FUSED_MAX_Q == SCAN3_FUSED_MAX_Q && SP_STREAM_MAX_Q == SCAN3_MAX_Q,
               "scan_plan.h: scan geometry");
+static_assert(DST_FP16_MAX_K == RV_K_MAX && DST_MAX_DEPTH == 1024, "knn_distinct.h: the producers' k limits");
 static_assert(SP_PHASE4_LDS == G2_LDS_BYTES && SP_FOLD_LDS == SCAN5_LDS_BYTES, "scan_plan.h: scan LDS bytes");
 static_assert(SP_K_SMALL == RV_K_SMALL && SP_K_SMALL64 == RV_K_SMALL64 && SP_K_MID == RV_K_MID && SP_BATCH8_QPW == RV_QPW && SP_LARGE_QPW == RVL_QPW &&
               SP_LARGE_QPW == RVX_QPW && SP_SMALL32_C == RV_C && SP_SMALL64_C == 64, "scan_plan.h: re-score geometry");
@@ -158,6 +160,13 @@ struct vq_index {
     DevBuf<uint64_t> d_gpart;
     DevBuf<unsigned long long> d_gcounters; PinnedBuf<unsigned long long> h_gcounters;
     DevBuf<int32_t> d_gout;        // vq_index_search_grouped: device results [3][nq][k]
+    // positions (vq_index_set_positions): one int32 per row; pos_n = the rows they cover (0 = none set).  A distinct search with
+    // pos_n != size is refused.  Distinct-search scratch (knn_distinct.h): the plain search's answer at the plan's depth
+    // (ids | distances), the filed queries' slot list, the redo's selection (ids | distances); its counters are d_gcounters
+    DevBuf<int32_t> d_pos; int64_t pos_n = 0;
+    DevBuf<int32_t> d_dpre;
+    DevBuf<int32_t> d_dslots;
+    DevBuf<int32_t> d_dsel;
     // clip-search scratch (knn_set.h): per-group sums [2][G], candidate list / positions [2][G] + count + flag, |q_i| [m],
     // order keys [G] + the selection's block lists, candidate keys, result staging of the host form
     DevBuf<double> d_ssum;
@@ -324,8 +333,14 @@ int check_labels(const vq_index* x, const char* fn) {
              "the index holds %lld (call vq_index_set_groups after adding rows)", fn, (long long)x->group_n, (long long)x->size);
     return 0;
 }
+int check_positions(const vq_index* x, const char* fn) {
+    VQ_CHECK(x->pos_n == x->size, "%s: the positions cover %lld rows, the index holds %lld (call vq_index_set_positions after "
+             "adding or removing rows)", fn, (long long)x->pos_n, (long long)x->size);
+    return 0;
+}
 // mode 0 (auto): the fp16 scans pay once the matrix is large enough to amortise their fixed costs
 constexpr int64_t FP16_AUTO_MIN_ROWS = 16384;
+static_assert(DST_FP16_MIN_ROWS == FP16_AUTO_MIN_ROWS, "knn_distinct.h: the auto mode's threshold");
 
 void fill_no_result(vq_index* x, int32_t* ids, float* dist, int64_t count) {
     hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, ids, dist, count);
@@ -378,10 +393,10 @@ int exact_topk(vq_index* x, int64_t m, int nq, int k, bool one_wg, const TieOrde
         VQ_TRY(dist(q0, cur, ld));
         Prof p(x, I_SELECT);
         if (one_wg) {
-            hipLaunchKernelGGL(select_small_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_dist, ld, m, k, ids0, out0, tie);
+            hipLaunchKernelGGL(select_small_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_dist, ld, m, k, ids0, out0, tie, nullptr, 0);
         } else {
-            hipLaunchKernelGGL(select_chunk_kernel, dim3(cur, nchunks), dim3(256), 0, x->stream, x->d_dist, ld, m, k, nchunks, x->d_partial, tie);
-            hipLaunchKernelGGL(merge_topk_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_partial, nchunks, k, ids0, out0, tie);
+            hipLaunchKernelGGL(select_chunk_kernel, dim3(cur, nchunks), dim3(256), 0, x->stream, x->d_dist, ld, m, k, nchunks, x->d_partial, tie, nullptr, 0);
+            hipLaunchKernelGGL(merge_topk_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_partial, nchunks, k, ids0, out0, tie, nullptr, 0);
         }
     }
     VQ_HIP(hipGetLastError());
@@ -716,6 +731,75 @@ int search_grouped_dispatch(vq_index* x, const float* d_queries, int nq, int k, 
     const bool use_fp16 = mode == 2 || (mode == 0 && fp16_ok && x->size >= FP16_AUTO_MIN_ROWS);       // the plain search's rule
     return use_fp16 ? search_grouped_fp16(x, d_queries, nq, k, groups, rows_out, dist)
                     : search_grouped_exact(x, d_queries, nq, k, groups, rows_out, dist);
+}
+
+// ---- distinct-moment search (knn_distinct.h) ----
+// tests only, read per call: a prefix depth that replaces the plan's rule
+int64_t distinct_depth_override() {
+    const char* e = getenv("VQ_AMD_DISTINCT_DEPTH");
+    return e ? std::max<long long>(0, atoll(e)) : 0;
+}
+
+// The plain search at the plan's depth -> the prefix walk; the queries it files are redone exactly, slice by slice: distances,
+// the per-group walk, the plain selection, the scatter.  Nothing here waits for the stream.
+int search_distinct_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode, int64_t min_gap, int32_t* d_ids, float* d_dist_out) {
+    static const char* fn = "vq_index_search_distinct";
+    VQ_TRY(check_mode(fn, mode));
+    VQ_TRY(check_ranks(x, fn));
+    VQ_TRY(check_labels(x, fn));
+    VQ_TRY(check_positions(x, fn));
+    const int64_t n = x->size, ld = round_up(n, 64);
+    const DistinctPlan p = plan_distinct(n, nq, k, min_gap, mode, distinct_depth_override());
+    const int D = (int)p.depth;
+    const bool one_wg = n <= SEL_SMALL_MAX_N;
+    const int nchunks = cdiv(n, SEL_CHUNK);
+    VQ_TRY(x->d_dpre.reserve(2 * (int64_t)nq * D));
+    VQ_TRY(x->d_dslots.reserve(nq));
+    VQ_TRY(ensure_gcounters(x));
+    if (p.slices) {
+        VQ_TRY(x->d_dist.reserve(p.slice_q * ld));
+        VQ_TRY(x->d_dsel.reserve(2 * p.slice_q * k));
+        if (!one_wg) VQ_TRY(x->d_partial.reserve(p.slice_q * nchunks * k));
+    }
+    int32_t* pre_ids = x->d_dpre;
+    float* pre_dist = (float*)(pre_ids + (int64_t)nq * D);
+    VQ_HIP(hipMemsetAsync(x->d_gcounters, 0, 3 * sizeof(unsigned long long), x->stream));
+    VQ_TRY(search_dispatch(x, d_queries, nq, D, mode, pre_ids, pre_dist));
+    {
+        Prof pr(x, I_SELECT);
+        hipLaunchKernelGGL(distinct_prefix_kernel, dim3(nq), dim3(64), 0, x->stream, pre_ids, pre_dist, D, n, k, min_gap, x->d_group, x->d_pos,
+                           d_ids, d_dist_out, x->d_dslots, x->d_gcounters);
+    }
+    const unsigned long long* cnt = x->d_gcounters;
+    const unsigned long long* filed = cnt + DST_FILED;
+    const int G = x->n_groups;
+    for (int sl = 0; sl < p.slices; ++sl) {
+        const int base = (int)(sl * p.slice_q), cap = (int)std::min<int64_t>(p.slice_q, nq - base);
+        int32_t* sel_ids = x->d_dsel;
+        float* sel_dist = (float*)(sel_ids + (int64_t)cap * k);
+        {
+            Prof pr(x, I_EXACT_DIST);
+            hipLaunchKernelGGL(distinct_dist_kernel, dim3(std::min(cdiv(n, 64), DST_DIST_GRID), cdiv(cap, 32)), dim3(256), 0, x->stream, x->rows, n, x->dim, d_queries,
+                               x->d_dslots, cnt, base, cap, x->d_dist, ld);
+        }
+        Prof pr(x, I_SELECT);
+        if (min_gap > 0)
+            hipLaunchKernelGGL(distinct_group_walk_kernel, dim3(std::max(1, std::min(cdiv(G, 4), 4096)), cap), dim3(256), 0, x->stream, x->d_dist, ld,
+                               x->d_goff, x->d_grows, G, x->d_pos, x->tie(), k, min_gap, cnt, base, cap);
+        if (one_wg) {
+            hipLaunchKernelGGL(select_small_kernel, dim3(cap), dim3(256), 0, x->stream, x->d_dist, ld, n, k, sel_ids, sel_dist, x->tie(), filed, base);
+        } else {
+            hipLaunchKernelGGL(select_chunk_kernel, dim3(cap, nchunks), dim3(256), 0, x->stream, x->d_dist, ld, n, k, nchunks, x->d_partial, x->tie(),
+                               filed, base);
+            hipLaunchKernelGGL(merge_topk_kernel, dim3(cap), dim3(256), 0, x->stream, x->d_partial, nchunks, k, sel_ids, sel_dist, x->tie(), filed, base);
+        }
+        hipLaunchKernelGGL(distinct_scatter_kernel, dim3(cap), dim3(256), 0, x->stream, sel_ids, sel_dist, k, x->d_dslots, cnt, base, cap, d_ids,
+                           d_dist_out);
+    }
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+    set_stats(x, STATS_GCOUNTERS);
+    return 0;
 }
 
 // ---- vq_index_remove_rows (knn_remove.h) ----
@@ -1131,6 +1215,13 @@ int check_set_args(const char* fn, const vq_index* x, int m, int k, const int32_
     return 0;
 }
 
+// (the arguments are judged before the library is asked for its device)
+int check_distinct_args(const char* fn, const vq_index* x, int nq, int k, int64_t min_gap, bool arrays) {
+    VQ_CHECK(k > 0 && k <= 1024, "%s: k %d outside [1, 1024]", fn, k);
+    VQ_CHECK(min_gap >= 0, "%s: min_gap %lld is negative", fn, (long long)min_gap);
+    return check_batch_args(fn, x, nq, k, arrays);
+}
+
 // a host form's answer from an empty index: no candidates (hnsw.py:243-244 returns []); b: the grouped forms' second id array, or null
 void host_empty(int64_t count, int32_t* a, int32_t* b, float* dist) {
     for (int64_t i = 0; i < count; ++i) { a[i] = -1; if (b) b[i] = -1; dist[i] = __builtin_inff(); }
@@ -1219,6 +1310,7 @@ int vq_index_clear(vq_index* x) {
     x->norm_dirty = false; x->near_unit = true; x->row_norm_max = 1.0f;
     x->rank_n = 0;
     x->group_n = 0; x->n_groups = 0; x->h_goff.clear();
+    x->pos_n = 0;
     return 0;
 }
 
@@ -1297,6 +1389,23 @@ int vq_index_set_groups(vq_index* x, const int32_t* group_of_row, int64_t n, int
     x->d_goff = x->d_group + n_pad; x->d_grows = x->d_goff + n_groups + 1; x->d_sgroup = x->d_grows + n;
     x->h_goff.assign(goff, goff + n_groups + 1);
     x->group_n = n; x->n_groups = n_groups;
+    return 0;
+}
+
+int vq_index_set_positions(vq_index* x, const int32_t* pos_of_row, int64_t n) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && n >= 0 && (n == 0 || pos_of_row), "vq_index_set_positions: bad argument");
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (n == 0) { x->pos_n = 0; return 0; }
+    VQ_CHECK(n == x->size, "vq_index_set_positions: %lld positions for an index of %lld rows", (long long)n, (long long)x->size);
+    if (n > x->d_pos.cap) {
+        VQ_HIP(hipStreamSynchronize(x->stream));                   // a search in flight may still read the old array
+        x->pos_n = 0;
+        VQ_TRY(x->d_pos.reserve(round_up(std::max<int64_t>(n, x->cap), 1024)));
+    }
+    VQ_HIP(hipMemcpyAsync(x->d_pos, pos_of_row, (size_t)n * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));                       // `pos_of_row` is the caller's
+    x->pos_n = n;
     return 0;
 }
 
@@ -1477,6 +1586,7 @@ int vq_index_remove_rows(vq_index* x, const int64_t* row_numbers, int64_t n) {
     }
     // the |row|^2 range stays as it is: it still covers every survivor (conservative, as in vq_index_update_rows)
     x->size = n_new;
+    x->pos_n = 0;                                  // positions are not compacted: set them again
     VQ_HIP(hipStreamSynchronize(x->stream));
     return 0;
 }
@@ -1552,6 +1662,39 @@ int vq_index_search_grouped(vq_index* x, const float* queries, int nq, int k, in
     VQ_HIP(hipMemcpyAsync(rows, d_r, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
     VQ_HIP(hipMemcpyAsync(dist, d_d, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
     VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+int vq_index_search_distinct_device(vq_index* x, const void* d_queries, int nq, int k, int mode, int64_t min_gap, void* d_ids, void* d_dist) {
+    VQ_TRY(check_distinct_args("vq_index_search_distinct_device", x, nq, k, min_gap, d_queries && d_ids && d_dist));
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_ids, nullptr, (float*)d_dist);
+    return search_distinct_dispatch(x, (const float*)d_queries, nq, k, mode, min_gap, (int32_t*)d_ids, (float*)d_dist);
+}
+
+int vq_index_search_distinct(vq_index* x, const float* queries, int nq, int k, int mode, int64_t min_gap, int32_t* ids, float* dist) {
+    VQ_TRY(check_distinct_args("vq_index_search_distinct", x, nq, k, min_gap, queries && ids && dist));
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    if (x->size == 0) { host_empty(count, ids, nullptr, dist); return 0; }
+    VQ_TRY(x->d_q.reserve((int64_t)nq * x->dim));
+    VQ_TRY(reserve_id_dist(x, count));
+    VQ_HIP(hipMemcpyAsync(x->d_q, queries, (size_t)nq * x->dim * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_TRY(search_distinct_dispatch(x, x->d_q, nq, k, mode, min_gap, x->d_ids, x->d_out));
+    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// plan_distinct's answer for this process's environment; needs no device
+int vq_debug_distinct_plan(int64_t n, int nq, int k, int64_t min_gap, int mode, int64_t* depth, int* producer, int* redo_slices) {
+    VQ_CHECK(depth && producer && redo_slices && n >= 1 && n < ((int64_t)1 << 31) && nq >= 1 && k >= 1 && k <= 1024 && min_gap >= 0 &&
+             mode >= 0 && mode <= 2, "vq_debug_distinct_plan: takes 1 <= n < 2^31, nq >= 1, 1 <= k <= 1024, min_gap >= 0, mode 0..2");
+    const DistinctPlan p = plan_distinct(n, nq, k, min_gap, mode, distinct_depth_override());
+    *depth = p.depth; *producer = p.producer; *redo_slices = p.slices;
     return 0;
 }
 

@@ -40,6 +40,46 @@ def video_of(node_id: Hashable) -> Hashable:
     return node_id.rsplit("_", 1)[0] if isinstance(node_id, str) else node_id
 
 
+def frame_of(node_id: Hashable) -> int:
+    """The default position of a node id for ``search_distinct``: the integer after the LAST underscore of a string id (the
+    reference caller's ``f"{video_id}_{i}"``), or an int id itself.  Anything else is a ``ValueError`` naming the id."""
+    if isinstance(node_id, (int, np.integer)) and not isinstance(node_id, bool):
+        return int(node_id)
+    if isinstance(node_id, str) and "_" in node_id:
+        try:
+            return int(node_id.rsplit("_", 1)[1])
+        except ValueError:
+            pass
+    raise ValueError(f"frame_of: id {node_id!r} carries no frame number (pass position_of=)")
+
+
+class _Positions:
+    """int32 positions of the rows for ``vq_index_set_positions``, kept like ``_GroupLabels``: only rows added since the last
+    call are mapped, the first distinct search after an add or a removal uploads them; a different ``position_of`` (or a
+    reloaded index) maps everything again.  Derived state: never saved."""
+
+    def __init__(self, position_of: Callable[[Hashable], int], ids: List[Hashable]):
+        self.position_of, self.ids = position_of, ids
+        self.values = np.empty(0, dtype=np.int32)
+        self.uploaded = -1                        # rows the device positions cover
+
+    def extend(self) -> bool:
+        """Map the rows added since the last call; True when the device positions are stale."""
+        n = len(self.ids)
+        if len(self.values) < n:
+            fn = self.position_of
+            new = np.array([int(fn(nid)) for nid in self.ids[len(self.values):]], dtype=np.int64)
+            if len(new) and (new.min() < -2 ** 31 or new.max() >= 2 ** 31):
+                raise ValueError("positions must fit a 32-bit signed integer")
+            self.values = np.concatenate([self.values, new.astype(np.int32)])
+        return self.uploaded != n
+
+    def compact(self, keep: np.ndarray) -> None:
+        """The positions of the surviving rows; vq_index_remove_rows drops the device's, so an upload is due."""
+        self.values = self.values[keep]
+        self.uploaded = -1
+
+
 class _GroupLabels:
     """Dense int labels of the rows for ``vq_index_set_groups``, kept like the tie order: group keys are mapped to ints
     incrementally (only rows added since the last upload are labelled), uploaded by the first grouped search after an add;
@@ -385,6 +425,11 @@ class HNSWIndex:
             gl = None                                            # labels of a replaced id list: relabelled on next use
         if gl is not None:
             gl.extend()                                          # host labels for every row (no upload)
+        ps = getattr(self, "_positions", None)
+        if ps is not None and ps.ids is not ids:
+            ps = self._positions = None
+        if ps is not None:
+            ps.extend()
         current = gl is not None and gl.uploaded == n
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         _lib.check(_lib.load().vq_index_remove_rows(self._h, rows.ctypes.data_as(POINTER(c_int64)), m))
@@ -404,6 +449,8 @@ class HNSWIndex:
         self.entry_point = ids[0] if ids else None
         if gl is not None:
             gl.compact(keep, current)
+        if ps is not None:
+            ps.compact(keep)
         return m
 
     # -- query --------------------------------------------------------------------
@@ -562,6 +609,74 @@ class HNSWIndex:
             return [[] for _ in queries]
         with self.lock:
             return self._grouped_many(queries, k, group_of, flt)
+
+    # -- distinct moments: the k best rows, two of one group at least min_gap positions apart ------------
+    def _sync_positions(self, position_of: Optional[Callable[[Hashable], int]]) -> _Positions:
+        fn = frame_of if position_of is None else position_of
+        ps = getattr(self, "_positions", None)
+        if ps is None or ps.position_of is not fn or ps.ids is not self._ids or len(ps.values) > len(self._ids):
+            ps = self._positions = _Positions(fn, self._ids)
+        if ps.extend():
+            n = len(ps.values)
+            _lib.check(_lib.load().vq_index_set_positions(self._h, ps.values.ctypes.data_as(POINTER(c_int32)), n))
+            ps.uploaded = n
+        return ps
+
+    def _distinct_many(self, queries: Sequence[np.ndarray], k: int, min_gap: int, group_of, position_of) -> List[List[Dict]]:
+        min_gap = int(min_gap)
+        if min_gap < 0:
+            raise ValueError(f"min_gap must be >= 0, got {min_gap}")
+        return self._distinct_unit(np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32), k, min_gap, group_of, position_of)
+
+    def _distinct_unit(self, unit: np.ndarray, k: int, min_gap: int, group_of, position_of) -> List[List[Dict]]:
+        """unit: [nq][dim] fp32 queries, used as given (SimpleVideoIndex normalises by its own rule)."""
+        if unit.shape[1] != self.dimension:
+            raise ValueError(f"query dimension {unit.shape[1]} != index dimension {self.dimension}")
+        kk = min(int(k), len(self._ids))
+        if kk <= 0:
+            return [[] for _ in unit]
+        if not self._identity:
+            self._sync_tie_order()
+        gl = self._sync_groups(group_of)
+        ps = self._sync_positions(position_of)
+        nq = unit.shape[0]
+        rows = np.empty((nq, kk), dtype=np.int32)
+        dist = np.empty((nq, kk), dtype=np.float32)
+        _lib.check(_lib.load().vq_index_search_distinct(self._h, _lib.fptr(unit), nq, kk, int(self.search_mode), min_gap,
+                                                        rows.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist)))
+        keys, labels, pos, names, identity = gl.keys, gl.labels, ps.values, self._ids, self._identity
+        return [[{"id": int(r) if identity else names[r], "group": keys[labels[r]], "position": int(pos[r]), "distance": d,
+                  "score": np.float32(1.0) - d} for r, d in zip(rr.tolist(), rd) if r >= 0]
+                for rr, rd in zip(rows, dist)]
+
+    def search_distinct(self, query: np.ndarray, k: int = 5, min_gap: int = 1, *,
+                        group_of: Optional[Callable[[Hashable], Hashable]] = None,
+                        position_of: Optional[Callable[[Hashable], int]] = None) -> List[Dict]:
+        """The k best distinct MOMENTS for one query: ``[{'id', 'group', 'position', 'distance', 'score'}]``.  Exactly the plain
+        search's exhaustive (distance, id) list, walked in order, with every row dropped that lies less than ``min_gap``
+        positions from an already kept row of the same group.  ``min_gap=0`` is ``search``; a gap above every position
+        difference is ``search_grouped``'s rows.  ``group_of`` as ``search_grouped``; ``position_of`` maps a node id to an
+        integer position that fits 32 bits (default ``frame_of``: the frame number of ``f"{video_id}_{i}"``; pass timestamps
+        in ms and a gap in ms alike) — keep passing the SAME callables, a different one maps every row again."""
+        if self.entry_point is None or self.element_count == 0:
+            if int(min_gap) < 0:
+                raise ValueError(f"min_gap must be >= 0, got {min_gap}")
+            return []
+        with self.lock:
+            return self._distinct_many([query], k, min_gap, group_of, position_of)[0]
+
+    def search_distinct_batch(self, queries: List[np.ndarray], k: int = 5, min_gap: int = 1, *,
+                              group_of: Optional[Callable[[Hashable], Hashable]] = None,
+                              position_of: Optional[Callable[[Hashable], int]] = None) -> List[List[Dict]]:
+        """``search_distinct`` for a batch of queries, one device pass."""
+        if int(min_gap) < 0:
+            raise ValueError(f"min_gap must be >= 0, got {min_gap}")
+        if len(queries) == 0:
+            return []
+        if self.entry_point is None or self.element_count == 0:
+            return [[] for _ in queries]
+        with self.lock:
+            return self._distinct_many(queries, k, min_gap, group_of, position_of)
 
     # -- filtered query: the plain search within, or excluding, a set of groups (videos) -------------
     @staticmethod

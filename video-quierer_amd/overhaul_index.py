@@ -17,12 +17,14 @@ to the GPU lazily, at the first search after an add.
 from __future__ import annotations
 
 import logging
+import math
 import pickle
 from pathlib import Path
 from typing import Dict, List
 
 import numpy as np
 
+from video_quierer_amd import _lib
 from video_quierer_amd.indexes.hnsw import MODE_AUTO, HNSWIndex
 
 logger = logging.getLogger(__name__)
@@ -51,7 +53,6 @@ class SimpleVideoIndex:
         block = np.ascontiguousarray(np.vstack(self.embeddings[self._pushed:]), dtype=np.float32)
         if self._dev is None:
             self._dev = HNSWIndex(dimension=block.shape[1])
-        from video_quierer_amd import _lib
         _lib.check(_lib.load().vq_index_add(self._dev._h, _lib.fptr(block), block.shape[0], 0))   # stored as given
         # ids = -frame_id: the scan's (distance, id) tie rule then yields the larger frame first,
         # like the reference's reversed argsort
@@ -60,6 +61,10 @@ class SimpleVideoIndex:
         self._dev.element_count = n
         self._dev.entry_point = 0
         self._pushed = n
+        if getattr(self, "_ranked_dev", None) is self._dev:
+            # search_moments had uploaded id ranks; they no longer cover the index, and `search` orders ties on the host
+            _lib.check(_lib.load().vq_index_set_id_ranks(self._dev._h, None, 0))
+            self._ranked_dev = None
 
     def remove_video(self, video_name: str) -> int:
         """Drop one video: its embeddings, metadata and ``video_hashes`` entry (so the next scan of the library re-processes
@@ -115,6 +120,44 @@ class SimpleVideoIndex:
 
     def _video_of_row_id(self, node_id: int) -> str:
         return self.metadata[-node_id]["video_name"]          # device ids are -position (see _sync_device)
+
+    def _timestamp_ms_of_row_id(self, node_id: int) -> int:
+        return int(round(self.metadata[-node_id]["timestamp"] * 1000))
+
+    def search_moments(self, query_embedding: np.ndarray, k: int = 5, min_gap_s: float = 2.0) -> List[Dict]:
+        """The k best distinct moments: ``search``'s exhaustive list (the same normalisation, scores and tie order), walked in
+        order, with every frame dropped that lies less than ``min_gap_s`` seconds from an already kept frame of the same video
+        (``HNSWIndex.search_distinct``: exact).  Positions are ``round(timestamp * 1000)`` ms, the gap ``ceil(min_gap_s *
+        1000)`` ms, groups the video names.  Results are ``search``'s dicts ``{'video_name', 'timestamp', 'frame_id', 'score'}``."""
+        if min_gap_s < 0:
+            raise ValueError(f"min_gap_s must be >= 0, got {min_gap_s}")
+        if not self.embeddings:
+            return []
+        self._sync_device()
+        q = np.asarray(query_embedding)
+        query_norm = (q / (np.linalg.norm(q) + 1e-10)).astype(np.float32)          # reference :50-51
+        dev = self._dev
+        dev.search_mode = MODE_AUTO
+        if getattr(self, "_ranked_dev", None) is not dev:       # (a reloaded or rebuilt index is another device matrix)
+            # ids are -position, so the id order puts the LARGER frame first, as `search` does; the device needs it as ranks here
+            # (the greedy walk runs there).  Removal keeps them (a stable compaction), an add clears them (_sync_device).
+            dev._tie_order = "stale"
+            dev._sync_tie_order()
+            self._ranked_dev = dev
+        gfn = getattr(self, "_group_fn", None)
+        if gfn is None:
+            gfn = self._group_fn = self._video_of_row_id
+        pfn = getattr(self, "_pos_fn", None)
+        if pfn is None:
+            pfn = self._pos_fn = self._timestamp_ms_of_row_id
+        with dev.lock:                                # the query as normalised above, not normalised again
+            res = dev._distinct_unit(np.ascontiguousarray(query_norm[None, :]), k, int(math.ceil(min_gap_s * 1000)), gfn, pfn)[0]
+        results = []
+        for r in res:
+            md = self.metadata[-r["id"]].copy()
+            md["score"] = float(r["score"])
+            results.append(md)
+        return results
 
     def similar_videos(self, video_name: str, k: int = 5) -> List[Dict]:
         """The k indexed videos most similar to ``video_name``, itself excluded: ``[{'video_name', 'score'}]``, best first.
