@@ -9,14 +9,19 @@ that table from one run.
 
 The second test does the same for the DEFAULT pass, which holds the residual stream between its residual epilogues as
 fp16 + one fp8 byte (debug_keep_stream: a layer-limited pass then runs its blocks exactly as the full pass does; the low
-bytes are read back raw and decoded here).  profiles/encoder_stages/ratios_split.txt is its table."""
-import ctypes
+bytes are read back raw and decoded here).  profiles/encoder_stages/ratios_split.txt is its table.
+
+The bodies of both live in tests/encoder_stage_run.py.  Every case also repeats its last layer-limited pass twice and wants
+the same bits.  Cases that name a GEMM kernel for q|k|v and fc1 (_multi_cases, _split_multi_cases: the multi-tile 256x256
+kernel gemm_tn256dm under the LayerNorm-consuming epilogues, the deep kernel under the split residual epilogue on many tile
+rows, the benchmark's own dispatch at n = 220) first ask vq_debug_gemm_plan and fail if the dispatch gives them another;
+tests/test_gemm_plan_cpu.py pins the same plans without a GPU.  The third test forces the tiles per multi-tile workgroup,
+which takes a fresh process per count."""
 import os
 
-import numpy as np
 import pytest
 
-import encoder_stage_ref as R
+import encoder_stage_run as S
 from video_quierer_amd.weights import TextConfig, VitConfig
 
 pytestmark = pytest.mark.gpu
@@ -56,66 +61,42 @@ def _cases():
     return out
 
 
-def _record(tag, ratios, table=None):
-    lines = [f"{tag:44s} {stage}{layer:<2d} {r:.4g}" for (stage, layer), r in ratios.items()]
-    print("\n".join(lines))
-    path = os.environ.get("VQ_STAGE_RATIOS_OUT")
-    if path and table:                                      # a second table next to the first
-        path = os.path.join(os.path.dirname(path), table)
-    if path:
-        with open(path, "a") as f:
-            f.write("\n".join(lines) + "\n")
+def _old(case, n_new):
+    """A case from before the trailing parameters existed: they are None, and the id is the one `ids=str` gave it."""
+    return pytest.param(*case, *(None,) * n_new, id="-".join(str(v) for v in case))
 
 
-def _read(enc, rows, names):
-    return {nm: enc.debug_read(nm, rows) for nm in names}
+def _multi_cases():
+    """(geometry, form, type, fixture, batch, concurrent, $VQ_AMD_GEMM, {GEMM: (kernel, tiles per workgroup)}): the LayerNorm-consuming
+    GEMMs on gemm_tn256dm.  Id 15 gives them that kernel once the shape tiles by 256 with tiles_n % 3 == 0 and >= 128 tiles.
+    t50: hidden 768, q|k|v 9 tiles across -> 15 tile rows (135 tiles; fc1 180): n = 72, whose 3,600 rows pad to 3,840, is the
+    smallest batch that has them (n = 71 pads to 3,584: 126 tiles, the 128x128 kernel).  text512: q|k|v 6 tiles across (two
+    workgroups of three on a tile row, K = 512) -> 22 tile rows = 5,632 rows, from n = 70 (5,390 rows) on; fc1 is 8 tiles across,
+    not divisible by 3: the deep kernel with the row-stat prologue on 22 tile rows.  out_proj and fc2 (45 / 44 tiles) stay on the
+    128x128 kernel, like the patch embedding and the CLS-only GEMMs."""
+    m3 = {"qkv": (S.MULTI, 3), "fc1": (S.MULTI, 3)}
+    return [pytest.param("t50", "default", "fp16", "stress", 72, False, 15, m3, id="t50-default-fp16-stress-72-False-gemm15-qkv16x3+fc116x3"),
+            pytest.param("t50", "default", "bf16", "stress", 72, False, 15, m3, id="t50-default-bf16-stress-72-False-gemm15-qkv16x3+fc116x3"),
+            pytest.param("text512", "default", "fp16", "stress", 70, False, 15, {"qkv": (S.MULTI, 3), "fc1": (S.DEEP, 1)},
+                         id="text512-default-fp16-stress-70-False-gemm15-qkv16x3+fc18x1")]
 
 
-@pytest.mark.parametrize("geo,form,dt,kind,n,concurrent", _cases(), ids=lambda v: str(v))
-def test_every_stage_against_fp64_on_the_device_inputs(gpu_lib, monkeypatch, geo, form, dt, kind, n, concurrent):
-    from video_quierer_amd.encoder import VitEncoder
-    from video_quierer_amd.text_encoder import TextEncoder
+@pytest.mark.parametrize("geo,form,dt,kind,n,concurrent,force,ln", [_old(c, 2) for c in _cases()] + _multi_cases())
+def test_every_stage_against_fp64_on_the_device_inputs(gpu_lib, monkeypatch, geo, form, dt, kind, n, concurrent, force, ln):
+    from video_quierer_amd import _lib
     is_text = geo in TEXT_GEOMETRIES
     cfg = (TEXT_GEOMETRIES if is_text else IMAGE_GEOMETRIES)[geo][0]
-    tower = "text" if is_text else "image"
-    W = R.make_weights(tower, cfg, kind)
-    inp = R.make_input(tower, cfg, n)
-    tw = R.Tower(tower, cfg, W, dt)
+    T = cfg.max_positions if is_text else cfg.tokens
     monkeypatch.setenv("VQ_AMD_RESID", "f32")              # the product pass below keeps the fp32 x (layer-limited passes always do)
     if form != "default":
         monkeypatch.setenv("VQ_AMD_ATTN", form)
-    enc = TextEncoder(cfg, W, max_batch=n, compute_dtype=dt) if is_text else \
-        VitEncoder(cfg, W, max_batch=n, compute_dtype=dt, concurrent=concurrent)
-    run = (lambda **kw: enc.encode_ids(inp)) if is_text else (lambda swap_rb=True: enc.encode(inp, swap_rb=swap_rb))
-    rows = n * tw.T
-    tag = f"{geo} {form} {dt} {kind} rows={rows}" + (" concurrent" if concurrent else "")
-    try:
-        runs = []
-        for k in range(cfg.layers + 1):
-            enc.debug_set_layers(k)
-            run()
-            runs.append(_read(enc, rows, ("x", "h") if k == 0 else ("x", "h", "qkv", "att", "mlp")))
-        ratios = R.check_chain(tw, n, inp, runs)
-        if not is_text:                                     # the other channel order through patchify
-            enc.debug_set_layers(0)
-            run(swap_rb=False)
-            ratios[("embed_rgb", 0)] = R.check_embed(tw, inp, enc.debug_read("x", rows), swap_rb=False)
-        enc.debug_set_layers(-1)
-        emb = run()
-        if is_text:
-            x = enc.debug_read("x", rows)
-            assert np.array_equal(x.view(np.uint32), runs[-1]["x"].view(np.uint32)), "full pass and the pass limited to every block differ"
-            ratios[("pool", cfg.layers - 1)] = R.check_pool(tw, x[R.eos_rows(inp, cfg)], emb)
-        else:
-            prod = {"x": enc.debug_read("x", rows), "att": enc.debug_read("att", rows), "h": enc.debug_read("h", n), "mlp": enc.debug_read("mlp", n)}
-            ratios.update(R.check_product_image(tw, n, runs[-2], prod, emb))
-    finally:
-        enc.close()
-    _record(tag, ratios)
-    amb = ratios.pop(("ambiguous", 0))
-    print(f"{tag}: {amb} fc1 operand elements with an ambiguous 16-bit rounding (none excluded)")
-    worst = max(ratios, key=ratios.get)
-    assert ratios[worst] <= 1.0, f"{tag}: stage {worst} is {ratios[worst]:.3g} x its bound"
+    tag = f"{geo} {form} {dt} {kind} rows={n * T}" + (" concurrent" if concurrent else "")
+    if force:
+        monkeypatch.setenv("VQ_AMD_GEMM", str(force))
+        rows = S.pad_rows(n * T)
+        assert S.plan_resid_rows(_lib.load(), cfg, n, concurrent) == (rows, rows), (geo, n)
+        tag += " " + S.assert_ln_plans(_lib.load(), cfg, T, n, force, ln, resid=(rows, TILE128))
+    S.run_f32_chain(cfg, is_text, dt, kind, n, concurrent, tag)
 
 
 # ---------------------------------------------------------------- the default pass: the split 16 + 8-bit residual stream
@@ -151,90 +132,76 @@ def _split_cases():
     return out
 
 
-def _plan_resid_rows(lib, cfg, n, concurrent):
-    """(out_proj rows, fc2 rows) of a handle with max_batch = n under this process's environment (vq_debug_encoder_plan)."""
+def _split_multi_cases():
+    """The cases of _split_cases + {GEMM: (kernel, tiles per workgroup)} of q|k|v and fc1 (and the patch embedding): see _multi_cases
+    for the batches under $VQ_AMD_GEMM=15.  Two more here:
+      * the benchmark's own dispatch, no $VQ_AMD_GEMM: a concurrent handle (it plans as id 6) at n = 220.  11,000 rows pad to
+        11,008 = 43 tile rows, the fewest at which the unforced dispatch picks the multi-tile kernel (its `worth` rule wants
+        tiles / 3 >= 128: q|k|v 387 tiles = 129 workgroups of three, fc1 516 = 172; 42 tile rows give 126), and batches 216 .. 220
+        are the ones that pad to exactly that.  out_proj and fc2 have 129 tiles: the deep kernel under the split residual
+        epilogue across 43 tile rows, no tail split; the patch embedding (10,780 -> 11,008 rows) is on the deep kernel too.
+      * $VQ_AMD_GEMM=8 at n = 77 (3,850 rows pad to 4,096): the deep kernel under every tower epilogue on 16 tile rows (the
+        CLS-only block is refused by that id, as at n = 5)."""
+    m3 = {"qkv": (S.MULTI, 3), "fc1": (S.MULTI, 3)}
+    d1 = {"qkv": (DEEP, 1), "fc1": (DEEP, 1)}
+    return [pytest.param("t50", "stress", 72, False, 15, None, 3840, TILE128, m3, id="t50-stress-72-False-15-None-3840-1-qkv16x3+fc116x3"),
+            pytest.param("text512", "stress", 70, False, 15, None, 5632, TILE128, {"qkv": (S.MULTI, 3), "fc1": (DEEP, 1)},
+                         id="text512-stress-70-False-15-None-5632-1-qkv16x3+fc18x1"),
+            pytest.param("t50", "stress", 220, True, None, None, 11008, DEEP, dict(m3, patch=(DEEP, 1)),
+                         id="t50-stress-220-True-None-None-11008-8-qkv16x3+fc116x3+patch8x1"),
+            pytest.param("t50", "stress", 77, False, DEEP, None, 4096, DEEP, d1, id="t50-stress-77-False-8-None-4096-8-qkv8x1+fc18x1")]
+
+
+@pytest.mark.parametrize("geo,kind,n,concurrent,force,resid,gemm_rows,kernel,ln", [_old(c, 1) for c in _split_cases()] + _split_multi_cases())
+def test_every_stage_of_the_split_stream_against_fp64(gpu_lib, monkeypatch, geo, kind, n, concurrent, force, resid, gemm_rows, kernel, ln):
     from video_quierer_amd import _lib
-    out = _lib.EncoderPlanC()
-    if isinstance(cfg, TextConfig):
-        c = _lib.TextConfigC(cfg.vocab, cfg.max_positions, cfg.hidden, cfg.mlp, cfg.layers, cfg.heads, cfg.proj_dim, cfg.eos_token_id, cfg.ln_eps)
-        args = (None, ctypes.byref(c))
-    else:
-        c = _lib.VitConfigC(cfg.image_size, cfg.patch_size, cfg.hidden, cfg.mlp, cfg.layers, cfg.heads, cfg.proj_dim, cfg.ln_eps)
-        args = (ctypes.byref(c), None)
-    assert lib.vq_debug_encoder_plan(*args, n, n, 1 | (2 if concurrent else 0), 0, -1, 0, ctypes.byref(out), None) == 0
-    return out.rows_out, out.rows_fc2
-
-
-def _plan_kernels(lib, M, N, K, force):
-    n = ctypes.c_int(0)
-    k, r, r0, t = ((ctypes.c_int * 2)() for _ in range(4))
-    assert lib.vq_debug_gemm_plan(M, N, K, K, K, 0, force, ctypes.byref(n), k, r, r0, t) == 0
-    return [(k[i], r[i]) for i in range(n.value)]
-
-
-@pytest.mark.parametrize("geo,kind,n,concurrent,force,resid,gemm_rows,kernel", _split_cases(), ids=lambda v: str(v))
-def test_every_stage_of_the_split_stream_against_fp64(gpu_lib, monkeypatch, geo, kind, n, concurrent, force, resid, gemm_rows, kernel):
-    from video_quierer_amd import _lib
-    from video_quierer_amd.encoder import VitEncoder
-    from video_quierer_amd.text_encoder import TextEncoder
     is_text = geo in SPLIT_TEXT
     cfg = (SPLIT_TEXT if is_text else SPLIT_IMAGE)[geo]
-    tower = "text" if is_text else "image"
-    tw = R.Tower(tower, cfg, R.make_weights(tower, cfg, kind), "fp16")
-    inp = R.make_input(tower, cfg, n)
+    T = cfg.max_positions if is_text else cfg.tokens
     monkeypatch.delenv("VQ_AMD_RESID", raising=False)
     monkeypatch.delenv("VQ_AMD_GEMM", raising=False)
     if resid:
         monkeypatch.setenv("VQ_AMD_RESID", resid)
     if force:
         monkeypatch.setenv("VQ_AMD_GEMM", str(force))
-    rows = n * tw.T
+    rows = n * T
     assert gemm_rows >= rows
-    assert _plan_resid_rows(_lib.load(), cfg, n, concurrent) == (gemm_rows, gemm_rows), (geo, n)
+    assert S.plan_resid_rows(_lib.load(), cfg, n, concurrent) == (gemm_rows, gemm_rows), (geo, n)
     plan_force = force or (6 if concurrent else 0)          # a concurrent handle plans as GK_AUTO_NO160
     for K in (cfg.hidden, cfg.mlp):                         # out_proj, fc2: the GEMMs that carry the wide residual epilogue
-        assert _plan_kernels(_lib.load(), gemm_rows, cfg.hidden, K, plan_force) == [(kernel, gemm_rows)], (geo, n, K)
-    full_pass = not (force and not is_text)                 # (see _split_cases: the forced id refuses the CLS-only GEMMs)
-    full_rows = cfg.layers if is_text else cfg.layers - 1   # blocks that run on every row
-    want_forms = R.split_forms(tw) if resid is None else [False] * (cfg.layers + 1)
-    enc = TextEncoder(cfg, tw.W, max_batch=n, compute_dtype="fp16") if is_text else \
-        VitEncoder(cfg, tw.W, max_batch=n, compute_dtype="fp16", concurrent=concurrent)
-    run = (lambda: enc.encode_ids(inp)) if is_text else (lambda: enc.encode(inp))
+        assert S.plan_kernels(_lib.load(), gemm_rows, cfg.hidden, K, plan_force) == [(kernel, gemm_rows, 0, 1)], (geo, n, K)
     tag = f"{geo} {kind} rows={rows} gemm={kernel}" + (" concurrent" if concurrent else "") + (" resid=f32" if resid else "")
+    if ln:
+        assert gemm_rows == S.pad_rows(rows)
+        tag += " " + S.assert_ln_plans(_lib.load(), cfg, T, n, plan_force, ln)
+    full_pass = not (force == DEEP and not is_text)         # (see _split_cases: that forced id refuses the CLS-only GEMMs)
+    S.run_split_chain(cfg, is_text, kind, n, concurrent, resid, full_pass, tag)
+
+
+_CHILD_STATUS = []          # the first child that did not end with status 0: no child is started after it
+
+
+@pytest.mark.parametrize("tpw", S.TPW_COUNTS)
+def test_multi_tile_tiles_per_workgroup_in_a_child(gpu_lib, tpw):
+    """Four, two, one and twelve tiles per multi-tile workgroup under the LayerNorm-consuming q|k|v epilogue: both chains above on
+    ViT-L's widths (S.TPW_CFG; q|k|v 11 x 12 tiles).  $VQ_AMD_GEMM_TPW is read once per process, so each count runs in a fresh
+    child (one at a time next to this process); the child first shows through vq_debug_gemm_plan that the switch took effect.
+    After a child that failed, died or ran into its time limit nothing more is started: the remaining counts fail without touching the GPU."""
+    import subprocess
+    import sys
+    assert not _CHILD_STATUS, f"not started: the child for {_CHILD_STATUS[0][0]} tiles per workgroup ended with status {_CHILD_STATUS[0][1]}"
+    env = dict(os.environ, VQ_AMD_GEMM="15", VQ_AMD_GEMM_TPW=str(tpw))
+    for name in ("VQ_AMD_RESID", "VQ_AMD_ATTN"):
+        env.pop(name, None)
     try:
-        enc.debug_keep_stream(True)
-        runs, forms = [], []
-        for k in range(cfg.layers + 1 if full_pass else full_rows + 1):
-            enc.debug_set_layers(k)
-            emb_k = run()
-            forms.append(enc.debug_stream_is_split())
-            r = _read(enc, rows, ("x", "h", "xl") if k == 0 else ("x", "h", "xl", "qkv", "att", "mlp"))
-            r["split"] = forms[-1]
-            runs.append(r)
-        assert forms == want_forms[:len(forms)], f"{tag}: stream forms {forms}, the rule gives {want_forms}"
-        ratios = R.check_chain(tw, n, inp, runs[:full_rows + 1], split=resid is None)
-        if full_pass:
-            enc.debug_set_layers(-1)
-            emb = run()
-            assert not enc.debug_stream_is_split()
-            x = enc.debug_read("x", rows)
-            assert np.array_equal(emb.view(np.uint32), emb_k.view(np.uint32)), "the pass limited to every block and the full pass differ"
-            if is_text:
-                assert np.array_equal(x.view(np.uint32), runs[full_rows]["x"].view(np.uint32)), "full pass and the pass limited to every block differ"
-                ratios[("pool", cfg.layers - 1)] = R.check_pool(tw, x[R.eos_rows(inp, cfg)], emb)
-            else:
-                # (check_product_image holds the non-CLS rows to the x that block 1's fc2 wrote back from a split input)
-                assert np.array_equal(x.view(np.uint32), runs[cfg.layers]["x"].view(np.uint32)), "full pass and the pass limited to every block differ"
-                prod = {"x": x, "att": enc.debug_read("att", rows), "h": enc.debug_read("h", n), "mlp": enc.debug_read("mlp", n)}
-                ratios.update(R.check_product_image(tw, n, runs[full_rows], prod, emb))
-        enc.debug_keep_stream(False)                        # off: a layer-limited pass keeps the fp32 stream, as before
-        enc.debug_set_layers(1)
-        run()
-        assert not enc.debug_stream_is_split()
-    finally:
-        enc.close()
-    _record(tag, ratios, table="ratios_split.txt")
-    amb = ratios.pop(("ambiguous", 0))
-    print(f"{tag}: {amb} fc1 operand elements with an ambiguous 16-bit rounding (none excluded)")
-    worst = max(ratios, key=ratios.get)
-    assert ratios[worst] <= 1.0, f"{tag}: stage {worst} is {ratios[worst]:.3g} x its bound"
+        child = subprocess.run([sys.executable, S.__file__, "tpw-child", str(tpw)], env=env, timeout=240,
+                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    except subprocess.TimeoutExpired as e:                  # run() has killed the child; a hang stops the remaining counts too
+        _CHILD_STATUS.append((tpw, "timeout"))
+        out = e.stdout.decode(errors="replace") if isinstance(e.stdout, bytes) else (e.stdout or "")
+        print(out)
+        pytest.fail(f"child for {tpw} tiles per workgroup did not end within {e.timeout:.0f} s:\n{out[-4000:]}")
+    print(child.stdout)
+    if child.returncode != 0:
+        _CHILD_STATUS.append((tpw, child.returncode))
+    assert child.returncode == 0, f"child for {tpw} tiles per workgroup ended with status {child.returncode}:\n{child.stdout[-4000:]}"

@@ -12,7 +12,7 @@ import os
 
 import pytest
 
-TILE128, PHASE4, RING160, AUTO_NO160, DEEP, DEEP_GLOBAL_LDS, MULTI, ASM256 = 1, 2, 5, 6, 8, 11, 16, 24
+TILE128, PHASE4, RING160, AUTO_NO160, DEEP, DEEP_GLOBAL_LDS, MULTI_WHERE_WORTH, MULTI, ASM256 = 1, 2, 5, 6, 8, 11, 15, 16, 24
 EXPERIMENTS = (3, 4, 7, 9, 10, 12, 13, 20, 21)
 
 
@@ -72,6 +72,41 @@ def test_plans_of_the_encoder_shapes(lib):
         assert plan(lib, 512, N, 640, force=MULTI) == one(MULTI, 512, tpw)
     for force in (PHASE4, DEEP, DEEP_GLOBAL_LDS):
         assert plan(lib, 512, 256, 384, force=force) == one(force, 512)
+
+
+def test_plans_the_encoder_stage_cases_rely_on(lib):
+    """tests/test_encoder_stages.py (GPU) has cases written for ONE kernel each and asserts these plans itself before it runs;
+    pinned here so that a dispatch change fails without a GPU first.  If one of these moves, move the stage case it names to a
+    shape that still gets the kernel the case is about (its _multi_cases / _split_multi_cases say how the batch was chosen)."""
+    assert DEFAULT_ENV, "the pins hold for the default switches"
+    one = lambda kernel, M, tpw=1: [(kernel, M, 0, tpw)]
+    W = MULTI_WHERE_WORTH
+    for M, why in ((3840, "t50 n=72 gemm15: the smallest batch on gemm_tn256dm"), (4096, "16 tile rows (t50 n=77)")):
+        assert plan(lib, M, 2304, 768, row_in=1, force=W) == one(MULTI, M, 3), f"q|k|v, {why}"
+        assert plan(lib, M, 3072, 768, row_in=1, force=W) == one(MULTI, M, 3), f"fc1, {why}"
+        for K in (768, 3072):
+            assert plan(lib, M, 768, K, force=W) == one(TILE128, M), f"out_proj / fc2, {why}"
+    assert plan(lib, 3584, 2304, 768, row_in=1, force=W) == one(TILE128, 3584), "t50 n=71 (126 tiles) would do: lower the n=72 cases"
+    why = "text512 n=70 gemm15"
+    assert plan(lib, 5632, 1536, 512, row_in=1, force=W) == one(MULTI, 5632, 3), f"q|k|v (two workgroups per tile row), {why}"
+    assert plan(lib, 5632, 2048, 512, row_in=1, force=W) == one(DEEP, 5632), f"fc1 (tiles_n = 8), {why}"
+    assert plan(lib, 5376, 1536, 512, row_in=1, force=W) == one(TILE128, 5376), "text512 n=69 (126 tiles) would do: lower the n=70 cases"
+    for K in (512, 2048):
+        assert plan(lib, 5632, 512, K, force=W) == one(TILE128, 5632), f"out_proj / fc2, {why}"
+    why = "t50 n=220 concurrent: the benchmark's own dispatch"
+    assert plan(lib, 11008, 2304, 768, row_in=1, force=AUTO_NO160) == one(MULTI, 11008, 3), f"q|k|v, {why}"
+    assert plan(lib, 11008, 3072, 768, row_in=1, force=AUTO_NO160) == one(MULTI, 11008, 3), f"fc1, {why}"
+    assert plan(lib, 10752, 2304, 768, row_in=1, force=AUTO_NO160) == one(DEEP, 10752), "42 tile rows would do: lower the n=220 case"
+    for K in (768, 3072):
+        assert plan(lib, 11008, 768, K, force=AUTO_NO160) == one(DEEP, 11008), f"out_proj / fc2 / patch embedding (K = 3072), {why}"
+    why = "t50 n=77 gemm8"
+    for N, K, row_in in ((2304, 768, 1), (3072, 768, 1), (768, 768, 0), (768, 3072, 0)):
+        assert plan(lib, 4096, N, K, row_in=row_in, force=DEEP) == one(DEEP, 4096), f"{N} x {K}, {why}"
+    # the child of test_multi_tile_tiles_per_workgroup_in_a_child ($VQ_AMD_GEMM_TPW there; three per workgroup without it)
+    assert plan(lib, 2816, 3072, 1024, row_in=1, force=W) == one(MULTI, 2816, 3)
+    assert plan(lib, 2816, 4096, 1024, row_in=1, force=W) == one(DEEP, 2816)
+    for K in (1024, 4096):
+        assert plan(lib, 2816, 1024, K, force=W) == one(TILE128, 2816)
 
 
 def test_ids_a_product_build_does_not_carry(lib):

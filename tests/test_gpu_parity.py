@@ -73,6 +73,39 @@ def test_gemm_multi_tile_workgroups_are_exact(gpu_lib):
             assert np.array_equal(c, debug_gemm(a, w, use_f16=f16, kernel=8))
 
 
+def test_gemm_mainloops_at_their_shortest_k(gpu_lib):
+    """The 256x256 pipelines at K = 128: two K-tiles, all of which the prologue has staged - `next2` is never true and the loop
+    body runs once - and at K = 256, the first length with a steady-state trip; the 128x128 kernel at the one K-tile its launcher
+    accepts (K % 64 == 0, K >= 64).  Every 256-row / 256-column tile count up to 3 x 6: under id 16 that is 1, 2, 3, 4 and 3 tiles
+    per workgroup, and N = 1536 puts two workgroups on a tile row.  Small integers, asymmetric W: every result is exact, and the
+    multi-tile kernel's is the deep kernel's bit for bit."""
+    from video_quierer_amd.encoder import debug_gemm
+    from encoder_stage_run import MULTI, plan_kernels
+    lib = gpu_lib.load()
+    for m in (256, 768):        # id 16 must BE the multi-tile kernel at these counts, or "16 equals 8" below compares 8 with itself
+        for n, tpw in ((256, 1), (512, 2), (768, 3), (1024, 4), (1536, 3)):
+            for k in (128, 256):
+                assert plan_kernels(lib, m, n, k, MULTI) == [(MULTI, m, 0, tpw)], (m, n, k)
+    rng = np.random.default_rng(9)
+    a_all = rng.integers(-4, 5, (768, 256)).astype(np.float32)
+    w_all = rng.integers(-8, 9, (1536, 256)).astype(np.float32)
+    for k in (128, 256):
+        for m in (256, 768):
+            for n in (256, 512, 768, 1024, 1536):
+                a, w = np.ascontiguousarray(a_all[:m, :k]), np.ascontiguousarray(w_all[:n, :k])
+                ref = a @ w.T
+                for f16 in (False, True):
+                    got = {kernel: debug_gemm(a, w, use_f16=f16, kernel=kernel) for kernel in (2, 8, 11, 16)}
+                    for kernel, c in got.items():
+                        assert np.array_equal(c, ref), (kernel, m, n, k, f16)
+                    assert np.array_equal(got[16], got[8]), (m, n, k, f16)
+    for m in (256, 768):
+        for n in (256, 1536):
+            a, w = np.ascontiguousarray(a_all[:m, :64]), np.ascontiguousarray(w_all[:n, :64])
+            for f16 in (False, True):
+                assert np.array_equal(debug_gemm(a, w, use_f16=f16, kernel=1), a @ w.T), (1, m, n, 64, f16)
+
+
 @pytest.mark.parametrize("kernel", GEMM_KERNELS)
 def test_gemm_mfma_random(gpu_lib, kernel):
     from video_quierer_amd.encoder import debug_gemm
