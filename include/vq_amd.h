@@ -401,6 +401,61 @@ int vq_index_search_distinct_device(vq_index* idx, const void* d_queries_f32, in
 int vq_debug_distinct_plan(int64_t n, int nq, int k, int64_t min_gap, int mode,
                            int64_t* depth, int* producer, int* redo_slices);
 
+/* Sequence search: the k groups (videos) that show a list of steps IN ORDER — a storyboard of text prompts ("opens the door,
+ * then sits down, then picks up the phone"), or "where, in which video, does this clip occur".  The clip search scores every
+ * step on its own, so a video that shows the steps reversed or minutes apart scores the same; this one joins the steps along
+ * the position axis (vq_index_set_positions).
+ *   Steps q_0 .. q_{m-1} [m][dim], used as given.  d(j, r) = the distance of q_j to row r exactly as vq_index_search reports
+ *   it (fp32 of the fixed-order fp64 chain); tie(r) = the row number, or the id rank once ranks are set.
+ *   A CHAIN in group g is a list of rows r_0 .. r_{m-1}, all of g, with min_gap <= pos(r_{j+1}) - pos(r_j) <= max_gap for every
+ *   j (the difference taken in 64-bit; 1 <= min_gap <= max_gap, both int64).  Positions therefore increase strictly: two rows
+ *   at one position never follow each other.
+ *   Cost, by dynamic programme (the order of the additions is part of the definition):  C_0(r) = (double)d(0, r);  for j >= 1,
+ *   C_j(r) = C_{j-1}(p*) + (double)d(j, r) added in fp64, where p* is the admissible predecessor of r (same group, position
+ *   difference within the gaps, C_{j-1} defined) with the smallest (C_{j-1}(p), tie(p));  C_j(r) is undefined when there is none.
+ *   A group's result: the row e with the smallest (C_{m-1}(e), tie(e));  D(g) = fp32(C_{m-1}(e) / m);  its chain is e followed
+ *   back through the p*.  A group with no defined C_{m-1} has no result and never appears.
+ *   The answer is the first min(k, allowed groups that hold a chain) groups by (D, label) ascending; chain_rows [k][m] (or
+ *   NULL): full-index row numbers in step order; unused slots are -1 / +inf / -1.
+ *   Limits: 1 <= m <= 64, 1 <= k <= 1024, 1 <= min_gap <= max_gap (else VQ_ERR_INVALID).
+ *   groups / n_sel / exclude: the filter of vq_index_search_filtered in host memory, with the checks and the two empty-list
+ *   cases of vq_index_search_set (n_sel = 0, exclude = 1: unfiltered; n_sel = 0, exclude = 0: every slot empty).  A group's D
+ *   does not depend on other groups.  Stale or missing labels, positions or id ranks are refused before any work is queued.
+ *   Consequences: m = 1 gives the groups, rows and distances of vq_index_search_grouped (filtered: _grouped_filtered);
+ *   D_seq(g) >= D_set(g) of vq_index_search_set in mode 1 for every group returned.
+ *   How it runs (csrc/knn_sequence.h): exact only, no mode.  Per chunk of steps the plain search's exact distances [chunk][n]
+ *   (chunks keep them within 512 MiB), then one workgroup per allowed group runs the chunk's steps over the group's rows in
+ *   (position, tie) order — a second permutation next to the by-group row list, sorted on the host and uploaded by the first
+ *   sequence search after the labels, the positions or the id ranks changed (that one call waits for the stream once).  A row's
+ *   admissible predecessors are a contiguous range of that order, found once per row and launch; the range minimum of the
+ *   (64-bit order-preserving cost key, tie) reads at most 126 + L / 64 entries per row and step in a group of L rows.  Groups
+ *   of at most 4,096 rows keep positions, ties, ranges and two cost arrays in LDS (36 B per row); longer groups run the same
+ *   arithmetic over global arrays with one more level of minima (at most 252 + L / 4096 reads; one group of a million rows is
+ *   legal: a bound, not a target).  The fp64 costs [n] are
+ *   carried between chunks.  A small kernel turns C_{m-1} into each group's (D, label) key and end row; the clip search's
+ *   selection takes the k smallest.  Chains: the DP kernels write a back-pointer table [m-1][n] int32 when that stays within
+ *   256 MiB; otherwise one workgroup per winner runs its group's DP again and keeps the back-pointers of one slice of steps at a
+ *   time, last slice first (slice [s][n] int32 <= 256 MiB, s >= 1: above 2^26 rows it is 4 B per row).
+ *   Scratch beyond that: 24 B per row of cost keys, 12 B per row of ranges and block minima, 12 B per row for the order itself,
+ *   and the clip search's per-group selection arrays.  The launches queued depend on the shapes only.
+ *   The _device form takes device steps and results, is asynchronous on the index's stream and reads nothing back.
+ *   vq_index_last_search_stats afterwards: [0] the groups that hold a chain, [1] the allowed groups run by the global form,
+ *   [2] the step chunks.
+ *   $VQ_AMD_SEQ_LDS_ROWS (the LDS form's row limit, at most 4,096), $VQ_AMD_SEQ_DIST_BYTES (the distance budget) and
+ *   $VQ_AMD_SEQ_BP_BYTES (the back-pointer budget): tests only, read per call.
+ *   vq_debug_sequence_plan (host only, as vq_debug_distinct_plan): for n rows whose longest group holds largest_group rows — the
+ *   step chunks, the LDS form's row limit and its dynamic LDS bytes, groups_global_form = 1 when the longest group (so at least
+ *   one) takes the global form, chain_table = 1 when the chains come from the back-pointer table, else chain_slices = the
+ *   slices of the per-winner redo. */
+int vq_index_search_sequence(vq_index* idx, const float* steps /*[m][dim]*/, int m, int k, int64_t min_gap, int64_t max_gap,
+                             const int32_t* groups, int32_t n_sel, int exclude,
+                             int32_t* groups_out /*[k]*/, float* dist_out /*[k]*/, int32_t* chain_rows /*[k][m] or NULL*/);
+int vq_index_search_sequence_device(vq_index* idx, const void* d_steps_f32, int m, int k, int64_t min_gap, int64_t max_gap,
+                                    const int32_t* groups, int32_t n_sel, int exclude,
+                                    void* d_groups_i32, void* d_dist_f32, void* d_chain_rows_i32 /*or NULL*/);
+int vq_debug_sequence_plan(int64_t n, int64_t largest_group, int m, int k, int* step_chunks, int* lds_rows, int* groups_global_form,
+                           int64_t* lds_bytes, int* chain_table, int* chain_slices);
+
 /* save / load support (hnsw.py:306-380): the stored (normalised) rows. */
 int vq_index_export(vq_index* idx, float* rows /*[size][dim]*/);
 /* Single stored rows (the reference reads `self.data[node_id]`, a dict lookup): out [n][dim] = rows row_numbers[0..n). */
@@ -448,7 +503,7 @@ int vq_merge_topk_device(const void* d_all_ids_i32, const void* d_all_dist_f32, 
                          void* d_ids_i32, void* d_dist_f32, void* hip_stream);
 
 /* Device timing of the scan kernels between begin/end (bench.py roofline leg). */
-#define VQ_IDX_NCLASS 6
+#define VQ_IDX_NCLASS 7
 int vq_index_profile_begin(vq_index* idx);
 int vq_index_profile_end(vq_index* idx, float* ms /*[VQ_IDX_NCLASS]*/, int* launches /*[VQ_IDX_NCLASS]*/);
 const char* vq_index_profile_class_name(int cls);

@@ -12,6 +12,7 @@
 #include "knn_filter.h"
 #include "knn_set.h"
 #include "knn_distinct.h"
+#include "knn_sequence.h"
 #include "scan_plan.h"
 #ifdef VQ_SCAN_EXPERIMENTS      // `make EXPERIMENTS=1`: the two superseded batch mainloops behind VQ_AMD_SCAN=2|4
 #include "experiments/scan_experiments.h"
@@ -26,9 +27,9 @@
 
 namespace vq {
 int require_init();
-enum IdxClass { I_NORMALIZE = 0, I_TO_F16, I_EXACT_DIST, I_SELECT, I_MFMA_SCAN, I_RESCORE };
+enum IdxClass { I_NORMALIZE = 0, I_TO_F16, I_EXACT_DIST, I_SELECT, I_MFMA_SCAN, I_RESCORE, I_SEQ_DP };
 static const char* kIdxClassNames[VQ_IDX_NCLASS] = {
-    "normalize_rows", "rows_to_f16", "exact_dist_f64chain", "select_topk", "scan_f16_mfma_top2", "rescore_verify"};
+    "normalize_rows", "rows_to_f16", "exact_dist_f64chain", "select_topk", "scan_f16_mfma_top2", "rescore_verify", "sequence_dp"};
 #ifdef VQ_DIAG
 constexpr bool SCAN_DIAG_BUILD = true;
 #else
@@ -167,6 +168,15 @@ struct vq_index {
     DevBuf<int32_t> d_dpre;
     DevBuf<int32_t> d_dslots;
     DevBuf<int32_t> d_dsel;
+    // sequence search (knn_sequence.h): every group's rows in (position, tie) order with their positions and ties beside them
+    // (order | positions | ties, [3][seq_n]), built on the host by the first sequence search after the labels, the positions or
+    // the id ranks changed (seq_n = the rows it covers, 0 = none; seq_largest = the longest group).  Scratch: cost keys (carry
+    // [n] | two working arrays [2][n]), words (lo | hi | block minima [3][n] | end rows [G]), back-pointers, the host form's results
+    DevBuf<int32_t> d_seq; int64_t seq_n = 0; int64_t seq_largest = 0;
+    DevBuf<uint64_t> d_seqc;
+    DevBuf<int32_t> d_seqw;
+    DevBuf<int32_t> d_seqbp;
+    DevBuf<int32_t> d_seqout;
     // clip-search scratch (knn_set.h): per-group sums [2][G], candidate list / positions [2][G] + count + flag, |q_i| [m],
     // order keys [G] + the selection's block lists, candidate keys, result staging of the host form
     DevBuf<double> d_ssum;
@@ -1195,6 +1205,141 @@ int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, i
     return 0;
 }
 
+// ---- sequence search (knn_sequence.h) ----
+// tests only, read per call: the LDS form's row limit, the distance budget and the back-pointer budget in bytes
+int64_t seq_env(const char* name) {
+    const char* e = getenv(name);
+    return e ? std::max<long long>(0, atoll(e)) : 0;
+}
+SequencePlan seq_plan_env(int64_t n, int64_t largest_group, int m) {
+    return plan_sequence(n, largest_group, m, seq_env("VQ_AMD_SEQ_LDS_ROWS"), seq_env("VQ_AMD_SEQ_DIST_BYTES"), seq_env("VQ_AMD_SEQ_BP_BYTES"));
+}
+
+// Every group's rows in (position, tie) order, with the positions and ties in that order: sorted on the host from the by-group
+// row list, the positions and the id ranks as the device holds them, and uploaded.  Blocks on the stream; runs once after the
+// labels, the positions or the ranks changed.
+int seq_order_prepare(vq_index* x) {
+    if (x->seq_n == x->size) return 0;
+    const int64_t n = x->size;
+    const int32_t G = x->n_groups;
+    std::vector<int32_t> grows((size_t)n), pos((size_t)n), rank;
+    std::vector<int32_t> h((size_t)(3 * n));
+    StreamDrain drain{x->stream};
+    VQ_HIP(hipMemcpyAsync(grows.data(), x->d_grows, (size_t)n * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(pos.data(), x->d_pos, (size_t)n * 4, hipMemcpyDeviceToHost, x->stream));
+    if (x->rank_n) {
+        rank.resize((size_t)n);
+        VQ_HIP(hipMemcpyAsync(rank.data(), x->d_rank, (size_t)n * 4, hipMemcpyDeviceToHost, x->stream));
+    }
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    const int32_t* rk = x->rank_n ? rank.data() : nullptr;
+    int64_t largest = 0;
+    for (int32_t g = 0; g < G; ++g) {
+        int32_t* b = grows.data() + x->h_goff[(size_t)g], *e = grows.data() + x->h_goff[(size_t)g + 1];
+        largest = std::max<int64_t>(largest, e - b);
+        std::sort(b, e, [&](int32_t a, int32_t c) {
+            if (pos[(size_t)a] != pos[(size_t)c]) return pos[(size_t)a] < pos[(size_t)c];
+            return rk ? rk[a] < rk[c] : a < c;
+        });
+    }
+    int32_t* so = h.data(); int32_t* sp = so + n; int32_t* st = sp + n;
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t r = grows[(size_t)i];
+        so[i] = r; sp[i] = pos[(size_t)r]; st[i] = rk ? rk[r] : r;
+    }
+    VQ_TRY(x->d_seq.reserve(3 * std::max<int64_t>(n, x->cap)));
+    VQ_HIP(hipMemcpyAsync(x->d_seq, h.data(), (size_t)n * 12, hipMemcpyHostToDevice, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    x->seq_n = n; x->seq_largest = largest;
+    return 0;
+}
+
+// Everything that can refuse a sequence search before any work is queued.
+int seq_precheck(vq_index* x, const char* fn, const FilterLabels& f) {
+    VQ_TRY(check_ranks(x, fn));
+    VQ_TRY(check_labels(x, fn));
+    VQ_TRY(check_positions(x, fn));
+    return check_label_range(x, fn, f);
+}
+
+// d_steps [m][dim], g_out / d_out [k], chain [k][m] or null: all device memory.  Asynchronous on the index's stream once the
+// (position, tie) order is on the device.
+int search_sequence_run(vq_index* x, const char* fn, const float* d_steps, int m, int k, int64_t min_gap, int64_t max_gap,
+                        const FilterLabels& f, int exclude, int32_t* g_out, float* d_out, int32_t* chain) {
+    FilterPlan fp;
+    VQ_TRY(filter_prepare(x, fn, f, exclude, true, &fp));
+    if (!fp.all && fp.m == 0) {                             // nothing allowed: every slot empty
+        if (chain) VQ_HIP(hipMemsetAsync(chain, 0xff, (size_t)k * m * 4, x->stream));
+        VQ_TRY(fill_empty(x, k, g_out, nullptr, d_out));
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    VQ_TRY(seq_order_prepare(x));
+    const uint32_t* allow = fp.all ? nullptr : fp.bits;
+    const int64_t n = x->size, ld = round_up(n, 64);
+    const int G = x->n_groups;
+    const int nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK);
+    const SequencePlan p = seq_plan_env(n, x->seq_largest, m);
+    // positions are 32-bit: a gap of 2^32 or more behaves as 2^32, and the differences below stay far inside 64 bits
+    const int64_t gap_cap = (int64_t)1 << 32;
+    min_gap = std::min(min_gap, gap_cap); max_gap = std::min(max_gap, gap_cap);
+    // the allowed groups the global form runs (the host mirror of goff and the sorted filter list)
+    int64_t global_groups = 0;
+    if (p.global_form) {
+        size_t si = 0;
+        for (int32_t g = 0; g < G; ++g) {
+            while (si < f.sel.size() && f.sel[si] < g) ++si;
+            const bool listed = si < f.sel.size() && f.sel[si] == g;
+            if ((exclude ? !listed : listed) && x->h_goff[(size_t)g + 1] - x->h_goff[(size_t)g] > p.lds_rows) ++global_groups;
+        }
+    }
+    const bool table = chain && p.bp_table && m > 1, redo = chain && !p.bp_table && m > 1;
+    VQ_TRY(x->d_dist.reserve((int64_t)p.chunk_steps * ld));
+    VQ_TRY(x->d_seqc.reserve(3 * n));
+    VQ_TRY(x->d_seqw.reserve(3 * n + G));
+    VQ_TRY(x->d_sekey.reserve((int64_t)G + (int64_t)nblocks * kl));
+    VQ_TRY(ensure_gcounters(x));
+    if (table) VQ_TRY(x->d_seqbp.reserve((int64_t)(m - 1) * n));
+    if (redo) VQ_TRY(x->d_seqbp.reserve((int64_t)p.bp_slice_steps * n));
+    VQ_TRY(set_dyn_lds(x, (const void*)seq_dp_lds_kernel, (size_t)p.lds_bytes));
+    const int32_t* sorder = x->d_seq; const int32_t* spos = sorder + n; const int32_t* stie = spos + n;
+    uint64_t* carry = x->d_seqc; uint64_t* cost = carry + n;
+    int32_t* work = x->d_seqw; int32_t* end_idx = work + 3 * n;
+    uint64_t* ekey = x->d_sekey; uint64_t* partial = ekey + G;
+    int32_t* bp = table ? x->d_seqbp.p : nullptr;
+    for (int j0 = 0; j0 < m; j0 += p.chunk_steps) {
+        const int cur = std::min(p.chunk_steps, m - j0);
+        VQ_TRY(exact_dist(x, false, d_steps + (int64_t)j0 * x->dim, cur, ld));         // always the tiled kernel
+        Prof pr(x, I_SEQ_DP);
+        hipLaunchKernelGGL(seq_dp_lds_kernel, dim3(G), dim3(SEQ_THREADS), (size_t)p.lds_bytes, x->stream, x->d_dist, ld, j0, cur, x->d_goff, sorder,
+                           spos, stie, p.lds_rows, p.lds_alloc_rows, min_gap, max_gap, carry, bp, n, m, allow);
+        if (p.global_form)
+            hipLaunchKernelGGL(seq_dp_global_kernel, dim3(G), dim3(SEQ_THREADS), 0, x->stream, x->d_dist, ld, j0, cur, x->d_goff, sorder, spos, stie,
+                               p.lds_rows, min_gap, max_gap, carry, work, cost, bp, n, m, allow);
+    }
+    {
+        Prof pr(x, I_SELECT);
+        hipLaunchKernelGGL(seq_final_kernel, dim3(G), dim3(SEQ_THREADS), 0, x->stream, carry, x->d_goff, stie, m, allow, ekey, end_idx);
+        hipLaunchKernelGGL(set_select_block_kernel, dim3(nblocks), dim3(256), 0, x->stream, ekey, G, kl, partial);
+        hipLaunchKernelGGL(set_select_merge_kernel, dim3(1), dim3(256), 0, x->stream, partial, (int64_t)nblocks * kl, k, g_out, d_out, nullptr,
+                           nullptr);
+        hipLaunchKernelGGL(seq_stats_kernel, dim3(1), dim3(256), 0, x->stream, ekey, G, (unsigned long long)global_groups,
+                           (unsigned long long)p.step_chunks, x->d_gcounters);
+    }
+    if (chain) {
+        Prof pr(x, I_SEQ_DP);
+        if (m == 1 || table)
+            hipLaunchKernelGGL(seq_trace_kernel, dim3(cdiv(k, 64)), dim3(64), 0, x->stream, g_out, k, m, x->d_goff, sorder, end_idx, bp, n, chain);
+        else
+            hipLaunchKernelGGL(seq_chain_redo_kernel, dim3(k), dim3(SEQ_THREADS), 0, x->stream, g_out, m, p.bp_slice_steps, x->rows, x->dim, d_steps,
+                               x->d_goff, sorder, spos, stie, min_gap, max_gap, end_idx, work, cost, x->d_seqbp, n, chain);
+    }
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+    set_stats(x, STATS_GCOUNTERS);
+    return 0;
+}
+
 // ---- what the search entry points share ----
 // One argument check per shape of call.  arrays: every array the call reads or writes is there.
 int check_batch_args(const char* fn, const vq_index* x, int nq, int k, bool arrays) {
@@ -1220,6 +1365,16 @@ int check_distinct_args(const char* fn, const vq_index* x, int nq, int k, int64_
     VQ_CHECK(k > 0 && k <= 1024, "%s: k %d outside [1, 1024]", fn, k);
     VQ_CHECK(min_gap >= 0, "%s: min_gap %lld is negative", fn, (long long)min_gap);
     return check_batch_args(fn, x, nq, k, arrays);
+}
+
+int check_sequence_args(const char* fn, const vq_index* x, int m, int k, int64_t min_gap, int64_t max_gap, const int32_t* groups,
+                        int32_t n_sel, int exclude, bool arrays) {
+    VQ_CHECK(m >= 1 && m <= SEQ_MAX_M && k > 0 && k <= 1024, "%s: bad argument (1 <= m <= %d, 1 <= k <= 1024)", fn, SEQ_MAX_M);
+    VQ_CHECK(min_gap >= 1 && min_gap <= max_gap, "%s: the gaps must satisfy 1 <= min_gap <= max_gap (got %lld, %lld)", fn,
+             (long long)min_gap, (long long)max_gap);
+    VQ_TRY(require_init());
+    VQ_CHECK(x && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) && arrays, "%s: bad argument", fn);
+    return 0;
 }
 
 // a host form's answer from an empty index: no candidates (hnsw.py:243-244 returns []); b: the grouped forms' second id array, or null
@@ -1310,7 +1465,7 @@ int vq_index_clear(vq_index* x) {
     x->norm_dirty = false; x->near_unit = true; x->row_norm_max = 1.0f;
     x->rank_n = 0;
     x->group_n = 0; x->n_groups = 0; x->h_goff.clear();
-    x->pos_n = 0;
+    x->pos_n = 0; x->seq_n = 0;
     return 0;
 }
 
@@ -1318,6 +1473,7 @@ int vq_index_set_id_ranks(vq_index* x, const int32_t* rank_of_row, int64_t n) {
     VQ_TRY(require_init());
     VQ_CHECK(x && n >= 0 && (n == 0 || rank_of_row), "vq_index_set_id_ranks: bad argument");
     std::lock_guard<std::mutex> lk(x->mu);
+    x->seq_n = 0;                                                // the (position, tie) order follows the ties
     if (n == 0) { x->rank_n = 0; return 0; }                     // back to row order
     VQ_CHECK(n == x->size, "vq_index_set_id_ranks: %lld ranks for an index of %lld rows", (long long)n, (long long)x->size);
     // a permutation of 0..n-1, checked here: the kernels index two arrays with these values
@@ -1348,6 +1504,7 @@ int vq_index_set_groups(vq_index* x, const int32_t* group_of_row, int64_t n, int
     VQ_TRY(require_init());
     VQ_CHECK(x && n >= 0 && (n == 0 || group_of_row), "vq_index_set_groups: bad argument");
     std::lock_guard<std::mutex> lk(x->mu);
+    x->seq_n = 0;
     if (n == 0) { x->group_n = 0; x->n_groups = 0; x->h_goff.clear(); return 0; }
     VQ_CHECK(n == x->size, "vq_index_set_groups: %lld labels for an index of %lld rows", (long long)n, (long long)x->size);
     VQ_CHECK(n_groups >= 1 && n_groups <= n, "vq_index_set_groups: n_groups %d outside [1, %lld]", (int)n_groups, (long long)n);
@@ -1396,6 +1553,7 @@ int vq_index_set_positions(vq_index* x, const int32_t* pos_of_row, int64_t n) {
     VQ_TRY(require_init());
     VQ_CHECK(x && n >= 0 && (n == 0 || pos_of_row), "vq_index_set_positions: bad argument");
     std::lock_guard<std::mutex> lk(x->mu);
+    x->seq_n = 0;
     if (n == 0) { x->pos_n = 0; return 0; }
     VQ_CHECK(n == x->size, "vq_index_set_positions: %lld positions for an index of %lld rows", (long long)n, (long long)x->size);
     if (n > x->d_pos.cap) {
@@ -1586,7 +1744,7 @@ int vq_index_remove_rows(vq_index* x, const int64_t* row_numbers, int64_t n) {
     }
     // the |row|^2 range stays as it is: it still covers every survivor (conservative, as in vq_index_update_rows)
     x->size = n_new;
-    x->pos_n = 0;                                  // positions are not compacted: set them again
+    x->pos_n = 0; x->seq_n = 0;                    // positions are not compacted: set them again
     VQ_HIP(hipStreamSynchronize(x->stream));
     return 0;
 }
@@ -1799,6 +1957,61 @@ int vq_index_search_set(vq_index* x, const float* queries, int m, int k, int mod
     VQ_HIP(hipMemcpyAsync(dist_out, d_d, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
     if (match_rows) VQ_HIP(hipMemcpyAsync(match_rows, d_m, (size_t)nm * 4, hipMemcpyDeviceToHost, x->stream));
     VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+int vq_index_search_sequence_device(vq_index* x, const void* d_steps, int m, int k, int64_t min_gap, int64_t max_gap, const int32_t* groups,
+                                    int32_t n_sel, int exclude, void* d_groups_out, void* d_dist_out, void* d_chain_rows) {
+    static const char* fn = "vq_index_search_sequence_device";
+    VQ_TRY(check_sequence_args(fn, x, m, k, min_gap, max_gap, groups, n_sel, exclude, d_steps && d_groups_out && d_dist_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) {
+        fill_no_result(x, (int32_t*)d_groups_out, (float*)d_dist_out, k);
+        if (d_chain_rows) VQ_HIP(hipMemsetAsync(d_chain_rows, 0xff, (size_t)k * m * 4, x->stream));
+        VQ_HIP(hipGetLastError());
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(seq_precheck(x, fn, f));
+    return search_sequence_run(x, fn, (const float*)d_steps, m, k, min_gap, max_gap, f, exclude, (int32_t*)d_groups_out, (float*)d_dist_out,
+                               (int32_t*)d_chain_rows);
+}
+
+int vq_index_search_sequence(vq_index* x, const float* steps, int m, int k, int64_t min_gap, int64_t max_gap, const int32_t* groups,
+                             int32_t n_sel, int exclude, int32_t* groups_out, float* dist_out, int32_t* chain_rows) {
+    static const char* fn = "vq_index_search_sequence";
+    VQ_TRY(check_sequence_args(fn, x, m, k, min_gap, max_gap, groups, n_sel, exclude, steps && groups_out && dist_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t nc = chain_rows ? (int64_t)k * m : 0;
+    if (x->size == 0) {
+        host_empty(k, groups_out, nullptr, dist_out);
+        std::fill(chain_rows, chain_rows + nc, -1);
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(seq_precheck(x, fn, f));
+    VQ_TRY(x->d_seqout.reserve(2 * (int64_t)k + nc));
+    int32_t* d_g = x->d_seqout; float* d_d = (float*)(d_g + k); int32_t* d_c = chain_rows ? d_g + 2 * k : nullptr;
+    VQ_TRY(stage_queries(x, steps, m));
+    VQ_TRY(search_sequence_run(x, fn, x->d_q, m, k, min_gap, max_gap, f, exclude, d_g, d_d, d_c));
+    VQ_HIP(hipMemcpyAsync(groups_out, d_g, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(dist_out, d_d, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
+    if (chain_rows) VQ_HIP(hipMemcpyAsync(chain_rows, d_c, (size_t)nc * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// plan_sequence's answer for this process's environment; needs no device
+int vq_debug_sequence_plan(int64_t n, int64_t largest_group, int m, int k, int* step_chunks, int* lds_rows, int* groups_global_form,
+                           int64_t* lds_bytes, int* chain_table, int* chain_slices) {
+    VQ_CHECK(step_chunks && lds_rows && groups_global_form && lds_bytes && chain_table && chain_slices && n >= 1 && n < ((int64_t)1 << 31) &&
+             largest_group >= 1 && largest_group <= n && m >= 1 && m <= SEQ_MAX_M && k >= 1 && k <= 1024,
+             "vq_debug_sequence_plan: takes 1 <= largest_group <= n < 2^31, 1 <= m <= %d, 1 <= k <= 1024", SEQ_MAX_M);
+    const SequencePlan p = seq_plan_env(n, largest_group, m);
+    *step_chunks = p.step_chunks; *lds_rows = p.lds_rows; *groups_global_form = p.global_form; *lds_bytes = p.lds_bytes;
+    *chain_table = p.bp_table; *chain_slices = p.bp_slices;
     return 0;
 }
 

@@ -850,6 +850,78 @@ class HNSWIndex:
             _lib.check(_lib.load().vq_index_read_rows(self._h, rn.ctypes.data_as(POINTER(c_int64)), len(rn), _lib.fptr(unit)))
             return self._search_set_unit(unit, k, flt, group_of, matches)
 
+    # -- sequence query: the k groups (videos) that show a list of steps in order -------------------
+    SEQ_MAX_STEPS = 64            # vq_index_search_sequence: steps per call
+
+    @staticmethod
+    def _sequence_gaps(min_gap, max_gap) -> Tuple[int, int]:
+        lo, hi = int(min_gap), int(max_gap)
+        if lo < 1 or hi < lo:
+            raise ValueError(f"the gaps must satisfy 1 <= min_gap <= max_gap, got min_gap={min_gap}, max_gap={max_gap}")
+        return lo, min(hi, 2 ** 62)
+
+    def _search_sequence_unit(self, unit: np.ndarray, k: int, min_gap: int, max_gap: int, flt, group_of, position_of) -> List[Dict]:
+        """unit: [m][dim] fp32 steps, used as given.  flt: None or (group keys, exclude?).  min_gap / max_gap: checked."""
+        m = unit.shape[0]
+        if m < 1 or m > self.SEQ_MAX_STEPS:
+            raise ValueError(f"a sequence query holds 1 to {self.SEQ_MAX_STEPS} steps, got {m}")
+        if unit.shape[1] != self.dimension:
+            raise ValueError(f"step dimension {unit.shape[1]} != index dimension {self.dimension}")
+        if k <= 0 or not self._ids:
+            return []
+        keys_f, excl = flt if flt is not None else ([], True)
+        if not excl and not keys_f:
+            return []                                    # nothing allowed: no device call
+        if not self._identity:
+            self._sync_tie_order()
+        gl = self._sync_groups(group_of)
+        ps = self._sync_positions(position_of)
+        labels = self._filter_labels(gl, keys_f)
+        if not excl and len(labels) == 0:
+            return []
+        kk = min(int(k), len(gl.keys), 1024)
+        groups = np.empty(kk, dtype=np.int32)
+        dist = np.empty(kk, dtype=np.float32)
+        rows = np.empty((kk, m), dtype=np.int32)
+        _lib.check(_lib.load().vq_index_search_sequence(
+            self._h, _lib.fptr(unit), m, kk, min_gap, max_gap, labels.ctypes.data_as(POINTER(c_int32)), len(labels), int(excl),
+            groups.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist), rows.ctypes.data_as(POINTER(c_int32))))
+        keys, names, identity, pos = gl.keys, self._ids, self._identity, ps.values
+        out = []
+        for j, (g, d) in enumerate(zip(groups.tolist(), dist)):
+            if g < 0:
+                break
+            chain = rows[j].tolist()
+            out.append({"group": keys[g], "distance": d, "score": np.float32(1.0) - d,
+                        "chain": [int(r) if identity else names[r] for r in chain], "positions": [int(pos[r]) for r in chain]})
+        return out
+
+    def search_sequence(self, steps: Sequence[np.ndarray], k: int = 5, *, max_gap: int, min_gap: int = 1,
+                        within: Optional[Iterable[Hashable]] = None, exclude: Optional[Iterable[Hashable]] = None,
+                        group_of: Optional[Callable[[Hashable], Hashable]] = None,
+                        position_of: Optional[Callable[[Hashable], int]] = None) -> List[Dict]:
+        """The k GROUPS (videos) that show the ``steps`` IN ORDER (a storyboard of prompts, the frames of a clip):
+        ``[{'group', 'distance', 'score', 'chain', 'positions'}]``.  A chain is one row of the group per step whose positions
+        increase by ``min_gap`` .. ``max_gap`` from step to step (``1 <= min_gap <= max_gap``); its cost adds the steps'
+        distances (normalised as ``search`` does) in fp64 in step order, a step always continuing the cheapest admissible
+        chain so far (ties by id, as ``search``).  ``distance`` is the group's cheapest chain over the number of steps, rounded
+        once to float32; ``chain`` its node ids in step order, ``positions`` their positions.  Groups without any chain do not
+        appear; groups come back by (distance, order in which the groups first appeared in the index).  One step is
+        ``search_grouped``; ``search_set`` of the same steps never scores a group worse.  ``group_of`` / ``within`` /
+        ``exclude`` as ``search_grouped``, ``position_of`` as ``search_distinct`` (timestamps in ms with gaps in ms alike).
+        At most 64 steps and 1,024 results."""
+        flt = self._filter_arg(within, exclude) if within is not None or exclude is not None else None
+        if len(steps) == 0:
+            raise ValueError("search_sequence needs at least one step")
+        if len(steps) > self.SEQ_MAX_STEPS:
+            raise ValueError(f"a sequence query holds at most {self.SEQ_MAX_STEPS} steps, got {len(steps)}")
+        lo, hi = self._sequence_gaps(min_gap, max_gap)
+        if self.entry_point is None or self.element_count == 0 or k <= 0:
+            return []
+        with self.lock:
+            unit = np.ascontiguousarray(self._unit_rows(steps), dtype=np.float32)
+            return self._search_sequence_unit(unit, k, lo, hi, flt, group_of, position_of)
+
     def synchronize(self) -> None:
         _lib.check(_lib.load().vq_index_synchronize(self._h))
 

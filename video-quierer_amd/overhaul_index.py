@@ -159,6 +159,44 @@ class SimpleVideoIndex:
             results.append(md)
         return results
 
+    def search_storyboard(self, step_embeddings, k: int = 5, max_gap_s: float = 10.0, min_gap_s: float = 0.0) -> List[Dict]:
+        """The k videos that show the steps IN ORDER (text prompts through ``extract_text_features``, or the frames of a clip):
+        ``[{'video_name', 'score', 'timestamps', 'frame_ids'}]``, best first.  One frame of the video per step, each
+        ``min_gap_s`` .. ``max_gap_s`` seconds after the one before (``HNSWIndex.search_sequence``: exact; ``score`` is one
+        minus the mean distance along the video's cheapest such chain, videos without a chain do not appear).  Every step is
+        normalised as ``search`` does; positions are ``round(timestamp * 1000)`` ms, the gaps ``max(1, ceil(min_gap_s *
+        1000))`` and ``floor(max_gap_s * 1000)`` ms, groups the video names; ties between frames as ``search``."""
+        steps = [np.asarray(e) for e in step_embeddings]
+        if not steps:
+            raise ValueError("search_storyboard needs at least one step")
+        if len(steps) > HNSWIndex.SEQ_MAX_STEPS:
+            raise ValueError(f"a storyboard holds at most {HNSWIndex.SEQ_MAX_STEPS} steps, got {len(steps)}")
+        if min_gap_s < 0 or max_gap_s < min_gap_s:
+            raise ValueError(f"the gaps must satisfy 0 <= min_gap_s <= max_gap_s, got {min_gap_s}, {max_gap_s}")
+        lo, hi = max(1, int(math.ceil(min_gap_s * 1000))), int(math.floor(max_gap_s * 1000))
+        if hi < lo:
+            raise ValueError(f"max_gap_s {max_gap_s} leaves no admissible gap in whole milliseconds")
+        if not self.embeddings or k <= 0:
+            return []
+        self._sync_device()
+        unit = np.ascontiguousarray(np.stack([(q / (np.linalg.norm(q) + 1e-10)).astype(np.float32) for q in steps]))   # reference :50-51
+        dev = self._dev
+        if getattr(self, "_ranked_dev", None) is not dev:       # as search_moments: the id order (larger frame first) as device ranks
+            dev._tie_order = "stale"
+            dev._sync_tie_order()
+            self._ranked_dev = dev
+        gfn = getattr(self, "_group_fn", None)
+        if gfn is None:
+            gfn = self._group_fn = self._video_of_row_id
+        pfn = getattr(self, "_pos_fn", None)
+        if pfn is None:
+            pfn = self._pos_fn = self._timestamp_ms_of_row_id
+        with dev.lock:                                # the steps as normalised above, not normalised again
+            res = dev._search_sequence_unit(unit, k, lo, hi, None, gfn, pfn)
+        return [{"video_name": r["group"], "score": float(r["score"]),
+                 "timestamps": [self.metadata[-i]["timestamp"] for i in r["chain"]],
+                 "frame_ids": [self.metadata[-i]["frame_id"] for i in r["chain"]]} for r in res]
+
     def similar_videos(self, video_name: str, k: int = 5) -> List[Dict]:
         """The k indexed videos most similar to ``video_name``, itself excluded: ``[{'video_name', 'score'}]``, best first.
         Every stored frame of the video takes its best match in the other video; ``score`` is the mean of those cosine
