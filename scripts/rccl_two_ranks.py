@@ -82,8 +82,7 @@ comm.check()
 from video_quierer_amd.indexes.hnsw import MODE_FP16
 bad = OptimizedHNSWIndex(dimension=D, device=DEV)
 big = np.ascontiguousarray(rows[:2000] * np.float32(3.0 if rank == 1 else 1.0))
-_lib.check(_lib.load().vq_index_add(bad._h, _lib.fptr(big), 2000, 0))
-bad._ids = list(range(2000)); bad.element_count = 2000; bad.entry_point = 0
+bad._append_stored(big, range(2000))
 ids.fill_(7)
 try:
     comm.search_sharded(bad, q_t.data_ptr(), 33, 10, 2000 * rank, ids.data_ptr(), dd.data_ptr(), mode=MODE_FP16)

@@ -11,10 +11,7 @@ allv = knn_oracle.normalize_rows(rng.standard_normal((24576, 512)).astype(np.flo
 allq = knn_oracle.normalize_rows(rng.standard_normal((300, 512)).astype(np.float32))
 for n, nq, k in ((16384, 256, 10), (20480, 256, 10), (20001, 256, 10), (20001, 130, 10), (18432, 17, 10), (24576, 300, 10)):
     idx = OptimizedHNSWIndex(dimension=512)
-    idx.add_device  # noqa
-    from video_quierer_amd import _lib
-    _lib.check(_lib.load().vq_index_add(idx._h, _lib.fptr(allv[:n]), n, 0))
-    idx._ids = list(range(n)); idx._row_of = {i: i for i in range(n)}; idx.element_count = n; idx.entry_point = 0
+    idx._append_stored(allv[:n], range(n))                   # stored as given: the rows are unit already
     idx.search_mode = MODE_FP16
     ids, d = idx._raw_search(allq[:nq], k)
     oid, od = knn_oracle.topk(allv[:n], allq[:nq], k)

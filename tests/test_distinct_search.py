@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import knn_oracle
+from index_host_fakes import tie_ranks as _tie_ranks, unit as _unit
 
 GPU = pytest.mark.gpu
 LENGTHS = [1, 7, 63, 64, 65, 300, 3000]          # singletons, both sides of a wave, multi-pass groups
@@ -77,17 +78,6 @@ def video_queries(rows, nq, seed):
     noise = rng.standard_normal((nq, rows.shape[1])) * (1.2 / math.sqrt(rows.shape[1]))
     q = rows[src] + noise
     return (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
-
-
-def _unit(qs):
-    return np.stack([q / np.linalg.norm(q) for q in qs]).astype(np.float32)
-
-
-def _tie_ranks(ids):
-    order = sorted(range(len(ids)), key=ids.__getitem__)
-    rank = np.empty(len(ids), dtype=np.int64)
-    rank[order] = np.arange(len(ids))
-    return rank
 
 
 def _i32(a):

@@ -6,6 +6,7 @@ from ctypes import POINTER, byref, c_float, c_int, c_int32, c_int64
 import numpy as np
 import pytest
 
+from index_host_fakes import bare_index
 from test_distinct_search import greedy_distinct
 
 
@@ -89,12 +90,7 @@ def test_arguments_are_refused_before_the_device_is_touched():
         assert lib.vq_index_search_distinct_device(None, None, 1, k, 1, gap, None, None) == -1
         assert word in lib.vq_last_error()
     # the wrapper: a negative gap raises, k <= 0 answers [] as the other searches do, neither reaches the library
-    import threading
-    from video_quierer_amd.indexes.hnsw import MODE_AUTO, HNSWIndex
-    idx = HNSWIndex.__new__(HNSWIndex)
-    idx._h, idx.dimension, idx.lock, idx.search_mode, idx.search_times = None, 4, threading.RLock(), MODE_AUTO, []
-    idx._ids = ["a_0", "a_1"]
-    idx._row_of, idx._identity, idx._tie_order, idx.element_count, idx.entry_point = {"a_0": 0, "a_1": 1}, False, "device", 2, "a_0"
+    idx = bare_index(["a_0", "a_1"], tie_order="device")
     with pytest.raises(ValueError):
         idx.search_distinct(np.ones(4, np.float32), 2, -1)
     with pytest.raises(ValueError):

@@ -10,19 +10,9 @@ import pytest
 
 from conftest import knn_big_ids, knn_big_inputs
 from oracle import knn_oracle
+from index_host_fakes import tie_ranks as _tie_ranks, unit as _unit
 
 pytestmark = pytest.mark.gpu
-
-
-def _unit(qs):
-    return np.stack([q / np.linalg.norm(q) for q in qs]).astype(np.float32)
-
-
-def _tie_ranks(ids):
-    order = sorted(range(len(ids)), key=ids.__getitem__)
-    rank = np.empty(len(ids), dtype=np.int64)
-    rank[order] = np.arange(len(ids))
-    return rank
 
 
 def _mk(vecs, ids):

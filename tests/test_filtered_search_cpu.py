@@ -1,56 +1,27 @@
 """Host side of the filtered search (HNSWIndex.search_filtered / search_filtered_batch, search_grouped(within=, exclude=)) without
 a device: the within / exclude argument checks, which labels reach the library, and the empty-within short cut."""
-import threading
-
 import numpy as np
 import pytest
 
+from index_host_fakes import bare_index as _index, fake_lib, fill, nothing
+
+
+def _search_filtered(calls, h, q, nq, k, mode, sel, n_sel, exclude, ids, dist):
+    calls.append(("search_filtered", k, mode, [sel[i] for i in range(n_sel)], exclude))
+    nothing((ids, -1), (dist, np.inf))(nq * k)
+    for j in range(nq):                                       # row 2 first, then nothing
+        fill(ids, [2], j * k), fill(dist, [np.float32(0.25)], j * k)
+
+
+def _search_grouped_filtered(calls, h, q, nq, k, mode, sel, n_sel, exclude, groups, rows, dist):
+    calls.append(("search_grouped_filtered", k, mode, [sel[i] for i in range(n_sel)], exclude))
+    nothing((groups, -1), (rows, -1), (dist, np.inf))(nq * k)
+    for j in range(nq):
+        fill(groups, [1], j * k), fill(rows, [2], j * k), fill(dist, [np.float32(0.25)], j * k)
+
 
 def _fake(monkeypatch):
-    from video_quierer_amd import _lib
-    calls = []
-
-    class FakeLib:
-        def vq_index_set_groups(self, h, ptr, n, n_groups):
-            calls.append(("set_groups", [ptr[i] for i in range(n)], n_groups))
-            return 0
-
-        def vq_index_set_id_ranks(self, h, ptr, n):
-            calls.append(("set_id_ranks", n))
-            return 0
-
-        def vq_index_search_grouped(self, h, q, nq, k, mode, groups, rows, dist):
-            calls.append(("search_grouped", k))
-            for i in range(nq * k):
-                groups[i], rows[i], dist[i] = -1, -1, np.inf
-            return 0
-
-        def vq_index_search_filtered(self, h, q, nq, k, mode, sel, n_sel, exclude, ids, dist):
-            calls.append(("search_filtered", k, mode, [sel[i] for i in range(n_sel)], exclude))
-            for i in range(nq * k):                               # row 2 first, then nothing
-                ids[i], dist[i] = (2, np.float32(0.25)) if i % k == 0 else (-1, np.inf)
-            return 0
-
-        def vq_index_search_grouped_filtered(self, h, q, nq, k, mode, sel, n_sel, exclude, groups, rows, dist):
-            calls.append(("search_grouped_filtered", k, mode, [sel[i] for i in range(n_sel)], exclude))
-            for i in range(nq * k):
-                groups[i], rows[i], dist[i] = (1, 2, np.float32(0.25)) if i % k == 0 else (-1, -1, np.inf)
-            return 0
-
-    monkeypatch.setattr(_lib, "load", lambda: FakeLib())
-    return calls
-
-
-def _index(ids):
-    from video_quierer_amd.indexes.hnsw import MODE_AUTO, HNSWIndex
-    idx = HNSWIndex.__new__(HNSWIndex)
-    idx._h, idx.dimension, idx.lock, idx.search_mode, idx.search_times = None, 4, threading.RLock(), MODE_AUTO, []
-    idx._ids = list(ids)
-    idx._row_of = {nid: r for r, nid in enumerate(idx._ids)}
-    idx._identity, idx._tie_order = False, "stale"
-    idx.element_count = len(idx._ids)
-    idx.entry_point = idx._ids[0] if idx._ids else None
-    return idx
+    return fake_lib(monkeypatch, vq_index_search_filtered=_search_filtered, vq_index_search_grouped_filtered=_search_grouped_filtered)
 
 
 IDS = ["a_0", "a_1", "b_0", "c_0", "c_1", "b_1"]        # videos a, b, c -> labels 0, 1, 2

@@ -1225,8 +1225,7 @@ def test_native_comm_world_of_one_over_rccl(gpu_lib):
     from video_quierer_amd.indexes.hnsw import MODE_FP16, OptimizedHNSWIndex
     bad = OptimizedHNSWIndex(dimension=512)
     big = np.ascontiguousarray(rows[:2000] * np.float32(3.0))
-    gpu_lib.check(gpu_lib.load().vq_index_add(bad._h, gpu_lib.fptr(big), 2000, 0))
-    bad._ids = list(range(2000)); bad.element_count = 2000; bad.entry_point = 0
+    bad._append_stored(big, range(2000))
     ids.fill_(7); dd.fill_(7.0)
     with pytest.raises(ValueError, match="fp16 scan needs"):
         comm.search_sharded(bad, q_t.data_ptr(), 33, 10, 0, ids.data_ptr(), dd.data_ptr(), mode=MODE_FP16)

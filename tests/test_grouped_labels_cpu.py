@@ -2,25 +2,11 @@
 vq_index_set_groups, and when."""
 import numpy as np
 
+from index_host_fakes import bare_index as _index, fake_lib
+
 
 def _fake(monkeypatch):
-    from video_quierer_amd import _lib
-    calls = []
-
-    class FakeLib:
-        def vq_index_set_groups(self, h, ptr, n, n_groups):
-            calls.append(([ptr[i] for i in range(n)], n_groups))
-            return 0
-
-    monkeypatch.setattr(_lib, "load", lambda: FakeLib())
-    return calls
-
-
-def _index(ids):
-    from video_quierer_amd.indexes.hnsw import HNSWIndex
-    idx = HNSWIndex.__new__(HNSWIndex)
-    idx._ids, idx._h = list(ids), None
-    return idx
+    return fake_lib(monkeypatch, vq_index_set_groups=lambda calls, h, ptr, n, n_groups: calls.append(([ptr[i] for i in range(n)], n_groups)))
 
 
 def test_default_group_is_the_callers_video_id():

@@ -9,6 +9,7 @@ import pytest
 from conftest import knn_big_ids, knn_big_inputs
 from oracle import knn_oracle
 from test_grouped_search import _expected
+from index_host_fakes import unit as _unit
 
 pytestmark = pytest.mark.gpu
 
@@ -19,10 +20,6 @@ def _i32(a):
 
 def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64).ctypes.data_as(POINTER(c_int64))
-
-
-def _unit(qs):
-    return np.stack([q / np.linalg.norm(q) for q in qs]).astype(np.float32)
 
 
 def _ranks(ids):

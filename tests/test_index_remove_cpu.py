@@ -1,54 +1,13 @@
 """Host-side bookkeeping of row removal (HNSWIndex.remove / remove_batch / remove_group, SimpleVideoIndex.remove_video) without
 a device: which row numbers reach vq_index_remove_rows, and that no search afterwards re-uploads ranks or labels."""
-import threading
-
 import numpy as np
 import pytest
 
-
-def _fake(monkeypatch):
-    from video_quierer_amd import _lib
-    calls = []
-
-    class FakeLib:
-        def vq_index_remove_rows(self, h, ptr, n):
-            calls.append(("remove", [ptr[i] for i in range(n)]))
-            return 0
-
-        def vq_index_set_groups(self, h, ptr, n, n_groups):
-            calls.append(("set_groups", [ptr[i] for i in range(n)], n_groups))
-            return 0
-
-        def vq_index_set_id_ranks(self, h, ptr, n):
-            calls.append(("set_id_ranks", n))
-            return 0
-
-        def vq_index_search(self, h, q, nq, k, mode, ids, dist):
-            calls.append(("search", k))
-            for i in range(nq * k):
-                ids[i], dist[i] = -1, np.inf
-            return 0
-
-        def vq_index_search_grouped(self, h, q, nq, k, mode, groups, rows, dist):
-            calls.append(("search_grouped", k))
-            for i in range(nq * k):
-                groups[i], rows[i], dist[i] = -1, -1, np.inf
-            return 0
-
-    monkeypatch.setattr(_lib, "load", lambda: FakeLib())
-    return calls
+from index_host_fakes import bare_index, fake_lib as _fake
 
 
 def _index(ids, tie_order="device", identity=False):
-    from video_quierer_amd.indexes.hnsw import MODE_AUTO, HNSWIndex
-    idx = HNSWIndex.__new__(HNSWIndex)
-    idx._h, idx.dimension, idx.lock, idx.search_mode, idx.search_times = None, 4, threading.RLock(), MODE_AUTO, []
-    idx._ids = list(ids)
-    idx._row_of = {nid: r for r, nid in enumerate(idx._ids)}
-    idx._identity, idx._tie_order = identity, tie_order
-    idx.element_count = len(idx._ids)
-    idx.entry_point = idx._ids[0] if idx._ids else None
-    return idx
+    return bare_index(ids, tie_order=tie_order, identity=identity)
 
 
 def _consistent(idx):
@@ -189,3 +148,28 @@ def test_simple_video_index_remove_video_bookkeeping(monkeypatch):
     assert svi.video_hashes == {"v2": "h2", "v3": "h3"}
     assert svi._pushed == 2 and dev._ids == [0, -1] and dev._row_of == {0: 0, -1: 1} and dev.element_count == 2
     assert svi.remove_video("nope") == 0 and len(calls) == 1
+
+
+def test_remove_video_labels_rows_added_since_the_last_grouped_search_by_their_old_positions(monkeypatch):
+    """Frames pushed after the labels were last uploaded are labelled inside the removal, through ids that are still the old
+    positions: the metadata must not have shrunk yet (it did once: an IndexError, or the neighbour's video name)."""
+    from index_host_fakes import fake_device, fill
+    from video_quierer_amd.overhaul_index import SimpleVideoIndex
+
+    def no_moment(calls, h, q, nq, k, mode, min_gap, rows, dist):
+        fill(rows, [-1] * (nq * k))
+
+    calls = fake_device(monkeypatch, vq_index_search_distinct=no_moment)
+    svi = SimpleVideoIndex()
+    for i in range(6):
+        svi.add_frame(np.ones(4, np.float32), "ab"[i % 2], float(i))
+    assert svi.search_moments(np.ones(4, np.float32), 2) == []            # ranks, labels and positions of six rows
+    svi.add_frame(np.ones(4, np.float32), "c", 0.0)
+    svi.add_frame(np.ones(4, np.float32), "a", 9.0)
+    svi.search(np.ones(4, np.float32), 1)                                 # pushes the two frames; their labels are not made yet
+    assert svi.remove_video("b") == 3 and calls[-1] == ("remove", [1, 3, 5])
+    dev = svi._dev
+    assert dev._groups.keys == ["a", "c"] and dev._groups.labels.tolist() == [0, 0, 0, 1, 0]
+    assert dev._positions.values.tolist() == [0, 2000, 4000, 0, 9000]
+    assert dev._ids == [0, -1, -2, -3, -4] and [m["video_name"] for m in svi.metadata] == ["a", "a", "a", "c", "a"]
+    _consistent(dev)

@@ -11,26 +11,16 @@ import pytest
 
 from conftest import knn_big_ids, knn_big_inputs
 from oracle import knn_oracle
+from index_host_fakes import tie_ranks as _tie_ranks, unit as _unit
 
 pytestmark = pytest.mark.gpu
 
 SET_KEY_BUDGET = 16 << 20          # csrc/knn_set.h: candidate (group, query) keys the fp16 path holds before it redoes the call exactly
 
 
-def _unit(qs):
-    return np.stack([q / np.linalg.norm(q) for q in qs]).astype(np.float32)
-
-
 def _dense(keys):
     seen = {}
     return np.array([seen.setdefault(g, len(seen)) for g in keys], dtype=np.int64), list(seen)
-
-
-def _tie_ranks(ids):
-    order = sorted(range(len(ids)), key=ids.__getitem__)
-    rank = np.empty(len(ids), dtype=np.int64)
-    rank[order] = np.arange(len(ids))
-    return rank
 
 
 def _expected(stored, uq, labels, tie, k, allowed=None):

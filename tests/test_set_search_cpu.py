@@ -1,57 +1,24 @@
 """Host side of the clip search (HNSWIndex.search_set / similar_groups, SimpleVideoIndex.similar_videos) without a device:
 which labels and flags reach vq_index_search_set, `within` and the self-exclusion folded into one include list, the error
 cases, the short cuts that make no device call, and the shape of the result dicts."""
-import threading
-
 import numpy as np
 import pytest
 
+from index_host_fakes import bare_index as _index, fake_lib, fill
+
 
 def _fake(monkeypatch, stored=None):
-    from video_quierer_amd import _lib
-    calls = []
+    def read_rows(calls, h, rn, n, out):
+        calls.append(("read_rows", [rn[i] for i in range(n)]))
+        fill(out, stored[[rn[i] for i in range(n)]].reshape(-1).tolist())
 
-    class FakeLib:
-        def vq_index_set_groups(self, h, ptr, n, n_groups):
-            calls.append(("set_groups", [ptr[i] for i in range(n)], n_groups))
-            return 0
+    def search_set(calls, h, q, m, k, mode, sel, n_sel, exclude, groups, dist, rows):
+        calls.append(("search_set", m, k, mode, [sel[i] for i in range(n_sel)], exclude, bool(rows), [q[i] for i in range(m * 4)]))
+        fill(groups, [1] + [-1] * (k - 1)), fill(dist, [np.float32(0.25)] + [np.inf] * (k - 1))      # group 1 first, then nothing
+        if rows:
+            fill(rows, [(2 if i % 2 == 0 else 5) if i < m else -1 for i in range(k * m)])
 
-        def vq_index_set_id_ranks(self, h, ptr, n):
-            calls.append(("set_id_ranks", n))
-            return 0
-
-        def vq_index_read_rows(self, h, rn, n, out):
-            calls.append(("read_rows", [rn[i] for i in range(n)]))
-            dim = stored.shape[1]
-            for i in range(n):
-                for c in range(dim):
-                    out[i * dim + c] = stored[rn[i], c]
-            return 0
-
-        def vq_index_search_set(self, h, q, m, k, mode, sel, n_sel, exclude, groups, dist, rows):
-            calls.append(("search_set", m, k, mode, [sel[i] for i in range(n_sel)], exclude, bool(rows),
-                          [q[i] for i in range(m * 4)]))
-            for j in range(k):                                    # group 1 first, then nothing
-                groups[j], dist[j] = (1, np.float32(0.25)) if j == 0 else (-1, np.inf)
-            if rows:
-                for i in range(k * m):
-                    rows[i] = (2 if i % 2 == 0 else 5) if i < m else -1
-            return 0
-
-    monkeypatch.setattr(_lib, "load", lambda: FakeLib())
-    return calls
-
-
-def _index(ids):
-    from video_quierer_amd.indexes.hnsw import MODE_AUTO, HNSWIndex
-    idx = HNSWIndex.__new__(HNSWIndex)
-    idx._h, idx.dimension, idx.lock, idx.search_mode, idx.search_times = None, 4, threading.RLock(), MODE_AUTO, []
-    idx._ids = list(ids)
-    idx._row_of = {nid: r for r, nid in enumerate(idx._ids)}
-    idx._identity, idx._tie_order = False, "stale"
-    idx.element_count = len(idx._ids)
-    idx.entry_point = idx._ids[0] if idx._ids else None
-    return idx
+    return fake_lib(monkeypatch, vq_index_read_rows=read_rows, vq_index_search_set=search_set)
 
 
 IDS = ["a_0", "a_1", "b_0", "c_0", "c_1", "b_1"]        # videos a, b, c -> labels 0, 1, 2

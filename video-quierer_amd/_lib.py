@@ -281,3 +281,11 @@ def device_count() -> int:
 
 def fptr(a):
     return a.ctypes.data_as(POINTER(c_float))
+
+
+def i32ptr(a):
+    return a.ctypes.data_as(POINTER(c_int32))
+
+
+def i64ptr(a):
+    return a.ctypes.data_as(POINTER(c_int64))

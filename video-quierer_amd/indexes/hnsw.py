@@ -23,7 +23,7 @@ import time
 from collections.abc import Iterable, Mapping
 from concurrent.futures import ThreadPoolExecutor
 from itertools import compress
-from ctypes import POINTER, c_float, c_int32, c_int64, c_void_p
+from ctypes import c_float, c_int64, c_void_p
 from typing import Callable, Dict, Hashable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -31,6 +31,8 @@ import numpy as np
 from video_quierer_amd import _lib
 
 MODE_AUTO, MODE_EXACT, MODE_FP16 = 0, 1, 2
+GROUP_OF = Optional[Callable[[Hashable], Hashable]]      # node id -> group key (None: video_of)
+POSITION_OF = Optional[Callable[[Hashable], int]]        # node id -> integer position (None: frame_of)
 
 
 def video_of(node_id: Hashable) -> Hashable:
@@ -53,26 +55,50 @@ def frame_of(node_id: Hashable) -> int:
     raise ValueError(f"frame_of: id {node_id!r} carries no frame number (pass position_of=)")
 
 
-class _Positions:
-    """int32 positions of the rows for ``vq_index_set_positions``, kept like ``_GroupLabels``: only rows added since the last
-    call are mapped, the first distinct search after an add or a removal uploads them; a different ``position_of`` (or a
-    reloaded index) maps everything again.  Derived state: never saved."""
+class _RowState:
+    """Per-row int32 state derived from the ids through a caller's mapping (group labels, positions) and mirrored on the device.
+    Kept like the tie order: only rows added since the last call are mapped, the first search that needs the state after an add
+    or a removal uploads it; another mapping or another id list (``load``) maps everything again.  Never saved."""
 
-    def __init__(self, position_of: Callable[[Hashable], int], ids: List[Hashable]):
-        self.position_of, self.ids = position_of, ids
+    def __init__(self, fn: Callable[[Hashable], Hashable], ids: List[Hashable]):
+        self.fn, self.ids = fn, ids
         self.values = np.empty(0, dtype=np.int32)
-        self.uploaded = -1                        # rows the device positions cover
+        self.uploaded = -1                        # rows the device copy covers
+
+    @classmethod
+    def current(cls, held, fn, ids):
+        """``held`` while it belongs to this mapping and this id list (an add only appends to the list), else a fresh state."""
+        if held is not None and held.fn is fn and held.ids is ids and len(held.values) <= len(ids):
+            return held
+        return cls(fn, ids)
 
     def extend(self) -> bool:
-        """Map the rows added since the last call; True when the device positions are stale."""
+        """Map the rows added since the last call; True when the device copy is stale."""
         n = len(self.ids)
         if len(self.values) < n:
-            fn = self.position_of
-            new = np.array([int(fn(nid)) for nid in self.ids[len(self.values):]], dtype=np.int64)
-            if len(new) and (new.min() < -2 ** 31 or new.max() >= 2 ** 31):
-                raise ValueError("positions must fit a 32-bit signed integer")
-            self.values = np.concatenate([self.values, new.astype(np.int32)])
+            self.values = np.concatenate([self.values, self._map(self.ids[len(self.values):])])
         return self.uploaded != n
+
+    def sync(self, h):
+        """``extend``, and upload when the device copy is stale."""
+        if self.extend():
+            _lib.check(self._upload(h, _lib.i32ptr(self.values), len(self.values)))
+            self.uploaded = len(self.values)
+        return self
+
+
+class _Positions(_RowState):
+    """int32 positions of the rows for ``vq_index_set_positions``."""
+
+    def _map(self, ids) -> np.ndarray:
+        fn = self.fn
+        new = np.array([int(fn(nid)) for nid in ids], dtype=np.int64)
+        if len(new) and (new.min() < -2 ** 31 or new.max() >= 2 ** 31):
+            raise ValueError("positions must fit a 32-bit signed integer")
+        return new.astype(np.int32)
+
+    def _upload(self, h, ptr, n):
+        return _lib.load().vq_index_set_positions(h, ptr, n)
 
     def compact(self, keep: np.ndarray) -> None:
         """The positions of the surviving rows; vq_index_remove_rows drops the device's, so an upload is due."""
@@ -80,45 +106,74 @@ class _Positions:
         self.uploaded = -1
 
 
-class _GroupLabels:
-    """Dense int labels of the rows for ``vq_index_set_groups``, kept like the tie order: group keys are mapped to ints
-    incrementally (only rows added since the last upload are labelled), uploaded by the first grouped search after an add;
-    a different ``group_of`` (or a reloaded index) relabels everything.  Derived state: never saved."""
+class _GroupLabels(_RowState):
+    """Dense int labels of the rows for ``vq_index_set_groups``: group keys are numbered in the order in which they first appear."""
 
-    def __init__(self, group_of: Callable[[Hashable], Hashable], ids: List[Hashable]):
-        self.group_of, self.ids = group_of, ids
+    def __init__(self, fn, ids):
+        super().__init__(fn, ids)
         self.index: Dict[Hashable, int] = {}
         self.keys: List[Hashable] = []
-        self.labels = np.empty(0, dtype=np.int32)
-        self.uploaded = -1                        # rows the device labels cover
 
-    def extend(self) -> bool:
-        """Label the rows added since the last call; True when the device labels are stale."""
-        n = len(self.ids)
-        if len(self.labels) < n:
-            index, keys, fn = self.index, self.keys, self.group_of
-            new = np.empty(n - len(self.labels), dtype=np.int32)
-            for j, nid in enumerate(self.ids[len(self.labels):]):
-                key = fn(nid)
-                g = index.get(key)
-                if g is None:
-                    g = index[key] = len(keys)
-                    keys.append(key)
-                new[j] = g
-            self.labels = np.concatenate([self.labels, new])
-        return self.uploaded != n
+    @property
+    def labels(self) -> np.ndarray:
+        return self.values
+
+    def _map(self, ids) -> np.ndarray:
+        index, keys, fn = self.index, self.keys, self.fn
+        new = np.empty(len(ids), dtype=np.int32)
+        for j, nid in enumerate(ids):
+            key = fn(nid)
+            g = index.get(key)
+            if g is None:
+                g = index[key] = len(keys)
+                keys.append(key)
+            new[j] = g
+        return new
+
+    def _upload(self, h, ptr, n):
+        return _lib.load().vq_index_set_groups(h, ptr, n, len(self.keys))
 
     def compact(self, keep: np.ndarray, current: bool) -> None:
         """The labels of the surviving rows (``keep`` = per-row mask), renumbered as vq_index_remove_rows renumbers the device
         labels: groups left without rows are dropped, the others keep their order.  ``current``: the device held these labels
         for every row before the removal (it then keeps them, renumbered, and no upload is due)."""
-        labels = self.labels[keep]
+        labels = self.values[keep]
         alive = np.bincount(labels, minlength=len(self.keys)) > 0
-        self.labels = (np.cumsum(alive, dtype=np.int64) - 1)[labels].astype(np.int32)
+        self.values = (np.cumsum(alive, dtype=np.int64) - 1)[labels].astype(np.int32)
         if not alive.all():
             self.keys = [key for key, a in zip(self.keys, alive.tolist()) if a]
             self.index = {key: g for g, key in enumerate(self.keys)}
-        self.uploaded = len(self.labels) if current else -1
+        self.uploaded = len(self.values) if current else -1
+
+
+_ONE = np.float32(1.0)
+
+
+def _scored(d: np.float32) -> Dict:
+    """The tail of every result dict: the scan's distance and the score the reference derives from it (hnsw.py:271-277)."""
+    return {"distance": d, "score": _ONE - d}
+
+
+def _hits(to_id, rows: List[int], dist: np.ndarray) -> List[Dict]:
+    """One query's ``[{'id', 'distance', 'score'}]`` from its row numbers (a list; -1 = no row) and distances."""
+    return [{"id": to_id(r), **_scored(d)} for r, d in zip(rows, dist) if r >= 0]
+
+
+def host_tie_order(run, kk: int, n: int, tie_key, finite_only: bool = False) -> List[List]:
+    """The (distance, id) order where the device cannot give it (it orders equal distances by row): ``run(fetch)`` returns the
+    (rows, distances) of the ``fetch`` best rows per query; fetch more than ``kk`` until no group of equal distances is cut at
+    rank ``kk`` (``n`` rows can come back at the most), then sort every query's candidates by ``(distance, tie_key(row))`` on
+    the host.  Returns the first ``kk`` pairs per query.  ``finite_only``: a run of inf (fewer than kk rows allowed) is no tie."""
+    fetch = min(n, kk + 8)
+    while True:
+        rows, dist = run(fetch)
+        cut = dist[:, kk - 1] == dist[:, fetch - 1]
+        if finite_only:
+            cut &= np.isfinite(dist[:, kk - 1])
+        if fetch >= n or not np.any(cut):
+            break
+        fetch = min(n, fetch * 2)
+    return [sorted((d, tie_key(r)) for r, d in zip(rr, rd) if r >= 0)[:kk] for rr, rd in zip(rows.tolist(), dist)]
 
 
 class _RowView(Mapping):
@@ -175,16 +230,27 @@ class HNSWIndex:
         self.search_times: List[float] = []
         self.search_mode = MODE_AUTO
 
+        self._reset_host_state()
+        _lib.init(device)
+        h = c_void_p()
+        _lib.check(_lib.load().vq_index_create(int(dimension), ctypes.byref(h)))
+        self._h = h
+
+    def _reset_host_state(self) -> None:
+        """All the host knows about the rows of an empty index (``__init__``, ``load``)."""
         self._ids: List[Hashable] = []            # row -> caller id
         self._row_of: Dict[Hashable, int] = {}    # caller id -> row
         self._identity = True                     # ids are exactly 0..n-1 in row order
         # (distance, id) tie order on the device (vq_index_set_id_ranks): "stale" until the ranks of the current ids
         # have been uploaded, "device" afterwards, "host" when the ids cannot be put in one order (see _sync_tie_order)
         self._tie_order = "device"
-        _lib.init(device)
-        h = c_void_p()
-        _lib.check(_lib.load().vq_index_create(int(dimension), ctypes.byref(h)))
-        self._h = h
+        self._groups, self._positions = None, None
+
+    # derived per-row state of the grouped / distinct searches, made by the first search that needs it (_sync_groups,
+    # _sync_positions).  Declared on the class as well, so an index that was never given any (one made without __init__)
+    # reads "none yet" like a fresh one.
+    _groups: Optional[_GroupLabels] = None
+    _positions: Optional[_Positions] = None
 
     # -- reference-shaped views of the state (hnsw.py:44-49) ---------------------
     @property
@@ -293,7 +359,7 @@ class HNSWIndex:
                 return
         rank = np.empty(n, dtype=np.int32)
         rank[order] = np.arange(n, dtype=np.int32)
-        _lib.check(_lib.load().vq_index_set_id_ranks(self._h, rank.ctypes.data_as(POINTER(c_int32)), n))
+        _lib.check(_lib.load().vq_index_set_id_ranks(self._h, _lib.i32ptr(rank), n))
         self._tie_order = "device"
 
     def add(self, vector: np.ndarray, node_id: Hashable) -> None:
@@ -316,47 +382,25 @@ class HNSWIndex:
             ids_n = node_ids[:n]
             if self._row_of.keys().isdisjoint(ids_n) and len(set(ids_n)) == n:
                 # the ingest case (video_search_system.py:168-176: every frame id is new): no per-id walk
-                base = len(self._ids)
-                identity = self._identity and self._ids_are_rows(ids_n, base)     # decided before anything is committed
-                _lib.check(_lib.load().vq_index_add(self._h, _lib.fptr(unit), n, 0))
-                self._row_of.update(zip(ids_n, range(base, base + n)))
-                self._identity = identity
-                if not identity:
-                    self._tie_order = "stale"
-                self._ids.extend(ids_n)
-                self.element_count += n                                   # reference counts every add (:229)
-                if self.entry_point is None:
-                    self.entry_point = self._ids[0]
-                self.build_time += time.time() - t0
-                return
-            fresh_rows, fresh_ids = [], []
-            upd_rows, upd_src = [], []                                   # re-added ids: (stored row, batch position), in call order
-            seen_now: Dict[Hashable, int] = {}
-            for j, nid in enumerate(ids_n):
-                if nid in self._row_of:
-                    upd_rows.append(self._row_of[nid]); upd_src.append(j)
-                elif nid in seen_now:                                    # later duplicate wins (dict semantics)
-                    fresh_rows[seen_now[nid]] = j
-                else:
-                    seen_now[nid] = len(fresh_rows)
-                    fresh_rows.append(j)
-                    fresh_ids.append(nid)
-                self.element_count += 1                                   # reference counts every add (:229)
-            if upd_rows:
-                self._overwrite(upd_rows, unit if len(upd_src) == n else np.ascontiguousarray(unit[upd_src]))
-            if fresh_rows:
-                block = unit if len(fresh_rows) == n else np.ascontiguousarray(unit[fresh_rows])
-                _lib.check(_lib.load().vq_index_add(self._h, _lib.fptr(block), len(fresh_rows), 0))
-                base = len(self._ids)
-                for j, nid in enumerate(fresh_ids):
-                    self._row_of[nid] = base + j
-                    if self._identity and not (isinstance(nid, (int, np.integer)) and int(nid) == base + j):
-                        self._identity = False
-                self._ids.extend(fresh_ids)
-                if not self._identity:
-                    self._tie_order = "stale"
-            if self.entry_point is None and self._ids:
-                self.entry_point = self._ids[0]
+                self._append_stored(unit, ids_n)
+            else:
+                fresh_rows, fresh_ids = [], []
+                upd_rows, upd_src = [], []                               # re-added ids: (stored row, batch position), in call order
+                seen_now: Dict[Hashable, int] = {}
+                for j, nid in enumerate(ids_n):
+                    if nid in self._row_of:
+                        upd_rows.append(self._row_of[nid]); upd_src.append(j)
+                    elif nid in seen_now:                                # later duplicate wins (dict semantics)
+                        fresh_rows[seen_now[nid]] = j
+                    else:
+                        seen_now[nid] = len(fresh_rows)
+                        fresh_rows.append(j)
+                        fresh_ids.append(nid)
+                if upd_rows:
+                    self._overwrite(upd_rows, unit if len(upd_src) == n else np.ascontiguousarray(unit[upd_src]))
+                if fresh_rows:
+                    self._append_stored(unit if len(fresh_rows) == n else np.ascontiguousarray(unit[fresh_rows]), fresh_ids)
+                self.element_count += n - len(fresh_ids)                  # reference counts every add (:229), re-adds included
         self.build_time += time.time() - t0
 
     def add_device(self, d_rows: int, n: int, node_ids: Sequence[Hashable], normalize: bool = True) -> None:
@@ -367,25 +411,46 @@ class HNSWIndex:
         with self.lock:
             if not self._row_of.keys().isdisjoint(node_ids) or len(set(node_ids)) != n:
                 raise ValueError("add_device: ids must be new and unique")
-            base = len(self._ids)
-            identity = self._identity and self._ids_are_rows(node_ids, base)
             _lib.check(_lib.load().vq_index_add_device(self._h, c_void_p(d_rows), n, int(bool(normalize))))
-            self._row_of.update(zip(node_ids, range(base, base + n)))       # (a per-id loop here cost 45 ms per 250k rows)
-            self._identity = identity
-            if not identity:
-                self._tie_order = "stale"
-            self._ids.extend(node_ids)
-            self.element_count += n
-            if self.entry_point is None and self._ids:
-                self.entry_point = self._ids[0]
+            self._commit_rows(node_ids)
+
+    def _append_stored(self, rows: np.ndarray, node_ids: Sequence[Hashable]) -> None:
+        """Append a block of fp32 rows stored AS GIVEN (the library measures them, vq_index_add normalize=0; a block that is
+        not unit-norm still searches exactly, on the fp32 scan) under new, unique ids of the caller's choice."""
+        node_ids = list(node_ids)
+        with self.lock:
+            _lib.check(_lib.load().vq_index_add(self._h, _lib.fptr(rows), len(node_ids), 0))
+            self._commit_rows(node_ids)
+
+    def _commit_rows(self, node_ids: List[Hashable]) -> None:
+        """The host's side of an append: ``node_ids`` (new, unique) name the rows the device just added at its end."""
+        base = len(self._ids)
+        identity = self._identity and self._ids_are_rows(node_ids, base)     # decided before anything changes
+        self._row_of.update(zip(node_ids, range(base, base + len(node_ids))))     # (a per-id loop here cost 45 ms per 250k rows)
+        self._ids.extend(node_ids)
+        self._identity = identity
+        if not identity:
+            self._tie_order = "stale"
+        self.element_count += len(node_ids)                               # reference counts every add (:229)
+        if self.entry_point is None:
+            self.entry_point = self._ids[0]
+
+    def _replace_ids(self, node_ids: List[Hashable]) -> None:
+        """Rename every row (a caller whose ids are positions renumbers them after a removal).  The new ids must sort as the old
+        ones did: ranks, labels and positions on the device stay as they are."""
+        with self.lock:
+            if len(node_ids) != len(self._ids):
+                raise ValueError("_replace_ids: one id per row")
+            self._ids[:] = node_ids                                       # in place: the derived state holds this list
+            self._row_of = {nid: r for r, nid in enumerate(node_ids)}
+            self.entry_point = node_ids[0] if node_ids else None
 
     def _overwrite(self, rows: Sequence[int], unit_vecs: np.ndarray) -> None:
         """Re-adding an id replaces its vector (a dict assignment in the reference, hnsw.py:160): the stored rows are
         replaced in place on the device — fp32 master, fp16 scan copy, norm range — in one call; a row named twice
         keeps its last vector, as sequential assignments would leave it."""
         rn = np.ascontiguousarray(rows, dtype=np.int64)
-        _lib.check(_lib.load().vq_index_update_rows(self._h, _lib.fptr(unit_vecs), rn.ctypes.data_as(POINTER(ctypes.c_int64)),
-                                                    len(rn), 0))
+        _lib.check(_lib.load().vq_index_update_rows(self._h, _lib.fptr(unit_vecs), _lib.i64ptr(rn), len(rn), 0))
 
     # -- removal (reference: `del self.data[node_id]`; video_search_system.py:427-463 delete_video) -------------------
     def remove(self, node_id: Hashable) -> None:
@@ -400,16 +465,19 @@ class HNSWIndex:
             rows = np.fromiter({row_of[nid] for nid in node_ids}, dtype=np.int64)
             return self._remove_rows(np.sort(rows))
 
-    def remove_group(self, group: Hashable, group_of: Optional[Callable[[Hashable], Hashable]] = None) -> int:
+    def remove_group(self, group: Hashable, group_of: GROUP_OF = None) -> int:
         """Take every row of one group out (default ``video_of``: the caller's ``delete_video(video_id)``); returns the number
         of rows removed (0 for a group the index does not hold).  The rows are found through the host group labels."""
         with self.lock:
-            gl = self._group_labels(group_of)
-            gl.extend()
-            g = gl.index.get(group)
-            if g is None:
-                return 0
-            return self._remove_rows(np.flatnonzero(gl.labels == g).astype(np.int64))
+            rows = self._group_rows(group, group_of)
+            return 0 if rows is None else self._remove_rows(rows)
+
+    def _group_rows(self, group: Hashable, group_of: GROUP_OF) -> Optional[np.ndarray]:
+        """The rows of one group, ascending, through the host labels (nothing is uploaded); None for a group the index lacks."""
+        gl = self._group_labels(group_of)
+        gl.extend()
+        g = gl.index.get(group)
+        return None if g is None else np.flatnonzero(gl.labels == g).astype(np.int64)
 
     def _remove_rows(self, rows: np.ndarray) -> int:
         """rows: sorted, unique, valid row numbers.  The device compacts the matrix, the id ranks and the group labels
@@ -420,19 +488,14 @@ class HNSWIndex:
             return 0
         ids = self._ids
         n = len(ids)
-        gl = getattr(self, "_groups", None)
-        if gl is not None and gl.ids is not ids:
-            gl = None                                            # labels of a replaced id list: relabelled on next use
-        if gl is not None:
-            gl.extend()                                          # host labels for every row (no upload)
-        ps = getattr(self, "_positions", None)
-        if ps is not None and ps.ids is not ids:
-            ps = self._positions = None
-        if ps is not None:
-            ps.extend()
+        # derived state of a replaced id list is mapped again on its next use; the rest gets every row mapped (no upload)
+        gl, ps = (st if st is not None and st.ids is ids else None for st in (self._groups, self._positions))
+        for st in (gl, ps):
+            if st is not None:
+                st.extend()
         current = gl is not None and gl.uploaded == n
         rows = np.ascontiguousarray(rows, dtype=np.int64)
-        _lib.check(_lib.load().vq_index_remove_rows(self._h, rows.ctypes.data_as(POINTER(c_int64)), m))
+        _lib.check(_lib.load().vq_index_remove_rows(self._h, _lib.i64ptr(rows), m))
         keep = np.ones(n, dtype=bool)
         keep[rows] = False
         first = int(rows[0])
@@ -459,10 +522,20 @@ class HNSWIndex:
         ids = np.empty((nq, k), dtype=np.int32)
         dist = np.empty((nq, k), dtype=np.float32)
         _lib.check(_lib.load().vq_index_search(self._h, _lib.fptr(unit_queries), nq, k, int(self.search_mode),
-                                               ids.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist)))
+                                               _lib.i32ptr(ids), _lib.fptr(dist)))
         return ids, dist
 
+    def _id_of(self):
+        """The function that maps a row number to the caller's id."""
+        return int if self._identity else self._ids.__getitem__
+
+    def _host_ties(self) -> bool:
+        """Do the ids lack a common order (``_sync_tie_order`` has run), so that (distance, id) is established on the host?"""
+        return not self._identity and self._tie_order != "device"
+
     def _search_many(self, queries: Sequence[np.ndarray], k: int) -> List[List[Dict]]:
+        # the plain search is the latency path (one synchronous call per query in the reference caller): its few steps are
+        # spelt out here instead of going through _prepare
         n = len(self._ids)
         unit = np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32)
         if unit.shape[1] != self.dimension:
@@ -470,32 +543,17 @@ class HNSWIndex:
         kk = min(k, n)
         if kk <= 0:
             return [[] for _ in queries]          # reference: sorted(candidates)[:0] == [] (hnsw.py:269)
-        if self._identity:
-            ids, dist = self._raw_search(unit, kk)
-            return [[{"id": int(i), "distance": d, "score": np.float32(1.0) - d} for i, d in zip(ri, rd) if i >= 0]
-                    for ri, rd in zip(ids, dist)]
-        self._sync_tie_order()
-        if self._tie_order == "device":
-            # the caller's ids (strings f"{video_id}_{i}", video_search_system.py:164-166): the device already ordered by
-            # (distance, id rank) — exactly k results fetched, rows mapped to ids, nothing re-sorted
-            ids, dist = self._raw_search(unit, kk)
-            names = self._ids
-            return [[{"id": names[i], "distance": d, "score": np.float32(1.0) - d} for i, d in zip(ri.tolist(), rd) if i >= 0]
-                    for ri, rd in zip(ids, dist)]
-        # ids without a common order: the library orders ties by row; the reference orders them by id
-        # (hnsw.py:269/518).  Over-fetch until no tie group is cut at rank k, then re-sort.
-        fetch = min(n, kk + 8)
-        while True:
-            ids, dist = self._raw_search(unit, fetch)
-            cut = fetch < n and np.any(dist[:, kk - 1] == dist[:, fetch - 1])
-            if not cut:
-                break
-            fetch = min(n, fetch * 2)
-        out = []
-        for ri, rd in zip(ids, dist):
-            cand = sorted(((d, self._ids[i]) for i, d in zip(ri, rd) if i >= 0))[:kk]
-            out.append([{"id": i, "distance": d, "score": np.float32(1.0) - d} for d, i in cand])
-        return out
+        if not self._identity:
+            self._sync_tie_order()
+        if self._host_ties():
+            # ids without a common order: the library orders ties by row, the reference by id (hnsw.py:269/518)
+            best = host_tie_order(lambda fetch: self._raw_search(unit, fetch), kk, n, self._ids.__getitem__)
+            return [[{"id": i, **_scored(d)} for d, i in cand] for cand in best]
+        # row numbers, or the caller's ids (strings f"{video_id}_{i}", video_search_system.py:164-166) with their ranks on the
+        # device: it already ordered by (distance, id) — exactly k results fetched, rows mapped to ids, nothing re-sorted
+        rows, dist = self._raw_search(unit, kk)
+        to_id = self._id_of()
+        return [_hits(to_id, rr, rd) for rr, rd in zip(rows.tolist(), dist)]
 
     def search(self, query: np.ndarray, k: int = 5) -> List[Dict]:
         """Reference :238-280 / :488-528."""
@@ -530,58 +588,62 @@ class HNSWIndex:
                                                           int(self.search_mode if mode is None else mode),
                                                           c_void_p(d_ids), c_void_p(d_dist)))
 
-    # -- grouped query: the k best videos, one best frame each ----------------------------
-    def _group_labels(self, group_of: Optional[Callable[[Hashable], Hashable]]) -> _GroupLabels:
-        fn = video_of if group_of is None else group_of
-        gl = getattr(self, "_groups", None)
-        # relabel when the mapping changed or the id list was replaced (load); add_batch only appends to it
-        if gl is None or gl.group_of is not fn or gl.ids is not self._ids or len(gl.labels) > len(self._ids):
-            gl = self._groups = _GroupLabels(fn, self._ids)
-        return gl
+    # -- what every other search family does before its C call ------------------------------------------------------------
+    def _empty(self) -> bool:
+        return self.entry_point is None or self.element_count == 0
 
-    def _sync_groups(self, group_of: Optional[Callable[[Hashable], Hashable]]) -> _GroupLabels:
-        gl = self._group_labels(group_of)
-        if gl.extend():
-            n = len(gl.labels)
-            _lib.check(_lib.load().vq_index_set_groups(self._h, gl.labels.ctypes.data_as(POINTER(c_int32)), n, len(gl.keys)))
-            gl.uploaded = n
-        return gl
+    def _group_labels(self, group_of: GROUP_OF) -> _GroupLabels:
+        """The host's labels under ``group_of`` (default ``video_of``); nothing is mapped or uploaded yet."""
+        self._groups = _GroupLabels.current(self._groups, video_of if group_of is None else group_of, self._ids)
+        return self._groups
 
-    def _grouped_many(self, queries: Sequence[np.ndarray], k: int, group_of, flt=None) -> List[List[Dict]]:
-        filtered = flt is not None
-        if filtered:
-            fkeys, excl = flt
-        unit = np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32)
+    def _sync_groups(self, group_of: GROUP_OF) -> _GroupLabels:
+        return self._group_labels(group_of).sync(self._h)
+
+    def _sync_positions(self, position_of: POSITION_OF) -> _Positions:
+        self._positions = _Positions.current(self._positions, frame_of if position_of is None else position_of, self._ids)
+        return self._positions.sync(self._h)
+
+    @staticmethod
+    def _filter_arg(within, exclude, required: bool = False) -> Optional[Tuple[List[Hashable], bool]]:
+        """(group keys, exclude?) of a ``within`` / ``exclude`` pair, each an iterable of keys; None when neither is given."""
+        if within is None and exclude is None and not required:
+            return None
+        if (within is None) == (exclude is None):
+            raise ValueError("give exactly one of `within` and `exclude` (an iterable of group keys)")
+        keys = within if within is not None else exclude
+        if isinstance(keys, (str, bytes)) or not isinstance(keys, Iterable):
+            raise ValueError("`within` / `exclude` take an iterable of group keys (a list of video ids), not one key")
+        return list(keys), exclude is not None
+
+    def _prepare(self, queries, k: int, *, given: bool = False, group_of: GROUP_OF = None, positions: bool = False,
+                 position_of: POSITION_OF = None, flt: Optional[Tuple[List[Hashable], bool]] = None, what: str = "query"):
+        """The common start of the grouped, filtered, distinct, clip and sequence searches, under the lock, in the order the
+        callers rely on: the queries normalised as ``search`` does (``given``: fp32 [nq][dim], used as they are), their
+        dimension checked; then the answers that need no device (k <= 0, an empty index, an empty ``within``: None is
+        returned and the caller answers empty); then the device is given what the C call needs: the tie order, the group
+        labels under ``group_of``, the positions under ``position_of`` if asked for, in that order, each uploaded only when
+        stale.  ``flt`` (``_filter_arg``) becomes the ascending labels of the keys the index holds (unknown keys hold no
+        rows); a ``within`` that names none of them is None again, after the uploads.  Without ``flt`` nothing is excluded.
+        Returns (unit queries, group labels, positions or None, filter labels, exclude flag)."""
+        unit = queries if given else np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32)
         if unit.shape[1] != self.dimension:
-            raise ValueError(f"query dimension {unit.shape[1]} != index dimension {self.dimension}")
-        if k <= 0 or not self._ids or (filtered and not excl and not fkeys):
-            return [[] for _ in queries]
+            raise ValueError(f"{what} dimension {unit.shape[1]} != index dimension {self.dimension}")
+        keys, excl = flt if flt is not None else ((), True)
+        if k <= 0 or not self._ids or (not excl and not keys):
+            return None
         if not self._identity:
             self._sync_tie_order()
         gl = self._sync_groups(group_of)
-        kk = min(int(k), len(gl.keys))
-        nq = unit.shape[0]
-        groups = np.empty((nq, kk), dtype=np.int32)
-        rows = np.empty((nq, kk), dtype=np.int32)
-        dist = np.empty((nq, kk), dtype=np.float32)
-        if not filtered:
-            _lib.check(_lib.load().vq_index_search_grouped(self._h, _lib.fptr(unit), nq, kk, int(self.search_mode),
-                                                           groups.ctypes.data_as(POINTER(c_int32)),
-                                                           rows.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist)))
-        else:
-            labels = self._filter_labels(gl, fkeys)
-            if not excl and len(labels) == 0:
-                return [[] for _ in queries]
-            _lib.check(_lib.load().vq_index_search_grouped_filtered(
-                self._h, _lib.fptr(unit), nq, kk, int(self.search_mode), labels.ctypes.data_as(POINTER(c_int32)), len(labels),
-                int(excl), groups.ctypes.data_as(POINTER(c_int32)), rows.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist)))
-        keys, names, identity = gl.keys, self._ids, self._identity
-        return [[{"group": keys[g], "id": int(r) if identity else names[r], "distance": d, "score": np.float32(1.0) - d}
-                 for g, r, d in zip(rg.tolist(), rr.tolist(), rd) if r >= 0]
-                for rg, rr, rd in zip(groups, rows, dist)]
+        ps = self._sync_positions(position_of) if positions else None
+        index = gl.index
+        labels = np.array(sorted({index[key] for key in keys if key in index}), dtype=np.int32)
+        if not excl and len(labels) == 0:
+            return None
+        return unit, gl, ps, labels, excl
 
-    def search_grouped(self, query: np.ndarray, k: int = 5,
-                       group_of: Optional[Callable[[Hashable], Hashable]] = None, *,
+    # -- grouped query: the k best videos, one best frame each ----------------------------
+    def search_grouped(self, query: np.ndarray, k: int = 5, group_of: GROUP_OF = None, *,
                        within: Optional[Iterable[Hashable]] = None, exclude: Optional[Iterable[Hashable]] = None) -> List[Dict]:
         """The k best GROUPS (videos) for one query, each with its best row: ``[{'group', 'id', 'distance', 'score'}]``.
         Exactly the plain search's exhaustive (distance, id) list with every row dropped whose group came earlier — what
@@ -591,222 +653,142 @@ class HNSWIndex:
         passes ``lambda nid: meta[nid]['video_id']`` — keep passing the SAME callable, a different one relabels every row.
         ``within`` / ``exclude`` (at most one, an iterable of group keys) restrict the search to those groups or to all the
         others, exactly as ``search_filtered`` does."""
-        flt = self._filter_arg(within, exclude) if within is not None or exclude is not None else None
-        if self.entry_point is None or self.element_count == 0:
-            return []
-        with self.lock:
-            return self._grouped_many([query], k, group_of, flt)[0]
+        return self.search_grouped_batch([query], k, group_of, within=within, exclude=exclude)[0]
 
-    def search_grouped_batch(self, queries: List[np.ndarray], k: int = 5,
-                             group_of: Optional[Callable[[Hashable], Hashable]] = None, *,
+    def search_grouped_batch(self, queries: List[np.ndarray], k: int = 5, group_of: GROUP_OF = None, *,
                              within: Optional[Iterable[Hashable]] = None,
                              exclude: Optional[Iterable[Hashable]] = None) -> List[List[Dict]]:
         """``search_grouped`` for a batch of queries, one device pass."""
-        flt = self._filter_arg(within, exclude) if within is not None or exclude is not None else None
+        flt = self._filter_arg(within, exclude)
         if len(queries) == 0:
             return []
-        if self.entry_point is None or self.element_count == 0:
+        if self._empty():
             return [[] for _ in queries]
         with self.lock:
-            return self._grouped_many(queries, k, group_of, flt)
+            ready = self._prepare(queries, k, group_of=group_of, flt=flt)
+            if ready is None:
+                return [[] for _ in queries]
+            unit, gl, _, labels, excl = ready
+            nq, kk = unit.shape[0], min(int(k), len(gl.keys))
+            groups = np.empty((nq, kk), dtype=np.int32)
+            rows = np.empty((nq, kk), dtype=np.int32)
+            dist = np.empty((nq, kk), dtype=np.float32)
+            out = _lib.i32ptr(groups), _lib.i32ptr(rows), _lib.fptr(dist)
+            if flt is None:
+                _lib.check(_lib.load().vq_index_search_grouped(self._h, _lib.fptr(unit), nq, kk, int(self.search_mode), *out))
+            else:
+                _lib.check(_lib.load().vq_index_search_grouped_filtered(self._h, _lib.fptr(unit), nq, kk, int(self.search_mode),
+                                                                        _lib.i32ptr(labels), len(labels), int(excl), *out))
+            keys, to_id = gl.keys, self._id_of()
+            return [[{"group": keys[g], "id": to_id(r), **_scored(d)} for g, r, d in zip(rg, rr, rd) if r >= 0]
+                    for rg, rr, rd in zip(groups.tolist(), rows.tolist(), dist)]
 
     # -- distinct moments: the k best rows, two of one group at least min_gap positions apart ------------
-    def _sync_positions(self, position_of: Optional[Callable[[Hashable], int]]) -> _Positions:
-        fn = frame_of if position_of is None else position_of
-        ps = getattr(self, "_positions", None)
-        if ps is None or ps.position_of is not fn or ps.ids is not self._ids or len(ps.values) > len(self._ids):
-            ps = self._positions = _Positions(fn, self._ids)
-        if ps.extend():
-            n = len(ps.values)
-            _lib.check(_lib.load().vq_index_set_positions(self._h, ps.values.ctypes.data_as(POINTER(c_int32)), n))
-            ps.uploaded = n
-        return ps
-
-    def _distinct_many(self, queries: Sequence[np.ndarray], k: int, min_gap: int, group_of, position_of) -> List[List[Dict]]:
-        min_gap = int(min_gap)
-        if min_gap < 0:
-            raise ValueError(f"min_gap must be >= 0, got {min_gap}")
-        return self._distinct_unit(np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32), k, min_gap, group_of, position_of)
-
-    def _distinct_unit(self, unit: np.ndarray, k: int, min_gap: int, group_of, position_of) -> List[List[Dict]]:
-        """unit: [nq][dim] fp32 queries, used as given (SimpleVideoIndex normalises by its own rule)."""
-        if unit.shape[1] != self.dimension:
-            raise ValueError(f"query dimension {unit.shape[1]} != index dimension {self.dimension}")
-        kk = min(int(k), len(self._ids))
-        if kk <= 0:
-            return [[] for _ in unit]
-        if not self._identity:
-            self._sync_tie_order()
-        gl = self._sync_groups(group_of)
-        ps = self._sync_positions(position_of)
-        nq = unit.shape[0]
-        rows = np.empty((nq, kk), dtype=np.int32)
-        dist = np.empty((nq, kk), dtype=np.float32)
-        _lib.check(_lib.load().vq_index_search_distinct(self._h, _lib.fptr(unit), nq, kk, int(self.search_mode), min_gap,
-                                                        rows.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist)))
-        keys, labels, pos, names, identity = gl.keys, gl.labels, ps.values, self._ids, self._identity
-        return [[{"id": int(r) if identity else names[r], "group": keys[labels[r]], "position": int(pos[r]), "distance": d,
-                  "score": np.float32(1.0) - d} for r, d in zip(rr.tolist(), rd) if r >= 0]
-                for rr, rd in zip(rows, dist)]
-
-    def search_distinct(self, query: np.ndarray, k: int = 5, min_gap: int = 1, *,
-                        group_of: Optional[Callable[[Hashable], Hashable]] = None,
-                        position_of: Optional[Callable[[Hashable], int]] = None) -> List[Dict]:
+    def search_distinct(self, query: np.ndarray, k: int = 5, min_gap: int = 1, *, group_of: GROUP_OF = None,
+                        position_of: POSITION_OF = None) -> List[Dict]:
         """The k best distinct MOMENTS for one query: ``[{'id', 'group', 'position', 'distance', 'score'}]``.  Exactly the plain
         search's exhaustive (distance, id) list, walked in order, with every row dropped that lies less than ``min_gap``
         positions from an already kept row of the same group.  ``min_gap=0`` is ``search``; a gap above every position
         difference is ``search_grouped``'s rows.  ``group_of`` as ``search_grouped``; ``position_of`` maps a node id to an
         integer position that fits 32 bits (default ``frame_of``: the frame number of ``f"{video_id}_{i}"``; pass timestamps
         in ms and a gap in ms alike) — keep passing the SAME callables, a different one maps every row again."""
-        if self.entry_point is None or self.element_count == 0:
-            if int(min_gap) < 0:
-                raise ValueError(f"min_gap must be >= 0, got {min_gap}")
-            return []
-        with self.lock:
-            return self._distinct_many([query], k, min_gap, group_of, position_of)[0]
+        return self.search_distinct_batch([query], k, min_gap, group_of=group_of, position_of=position_of)[0]
 
-    def search_distinct_batch(self, queries: List[np.ndarray], k: int = 5, min_gap: int = 1, *,
-                              group_of: Optional[Callable[[Hashable], Hashable]] = None,
-                              position_of: Optional[Callable[[Hashable], int]] = None) -> List[List[Dict]]:
+    def search_distinct_batch(self, queries: List[np.ndarray], k: int = 5, min_gap: int = 1, *, group_of: GROUP_OF = None,
+                              position_of: POSITION_OF = None) -> List[List[Dict]]:
         """``search_distinct`` for a batch of queries, one device pass."""
         if int(min_gap) < 0:
             raise ValueError(f"min_gap must be >= 0, got {min_gap}")
         if len(queries) == 0:
             return []
-        if self.entry_point is None or self.element_count == 0:
+        if self._empty():
             return [[] for _ in queries]
         with self.lock:
-            return self._distinct_many(queries, k, min_gap, group_of, position_of)
+            return self._distinct_many(queries, k, int(min_gap), group_of, position_of)
+
+    def _distinct_many(self, queries, k: int, min_gap: int, group_of, position_of, given: bool = False) -> List[List[Dict]]:
+        """``given``: see ``_prepare`` (SimpleVideoIndex normalises by its own rule).  min_gap: checked."""
+        ready = self._prepare(queries, k, given=given, group_of=group_of, positions=True, position_of=position_of)
+        if ready is None:
+            return [[] for _ in queries]
+        unit, gl, ps, _, _ = ready
+        nq, kk = unit.shape[0], min(int(k), len(self._ids))
+        rows = np.empty((nq, kk), dtype=np.int32)
+        dist = np.empty((nq, kk), dtype=np.float32)
+        _lib.check(_lib.load().vq_index_search_distinct(self._h, _lib.fptr(unit), nq, kk, int(self.search_mode), min_gap,
+                                                        _lib.i32ptr(rows), _lib.fptr(dist)))
+        keys, labels, pos, to_id = gl.keys, gl.labels, ps.values, self._id_of()
+        return [[{"id": to_id(r), "group": keys[labels[r]], "position": int(pos[r]), **_scored(d)} for r, d in zip(rr, rd) if r >= 0]
+                for rr, rd in zip(rows.tolist(), dist)]
 
     # -- filtered query: the plain search within, or excluding, a set of groups (videos) -------------
-    @staticmethod
-    def _filter_arg(within, exclude) -> Tuple[List[Hashable], bool]:
-        """(group keys, exclude?) of a ``within`` / ``exclude`` pair: exactly one of them, an iterable of keys."""
-        if (within is None) == (exclude is None):
-            raise ValueError("give exactly one of `within` and `exclude` (an iterable of group keys)")
-        keys = within if within is not None else exclude
-        if isinstance(keys, (str, bytes)) or not isinstance(keys, Iterable):
-            raise ValueError("`within` / `exclude` take an iterable of group keys (a list of video ids), not one key")
-        return list(keys), exclude is not None
-
-    @staticmethod
-    def _filter_labels(gl: _GroupLabels, keys: List[Hashable]) -> np.ndarray:
-        """The dense labels of the keys the index holds, ascending; unknown keys hold no rows and are dropped."""
-        index = gl.index
-        return np.array(sorted({index[key] for key in keys if key in index}), dtype=np.int32)
-
-    def _filtered_many(self, queries: Sequence[np.ndarray], k: int, flt: Tuple[List[Hashable], bool], group_of) -> List[List[Dict]]:
-        keys, excl = flt
-        unit = np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32)
-        if unit.shape[1] != self.dimension:
-            raise ValueError(f"query dimension {unit.shape[1]} != index dimension {self.dimension}")
-        n = len(self._ids)
-        kk = min(int(k), n)
-        if kk <= 0 or (not excl and not keys):
-            return [[] for _ in queries]                 # nothing allowed: no device call
-        if not self._identity:
-            self._sync_tie_order()
-        gl = self._sync_groups(group_of)
-        labels = self._filter_labels(gl, keys)
-        if not excl and len(labels) == 0:
-            return [[] for _ in queries]
-        nq = unit.shape[0]
-
-        def run(fetch):
-            ids = np.empty((nq, fetch), dtype=np.int32)
-            dist = np.empty((nq, fetch), dtype=np.float32)
-            _lib.check(_lib.load().vq_index_search_filtered(
-                self._h, _lib.fptr(unit), nq, fetch, int(self.search_mode), labels.ctypes.data_as(POINTER(c_int32)), len(labels),
-                int(excl), ids.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist)))
-            return ids, dist
-
-        if self._identity or self._tie_order == "device":
-            ids, dist = run(kk)
-            names = None if self._identity else self._ids
-            return [[{"id": int(i) if names is None else names[i], "distance": d, "score": np.float32(1.0) - d}
-                     for i, d in zip(ri.tolist(), rd) if i >= 0] for ri, rd in zip(ids, dist)]
-        # ids without a common order: as _search_many, over-fetch until no tie group is cut at rank k, then re-sort
-        fetch = min(n, kk + 8)
-        while True:
-            ids, dist = run(fetch)
-            cut = fetch < n and np.any((dist[:, kk - 1] == dist[:, fetch - 1]) & np.isfinite(dist[:, kk - 1]))
-            if not cut:
-                break
-            fetch = min(n, fetch * 2)
-        out = []
-        for ri, rd in zip(ids, dist):
-            cand = sorted(((d, self._ids[i]) for i, d in zip(ri, rd) if i >= 0))[:kk]
-            out.append([{"id": i, "distance": d, "score": np.float32(1.0) - d} for d, i in cand])
-        return out
-
     def search_filtered(self, query: np.ndarray, k: int = 5, *, within: Optional[Iterable[Hashable]] = None,
-                        exclude: Optional[Iterable[Hashable]] = None,
-                        group_of: Optional[Callable[[Hashable], Hashable]] = None) -> List[Dict]:
+                        exclude: Optional[Iterable[Hashable]] = None, group_of: GROUP_OF = None) -> List[Dict]:
         """``search`` restricted to the rows of some groups (videos): ``within=[video_id]`` searches inside one video,
         ``exclude=[video_of(frame_id)]`` finds more like a frame from the other videos, ``within=collection`` searches a set.
         Exactly one of ``within`` / ``exclude`` is given, as an iterable of group keys (``group_of`` as ``search_grouped``;
         unknown keys hold no rows).  The result is what ``search`` returns on an index holding only the allowed rows: the same
         dicts, distances and (distance, id) order, exact for any k however few rows the filter allows."""
-        flt = self._filter_arg(within, exclude)
-        if self.entry_point is None or self.element_count == 0:
-            return []
-        with self.lock:
-            return self._filtered_many([query], k, flt, group_of)[0]
+        return self.search_filtered_batch([query], k, within=within, exclude=exclude, group_of=group_of)[0]
 
     def search_filtered_batch(self, queries: List[np.ndarray], k: int = 5, *, within: Optional[Iterable[Hashable]] = None,
-                              exclude: Optional[Iterable[Hashable]] = None,
-                              group_of: Optional[Callable[[Hashable], Hashable]] = None) -> List[List[Dict]]:
+                              exclude: Optional[Iterable[Hashable]] = None, group_of: GROUP_OF = None) -> List[List[Dict]]:
         """``search_filtered`` for a batch of queries (one filter for all of them), one device pass."""
-        flt = self._filter_arg(within, exclude)
+        flt = self._filter_arg(within, exclude, required=True)
         if len(queries) == 0:
             return []
-        if self.entry_point is None or self.element_count == 0:
+        if self._empty():
             return [[] for _ in queries]
         with self.lock:
-            return self._filtered_many(queries, k, flt, group_of)
+            ready = self._prepare(queries, k, group_of=group_of, flt=flt)
+            if ready is None:
+                return [[] for _ in queries]                 # nothing allowed: no device call
+            unit, _, _, labels, excl = ready
+            nq, n = unit.shape[0], len(self._ids)
+            kk = min(int(k), n)
+
+            def run(fetch):
+                rows = np.empty((nq, fetch), dtype=np.int32)
+                dist = np.empty((nq, fetch), dtype=np.float32)
+                _lib.check(_lib.load().vq_index_search_filtered(self._h, _lib.fptr(unit), nq, fetch, int(self.search_mode),
+                                                                _lib.i32ptr(labels), len(labels), int(excl), _lib.i32ptr(rows),
+                                                                _lib.fptr(dist)))
+                return rows, dist
+
+            if self._host_ties():                            # as _search_many; fewer than kk allowed rows end in inf: no tie
+                best = host_tie_order(run, kk, n, self._ids.__getitem__, finite_only=True)
+                return [[{"id": i, **_scored(d)} for d, i in cand] for cand in best]
+            rows, dist = run(kk)
+            to_id = self._id_of()
+            return [_hits(to_id, rr, rd) for rr, rd in zip(rows.tolist(), dist)]
 
     # -- clip query: the k groups (videos) most similar to a SET of frames -------------------------
     SET_MAX_QUERIES = 4096        # vq_index_search_set: query frames per call
 
-    def _search_set_unit(self, unit: np.ndarray, k: int, flt, group_of, matches: bool) -> List[Dict]:
-        """unit: [m][dim] fp32 query frames, used as given.  flt: None or (group keys, exclude?)."""
-        m = unit.shape[0]
-        if m > self.SET_MAX_QUERIES:
-            raise ValueError(f"a clip query holds at most {self.SET_MAX_QUERIES} frames, got {m}")
-        if unit.shape[1] != self.dimension:
-            raise ValueError(f"query dimension {unit.shape[1]} != index dimension {self.dimension}")
-        if k <= 0 or not self._ids:
+    def _search_set(self, queries, k: int, flt, group_of, matches: bool, given: bool = False) -> List[Dict]:
+        """queries: at most SET_MAX_QUERIES frames (``given``: see ``_prepare``).  flt: ``_filter_arg``'s."""
+        ready = self._prepare(queries, k, given=given, group_of=group_of, flt=flt)
+        if ready is None:
             return []
-        keys_f, excl = flt if flt is not None else ([], True)
-        if not excl and not keys_f:
-            return []                                    # nothing allowed: no device call
-        if not self._identity:
-            self._sync_tie_order()
-        gl = self._sync_groups(group_of)
-        labels = self._filter_labels(gl, keys_f)
-        if not excl and len(labels) == 0:
-            return []
-        kk = min(int(k), len(gl.keys), 1024)
+        unit, gl, _, labels, excl = ready
+        m, kk = unit.shape[0], min(int(k), len(gl.keys), 1024)
         groups = np.empty(kk, dtype=np.int32)
         dist = np.empty(kk, dtype=np.float32)
         rows = np.empty((kk, m), dtype=np.int32) if matches else None
-        _lib.check(_lib.load().vq_index_search_set(
-            self._h, _lib.fptr(unit), m, kk, int(self.search_mode), labels.ctypes.data_as(POINTER(c_int32)), len(labels), int(excl),
-            groups.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist), rows.ctypes.data_as(POINTER(c_int32)) if matches else None))
-        keys, names, identity = gl.keys, self._ids, self._identity
+        _lib.check(_lib.load().vq_index_search_set(self._h, _lib.fptr(unit), m, kk, int(self.search_mode), _lib.i32ptr(labels), len(labels),
+                                                   int(excl), _lib.i32ptr(groups), _lib.fptr(dist), _lib.i32ptr(rows) if matches else None))
+        keys, to_id = gl.keys, self._id_of()
         out = []
         for j, (g, d) in enumerate(zip(groups.tolist(), dist)):
             if g < 0:
                 break
-            item = {"group": keys[g], "distance": d, "score": np.float32(1.0) - d}
+            out.append({"group": keys[g], **_scored(d)})
             if matches:
-                item["matches"] = [int(r) if identity else names[r] for r in rows[j].tolist()]
-            out.append(item)
+                out[-1]["matches"] = [to_id(r) for r in rows[j].tolist()]
         return out
 
     def search_set(self, queries: Sequence[np.ndarray], k: int = 5, *, within: Optional[Iterable[Hashable]] = None,
-                   exclude: Optional[Iterable[Hashable]] = None, group_of: Optional[Callable[[Hashable], Hashable]] = None,
-                   matches: bool = False) -> List[Dict]:
+                   exclude: Optional[Iterable[Hashable]] = None, group_of: GROUP_OF = None, matches: bool = False) -> List[Dict]:
         """The k GROUPS (videos) most similar to a set of query frames (a clip, several example frames, several prompts):
         ``[{'group', 'distance', 'score'[, 'matches']}]``.  Every query frame (normalised as ``search`` does) takes its
         smallest distance to a row of the group; ``distance`` is the mean of those over the frames (added in fp64 in the
@@ -815,29 +797,27 @@ class HNSWIndex:
         clip finds the long video it was cut from.  ``matches=True`` adds, per result, the node id of the matching row for
         every query frame (ties inside a group by id, as ``search``).  ``within`` / ``exclude`` / ``group_of`` as
         ``search_grouped``; giving neither searches every group.  At most 4,096 frames and 1,024 results."""
-        flt = self._filter_arg(within, exclude) if within is not None or exclude is not None else None
+        flt = self._filter_arg(within, exclude)
         if len(queries) == 0:
             raise ValueError("search_set needs at least one query frame")
-        if self.entry_point is None or self.element_count == 0 or k <= 0:
+        if self._empty() or k <= 0:
             return []
+        if len(queries) > self.SET_MAX_QUERIES:
+            raise ValueError(f"a clip query holds at most {self.SET_MAX_QUERIES} frames, got {len(queries)}")
         with self.lock:
-            unit = np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32)
-            return self._search_set_unit(unit, k, flt, group_of, matches)
+            return self._search_set(queries, k, flt, group_of, matches)
 
     def similar_groups(self, group: Hashable, k: int = 5, *, within: Optional[Iterable[Hashable]] = None,
-                       group_of: Optional[Callable[[Hashable], Hashable]] = None, matches: bool = False) -> List[Dict]:
+                       group_of: GROUP_OF = None, matches: bool = False) -> List[Dict]:
         """"More like this video": ``search_set`` with the stored rows of ``group`` (in row order) as the query set and
         ``group`` itself excluded; ``within`` restricts the answer to those groups.  ``KeyError`` for a group the index does
         not hold, ``ValueError`` for a group of more than 4,096 rows."""
         if within is not None:
             within = self._filter_arg(within, None)[0]
         with self.lock:
-            gl = self._group_labels(group_of)
-            gl.extend()
-            g = gl.index.get(group)
-            if g is None:
+            rn = self._group_rows(group, group_of)
+            if rn is None:
                 raise KeyError(group)
-            rn = np.flatnonzero(gl.labels == g).astype(np.int64)
             if len(rn) > self.SET_MAX_QUERIES:
                 raise ValueError(f"group {group!r} holds {len(rn)} rows; a clip query holds at most {self.SET_MAX_QUERIES}")
             if k <= 0:
@@ -847,59 +827,36 @@ class HNSWIndex:
             if not flt[1] and not flt[0]:
                 return []
             unit = np.empty((len(rn), self.dimension), dtype=np.float32)
-            _lib.check(_lib.load().vq_index_read_rows(self._h, rn.ctypes.data_as(POINTER(c_int64)), len(rn), _lib.fptr(unit)))
-            return self._search_set_unit(unit, k, flt, group_of, matches)
+            _lib.check(_lib.load().vq_index_read_rows(self._h, _lib.i64ptr(rn), len(rn), _lib.fptr(unit)))
+            return self._search_set(unit, k, flt, group_of, matches, given=True)
 
     # -- sequence query: the k groups (videos) that show a list of steps in order -------------------
     SEQ_MAX_STEPS = 64            # vq_index_search_sequence: steps per call
 
-    @staticmethod
-    def _sequence_gaps(min_gap, max_gap) -> Tuple[int, int]:
-        lo, hi = int(min_gap), int(max_gap)
-        if lo < 1 or hi < lo:
-            raise ValueError(f"the gaps must satisfy 1 <= min_gap <= max_gap, got min_gap={min_gap}, max_gap={max_gap}")
-        return lo, min(hi, 2 ** 62)
-
-    def _search_sequence_unit(self, unit: np.ndarray, k: int, min_gap: int, max_gap: int, flt, group_of, position_of) -> List[Dict]:
-        """unit: [m][dim] fp32 steps, used as given.  flt: None or (group keys, exclude?).  min_gap / max_gap: checked."""
-        m = unit.shape[0]
-        if m < 1 or m > self.SEQ_MAX_STEPS:
-            raise ValueError(f"a sequence query holds 1 to {self.SEQ_MAX_STEPS} steps, got {m}")
-        if unit.shape[1] != self.dimension:
-            raise ValueError(f"step dimension {unit.shape[1]} != index dimension {self.dimension}")
-        if k <= 0 or not self._ids:
+    def _search_sequence(self, steps, k: int, min_gap: int, max_gap: int, flt, group_of, position_of, given: bool = False) -> List[Dict]:
+        """steps: 1 to SEQ_MAX_STEPS of them (``given``: see ``_prepare``).  flt: ``_filter_arg``'s.  min_gap / max_gap: checked."""
+        ready = self._prepare(steps, k, given=given, group_of=group_of, positions=True, position_of=position_of, flt=flt, what="step")
+        if ready is None:
             return []
-        keys_f, excl = flt if flt is not None else ([], True)
-        if not excl and not keys_f:
-            return []                                    # nothing allowed: no device call
-        if not self._identity:
-            self._sync_tie_order()
-        gl = self._sync_groups(group_of)
-        ps = self._sync_positions(position_of)
-        labels = self._filter_labels(gl, keys_f)
-        if not excl and len(labels) == 0:
-            return []
-        kk = min(int(k), len(gl.keys), 1024)
+        unit, gl, ps, labels, excl = ready
+        m, kk = unit.shape[0], min(int(k), len(gl.keys), 1024)
         groups = np.empty(kk, dtype=np.int32)
         dist = np.empty(kk, dtype=np.float32)
         rows = np.empty((kk, m), dtype=np.int32)
-        _lib.check(_lib.load().vq_index_search_sequence(
-            self._h, _lib.fptr(unit), m, kk, min_gap, max_gap, labels.ctypes.data_as(POINTER(c_int32)), len(labels), int(excl),
-            groups.ctypes.data_as(POINTER(c_int32)), _lib.fptr(dist), rows.ctypes.data_as(POINTER(c_int32))))
-        keys, names, identity, pos = gl.keys, self._ids, self._identity, ps.values
+        _lib.check(_lib.load().vq_index_search_sequence(self._h, _lib.fptr(unit), m, kk, min_gap, max_gap, _lib.i32ptr(labels), len(labels),
+                                                        int(excl), _lib.i32ptr(groups), _lib.fptr(dist), _lib.i32ptr(rows)))
+        keys, pos, to_id = gl.keys, ps.values, self._id_of()
         out = []
         for j, (g, d) in enumerate(zip(groups.tolist(), dist)):
             if g < 0:
                 break
             chain = rows[j].tolist()
-            out.append({"group": keys[g], "distance": d, "score": np.float32(1.0) - d,
-                        "chain": [int(r) if identity else names[r] for r in chain], "positions": [int(pos[r]) for r in chain]})
+            out.append({"group": keys[g], **_scored(d), "chain": [to_id(r) for r in chain], "positions": [int(pos[r]) for r in chain]})
         return out
 
     def search_sequence(self, steps: Sequence[np.ndarray], k: int = 5, *, max_gap: int, min_gap: int = 1,
                         within: Optional[Iterable[Hashable]] = None, exclude: Optional[Iterable[Hashable]] = None,
-                        group_of: Optional[Callable[[Hashable], Hashable]] = None,
-                        position_of: Optional[Callable[[Hashable], int]] = None) -> List[Dict]:
+                        group_of: GROUP_OF = None, position_of: POSITION_OF = None) -> List[Dict]:
         """The k GROUPS (videos) that show the ``steps`` IN ORDER (a storyboard of prompts, the frames of a clip):
         ``[{'group', 'distance', 'score', 'chain', 'positions'}]``.  A chain is one row of the group per step whose positions
         increase by ``min_gap`` .. ``max_gap`` from step to step (``1 <= min_gap <= max_gap``); its cost adds the steps'
@@ -910,17 +867,18 @@ class HNSWIndex:
         ``search_grouped``; ``search_set`` of the same steps never scores a group worse.  ``group_of`` / ``within`` /
         ``exclude`` as ``search_grouped``, ``position_of`` as ``search_distinct`` (timestamps in ms with gaps in ms alike).
         At most 64 steps and 1,024 results."""
-        flt = self._filter_arg(within, exclude) if within is not None or exclude is not None else None
+        flt = self._filter_arg(within, exclude)
         if len(steps) == 0:
             raise ValueError("search_sequence needs at least one step")
         if len(steps) > self.SEQ_MAX_STEPS:
             raise ValueError(f"a sequence query holds at most {self.SEQ_MAX_STEPS} steps, got {len(steps)}")
-        lo, hi = self._sequence_gaps(min_gap, max_gap)
-        if self.entry_point is None or self.element_count == 0 or k <= 0:
+        lo, hi = int(min_gap), int(max_gap)
+        if lo < 1 or hi < lo:
+            raise ValueError(f"the gaps must satisfy 1 <= min_gap <= max_gap, got min_gap={min_gap}, max_gap={max_gap}")
+        if self._empty() or k <= 0:
             return []
         with self.lock:
-            unit = np.ascontiguousarray(self._unit_rows(steps), dtype=np.float32)
-            return self._search_sequence_unit(unit, k, lo, hi, flt, group_of, position_of)
+            return self._search_sequence(steps, k, lo, min(hi, 2 ** 62), flt, group_of, position_of)
 
     def synchronize(self) -> None:
         _lib.check(_lib.load().vq_index_synchronize(self._h))
@@ -959,7 +917,7 @@ class HNSWIndex:
     def load(self, filepath: str) -> None:
         """Reference :341-380 (checksum check, missing sidecar tolerated, ValueError on mismatch).  Only ``data`` (and
         the parameters) are used; the rows are stored as given and MEASURED by the library (vq_index_add
-        normalize=0): a file whose rows are not unit-norm still searches exactly, on the fp32 scan."""
+        normalize=0, ``_append_stored``): a file whose rows are not unit-norm still searches exactly, on the fp32 scan."""
         try:
             with open(filepath, "rb") as f:
                 current = hashlib.sha256(f.read()).hexdigest()
@@ -984,18 +942,10 @@ class HNSWIndex:
             self.M, self.max_M = s["M"], s["max_M"]
             self.ef_construction, self.ef_search = s["ef_construction"], s["ef_search"]
             self.level_generation_factor = s["level_generation_factor"]
-            self._ids, self._row_of, self._identity, self._tie_order = [], {}, True, "device"
+            self._reset_host_state()
             ids = list(s["data"].keys())
-            if ids:
-                rows = np.ascontiguousarray(np.stack([np.asarray(s["data"][i], dtype=np.float32) for i in ids]))
-                _lib.check(_lib.load().vq_index_add(self._h, _lib.fptr(rows), len(ids), 0))   # stored rows are already unit
-                for r, nid in enumerate(ids):
-                    self._row_of[nid] = r
-                    if self._identity and not (isinstance(nid, (int, np.integer)) and int(nid) == r):
-                        self._identity = False
-                self._ids = ids
-                if not self._identity:
-                    self._tie_order = "stale"
+            if ids:                                                      # stored rows are already unit
+                self._append_stored(np.ascontiguousarray(np.stack([np.asarray(s["data"][i], dtype=np.float32) for i in ids])), ids)
             self.entry_point = s["entry_point"]
             self.element_count = s["element_count"]
 

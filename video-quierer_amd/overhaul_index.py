@@ -25,9 +25,14 @@ from typing import Dict, List
 import numpy as np
 
 from video_quierer_amd import _lib
-from video_quierer_amd.indexes.hnsw import MODE_AUTO, HNSWIndex
+from video_quierer_amd.indexes.hnsw import MODE_AUTO, HNSWIndex, host_tie_order
 
 logger = logging.getLogger(__name__)
+
+
+def _unit_query(q) -> np.ndarray:
+    q = np.asarray(q)
+    return (q / (np.linalg.norm(q) + 1e-10)).astype(np.float32)          # reference :50-51
 
 
 class SimpleVideoIndex:
@@ -35,8 +40,12 @@ class SimpleVideoIndex:
         self.embeddings: List[np.ndarray] = []
         self.metadata: List[Dict] = []
         self.video_hashes: Dict = {}
-        self._dev = None          # HNSWIndex used as the raw device matrix
+        self._dev = None          # HNSWIndex used as the raw device matrix; its ids are -position (see _sync_device)
         self._pushed = 0
+        self._ranked_dev = None   # the device matrix that holds the id ranks of all its rows (_device)
+        # one callable each for the index's life: the device matrix keeps its labels and positions while they stay the same
+        self._group_fn = self._video_of_row_id
+        self._pos_fn = self._timestamp_ms_of_row_id
 
     def add_frame(self, embedding: np.ndarray, video_name: str, timestamp: float):
         self.embeddings.append(embedding.astype(np.float32))
@@ -53,18 +62,29 @@ class SimpleVideoIndex:
         block = np.ascontiguousarray(np.vstack(self.embeddings[self._pushed:]), dtype=np.float32)
         if self._dev is None:
             self._dev = HNSWIndex(dimension=block.shape[1])
-        _lib.check(_lib.load().vq_index_add(self._dev._h, _lib.fptr(block), block.shape[0], 0))   # stored as given
-        # ids = -frame_id: the scan's (distance, id) tie rule then yields the larger frame first,
+        # stored as given; ids = -frame position: the scan's (distance, id) tie rule then yields the larger frame first,
         # like the reference's reversed argsort
-        self._dev._ids.extend(-i for i in range(self._pushed, n))
-        self._dev._identity = False
-        self._dev.element_count = n
-        self._dev.entry_point = 0
+        self._dev._append_stored(block, [-i for i in range(self._pushed, n)])
         self._pushed = n
-        if getattr(self, "_ranked_dev", None) is self._dev:
-            # search_moments had uploaded id ranks; they no longer cover the index, and `search` orders ties on the host
+        if self._ranked_dev is self._dev:
+            # the id ranks no longer cover the index, and `search` orders ties on the host
             _lib.check(_lib.load().vq_index_set_id_ranks(self._dev._h, None, 0))
             self._ranked_dev = None
+
+    def _device(self, ranks: bool = False) -> HNSWIndex:
+        """The device matrix with every frame pushed.  ``ranks``: with the id order (larger frame first, as `search` orders
+        ties) as ranks on the device, where the grouped families run their walks.  A removal keeps them (a stable
+        compaction), an add clears them (_sync_device), a reloaded or rebuilt index is another device matrix."""
+        self._sync_device()
+        dev = self._dev
+        # rows are stored as given: the library measures |row|^2 of what it holds and only takes its fp16 scan
+        # while the matrix is near-unit (include/vq_amd.h vq_index_add), so un-normalised embeddings stay exact
+        dev.search_mode = MODE_AUTO
+        if ranks and self._ranked_dev is not dev:
+            with dev.lock:
+                dev._sync_tie_order()
+            self._ranked_dev = dev
+        return dev
 
     def remove_video(self, video_name: str) -> int:
         """Drop one video: its embeddings, metadata and ``video_hashes`` entry (so the next scan of the library re-processes
@@ -75,44 +95,29 @@ class SimpleVideoIndex:
         pos = [i for i, md in enumerate(self.metadata) if md.get("video_name") == video_name]
         if not pos:
             return 0
+        on_dev = np.array([i for i in pos if i < self._pushed], dtype=np.int64)
+        if self._dev is not None and len(on_dev):
+            with self._dev.lock:
+                # before the lists shrink: the removal labels the rows added since the last grouped search, by their old positions
+                self._dev._remove_rows(on_dev)
+                # rows keep their order, so the ids stay -position (the tie rule of search) without new ranks
+                self._pushed -= len(on_dev)
+                self._dev._replace_ids([-i for i in range(self._pushed)])
         gone = set(pos)
         self.embeddings = [e for i, e in enumerate(self.embeddings) if i not in gone]
         self.metadata = [md for i, md in enumerate(self.metadata) if i not in gone]
-        on_dev = np.array([i for i in pos if i < self._pushed], dtype=np.int64)
-        if self._dev is not None and len(on_dev):
-            dev = self._dev
-            with dev.lock:
-                dev._row_of = {-i: i for i in range(self._pushed)}      # (_sync_device keeps only the id list)
-                dev._remove_rows(on_dev)
-                # rows keep their order, so the ids stay -position (the tie rule of search) without new ranks
-                n = self._pushed - len(on_dev)
-                dev._ids[:] = [-i for i in range(n)]
-                dev._row_of = {-i: i for i in range(n)}
-                dev.entry_point = 0 if n else None
-            self._pushed = n
         return len(pos)
 
     def search(self, query_embedding: np.ndarray, k: int = 5) -> List[Dict]:
         if not self.embeddings:
             return []
-        self._sync_device()
-        q = np.asarray(query_embedding)
-        query_norm = (q / (np.linalg.norm(q) + 1e-10)).astype(np.float32)          # reference :50-51
-        dev = self._dev
-        # rows are stored as given: the library measures |row|^2 of what it holds and only takes its fp16 scan
-        # while the matrix is near-unit (include/vq_amd.h vq_index_add), so un-normalised embeddings stay exact
-        dev.search_mode = MODE_AUTO
-        n, kk = len(self.embeddings), min(k, len(self.embeddings))
-        unit = np.ascontiguousarray(query_norm[None, :])
-        fetch = min(n, kk + 8)
-        while True:                                   # do not cut a tie group at rank k
-            rows, dist = dev._raw_search(unit, fetch)
-            if fetch >= n or dist[0, kk - 1] != dist[0, fetch - 1]:
-                break
-            fetch = min(n, fetch * 2)
-        order = sorted(((d, -int(r)) for r, d in zip(rows[0], dist[0]) if r >= 0))[:kk]
+        dev = self._device()
+        unit = np.ascontiguousarray(_unit_query(query_embedding)[None, :])
+        n = len(self.embeddings)
+        # ties on the host: no ranks are kept on the device for this search (an add would have to upload them again)
+        best = host_tie_order(lambda fetch: dev._raw_search(unit, fetch), min(k, n), n, lambda row: -row)[0]
         results = []
-        for d, neg in order:
+        for d, neg in best:
             md = self.metadata[-neg].copy()
             md["score"] = float(np.float32(1.0) - d)
             results.append(md)
@@ -133,25 +138,10 @@ class SimpleVideoIndex:
             raise ValueError(f"min_gap_s must be >= 0, got {min_gap_s}")
         if not self.embeddings:
             return []
-        self._sync_device()
-        q = np.asarray(query_embedding)
-        query_norm = (q / (np.linalg.norm(q) + 1e-10)).astype(np.float32)          # reference :50-51
-        dev = self._dev
-        dev.search_mode = MODE_AUTO
-        if getattr(self, "_ranked_dev", None) is not dev:       # (a reloaded or rebuilt index is another device matrix)
-            # ids are -position, so the id order puts the LARGER frame first, as `search` does; the device needs it as ranks here
-            # (the greedy walk runs there).  Removal keeps them (a stable compaction), an add clears them (_sync_device).
-            dev._tie_order = "stale"
-            dev._sync_tie_order()
-            self._ranked_dev = dev
-        gfn = getattr(self, "_group_fn", None)
-        if gfn is None:
-            gfn = self._group_fn = self._video_of_row_id
-        pfn = getattr(self, "_pos_fn", None)
-        if pfn is None:
-            pfn = self._pos_fn = self._timestamp_ms_of_row_id
+        dev = self._device(ranks=True)
+        unit = np.ascontiguousarray(_unit_query(query_embedding)[None, :])
         with dev.lock:                                # the query as normalised above, not normalised again
-            res = dev._distinct_unit(np.ascontiguousarray(query_norm[None, :]), k, int(math.ceil(min_gap_s * 1000)), gfn, pfn)[0]
+            res = dev._distinct_many(unit, k, int(math.ceil(min_gap_s * 1000)), self._group_fn, self._pos_fn, given=True)[0]
         results = []
         for r in res:
             md = self.metadata[-r["id"]].copy()
@@ -166,7 +156,7 @@ class SimpleVideoIndex:
         minus the mean distance along the video's cheapest such chain, videos without a chain do not appear).  Every step is
         normalised as ``search`` does; positions are ``round(timestamp * 1000)`` ms, the gaps ``max(1, ceil(min_gap_s *
         1000))`` and ``floor(max_gap_s * 1000)`` ms, groups the video names; ties between frames as ``search``."""
-        steps = [np.asarray(e) for e in step_embeddings]
+        steps = list(step_embeddings)
         if not steps:
             raise ValueError("search_storyboard needs at least one step")
         if len(steps) > HNSWIndex.SEQ_MAX_STEPS:
@@ -178,21 +168,10 @@ class SimpleVideoIndex:
             raise ValueError(f"max_gap_s {max_gap_s} leaves no admissible gap in whole milliseconds")
         if not self.embeddings or k <= 0:
             return []
-        self._sync_device()
-        unit = np.ascontiguousarray(np.stack([(q / (np.linalg.norm(q) + 1e-10)).astype(np.float32) for q in steps]))   # reference :50-51
-        dev = self._dev
-        if getattr(self, "_ranked_dev", None) is not dev:       # as search_moments: the id order (larger frame first) as device ranks
-            dev._tie_order = "stale"
-            dev._sync_tie_order()
-            self._ranked_dev = dev
-        gfn = getattr(self, "_group_fn", None)
-        if gfn is None:
-            gfn = self._group_fn = self._video_of_row_id
-        pfn = getattr(self, "_pos_fn", None)
-        if pfn is None:
-            pfn = self._pos_fn = self._timestamp_ms_of_row_id
+        dev = self._device(ranks=True)
+        unit = np.ascontiguousarray(np.stack([_unit_query(q) for q in steps]))
         with dev.lock:                                # the steps as normalised above, not normalised again
-            res = dev._search_sequence_unit(unit, k, lo, hi, None, gfn, pfn)
+            res = dev._search_sequence(unit, k, lo, hi, None, self._group_fn, self._pos_fn, given=True)
         return [{"video_name": r["group"], "score": float(r["score"]),
                  "timestamps": [self.metadata[-i]["timestamp"] for i in r["chain"]],
                  "frame_ids": [self.metadata[-i]["frame_id"] for i in r["chain"]]} for r in res]
@@ -204,13 +183,7 @@ class SimpleVideoIndex:
         comparison, video_search_overhaul.py:143-147, sees two different files).  ``KeyError`` for an unknown video."""
         if not self.embeddings:
             raise KeyError(video_name)
-        self._sync_device()
-        dev = self._dev
-        dev.search_mode = MODE_AUTO
-        fn = getattr(self, "_group_fn", None)
-        if fn is None:
-            fn = self._group_fn = self._video_of_row_id      # one callable for the index's life: the labels are kept
-        res = dev.similar_groups(video_name, k, group_of=fn)
+        res = self._device(ranks=True).similar_groups(video_name, k, group_of=self._group_fn)
         return [{"video_name": r["group"], "score": float(r["score"])} for r in res]
 
     def save_to_disk(self, cache_path: Path):
