@@ -531,6 +531,30 @@ typedef struct vq_scan_plan {
 } vq_scan_plan;
 int vq_debug_scan_plan(int dim, int64_t n, int nq, int k, int force_scan, vq_scan_plan* out);
 
+/* Stage read-back of the fp16 scans (tests/test_scan_stages.py): what pass 1 of the last fp16 search left on the device,
+ * before any re-score.  Both calls wait for the handle's stream, copy, and change nothing; no search launches or waits
+ * anything for them (the handle only remembers the geometry of its last scan).  VQ_ERR_STATE when no such search has run on
+ * the handle since its rows last changed (vq_index_add*, _update_rows, _remove_rows, _clear).
+ *   vq_index_debug_read_scan_keys: after vq_index_search* in mode 2 (or mode 0 where it took the fp16 path), or after
+ *   vq_index_search_filtered* where it took the masked fp16 path (info[4] = 1).  The keys of the LAST chunk of that search:
+ *   info = {q0, cur, layout, streams, masked}: the chunk covered queries q0 .. q0 + cur - 1; layout 1, 2 or 3 as in
+ *   vq_scan_plan; streams = key pairs per query.  keys [cur][streams][2]: the raw 32-bit patterns, first and second key of
+ *   every (query, stream), gathered through the offset functions the re-score kernels read them with.  A key is the fp32
+ *   score of one row of the stream with the row's index inside the stream in its low 7 bits (vq_debug_scan_row_of gives the
+ *   row number); "no row" (a row past the end, a disallowed row, a stream the masked scan did not read) reads as a float
+ *   below -1e38.  keys == NULL: info only.  capacity: the words `keys` holds; fewer than cur * streams * 2 is
+ *   VQ_ERR_INVALID.
+ *   vq_index_debug_read_group_best: after vq_index_search_grouped* or vq_index_search_grouped_filtered* where they took the
+ *   fp16 path.  info = {q0, cur, n_groups}; best [cur][n_groups]: the largest fp16 score the group-max scan saw for the
+ *   (query, group), decoded from its order-preserving key to a float.  A group no (allowed) row was seen for reads as NaN:
+ *   its key is 0, which no score encodes (a score's key is never 0, and a scan never produces a NaN score from finite
+ *   rows and queries).  best == NULL: info only.  A clip search overwrites the same buffer: afterwards VQ_ERR_STATE.
+ *   vq_debug_scan_row_of: the row number of index `local` (0 .. 127) of stream `stream` under key layout 1, 2 or 3, by
+ *   the functions the re-score kernels use; -1 for any other argument.  Pure host arithmetic: no device. */
+int vq_index_debug_read_scan_keys(vq_index* idx, int64_t* info /*[5]*/, uint32_t* keys, int64_t capacity);
+int vq_index_debug_read_group_best(vq_index* idx, int64_t* info /*[3]*/, float* best, int64_t capacity);
+int64_t vq_debug_scan_row_of(int layout, int64_t stream, int local);
+
 /* ------------------------------------------------------------------ frame preprocessing
  * The resize in front of the encoder, bit-identical to Pillow's 8-bit separable resample
  * (Pillow src/libImaging/Resample.c), which is what the reference runs in two places:

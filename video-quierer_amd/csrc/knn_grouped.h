@@ -49,7 +49,7 @@ __device__ __forceinline__ uint32_t score_key(float s) {
     const uint32_t u = __builtin_bit_cast(uint32_t, s);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-__device__ __forceinline__ float key_score(uint32_t k) {
+__host__ __device__ __forceinline__ float key_score(uint32_t k) {
     return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 

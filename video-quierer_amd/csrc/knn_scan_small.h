@@ -31,6 +31,8 @@ constexpr int SCAN3_FUSED_MAX_Q = 4;    // up to this many queries the scan conv
 constexpr int SCAN3_MAX_Q = 96;         // three 32-query passes (0.22 ms each over 1M x 512) still beat one 256-query MFMA tile (0.83 ms)
 
 __host__ __device__ inline int64_t scan3_row_of(int64_t stream, int local) { return stream * 128 + local; }
+// key layout 3: element index of the key pair of (stream, query), query-major [q_pad][streams][2]
+__host__ __device__ inline size_t scan3_key_index(int64_t stream, int64_t q, int64_t streams) { return ((size_t)q * streams + stream) * 2; }
 
 // FUSED (one to four queries — the reference's own call is ONE): the queries arrive as fp32 [nq_real][dim] and are rounded to
 // fp16 here, by the lanes that hold a real query; the other lanes of the B operand are zero without a load, and only real

@@ -207,6 +207,11 @@ struct vq_index {
     bool norm_dirty = false, near_unit = true;
     float row_norm_max = 1.0f;
     ScanSwitches scan_switches;    // the fp16 search's A/B switches (scan_plan.h), read from the environment at create
+    // What pass 1 of the last fp16 search left in d_keys / d_gbest (vq_index_debug_read_scan_keys / _group_best): host
+    // bookkeeping only, no launch and no wait.  Forgotten when the rows change (rows_changed) or another search takes the buffer.
+    struct LastScan { bool valid = false, masked = false; int layout = 0, cur = 0; int64_t streams = 0, q0 = 0; } last_scan;
+    struct LastGroupScan { bool valid = false; int cur = 0; int32_t n_groups = 0; int64_t q0 = 0; } last_gscan;
+    void rows_changed() { last_scan.valid = false; last_gscan.valid = false; }
     bool profiling = false;
     struct Ev { int cls; hipEvent_t a, b; };
     std::vector<Ev> events;
@@ -288,6 +293,7 @@ int finish_add(vq_index* x, int64_t n, int normalize) {
     }
     VQ_HIP(hipGetLastError());
     x->size += n;
+    x->rows_changed();
     return 0;
 }
 
@@ -590,11 +596,13 @@ int search_fp16(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_i
     VQ_TRY(x->d_flags.reserve(q_pad(p, nq)));
     VQ_TRY(reserve_fallback(x, nq, k));
     int32_t* const counters = host_sync ? x->h_counters.dev : x->d_counters.p;
+    x->last_scan.valid = false;
     for (int64_t q0 = 0; q0 < nq; q0 += p.q_chunk) {
         const int cur = (int)std::min<int64_t>(p.q_chunk, nq - q0);
         const float* qp = d_queries + q0 * x->dim;
         if (!p.fused_q) queries_to_f16(x, qp, cur, q_pad(p, cur));
         VQ_TRY(launch_scan(x, p, qp, cur));
+        x->last_scan = {true, false, p.layout, cur, p.streams, q0};
         VQ_TRY(launch_rescore(x, p, qp, cur, k, d_ids + q0 * k, d_dist_out + q0 * k, x->d_flags + q0, counters));
     }
     VQ_HIP(hipGetLastError());
@@ -695,6 +703,7 @@ int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int3
     // k among the allowed groups: the threshold is the k'-th largest gbest with k' = min(k, allowed) (a disallowed group's 0 is
     // below it), the finalize test asks for min(k, allowed) re-scored groups
     const int k_sel = allow ? std::min(k, (int)n_allowed) : k, g_fin = allow ? n_allowed : G;
+    x->last_gscan.valid = false;
     for (int64_t q0 = 0; q0 < nq; q0 += qc) {
         const int cur = (int)std::min<int64_t>(qc, nq - q0);
         const int64_t q_pad = round_up(cur, 16);
@@ -706,6 +715,7 @@ int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int3
             hipLaunchKernelGGL(scan, dim3(cdiv(streams, 4), (int)(q_pad / 16)), dim3(256), 0, x->stream, x->d_q16, x->rows16, streams,
                                x->d_group, x->d_sgroup, cur, G, x->d_gbest, allow);
         }
+        x->last_gscan = {true, cur, (int32_t)G, q0};
         {
             Prof p(x, I_RESCORE);
             hipLaunchKernelGGL(group_threshold_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gbest, G, k_sel, qp, x->dim, eps_rows, x->d_goff,
@@ -992,12 +1002,14 @@ int search_filtered_fp16(vq_index* x, const float* d_queries, int nq, int k, con
     int32_t* ln = cn + nq;
     float* thr = (float*)(ln + nq);
     const GroupMask gm{x->d_group, x->d_sgroup, p.bits};
+    x->last_scan.valid = false;
     queries_to_f16(x, d_queries, nq, q_pad);
     {
         Prof pr(x, I_MFMA_SCAN);
         hipLaunchKernelGGL((scan3_instance<false, true>(x->dim, 1)), dim3(cdiv(streams, 4), (int)(q_pad / SCAN3_QB)), dim3(256), 0, x->stream, x->d_q16, x->rows16, n, streams, q_pad,
                            x->d_keys, 0, gm);
     }
+    x->last_scan = {true, true, 3, nq, streams, 0};
     {
         Prof pr(x, I_RESCORE);
         const TieOrder tie = x->tie();
@@ -1143,6 +1155,7 @@ int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, i
         if (qc >= SCAN2_QT) qc = qc / SCAN2_QT * SCAN2_QT;                              // whole query tiles of the batch mainloop
         VQ_TRY(x->d_q16.reserve(round_up(qc, SCAN2_QT) * x->dim));
         VQ_TRY(x->d_gbest.reserve(qc * G));
+        x->last_gscan.valid = false;                        // the clip search's maxima take the grouped search's buffer
         VQ_TRY(x->d_sqn.reserve(m));
         VQ_TRY(x->d_sckeys.reserve(std::min<int64_t>(SET_KEY_BUDGET, (int64_t)G * m)));
         VQ_TRY(ensure_gcounters(x));
@@ -1441,6 +1454,53 @@ int vq_debug_scan_plan(int dim, int64_t n, int nq, int k, int force_scan, vq_sca
     return 0;
 }
 
+int64_t vq_debug_scan_row_of(int layout, int64_t stream, int local) {
+    if (stream < 0 || local < 0 || local >= SCAN_STREAM_ROWS) return -1;
+    return layout == 1 ? scan_row_of(stream, local) : layout == 2 ? scan2_row_of(stream, local) : layout == 3 ? scan3_row_of(stream, local) : -1;
+}
+
+// the last chunk's keys, [cur][streams][2], gathered on the host through the offset functions the re-score kernels read them with
+int vq_index_debug_read_scan_keys(vq_index* x, int64_t* info, uint32_t* keys, int64_t capacity) {
+    VQ_CHECK(x && info, "vq_index_debug_read_scan_keys: null argument");
+    std::lock_guard<std::mutex> lk(x->mu);
+    const vq_index::LastScan& s = x->last_scan;
+    if (!s.valid) return fail(VQ_ERR_STATE, "vq_index_debug_read_scan_keys: no fp16 search has run on this handle since its rows last changed");
+    info[0] = s.q0; info[1] = s.cur; info[2] = s.layout; info[3] = s.streams; info[4] = s.masked ? 1 : 0;
+    if (!keys) return 0;
+    const int64_t want = (int64_t)s.cur * s.streams * 2;
+    VQ_CHECK(capacity >= want, "vq_index_debug_read_scan_keys: %lld words for %d queries x %lld streams x 2", (long long)capacity, s.cur, (long long)s.streams);
+    // every layout keeps a query's keys inside the first round_up(cur, 16) query slots
+    const int64_t words = round_up((int64_t)s.cur, 16) * s.streams * 2;
+    VQ_CHECK(words <= x->d_keys.cap, "vq_index_debug_read_scan_keys: the key buffer holds %lld words, the last scan wrote %lld", (long long)x->d_keys.cap, (long long)words);
+    std::vector<uint32_t> raw((size_t)words);
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    VQ_HIP(hipMemcpy(raw.data(), x->d_keys, (size_t)words * 4, hipMemcpyDeviceToHost));
+    for (int64_t q = 0; q < s.cur; ++q)
+        for (int64_t st = 0; st < s.streams; ++st) {
+            const size_t at = s.layout == 3 ? scan3_key_index(st, q, s.streams) : batch_key_index(st, q, s.streams);
+            keys[(q * s.streams + st) * 2] = raw[at];
+            keys[(q * s.streams + st) * 2 + 1] = raw[at + 1];
+        }
+    return 0;
+}
+
+int vq_index_debug_read_group_best(vq_index* x, int64_t* info, float* best, int64_t capacity) {
+    VQ_CHECK(x && info, "vq_index_debug_read_group_best: null argument");
+    std::lock_guard<std::mutex> lk(x->mu);
+    const vq_index::LastGroupScan& s = x->last_gscan;
+    if (!s.valid) return fail(VQ_ERR_STATE, "vq_index_debug_read_group_best: no fp16 grouped search has run on this handle since its rows last changed");
+    info[0] = s.q0; info[1] = s.cur; info[2] = s.n_groups;
+    if (!best) return 0;
+    const int64_t want = (int64_t)s.cur * s.n_groups;
+    VQ_CHECK(capacity >= want, "vq_index_debug_read_group_best: %lld floats for %d queries x %d groups", (long long)capacity, s.cur, (int)s.n_groups);
+    VQ_CHECK(want <= x->d_gbest.cap, "vq_index_debug_read_group_best: the buffer holds %lld words, the last scan wrote %lld", (long long)x->d_gbest.cap, (long long)want);
+    std::vector<uint32_t> raw((size_t)want);
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    VQ_HIP(hipMemcpy(raw.data(), x->d_gbest, (size_t)want * 4, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < want; ++i) best[i] = key_score(raw[(size_t)i]);      // key 0 = no row seen -> NaN (all bits set)
+    return 0;
+}
+
 int vq_index_destroy(vq_index* x) {
     if (!x) return 0;
     if (x->stream) (void)hipStreamSynchronize(x->stream);
@@ -1461,6 +1521,7 @@ int vq_index_clear(vq_index* x) {
     VQ_CHECK(x, "vq_index_clear: null handle");
     std::lock_guard<std::mutex> lk(x->mu);
     x->size = 0;
+    x->rows_changed();
     if (x->d_norm_range) VQ_TRY(init_norm_range(x));
     x->norm_dirty = false; x->near_unit = true; x->row_norm_max = 1.0f;
     x->rank_n = 0;
@@ -1614,6 +1675,7 @@ int vq_index_update_rows(vq_index* x, const float* rows, const int64_t* row_numb
     }
     const int64_t m = (int64_t)keep.size();
     const int64_t row_bytes = (int64_t)x->dim * 4;
+    x->rows_changed();
     VQ_TRY(x->d_upd.reserve(m * x->dim + m * 2 + 4));
     int64_t* d_rn = (int64_t*)(x->d_upd + round_up(m * x->dim, 2));       // 8-byte aligned behind the rows
     std::vector<int64_t> rn((size_t)m);
@@ -1658,6 +1720,7 @@ int vq_index_remove_rows(vq_index* x, const int64_t* row_numbers, int64_t n) {
     std::sort(rm.begin(), rm.end());
     rm.erase(std::unique(rm.begin(), rm.end()), rm.end());      // a row named twice is removed once
     const int64_t m = (int64_t)rm.size(), n_new = size - m, r0 = rm[0], moved = n_new - r0;
+    x->rows_changed();
     const bool ranks = x->rank_n == size, groups = x->group_n == size;      // labels / ranks that cover the index stay valid
     const int32_t G = groups ? x->n_groups : 0;
     const int64_t n_pad = round_up(size, SCAN_STREAM_ROWS), streams = n_pad / SCAN_STREAM_ROWS;
