@@ -456,6 +456,64 @@ int vq_index_search_sequence_device(vq_index* idx, const void* d_steps_f32, int 
 int vq_debug_sequence_plan(int64_t n, int64_t largest_group, int m, int k, int* step_chunks, int* lds_rows, int* groups_global_form,
                            int64_t* lds_bytes, int* chain_table, int* chain_slices);
 
+/* Keyframe summary: the k most representative rows of each listed group (video) — the poster frame and thumbnail strip of a
+ * video, the few frames that stand in for a long one (as the query set of vq_index_search_set, say).  An iterative
+ * farthest-point (greedy k-centre) pass per group: its covering radius is within a factor 2 of the best possible for every k,
+ * and its answer for k is a prefix of its answer for k + 1.
+ *   Notation: for rows a, b of the index, d(a, b) = 1.0f - fp32(sum_i (double)x_a[i] * (double)x_b[i]), summed in index order:
+ *   vq_index_search's distance with row b as the query; symmetric.  tie(r) = the row number, or the id rank once ranks are set.
+ *   For one group g (vq_index_set_groups) with rows r_0 < r_1 < .. < r_{L-1} (ascending row number), L >= 1 — the order of the
+ *   operations is part of the definition:
+ *   1. Mean direction.  The ascending row list is cut into consecutive blocks of 256 rows; per component, B_j[i] = the fp64 sum
+ *      of the block's rows in order, each term (double)x[i];  S[i] = B_0[i] + B_1[i] + .. added in fp64 in block order;
+ *      c[i] = (float)S[i].  There is no division anywhere (the blocks can run in parallel).
+ *   2. Seed.  s_0 = the row of g with the smallest (1.0f - fp32(chain(x_r, c)), tie(r)), the same fp64 chain with c as the
+ *      query: the frame most like the video as a whole.
+ *   3. State.  near_0(r) = d(r, s_0) and owner_0(r) = 0 for every other row of g.  Chosen rows leave the state for good;
+ *      owner(s_t) = t.
+ *   4. Radius.  radius[t] = the largest near_t(r) over the rows not yet chosen, 0.0f when none is left: every row of the group
+ *      lies within radius[t] of one of the first t + 1 keyframes.
+ *   5. Step t + 1.  If t + 1 == k, or no row is left, or radius[t] <= max_radius (an fp32 compare): stop.  Otherwise s_{t+1} =
+ *      the row not yet chosen with the largest near_t, the smallest tie among equals; for every other row not yet chosen,
+ *      d = d(r, s_{t+1}): if d < near_t(r) (strictly) then near_{t+1}(r) = d and owner_{t+1}(r) = t + 1, else both are kept.
+ *   6. Result, with kappa the number of keyframes chosen: rows [0, kappa) = the keyframes in selection order, full-index row
+ *      numbers; radius [0, kappa) = the radii; members [t] = the rows of g whose final owner is t (they sum to L).  Unused
+ *      slots are -1 / +inf / 0.
+ *   Consequences: kappa = min(k, L) when max_radius = -inf; the answer for k is a prefix of the answer for k' > k (rows and
+ *   radius; members differ); radius never increases; a group's answer does not depend on any other group; max_radius = rho
+ *   returns the shortest prefix whose last radius is <= rho.  Rows that are not finite are outside the definition: such a call
+ *   may return anything, but it ends (every loop is bounded by the shapes).
+ *   groups [n_sel]: labels of vq_index_set_groups in host memory; duplicates are allowed, each entry is answered on its own
+ *   ([n_sel][k] outputs, members_out may be NULL).  A label outside [0, n_groups) is VQ_ERR_INVALID; a label that holds no row
+ *   gives empty slots.  Limits: n_sel >= 1, 1 <= k <= 256, max_radius not NaN (-inf: no early stop), else VQ_ERR_INVALID, judged
+ *   before the device is asked for.  Stale or missing labels and stale id ranks are refused before any work is queued; no
+ *   positions are needed.  An empty index returns every slot empty.
+ *   How it runs (csrc/knn_summary.h): exact only.  A listed group of at most 4,096 rows is one workgroup of 256 threads that
+ *   runs steps 1 - 6 in one launch: near (as an order-preserving 32-bit key), owner, row and tie per row in LDS (14 B per row,
+ *   sized for the longest such group listed, so that several workgroups share a CU), the centre staged in LDS as fp64 once per
+ *   step, the pick as the workgroup's maximum of the packed (near key, inverted tie).  Longer groups take the wide form: state
+ *   in global memory; per step one update launch over a host-built list of 256-row blocks of all long groups (distance,
+ *   min-update, the block's maximum to its own slot) and one pick launch, a workgroup per long group over its blocks' slots
+ *   (radius, stop rule, next centre); the mean's block sums run over the same block list.  A group that has stopped sets a
+ *   flag and its later blocks return at once; the host never reads between steps.  The launches queued depend on the shapes and
+ *   k only: 2, plus 5 + 2 k when a listed group takes the wide form.  No global atomics, no waiting of one workgroup on another.
+ *   They are accounted under the existing profile class exact_dist_f64chain (VQ_IDX_NCLASS stays 7).
+ *   Scratch: 4 B per listed group and output slot lists; wide form: 8 B per row of the long groups listed, 16 B + dim x 8 B per
+ *   256-row block.
+ *   The _device form takes device results, is asynchronous on the index's stream and reads nothing back.
+ *   vq_index_last_search_stats afterwards: [0] listed groups run by the LDS form, [1] listed groups run by the wide form,
+ *   [2] keyframes written.
+ *   $VQ_AMD_SUM_LDS_ROWS (tests only, read per call, at most 4,096) lowers the LDS form's row limit.
+ *   vq_debug_summary_plan (host only, as vq_debug_sequence_plan): for n rows of dimension dim whose longest listed group holds
+ *   largest_group rows — the LDS form's row limit, its dynamic LDS bytes (sized for min(limit, largest_group) rows),
+ *   groups_wide_form = 1 when that group (so at least one) takes the wide form, and the launches a call queues. */
+int vq_index_summarize_groups(vq_index* idx, const int32_t* groups /*[n_sel]*/, int32_t n_sel, int k, float max_radius,
+                              int32_t* rows_out /*[n_sel][k]*/, float* radius_out /*[n_sel][k]*/, int32_t* members_out /*[n_sel][k] or NULL*/);
+int vq_index_summarize_groups_device(vq_index* idx, const int32_t* groups /*[n_sel], host*/, int32_t n_sel, int k, float max_radius,
+                                     void* d_rows_i32, void* d_radius_f32, void* d_members_i32 /*or NULL*/);
+int vq_debug_summary_plan(int64_t n, int64_t largest_group, int dim, int k, int* lds_rows, int64_t* lds_bytes,
+                          int* groups_wide_form, int* launches);
+
 /* save / load support (hnsw.py:306-380): the stored (normalised) rows. */
 int vq_index_export(vq_index* idx, float* rows /*[size][dim]*/);
 /* Single stored rows (the reference reads `self.data[node_id]`, a dict lookup): out [n][dim] = rows row_numbers[0..n). */

@@ -13,6 +13,7 @@
 #include "knn_set.h"
 #include "knn_distinct.h"
 #include "knn_sequence.h"
+#include "knn_summary.h"
 #include "scan_plan.h"
 #ifdef VQ_SCAN_EXPERIMENTS      // `make EXPERIMENTS=1`: the two superseded batch mainloops behind VQ_AMD_SCAN=2|4
 #include "experiments/scan_experiments.h"
@@ -177,6 +178,12 @@ struct vq_index {
     DevBuf<int32_t> d_seqw;
     DevBuf<int32_t> d_seqbp;
     DevBuf<int32_t> d_seqout;
+    // keyframe summary (knn_summary.h): the call's lists, keyframe counts and the wide form's per-row / per-block words; the
+    // blocks' packed maxima; the mean's block sums and the widened mean directions; the host form's results
+    DevBuf<int32_t> d_sumw;
+    DevBuf<uint64_t> d_sumk;
+    DevBuf<double> d_sumd;
+    DevBuf<int32_t> d_sumout;
     // clip-search scratch (knn_set.h): per-group sums [2][G], candidate list / positions [2][G] + count + flag, |q_i| [m],
     // order keys [G] + the selection's block lists, candidate keys, result staging of the host form
     DevBuf<double> d_ssum;
@@ -892,6 +899,18 @@ int check_label_range(const vq_index* x, const char* fn, const FilterLabels& f) 
     return 0;
 }
 
+// The next slot of the staging ring, holding at least `words`, free to be written: the copy that last read it has completed.
+// The caller fills it, queues its copy and records the slot's event behind it.
+int stage_slot(vq_index* x, int64_t words, StageSlot** out) {
+    StageSlot& st = x->flt_stage[x->flt_slot];
+    x->flt_slot = (x->flt_slot + 1) % vq_index::FLT_STAGE_SLOTS;
+    if (st.ev) VQ_HIP(hipEventSynchronize(st.ev));
+    else VQ_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    VQ_TRY(st.h.reserve(words, 16 << 10));
+    *out = &st;
+    return 0;
+}
+
 // Checks the labels and the filter.  Then, on the device, S's row list (gather path) or the allowed groups' bitmap (fp16 path).
 // The list goes up from a ring of pinned staging slots: a slot is reused only after the copy vq_index::FLT_STAGE_SLOTS calls
 // back has completed, so back-to-back asynchronous calls do not wait for each other.
@@ -922,12 +941,9 @@ int filter_prepare(vq_index* x, const char* fn, const FilterLabels& f, int exclu
     p->list = list ? E + w_E : nullptr;
     p->tie_w = list ? E + w_E + w_list : nullptr;
     p->bits = fp16 ? (uint32_t*)(E + w_E + 2 * w_list) : nullptr;
-    // a staging slot of the ring
-    StageSlot& st = x->flt_stage[x->flt_slot];
-    x->flt_slot = (x->flt_slot + 1) % vq_index::FLT_STAGE_SLOTS;
-    if (st.ev) VQ_HIP(hipEventSynchronize(st.ev));
-    else VQ_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
-    VQ_TRY(st.h.reserve(exclude ? ns : w_A + nA + 1, 16 << 10));
+    StageSlot* slot;
+    VQ_TRY(stage_slot(x, exclude ? ns : w_A + nA + 1, &slot));
+    StageSlot& st = *slot;
     int32_t* h = st.h;
     if (!exclude) {
         // the include list is the allowed groups: A and their offsets go up in one copy
@@ -1353,6 +1369,106 @@ int search_sequence_run(vq_index* x, const char* fn, const float* d_steps, int m
     return 0;
 }
 
+// ---- keyframe summary (knn_summary.h) ----
+SummaryPlan sum_plan_env(int64_t largest_group, int dim, int k) {
+    return plan_summary(largest_group, dim, k, seq_env("VQ_AMD_SUM_LDS_ROWS"));      // tests only, read per call
+}
+
+// Everything that can refuse a summary before any work is queued.
+int sum_precheck(vq_index* x, const char* fn, const int32_t* groups, int32_t n_sel) {
+    VQ_TRY(check_ranks(x, fn));
+    VQ_TRY(check_labels(x, fn));
+    for (int32_t i = 0; i < n_sel; ++i)
+        VQ_CHECK(groups[i] >= 0 && groups[i] < x->n_groups, "%s: group %d outside [0, %d)", fn, (int)groups[i], (int)x->n_groups);
+    return 0;
+}
+
+// groups [n_sel]: host, checked.  rows_out / radius_out / members_out (or null) [n_sel][k]: device.  Asynchronous on the index's
+// stream.  Entries of more than the plan's lds_rows rows (a group named twice: twice) go to the wide form through host-built lists.
+int summarize_run(vq_index* x, const char* fn, const int32_t* groups, int32_t n_sel, int k, float max_radius, int32_t* rows_out,
+                  float* radius_out, int32_t* members_out) {
+    const int dim = x->dim;
+    const int32_t* hg = x->h_goff.data();
+    auto len_of = [&](int32_t g) { return (int64_t)hg[g + 1] - hg[g]; };
+    int64_t largest = 0;
+    for (int32_t i = 0; i < n_sel; ++i) largest = std::max(largest, len_of(groups[i]));
+    const SummaryPlan p = sum_plan_env(largest, dim, k);
+    int64_t lds_longest = 0, nw = 0, nb = 0, W = 0;
+    for (int32_t i = 0; i < n_sel; ++i) {
+        const int64_t L = len_of(groups[i]);
+        if (L <= p.lds_rows) lds_longest = std::max(lds_longest, L);
+        else { ++nw; nb += cdiv(L, SUM_BLOCK); W += L; }
+    }
+    VQ_CHECK(W < ((int64_t)1 << 31), "%s: the listed groups above %d rows hold %lld rows together, 2^31 or more", fn, p.lds_rows, (long long)W);
+    auto words = [](int64_t c) { return round_up(std::max<int64_t>(c, 1), 4); };        // 16-byte aligned regions
+    // host-built lists, one copy: sel [n_sel] | slot [nw] | group [nw] | boff [nw + 1] | soff [nw + 1] | blk_entry [nb]
+    const int64_t w_sel = words(n_sel), w_nw = words(nw), w_nw1 = words(nw + 1), w_nb = words(nb);
+    const int64_t w_lists = w_sel + 2 * w_nw + 2 * w_nw1 + w_nb;
+    // behind them: kap [n_sel] | near [W] | owner [W] | bidx [nb] | cur [nw] | done [nw] | kappa [nw]
+    VQ_TRY(x->d_sumw.reserve(w_lists + w_sel + 2 * words(W) + w_nb + 3 * w_nw));
+    if (nw) {
+        VQ_TRY(x->d_sumk.reserve(nb));
+        VQ_TRY(x->d_sumd.reserve((nb + nw) * dim));
+    }
+    VQ_TRY(ensure_gcounters(x));
+    const int alloc_rows = (int)round_up(std::max<int64_t>(lds_longest, 1), 64);
+    const size_t lds_bytes = (size_t)summary_lds_bytes(lds_longest, dim), wide_lds = (size_t)dim * 8 + 64;
+    VQ_TRY(set_dyn_lds(x, (const void*)sum_lds_kernel, lds_bytes));
+    if (nw) {
+        VQ_TRY(set_dyn_lds(x, (const void*)sum_wide_update_kernel<true>, wide_lds));
+        VQ_TRY(set_dyn_lds(x, (const void*)sum_wide_update_kernel<false>, wide_lds));
+    }
+    StageSlot* slot;
+    VQ_TRY(stage_slot(x, w_lists, &slot));
+    int32_t* h = slot->h;
+    int32_t* h_slot = h + w_sel; int32_t* h_group = h_slot + w_nw; int32_t* h_boff = h_group + w_nw; int32_t* h_soff = h_boff + w_nw1;
+    int32_t* h_blk = h_soff + w_nw1;
+    std::memcpy(h, groups, (size_t)n_sel * 4);
+    int64_t e = 0, blk = 0, st = 0;
+    for (int32_t i = 0; i < n_sel; ++i) {
+        const int64_t L = len_of(groups[i]);
+        if (L <= p.lds_rows) continue;
+        h_slot[e] = i; h_group[e] = groups[i]; h_boff[e] = (int32_t)blk; h_soff[e] = (int32_t)st;
+        for (int j = 0; j < cdiv(L, SUM_BLOCK); ++j) h_blk[blk++] = (int32_t)e;
+        st += L; ++e;
+    }
+    h_boff[nw] = (int32_t)blk; h_soff[nw] = (int32_t)st;
+    int32_t* d = x->d_sumw;
+    VQ_HIP(hipMemcpyAsync(d, h, (size_t)w_lists * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_HIP(hipEventRecord(slot->ev, x->stream));
+    const int32_t* sel = d;
+    SumWide w;
+    w.slot = d + w_sel; w.group = w.slot + w_nw; w.boff = w.group + w_nw; w.soff = w.boff + w_nw1; w.blk_entry = w.soff + w_nw1;
+    int32_t* kap = d + w_lists;
+    w.near = (uint32_t*)(kap + w_sel); w.owner = (int32_t*)w.near + words(W); w.bidx = w.owner + words(W);
+    w.cur = w.bidx + w_nb; w.done = w.cur + w_nw; w.kappa = w.done + w_nw;
+    w.bmax = x->d_sumk; w.bsum = x->d_sumd; w.cvec = nw ? x->d_sumd + nb * dim : nullptr;
+    const TieOrder tie = x->tie();
+    {
+        Prof pr(x, I_EXACT_DIST);
+        hipLaunchKernelGGL(sum_lds_kernel, dim3(n_sel), dim3(SUM_THREADS), lds_bytes, x->stream, x->rows, dim, x->d_goff, x->d_grows, tie, sel, k,
+                           max_radius, p.lds_rows, alloc_rows, rows_out, radius_out, members_out, kap);
+        if (nw) {
+            const dim3 gb((unsigned)nb), ge((unsigned)nw), th(SUM_THREADS);
+            hipLaunchKernelGGL(sum_wide_blocksum_kernel, gb, th, 0, x->stream, x->rows, dim, x->d_goff, x->d_grows, w);
+            hipLaunchKernelGGL(sum_wide_mean_kernel, ge, th, 0, x->stream, dim, w);
+            hipLaunchKernelGGL(sum_wide_update_kernel<true>, gb, th, wide_lds, x->stream, x->rows, dim, x->d_goff, x->d_grows, tie, w, 0);
+            hipLaunchKernelGGL(sum_wide_pick_kernel, ge, th, 0, x->stream, x->d_goff, x->d_grows, w, 1, 0, k, max_radius, rows_out, radius_out);
+            for (int t = 0; t < k; ++t) {
+                hipLaunchKernelGGL(sum_wide_update_kernel<false>, gb, th, wide_lds, x->stream, x->rows, dim, x->d_goff, x->d_grows, tie, w, t);
+                hipLaunchKernelGGL(sum_wide_pick_kernel, ge, th, 0, x->stream, x->d_goff, x->d_grows, w, 0, t, k, max_radius, rows_out, radius_out);
+            }
+            hipLaunchKernelGGL(sum_wide_members_kernel, ge, th, 0, x->stream, w, k, rows_out, radius_out, members_out, kap);
+        }
+        hipLaunchKernelGGL(sum_stats_kernel, dim3(1), dim3(256), 0, x->stream, kap, n_sel, (unsigned long long)(n_sel - nw), (unsigned long long)nw,
+                           x->d_gcounters);
+    }
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+    set_stats(x, STATS_GCOUNTERS);
+    return 0;
+}
+
 // ---- what the search entry points share ----
 // One argument check per shape of call.  arrays: every array the call reads or writes is there.
 int check_batch_args(const char* fn, const vq_index* x, int nq, int k, bool arrays) {
@@ -1387,6 +1503,15 @@ int check_sequence_args(const char* fn, const vq_index* x, int m, int k, int64_t
              (long long)min_gap, (long long)max_gap);
     VQ_TRY(require_init());
     VQ_CHECK(x && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) && arrays, "%s: bad argument", fn);
+    return 0;
+}
+
+// (the arguments are judged before the library is asked for its device)
+int check_summary_args(const char* fn, const vq_index* x, const int32_t* groups, int32_t n_sel, int k, float max_radius, bool arrays) {
+    VQ_CHECK(k >= 1 && k <= SUM_MAX_K && n_sel >= 1, "%s: bad argument (1 <= k <= %d, n_sel >= 1)", fn, SUM_MAX_K);
+    VQ_CHECK(max_radius == max_radius, "%s: max_radius is NaN (-inf: no early stop)", fn);
+    VQ_TRY(require_init());
+    VQ_CHECK(x && groups && arrays, "%s: bad argument", fn);
     return 0;
 }
 
@@ -2075,6 +2200,57 @@ int vq_debug_sequence_plan(int64_t n, int64_t largest_group, int m, int k, int* 
     const SequencePlan p = seq_plan_env(n, largest_group, m);
     *step_chunks = p.step_chunks; *lds_rows = p.lds_rows; *groups_global_form = p.global_form; *lds_bytes = p.lds_bytes;
     *chain_table = p.bp_table; *chain_slices = p.bp_slices;
+    return 0;
+}
+
+int vq_index_summarize_groups_device(vq_index* x, const int32_t* groups, int32_t n_sel, int k, float max_radius, void* d_rows_out,
+                                     void* d_radius_out, void* d_members_out) {
+    static const char* fn = "vq_index_summarize_groups_device";
+    VQ_TRY(check_summary_args(fn, x, groups, n_sel, k, max_radius, d_rows_out && d_radius_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) {
+        const int64_t count = (int64_t)n_sel * k;
+        fill_no_result(x, (int32_t*)d_rows_out, (float*)d_radius_out, count);
+        if (d_members_out) VQ_HIP(hipMemsetAsync(d_members_out, 0, (size_t)count * 4, x->stream));
+        VQ_HIP(hipGetLastError());
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    VQ_TRY(sum_precheck(x, fn, groups, n_sel));
+    return summarize_run(x, fn, groups, n_sel, k, max_radius, (int32_t*)d_rows_out, (float*)d_radius_out, (int32_t*)d_members_out);
+}
+
+int vq_index_summarize_groups(vq_index* x, const int32_t* groups, int32_t n_sel, int k, float max_radius, int32_t* rows_out,
+                              float* radius_out, int32_t* members_out) {
+    static const char* fn = "vq_index_summarize_groups";
+    VQ_TRY(check_summary_args(fn, x, groups, n_sel, k, max_radius, rows_out && radius_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)n_sel * k;
+    if (x->size == 0) {
+        host_empty(count, rows_out, nullptr, radius_out);
+        if (members_out) std::fill(members_out, members_out + count, 0);
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    VQ_TRY(sum_precheck(x, fn, groups, n_sel));
+    VQ_TRY(x->d_sumout.reserve(3 * count));
+    int32_t* d_r = x->d_sumout; float* d_f = (float*)(d_r + count); int32_t* d_m = members_out ? d_r + 2 * count : nullptr;
+    VQ_TRY(summarize_run(x, fn, groups, n_sel, k, max_radius, d_r, d_f, d_m));
+    VQ_HIP(hipMemcpyAsync(rows_out, d_r, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(radius_out, d_f, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    if (members_out) VQ_HIP(hipMemcpyAsync(members_out, d_m, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// plan_summary's answer for this process's environment; needs no device
+int vq_debug_summary_plan(int64_t n, int64_t largest_group, int dim, int k, int* lds_rows, int64_t* lds_bytes, int* groups_wide_form,
+                          int* launches) {
+    VQ_CHECK(lds_rows && lds_bytes && groups_wide_form && launches && n >= 1 && n < ((int64_t)1 << 31) && largest_group >= 1 &&
+             largest_group <= n && dim > 0 && dim % 4 == 0 && dim <= 4096 && k >= 1 && k <= SUM_MAX_K,
+             "vq_debug_summary_plan: takes 1 <= largest_group <= n < 2^31, a dim vq_index_create takes, 1 <= k <= %d", SUM_MAX_K);
+    const SummaryPlan p = sum_plan_env(largest_group, dim, k);
+    *lds_rows = p.lds_rows; *lds_bytes = p.lds_bytes; *groups_wide_form = p.wide_form; *launches = p.launches;
     return 0;
 }
 

@@ -808,20 +808,26 @@ class HNSWIndex:
             return self._search_set(queries, k, flt, group_of, matches)
 
     def similar_groups(self, group: Hashable, k: int = 5, *, within: Optional[Iterable[Hashable]] = None,
-                       group_of: GROUP_OF = None, matches: bool = False) -> List[Dict]:
+                       group_of: GROUP_OF = None, matches: bool = False, keyframes: Optional[int] = None) -> List[Dict]:
         """"More like this video": ``search_set`` with the stored rows of ``group`` (in row order) as the query set and
         ``group`` itself excluded; ``within`` restricts the answer to those groups.  ``KeyError`` for a group the index does
-        not hold, ``ValueError`` for a group of more than 4,096 rows."""
+        not hold, ``ValueError`` for a group of more than 4,096 rows.  ``keyframes=m`` (m >= 1) sends the group's m-keyframe
+        summary (``summarize_group``, in selection order) instead of all its rows: a group of any length is then accepted."""
         if within is not None:
             within = self._filter_arg(within, None)[0]
+        if keyframes is not None and int(keyframes) < 1:
+            raise ValueError(f"keyframes must be >= 1, got {keyframes}")
         with self.lock:
             rn = self._group_rows(group, group_of)
             if rn is None:
                 raise KeyError(group)
-            if len(rn) > self.SET_MAX_QUERIES:
+            if keyframes is None and len(rn) > self.SET_MAX_QUERIES:
                 raise ValueError(f"group {group!r} holds {len(rn)} rows; a clip query holds at most {self.SET_MAX_QUERIES}")
             if k <= 0:
                 return []
+            if keyframes is not None:
+                rows, _, _ = self._summarize([self._groups.index[group]], int(keyframes), None, group_of)
+                rn = rows[0][rows[0] >= 0].astype(np.int64)
             # one include list: `within` without the group itself; without `within`, one exclude list
             flt = ([key for key in within if key != group], False) if within is not None else ([group], True)
             if not flt[1] and not flt[0]:
@@ -829,6 +835,54 @@ class HNSWIndex:
             unit = np.empty((len(rn), self.dimension), dtype=np.float32)
             _lib.check(_lib.load().vq_index_read_rows(self._h, _lib.i64ptr(rn), len(rn), _lib.fptr(unit)))
             return self._search_set(unit, k, flt, group_of, matches, given=True)
+
+    # -- keyframe summary: the k most representative rows of a group (video) -------------------------
+    SUMMARY_MAX_K = 256           # vq_index_summarize_groups: keyframes per group
+
+    def _summarize(self, labels: List[int], k: int, max_radius: Optional[float], group_of: GROUP_OF):
+        """labels: dense labels of the host's labels under ``group_of`` (at least one), k >= 1, the index not empty; under the
+        lock.  One device call -> (rows, radius, members), each [len(labels)][min(k, SUMMARY_MAX_K)]; -1 / inf / 0 in unused slots."""
+        rho = -math.inf if max_radius is None else float(max_radius)
+        if math.isnan(rho):
+            raise ValueError("max_radius must not be NaN (None: no early stop)")
+        self._prepare(np.empty((0, self.dimension), dtype=np.float32), k, given=True, group_of=group_of, what="index")
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        kk = min(int(k), self.SUMMARY_MAX_K)
+        rows = np.empty((len(lab), kk), dtype=np.int32)
+        radius = np.empty((len(lab), kk), dtype=np.float32)
+        members = np.empty((len(lab), kk), dtype=np.int32)
+        _lib.check(_lib.load().vq_index_summarize_groups(self._h, _lib.i32ptr(lab), len(lab), kk, rho, _lib.i32ptr(rows), _lib.fptr(radius),
+                                                         _lib.i32ptr(members)))
+        return rows, radius, members
+
+    def summarize_groups(self, groups: Optional[Iterable[Hashable]] = None, k: int = 5, *, max_radius: Optional[float] = None,
+                         group_of: GROUP_OF = None) -> Dict[Hashable, List[Dict]]:
+        """The k most representative rows (keyframes) of each listed group (default: every group the index holds), from one
+        device call: ``{group: [{'id', 'rank', 'radius', 'members'}]}``, each list in selection order.  Greedy farthest-point
+        selection on the stored rows: the first keyframe is the row most like the group's mean direction, every further one
+        the row farthest (in ``search``'s distance, ties by id as ``search``) from the keyframes chosen so far; ``radius`` is
+        the distance of the farthest remaining row once this keyframe is in (it never increases: every row of the group lies
+        within ``radius`` of one of the keyframes up to this one), ``members`` the number of rows, the keyframe included, that
+        the keyframe is the nearest of (first-chosen on equal distance).  The list for k is a prefix of the list for k + 1.
+        ``max_radius`` stops as soon as ``radius <= max_radius`` (at least one keyframe is always returned); a group of fewer
+        than k rows returns them all.  ``group_of`` as ``search_grouped``; a key the index does not hold raises ``KeyError``
+        before any device work; a key named twice is answered once.  At most 256 keyframes per group."""
+        with self.lock:
+            gl = self._group_labels(group_of)
+            gl.extend()
+            keys = list(gl.keys) if groups is None else list(dict.fromkeys(groups))
+            labels = [gl.index[key] for key in keys]                 # KeyError: before any device work
+            if k <= 0 or not keys:
+                return {key: [] for key in keys}
+            rows, radius, members = self._summarize(labels, k, max_radius, group_of)
+            to_id = self._id_of()
+            return {key: [{"id": to_id(r), "rank": t, "radius": d, "members": m} for t, (r, d, m) in enumerate(zip(rr, rd, rm)) if r >= 0]
+                    for key, rr, rd, rm in zip(keys, rows.tolist(), radius, members.tolist())}
+
+    def summarize_group(self, group: Hashable, k: int = 5, *, max_radius: Optional[float] = None, group_of: GROUP_OF = None) -> List[Dict]:
+        """``summarize_groups`` for one group: ``[{'id', 'rank', 'radius', 'members'}]`` in selection order.  ``KeyError`` for a
+        group the index does not hold, ``[]`` for k <= 0."""
+        return self.summarize_groups([group], k, max_radius=max_radius, group_of=group_of)[group]
 
     # -- sequence query: the k groups (videos) that show a list of steps in order -------------------
     SEQ_MAX_STEPS = 64            # vq_index_search_sequence: steps per call

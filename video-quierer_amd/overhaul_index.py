@@ -20,7 +20,7 @@ import logging
 import math
 import pickle
 from pathlib import Path
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 
@@ -176,15 +176,36 @@ class SimpleVideoIndex:
                  "timestamps": [self.metadata[-i]["timestamp"] for i in r["chain"]],
                  "frame_ids": [self.metadata[-i]["frame_id"] for i in r["chain"]]} for r in res]
 
-    def similar_videos(self, video_name: str, k: int = 5) -> List[Dict]:
+    def similar_videos(self, video_name: str, k: int = 5, keyframes: Optional[int] = None) -> List[Dict]:
         """The k indexed videos most similar to ``video_name``, itself excluded: ``[{'video_name', 'score'}]``, best first.
         Every stored frame of the video takes its best match in the other video; ``score`` is the mean of those cosine
         scores (``HNSWIndex.similar_groups``: exact, a re-encode or a cut scores close to 1 where the reference's file-hash
-        comparison, video_search_overhaul.py:143-147, sees two different files).  ``KeyError`` for an unknown video."""
+        comparison, video_search_overhaul.py:143-147, sees two different files).  ``keyframes=m`` compares the video's m
+        keyframes (``video_summary``) instead of all its frames, which also lifts the 4,096-frame limit.  ``KeyError`` for
+        an unknown video."""
         if not self.embeddings:
             raise KeyError(video_name)
-        res = self._device(ranks=True).similar_groups(video_name, k, group_of=self._group_fn)
+        res = self._device(ranks=True).similar_groups(video_name, k, group_of=self._group_fn, keyframes=keyframes)
         return [{"video_name": r["group"], "score": float(r["score"])} for r in res]
+
+    def video_summary(self, video_name: str, k: int = 5, max_radius: Optional[float] = None, chronological: bool = False) -> List[Dict]:
+        """The k frames that show what is in ``video_name`` (a poster frame and a thumbnail strip): ``search``'s metadata dicts
+        ``{'video_name', 'timestamp', 'frame_id'}`` plus ``'rank'`` (selection order: rank 0 is the frame most like the video as
+        a whole), ``'radius'`` (every frame of the video lies within this cosine distance of one of the keyframes up to this
+        one) and ``'members'`` (the frames this keyframe stands for).  ``HNSWIndex.summarize_group`` on the embeddings as
+        stored: exact greedy farthest-point selection, ties between frames as ``search``; ``max_radius`` stops early.  In
+        selection order, or by timestamp with ``chronological=True``.  ``KeyError`` for an unknown video."""
+        if not self.embeddings:
+            raise KeyError(video_name)
+        res = self._device(ranks=True).summarize_group(video_name, k, max_radius=max_radius, group_of=self._group_fn)
+        results = []
+        for r in res:
+            md = self.metadata[-r["id"]].copy()
+            md.update(rank=r["rank"], radius=float(r["radius"]), members=r["members"])
+            results.append(md)
+        if chronological:
+            results.sort(key=lambda md: md["timestamp"])
+        return results
 
     def save_to_disk(self, cache_path: Path):
         try:
