@@ -613,6 +613,29 @@ int vq_index_debug_read_scan_keys(vq_index* idx, int64_t* info /*[5]*/, uint32_t
 int vq_index_debug_read_group_best(vq_index* idx, int64_t* info /*[3]*/, float* best, int64_t capacity);
 int64_t vq_debug_scan_row_of(int layout, int64_t stream, int local);
 
+/* Stage entry of the fp16 re-score (tests/test_rescore_stages.py): pass 2 of an fp16 search on a key table the CALLER wrote.
+ * It plans as vq_index_search(mode = 2) does for (nq, k) over the handle's rows, under the same preconditions (dim % 64 == 0,
+ * k <= 100, a non-empty index of near-unit rows, id ranks that cover the index or none), scatters `keys` [nq][streams][2]
+ * (streams and the layout as in vq_scan_plan; the words as vq_index_debug_read_scan_keys returns them) into the key buffer
+ * through the plan layout's offset function, the query slots from nq to q_pad holding "no row", uploads the queries and makes
+ * the re-score launch of the search: the same function, the same kernel choice.  Nothing else is launched: no conversion,
+ * no scan, no flag collection, no exact fallback (a one-query launch of the 32- or 64-candidate kernel files its own flagged
+ * slot and counters, as in the search).  It waits and returns what pass 2 left: ids and dist [nq][k], flags [nq] (0 proven
+ * exact, 1 proven exact after stream rescans, 2 not proven: the search would redo the query exactly, and ids / dist of such a
+ * query mean nothing).  Afterwards vq_index_debug_read_scan_keys returns the table just written; the search statistics are not
+ * touched.  nq must fit one chunk of the plan (VQ_ERR_INVALID otherwise); capacity: the words `keys` holds.
+ * THE CONTRACT a table must meet for flags 0 / 1 to mean "exact" (what tests/scan_stage_ref.py::check_keys asserts of a scan),
+ * with E = scan_eps_unit(dim) x max(1, largest |row|) x |q|, for every (query, stream):
+ *   - a key that names a row (a float above -1e38; the row is vq_debug_scan_row_of(layout, stream, key & 127), below the row
+ *     count) lies within E of that row's exact score; the two keys of a stream name different rows;
+ *   - key1 >= key2; a stream with one row has one such key, a stream with none has none;
+ *   - every row of the stream that neither key names scores at or below key2 + E.
+ * A table outside the contract is the caller's problem: the kernels stay inside their buffers for ANY words (a key whose row
+ * lies past the end is skipped), but what they prove about such a table is not a statement about the rows. */
+int vq_index_debug_rescore(vq_index* idx, const float* queries /*[nq][dim], host*/, int nq, int k,
+                           const uint32_t* keys /*[nq][streams][2], host*/, int64_t capacity,
+                           int32_t* ids /*[nq][k]*/, float* dist /*[nq][k]*/, int32_t* flags /*[nq]*/);
+
 /* ------------------------------------------------------------------ frame preprocessing
  * The resize in front of the encoder, bit-identical to Pillow's 8-bit separable resample
  * (Pillow src/libImaging/Resample.c), which is what the reference runs in two places:

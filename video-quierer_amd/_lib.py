@@ -167,6 +167,8 @@ SIGNATURES = {
     "vq_index_debug_read_scan_keys": (c_int, [c_void_p, POINTER(c_int64), POINTER(ctypes.c_uint32), c_int64]),
     "vq_index_debug_read_group_best": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_float), c_int64]),
     "vq_debug_scan_row_of": (c_int64, [c_int, c_int64, c_int]),
+    "vq_index_debug_rescore": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, POINTER(ctypes.c_uint32), c_int64, POINTER(c_int32),
+                                       POINTER(c_float), POINTER(c_int32)]),
     "vq_encoder_stage_frames": (c_int, [c_void_p, c_int, POINTER(c_void_p), c_int, c_int]),
     "vq_encoder_submit_staged": (c_int, [c_void_p, c_int, c_int, c_int]),
     "vq_encoder_wait_staged": (c_int, [c_void_p, c_int, POINTER(c_float)]),

@@ -12,15 +12,20 @@
 //   t*16 + ni*4 + r (7 bits) stored in the low mantissa bits of the score.
 //   Output: keys[stream][query][2] (fp32 bit patterns), 8 B per (stream, query).
 //
-// Pass 2  rescore_verify_kernel  (RV_QPW = 8 queries per workgroup)
-//   per query: keep the best 4 keys of each of 32 interleaved stream shares,
-//   take the best C=32 of those 128, re-score them EXACTLY from the fp32 master
+// Pass 2  rescore_verify_kernel_t<QPW, KEEP, C>  (<8, 6, 32> for k <= 20; <4, 10, 80>, <4, 12, 128> and their one-query forms above)
+//   per query: keep the best KEEP keys of each of 256 / QPW interleaved stream shares (stream s belongs to share s mod 256 / QPW),
+//   take the best C of the kept keys, re-score them EXACTLY from the fp32 master
 //   (fixed-order fp64 chain, bit-identical to oracle/knn_oracle.c), and prove the
-//   result: with s_k the k-th best exact score and EPS the worst-case fp16
-//   scoring error, every row that was NOT re-scored has an upper bound
+//   result: with s_k the k-th best exact score among the re-scored rows and EPS = eps_rows |q| the worst-case fp16
+//   scoring error, every row that was NOT re-scored has an upper bound, and bound + EPS < s_k must hold for
 //     - rows a stream did not emit        <= that stream's 2nd key
-//     - keys a share dropped              <= the largest key that share dropped
+//     - keys a share dropped              <= the largest key that share dropped (its floor)
 //     - kept keys outside the best C      <= the (C+1)-th kept key
+//   (C > 32: the best C + 1 are found through a collected list of 4 C entries; more keys tied above its threshold -> 2.)
+//   rescore_verify_small_kernel_t<C> (one query per workgroup, C = 32 / 64) has no shares: the keys above a wave threshold are
+//   collected (more than 4 C of them -> 2), the best C become candidates, and the largest key not among them — the (C+1)-th
+//   collected or the best below the threshold — is the one bound on all the others.  It re-scores in two passes; a candidate
+//   the second pass skipped lies below s_k - EPS and leaves the pool.
 //   If a stream's 2nd key could still matter (key + EPS >= s_k) its 128 rows are
 //   re-scored exactly too (up to RESCAN_MAX streams).  If a bound cannot be
 //   closed the query is flagged and the caller runs the full exact scan for it.

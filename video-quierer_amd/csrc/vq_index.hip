@@ -1609,6 +1609,53 @@ int vq_index_debug_read_scan_keys(vq_index* x, int64_t* info, uint32_t* keys, in
     return 0;
 }
 
+// Pass 2 alone, on a key table the caller wrote: the plan and the launch_rescore call of search_fp16, nothing in front of them
+// (no conversion, no scan) and nothing behind (no collect_flags_kernel, no fallback).  The table goes into d_keys through the
+// offset functions vq_index_debug_read_scan_keys gathers through; the query slots from nq to q_pad hold "no row".
+int vq_index_debug_rescore(vq_index* x, const float* queries, int nq, int k, const uint32_t* keys, int64_t capacity, int32_t* ids,
+                           float* dist, int32_t* flags) {
+    static const char* fn = "vq_index_debug_rescore";
+    VQ_TRY(check_batch_args(fn, x, nq, k, queries && keys && ids && dist && flags));
+    VQ_CHECK(nq >= 1, "%s: no query", fn);
+    std::lock_guard<std::mutex> lk(x->mu);
+    VQ_TRY(check_ranks(x, fn));
+    VQ_TRY(refresh_norm_range(x));
+    VQ_CHECK(x->dim % GEMM_BK == 0 && k <= RV_K_MAX && x->size >= 1 && x->near_unit, "%s: the fp16 search needs dim %% 64 == 0, k <= %d, "
+             "a non-empty index and near-unit rows (0.5 <= |row|^2 <= 2)", fn, RV_K_MAX);
+    const ScanPlan p = plan_scan(x->dim, x->size, nq, k, x->scan_switches, SCAN_DIAG_BUILD, SCAN_EXPERIMENTS_BUILD);
+    if (p.err) return fail(p.err, "%s", p.msg);
+    VQ_CHECK(nq <= p.q_chunk, "%s: %d queries do not fit one chunk of %lld", fn, nq, (long long)p.q_chunk);
+    const int64_t want = (int64_t)nq * p.streams * 2, count = (int64_t)nq * k;
+    VQ_CHECK(capacity >= want, "%s: %lld words for %d queries x %lld streams x 2", fn, (long long)capacity, nq, (long long)p.streams);
+    const int64_t qpad = q_pad(p, nq), words = qpad * p.streams * 2;      // every layout: q_pad query slots of streams key pairs (q_pad % 16 == 0)
+    VQ_TRY(x->d_keys.reserve(p.streams * p.q_chunk * 2));
+    VQ_CHECK(words <= x->d_keys.cap, "%s: the key buffer holds %lld words, the table takes %lld", fn, (long long)x->d_keys.cap, (long long)words);
+    VQ_TRY(x->d_flags.reserve(qpad));
+    VQ_TRY(x->d_slots.reserve(round_up(nq, 1024)));
+    VQ_TRY(ensure_counters(x));
+    VQ_TRY(reserve_id_dist(x, count));
+    const float no_row = -3.0e38f;                                       // what the scans write for a row past the end
+    std::vector<uint32_t> raw((size_t)words, __builtin_bit_cast(uint32_t, no_row));
+    for (int64_t q = 0; q < nq; ++q)
+        for (int64_t st = 0; st < p.streams; ++st) {
+            const size_t at = p.layout == 3 ? scan3_key_index(st, q, p.streams) : batch_key_index(st, q, p.streams);
+            raw[at] = keys[(q * p.streams + st) * 2];
+            raw[at + 1] = keys[(q * p.streams + st) * 2 + 1];
+        }
+    x->last_scan.valid = false;
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    VQ_HIP(hipMemcpy(x->d_keys, raw.data(), (size_t)words * 4, hipMemcpyHostToDevice));
+    VQ_TRY(stage_queries(x, queries, nq));
+    x->last_scan = {true, false, p.layout, nq, p.streams, 0};
+    VQ_TRY(launch_rescore(x, p, x->d_q, nq, k, x->d_ids, x->d_out, x->d_flags, x->d_counters));
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(flags, x->d_flags, (size_t)nq * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
 int vq_index_debug_read_group_best(vq_index* x, int64_t* info, float* best, int64_t capacity) {
     VQ_CHECK(x && info, "vq_index_debug_read_group_best: null argument");
     std::lock_guard<std::mutex> lk(x->mu);
