@@ -727,6 +727,28 @@ int vq_frame_postprocess_u8_list(vq_resampler* r, const uint8_t* const* frames, 
  * vq_init nor a device. */
 int vq_frame_postprocess_plan(int out_h, int out_w, int* band_rows, int* n_bands, int* fused);
 
+/* What a Pillow resize (BILINEAR / BICUBIC) of n frames of h x w to out_h x out_w, cropped to crop_h x crop_w at (crop_top,
+ * crop_left), would launch (csrc/preproc_plan.h).  The three A/B switches of the horizontal pass are arguments here, not the
+ * environment: force_seg ($VQ_AMD_RSH=seg), lds_kb ($VQ_AMD_RSH_LDS_KB), spw ($VQ_AMD_RSH_SPW); 0 = unset.  tmp_align / dst_align:
+ * address & 15 of the intermediate and of the output (0 for the handle's own buffers).
+ * row_first, rows_needed: the source rows the horizontal pass produces; tmp_bytes: its intermediate.  hx: 1 the row-block-major
+ * kernel, 0 the segment-major one; oc output columns per segment, whose widest source span is `span` pixels; pitch_dw dwords per
+ * staged row, tile_pitch bytes per result-tile row, lds bytes of dynamic LDS; dword_store; spw segments per workgroup; the
+ * horizontal grid; the two tables' row lengths; row_bytes = crop_w * 3; the vertical pass's access width (16, 4 or 1 bytes) and grid.
+ * Pure host arithmetic: needs neither vq_init nor a device.  A row no LDS image holds returns VQ_ERR_INVALID, as the resize does. */
+typedef struct vq_resample_plan {
+    int64_t row_first, rows_needed, tmp_bytes, hx, oc, span, pitch_dw, tile_pitch, lds, dword_store, spw, hgrid_x, hgrid_y, hgrid_z;
+    int64_t ksize_h, ksize_v, row_bytes, vvec, vgrid_x, vgrid_y, vgrid_z;
+} vq_resample_plan;
+int vq_debug_resample_plan(int h, int w, int filter, int out_h, int out_w, int crop_top, int crop_left, int crop_h, int crop_w, int n,
+                           int tmp_align, int dst_align, int force_seg, int lds_kb, int spw, vq_resample_plan* out);
+/* The small plans of the other paths, same header, same rules.  out[0]: frames per slice of n host frames of frame_bytes under
+ * slice_budget bytes.  out[1..3]: frames per batch, histogram bytes and squared-difference bytes of a scene pass over m frames of
+ * `tiles` tiles under scratch_budget bytes.  out[4..8]: the post-processing result layout of post_m frames of post_bands bands:
+ * byte offsets of partials, res, prefix, keep, and the total. */
+int vq_debug_preproc_small_plans(int n, int64_t frame_bytes, int64_t slice_budget, int m, int tiles, int64_t scratch_budget,
+                                 int post_m, int post_bands, int64_t* out /*[9]*/);
+
 #ifdef __cplusplus
 }
 #endif

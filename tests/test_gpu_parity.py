@@ -1710,19 +1710,23 @@ def test_resample_matches_pillow_golden(pre, golden_resample):
 def test_resample_ragged_sizes_filters_crops_vs_oracle(pre):
     from oracle import resample_oracle as ro
     from video_quierer_amd.preprocess import BICUBIC, BILINEAR
+    # the cases, and which launch forms they reach between them: tests/test_preproc_plan_cpu.py
+    from test_preproc_plan_cpu import MANY_FRAMES_CASE, RAGGED_CASES, ragged_frames, ragged_window
     rng = np.random.default_rng(8)
-    cases = [(37, 53, 224, 224), (300, 400, 201, 640), (2, 3, 7, 5), (1, 1, 4, 4), (500, 224, 224, 100), (64, 64, 64, 17),
-             (1080, 1920, 398, 224), (719, 405, 224, 397), (5, 5461, 31, 9), (480, 640, 640, 480)]
-    for (h, w, ow, oh) in cases:
-        n = 3 if h * w < 200000 else 1
+    for (h, w, ow, oh) in RAGGED_CASES:
+        n = ragged_frames(h, w)
         frames = rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)
         for filt in (BILINEAR, BICUBIC):
             ref = np.stack([ro.resize_u8(f, ow, oh, filt) for f in frames])
             assert np.array_equal(pre.resize(frames, oh, ow, filt), ref), (h, w, ow, oh, filt)
-            ct, cl = oh // 3, ow // 4                         # a window of the resized frame = the same pixels of the full result
-            ch, cw = max(1, oh // 2), max(1, ow // 2)
+            ct, cl, ch, cw = ragged_window(ow, oh)            # a window of the resized frame = the same pixels of the full result
             got = pre.resize(frames, oh, ow, filt, crop=(ct, cl, ch, cw))
             assert np.array_equal(got, ref[:, ct:ct + ch, cl:cl + cw]), ("crop", h, w, ow, oh, filt)
+    n, h, w, ow, oh = MANY_FRAMES_CASE                        # several segments per workgroup
+    frames = rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)
+    for filt in (BILINEAR, BICUBIC):
+        ref = np.stack([ro.resize_u8(f, ow, oh, filt) for f in frames])
+        assert np.array_equal(pre.resize(frames, oh, ow, filt), ref), ("many frames", filt)
     # list of separately allocated frames == stacked frames; empty list
     frames = [rng.integers(0, 256, (90, 160, 3), dtype=np.uint8) for _ in range(5)]
     assert np.array_equal(pre.resize_list(frames, 224, 224), pre.resize(np.stack(frames), 224, 224))
@@ -1798,6 +1802,24 @@ def test_cv_resize_vs_oracle(pre):
     # a Pillow resize after it on the same handle still uses its own tables
     f = rng.integers(0, 256, (1, 90, 160, 3), dtype=np.uint8)
     a = pre.stretch(f); pre.cv_resize(f, (224, 224)); assert np.array_equal(pre.stretch(f), a)
+
+
+def test_table_cache_across_interleaved_filters(pre):
+    """One handle, one geometry, the filters in turn: every call finds its own tables on the device, whatever the call
+    before it left there (Pillow's and OpenCV's tables share one cache)."""
+    from oracle import cv_resize_oracle as cv
+    from oracle import resample_oracle as ro
+    from video_quierer_amd.preprocess import BICUBIC, BILINEAR
+    frames = np.random.default_rng(16).integers(0, 256, (3, 37, 53, 3), dtype=np.uint8)
+    oh, ow = 24, 40
+    pil = {f: np.stack([ro.resize_u8(x, ow, oh, f) for x in frames]) for f in (BILINEAR, BICUBIC)}
+    lin = np.stack([cv.resize_linear_u8(x, ow, oh) for x in frames])
+    assert np.array_equal(pre.resize(frames, oh, ow, BILINEAR), pil[BILINEAR])
+    assert np.array_equal(pre.cv_resize(frames, (ow, oh)), lin)
+    assert np.array_equal(pre.resize(frames, oh, ow, BICUBIC), pil[BICUBIC])
+    out, keep, _ = pre.postprocess(frames, (ow, oh), quality_filter=False)       # the fused pass in its linear mode
+    assert keep.all() and np.array_equal(out, lin)
+    assert np.array_equal(pre.resize(frames, oh, ow, BILINEAR), pil[BILINEAR])
 
 
 def test_frame_quality_vs_oracle(pre):

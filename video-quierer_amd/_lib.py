@@ -83,6 +83,13 @@ class ScanPlanC(ctypes.Structure):
         "rescore_files_flags q_pad q_tiles scan_grid_x scan_grid_y rescore_grid").split()]
 
 
+class ResamplePlanC(ctypes.Structure):
+    """vq_resample_plan: int64 fields, in the header's order."""
+    _fields_ = [(name, c_int64) for name in (
+        "row_first rows_needed tmp_bytes hx oc span pitch_dw tile_pitch lds dword_store spw hgrid_x hgrid_y hgrid_z "
+        "ksize_h ksize_v row_bytes vvec vgrid_x vgrid_y vgrid_z").split()]
+
+
 # name -> (restype, argtypes); every symbol include/vq_amd.h declares
 SIGNATURES = {
     "vq_init": (c_int, [c_int]),
@@ -198,6 +205,8 @@ SIGNATURES = {
     "vq_frame_postprocess_u8_list": (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                              POINTER(c_int64), c_void_p, c_void_p]),
     "vq_frame_postprocess_plan": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "vq_debug_resample_plan": (c_int, [c_int] * 15 + [POINTER(ResamplePlanC)]),
+    "vq_debug_preproc_small_plans": (c_int, [c_int, c_int64, c_int64, c_int, c_int, c_int64, c_int, c_int, POINTER(c_int64)]),
 }
 
 # include/vq_amd_diag.h: present only in a `make DIAG=1` build (scripts/ point $VQ_AMD_LIB at one); bound when found

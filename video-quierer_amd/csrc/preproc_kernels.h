@@ -26,6 +26,7 @@ __device__ __forceinline__ uint8_t rs_clip8(int v) {
 //   src  [n][h][w][3]; the pass covers source rows [row_first, row_first + rows_needed) of every frame
 //   tmp  [n][rows_needed][out_cols][3] for output columns [col_first, col_first + out_cols)
 //   kk rows are `ksize` ints, ksize a multiple of 4, zero beyond the tap count
+// oc, pitch_dw, tile_pitch, the LDS bytes and the grid are plan_resample's (preproc_plan.h, which computes with RP_ROWS = RSH_ROWS)
 constexpr int RSH_ROWS = 64;
 typedef __attribute__((address_space(3))) void rs_lds_t;
 typedef const __attribute__((address_space(1))) void rs_gbl_t;
@@ -145,7 +146,7 @@ void resample_hx_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ t
     const uint8_t* frame = src + ((size_t)img * h + row_first) * pitch;
 
     uint4 v[RSH_ROWS / 4];
-    int kw[4];                                                       // host: oc * ksize <= 4 * RS_THREADS
+    int kw[4];                                                       // plan_resample: oc * ksize <= RP_HX_KW * RS_THREADS
     auto issue = [&](int sg) {                                       // segment sg: pixels of rows w, w+4, ... and its weights -> registers
         const int xo0 = sg * oc, ncol = min(oc, out_cols - xo0), xx0 = col_first + xo0;
         const int sx0 = bounds[2 * xx0];

@@ -15,6 +15,7 @@
 #include "knn_sequence.h"
 #include "knn_summary.h"
 #include "scan_plan.h"
+#include "host_buffers.h"
 #ifdef VQ_SCAN_EXPERIMENTS      // `make EXPERIMENTS=1`: the two superseded batch mainloops behind VQ_AMD_SCAN=2|4
 #include "experiments/scan_experiments.h"
 #endif
@@ -55,52 +56,8 @@ using namespace vq;
 
 namespace {
 
-// Device memory a handle owns: freed with the handle.  reserve() keeps no contents (free, then allocate); storage that grows by
-// other rules (the rows: with a copy; ranks and labels: behind a stream synchronise, under their own message) is allocated by the
-// code that grows it, straight into p.
-template <class T> struct DevBuf {
-    T* p = nullptr;
-    int64_t cap = 0;               // elements
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    operator T*() const { return p; }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
-    int reserve(int64_t need) {
-        if (need <= cap) return 0;
-        release();
-        hipError_t e = hipMalloc((void**)&p, (size_t)need * sizeof(T));
-        if (e != hipSuccess) return fail(VQ_ERR_OOM, "index: scratch hipMalloc(%lld) failed: %s", (long long)(need * sizeof(T)), hipGetErrorString(e));
-        cap = need;
-        return 0;
-    }
-};
-
-// Pinned host memory a handle owns; a mapped one also has a device address (dev) that kernels write through.  Whoever replaces a
-// buffer the device may still be using waits for the stream first (host_results).
-template <class T> struct PinnedBuf {
-    T* p = nullptr;
-    T* dev = nullptr;              // mapped only
-    int64_t cap = 0;               // elements
-    const bool mapped;
-    explicit PinnedBuf(bool map = false) : mapped(map) {}
-    PinnedBuf(const PinnedBuf&) = delete;
-    PinnedBuf& operator=(const PinnedBuf&) = delete;
-    ~PinnedBuf() { release(); }
-    operator T*() const { return p; }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; dev = nullptr; cap = 0; }
-    int reserve(int64_t need, int64_t at_least = 0) {          // no contents kept; a new buffer holds max(need, at_least)
-        if (need <= cap) return 0;
-        release();
-        const int64_t ncap = std::max(need, at_least);
-        VQ_HIP(hipHostMalloc((void**)&p, (size_t)ncap * sizeof(T), mapped ? hipHostMallocMapped : hipHostMallocDefault));
-        if (mapped) VQ_HIP(hipHostGetDevicePointer((void**)&dev, p, 0));
-        cap = ncap;
-        return 0;
-    }
-};
+// the index's device buffers: DevBuf under the index's out-of-memory message
+template <class T> struct IdxBuf : DevBuf<T> { IdxBuf() : DevBuf<T>("index: scratch ") {} };
 
 // One slot of the filtered search's staging ring: pinned memory and the event of the copy that last read it.
 struct StageSlot {
@@ -123,85 +80,85 @@ enum StatsAt {
 struct vq_index {
     int dim = 0;
     int64_t size = 0, cap = 0;     // rows held / allocated
-    DevBuf<float> rows;            // fp32 master [cap][dim] (normalised rows, what the reference keeps in .data); `cap` above counts its rows
-    DevBuf<uint16_t> rows16;       // fp16 scan copy [cap][dim]
+    IdxBuf<float> rows;            // fp32 master [cap][dim] (normalised rows, what the reference keeps in .data); `cap` above counts its rows
+    IdxBuf<uint16_t> rows16;       // fp16 scan copy [cap][dim]
     hipStream_t stream = nullptr, own_stream = nullptr;
     std::mutex mu;
     std::vector<std::pair<const void*, size_t>> dyn_lds;    // kernels whose dynamic-LDS limit this handle has raised (set_dyn_lds)
     // scratch
-    DevBuf<float> d_q;             // queries [nq][dim]
-    DevBuf<float> d_dist;          // exact distances
-    DevBuf<uint64_t> d_partial;    // per-chunk top-k keys
-    DevBuf<int32_t> d_ids;         // host forms: device results
-    DevBuf<float> d_out;
-    DevBuf<float> d_upd;           // vq_index_update_rows: staged rows [n][dim] + their row numbers behind them;
+    IdxBuf<float> d_q;             // queries [nq][dim]
+    IdxBuf<float> d_dist;          // exact distances
+    IdxBuf<uint64_t> d_partial;    // per-chunk top-k keys
+    IdxBuf<int32_t> d_ids;         // host forms: device results
+    IdxBuf<float> d_out;
+    IdxBuf<float> d_upd;           // vq_index_update_rows: staged rows [n][dim] + their row numbers behind them;
                                    // vq_index_remove_rows: one chunk of moved rows
-    DevBuf<int32_t> d_rmw;         // vq_index_remove_rows: row maps, prefix sums, rebuilt ranks / labels (words)
+    IdxBuf<int32_t> d_rmw;         // vq_index_remove_rows: row maps, prefix sums, rebuilt ranks / labels (words)
     // (distance, id) tie order (vq_index_set_id_ranks): rank of each row's id in the caller's id order + the inverse behind it in one
     // allocation; rank_n = the number of rows they cover (0 = none set: ties come back in row order).  A search with
     // rank_n != size is refused.
-    DevBuf<int32_t> d_rank; int32_t* d_rank_inv = nullptr; int64_t rank_n = 0;      // d_rank.cap = 2 x the rows it holds (rank | inverse)
+    IdxBuf<int32_t> d_rank; int32_t* d_rank_inv = nullptr; int64_t rank_n = 0;      // d_rank.cap = 2 x the rows it holds (rank | inverse)
     TieOrder tie() const { return rank_n ? TieOrder{d_rank, d_rank_inv} : TieOrder{nullptr, nullptr}; }
     // group labels (vq_index_set_groups), one allocation: label per row, padded with -1 to whole 128-row streams; the by-group CSR
     // row list (goff [n_groups + 1], grows [n]); per stream the label its 128 rows share, or -1.  group_n = the rows they cover
     // (0 = none set); a grouped search with group_n != size is refused.
-    DevBuf<int32_t> d_group; int32_t* d_goff = nullptr; int32_t* d_grows = nullptr; int32_t* d_sgroup = nullptr;
+    IdxBuf<int32_t> d_group; int32_t* d_goff = nullptr; int32_t* d_grows = nullptr; int32_t* d_sgroup = nullptr;
     int64_t group_n = 0; int32_t n_groups = 0;
     std::vector<int32_t> h_goff;    // host mirror of goff (kept by set_groups / remove_rows): a filtered search sizes itself from it
     // filtered-search scratch (knn_filter.h): allowed groups, their row offsets, the row list and its tie words or the allowed
     // groups' bitmap; the filter list goes up from a ring of pinned staging slots, each reused once its event (the copy) is done
-    DevBuf<int32_t> d_flt;
+    IdxBuf<int32_t> d_flt;
     static constexpr int FLT_STAGE_SLOTS = 4;
     StageSlot flt_stage[FLT_STAGE_SLOTS]; int flt_slot = 0;
-    DevBuf<int32_t> d_fcand;       // masked fp16 path: candidate streams [nq][FLT_CAND] | n [nq] | listed [nq] | thr [nq]
-    DevBuf<uint64_t> d_flist;      // ... re-scored keys [nq][FLT_LIST]
+    IdxBuf<int32_t> d_fcand;       // masked fp16 path: candidate streams [nq][FLT_CAND] | n [nq] | listed [nq] | thr [nq]
+    IdxBuf<uint64_t> d_flist;      // ... re-scored keys [nq][FLT_LIST]
     // grouped-search scratch (knn_grouped.h) and its outcome counters (pinned copy read by last_search_stats)
-    DevBuf<uint32_t> d_gbest;
-    DevBuf<int32_t> d_gcand;       // cand [qc][CAND] | pref [qc][CAND + 1] | n [qc] | flags [qc] | thr [qc]
-    DevBuf<uint64_t> d_gkeys;      // best [qc][CAND] (fp16 path), per-block lists (exact path / redo)
-    DevBuf<uint64_t> d_gpart;
-    DevBuf<unsigned long long> d_gcounters; PinnedBuf<unsigned long long> h_gcounters;
-    DevBuf<int32_t> d_gout;        // vq_index_search_grouped: device results [3][nq][k]
+    IdxBuf<uint32_t> d_gbest;
+    IdxBuf<int32_t> d_gcand;       // cand [qc][CAND] | pref [qc][CAND + 1] | n [qc] | flags [qc] | thr [qc]
+    IdxBuf<uint64_t> d_gkeys;      // best [qc][CAND] (fp16 path), per-block lists (exact path / redo)
+    IdxBuf<uint64_t> d_gpart;
+    IdxBuf<unsigned long long> d_gcounters; PinnedBuf<unsigned long long> h_gcounters;
+    IdxBuf<int32_t> d_gout;        // vq_index_search_grouped: device results [3][nq][k]
     // positions (vq_index_set_positions): one int32 per row; pos_n = the rows they cover (0 = none set).  A distinct search with
     // pos_n != size is refused.  Distinct-search scratch (knn_distinct.h): the plain search's answer at the plan's depth
     // (ids | distances), the filed queries' slot list, the redo's selection (ids | distances); its counters are d_gcounters
-    DevBuf<int32_t> d_pos; int64_t pos_n = 0;
-    DevBuf<int32_t> d_dpre;
-    DevBuf<int32_t> d_dslots;
-    DevBuf<int32_t> d_dsel;
+    IdxBuf<int32_t> d_pos; int64_t pos_n = 0;
+    IdxBuf<int32_t> d_dpre;
+    IdxBuf<int32_t> d_dslots;
+    IdxBuf<int32_t> d_dsel;
     // sequence search (knn_sequence.h): every group's rows in (position, tie) order with their positions and ties beside them
     // (order | positions | ties, [3][seq_n]), built on the host by the first sequence search after the labels, the positions or
     // the id ranks changed (seq_n = the rows it covers, 0 = none; seq_largest = the longest group).  Scratch: cost keys (carry
     // [n] | two working arrays [2][n]), words (lo | hi | block minima [3][n] | end rows [G]), back-pointers, the host form's results
-    DevBuf<int32_t> d_seq; int64_t seq_n = 0; int64_t seq_largest = 0;
-    DevBuf<uint64_t> d_seqc;
-    DevBuf<int32_t> d_seqw;
-    DevBuf<int32_t> d_seqbp;
-    DevBuf<int32_t> d_seqout;
+    IdxBuf<int32_t> d_seq; int64_t seq_n = 0; int64_t seq_largest = 0;
+    IdxBuf<uint64_t> d_seqc;
+    IdxBuf<int32_t> d_seqw;
+    IdxBuf<int32_t> d_seqbp;
+    IdxBuf<int32_t> d_seqout;
     // keyframe summary (knn_summary.h): the call's lists, keyframe counts and the wide form's per-row / per-block words; the
     // blocks' packed maxima; the mean's block sums and the widened mean directions; the host form's results
-    DevBuf<int32_t> d_sumw;
-    DevBuf<uint64_t> d_sumk;
-    DevBuf<double> d_sumd;
-    DevBuf<int32_t> d_sumout;
+    IdxBuf<int32_t> d_sumw;
+    IdxBuf<uint64_t> d_sumk;
+    IdxBuf<double> d_sumd;
+    IdxBuf<int32_t> d_sumout;
     // clip-search scratch (knn_set.h): per-group sums [2][G], candidate list / positions [2][G] + count + flag, |q_i| [m],
     // order keys [G] + the selection's block lists, candidate keys, result staging of the host form
-    DevBuf<double> d_ssum;
-    DevBuf<int32_t> d_scand;
-    DevBuf<float> d_sqn;
-    DevBuf<uint64_t> d_sekey;
-    DevBuf<uint64_t> d_sckeys;
-    DevBuf<int32_t> d_sout;
+    IdxBuf<double> d_ssum;
+    IdxBuf<int32_t> d_scand;
+    IdxBuf<float> d_sqn;
+    IdxBuf<uint64_t> d_sekey;
+    IdxBuf<uint64_t> d_sckeys;
+    IdxBuf<int32_t> d_sout;
     // fp16 scan scratch
-    DevBuf<uint16_t> d_q16;
-    DevBuf<uint32_t> d_keys;
-    DevBuf<int32_t> d_flags;
+    IdxBuf<uint16_t> d_q16;
+    IdxBuf<uint32_t> d_keys;
+    IdxBuf<int32_t> d_flags;
     // device-side fallback (knn_fallback.h): flagged query numbers, counters {flagged, proven, rescanned, fallback},
     // per-split top-k lists; the counters travel to pinned memory behind the search, read by last_search_stats.  h_counters is
     // mapped: a host-synchronous search lets its kernels write the counters there (h_counters.dev)
-    DevBuf<int32_t> d_slots;
-    DevBuf<int32_t> d_counters; PinnedBuf<int32_t> h_counters{true};
-    DevBuf<uint64_t> d_fb_partial;
+    IdxBuf<int32_t> d_slots;
+    IdxBuf<int32_t> d_counters; PinnedBuf<int32_t> h_counters{true};
+    IdxBuf<uint64_t> d_fb_partial;
     // host forms: pinned staging for the queries, and a pinned + MAPPED result buffer.  vq_index_search (host arrays in and out, the
     // reference caller's call) has its kernels write straight into it — no device-to-host copy command on the one-query path
     PinnedBuf<float> h_q;
@@ -210,7 +167,7 @@ struct vq_index {
     int64_t stats[3] = {0, 0, 0};
     // |row|^2 range of rows added without normalisation (device: min/max fp32 bits); read back lazily by the first
     // search after such an add.  near_unit = the fp16 scan's error bound applies (knn_scan_f16.h scan_eps_unit).
-    DevBuf<uint32_t> d_norm_range;
+    IdxBuf<uint32_t> d_norm_range;
     bool norm_dirty = false, near_unit = true;
     float row_norm_max = 1.0f;
     ScanSwitches scan_switches;    // the fp16 search's A/B switches (scan_plan.h), read from the environment at create
@@ -243,7 +200,7 @@ int reserve_rows(vq_index* x, int64_t need) {
     if (need <= x->cap) return 0;
     int64_t ncap = std::max<int64_t>(need, std::max<int64_t>(1024, x->cap * 2));
     ncap = round_up(ncap, SCAN2_RANGE);       // the fp16 scans walk whole 1024/2048-row ranges
-    DevBuf<float> nr; DevBuf<uint16_t> nh;                    // freed again if a step below fails
+    IdxBuf<float> nr; IdxBuf<uint16_t> nh;                    // freed again if a step below fails
     hipError_t e = hipMalloc((void**)&nr.p, (size_t)ncap * x->dim * 4);
     if (e != hipSuccess) return fail(VQ_ERR_OOM, "index: hipMalloc of %lld rows failed: %s", (long long)ncap, hipGetErrorString(e));
     e = hipMalloc((void**)&nh.p, (size_t)ncap * x->dim * 2);

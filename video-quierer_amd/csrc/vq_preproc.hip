@@ -1,324 +1,194 @@
-// libvq_amd — frame preprocessing handle: Pillow-exact resize on the GPU in front of the
-// encoder, and the frame-quality statistics of the reference's frame extractor.  See include/vq_amd.h.
+// libvq_amd — frame preprocessing handle: Pillow-exact resize on the GPU in front of the encoder, the
+// frame extractor's quality statistics, scene-change scores and fused post-processing.  preproc_plan.h decides what is launched.
 #include "vq_common.h"
 #include "preproc_kernels.h"
-#include <algorithm>
-#include <cmath>
-#include <cstdlib>
+#include "preproc_plan.h"
+#include "host_buffers.h"
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace vq {
 int require_init();
-
-// ---- Resample.c precompute_coeffs + normalize_coeffs_8bpc, in IEEE double like the C original ------------
-static double filt_bilinear(double x) {
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return 1.0 - x;
-    return 0.0;
-}
-static double filt_bicubic(double x) {
-    const double a = -0.5;
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-
-struct Coeffs {
-    int ksize = 0;
-    std::vector<int> bounds;     // [out][2]: first tap, tap count
-    std::vector<int> kk;         // [out][ksize] fixed-point weights
-};
-
-static void precompute_coeffs(int in_size, int out_size, int filter, Coeffs& c) {
-    double (*fn)(double) = filter == VQ_RESAMPLE_BICUBIC ? filt_bicubic : filt_bilinear;
-    const double fsupport = filter == VQ_RESAMPLE_BICUBIC ? 2.0 : 1.0;
-    const double in0 = 0.0, in1 = (double)in_size;
-    double scale = (in1 - in0) / out_size, filterscale = scale;
-    if (filterscale < 1.0) filterscale = 1.0;
-    const double support = fsupport * filterscale;
-    const int ksize = (int)std::ceil(support) * 2 + 1;       // Resample.c's row length; rows here are padded to x4 with zeros
-    c.ksize = (ksize + 3) & ~3;
-    c.bounds.assign((size_t)out_size * 2, 0);
-    c.kk.assign((size_t)out_size * c.ksize, 0);
-    std::vector<double> w(ksize);
-    const double ss = 1.0 / filterscale;
-    for (int xx = 0; xx < out_size; ++xx) {
-        const double center = in0 + (xx + 0.5) * scale;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        double ww = 0.0;
-        for (int x = 0; x < xmax; ++x) {
-            w[x] = fn((x + xmin - center + 0.5) * ss);
-            ww += w[x];
-        }
-        int* k = &c.kk[(size_t)xx * c.ksize];
-        for (int x = 0; x < xmax; ++x) {
-            double v = w[x];
-            if (ww != 0.0) v /= ww;
-            k[x] = v < 0 ? (int)(-0.5 + v * (1 << RS_PRECISION_BITS)) : (int)(0.5 + v * (1 << RS_PRECISION_BITS));
-        }
-        c.bounds[2 * xx] = xmin;
-        c.bounds[2 * xx + 1] = xmax;
-    }
-}
-
-// OpenCV resize.cpp INTER_LINEAR tables for one axis: first tap and the two 11-bit weights per output index.
-// snap_borders = the horizontal rule (weight 1 on the edge pixel outside [0, src-1)); rows are clipped by the kernel.
-static void cv_linear_coeffs(int src, int dst, bool snap_borders, std::vector<int>& ofs, std::vector<int>& wts) {
-    const double scale = (double)src / dst;
-    ofs.resize(dst); wts.resize((size_t)dst * 2);
-    for (int d = 0; d < dst; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)std::floor(f);
-        f -= s;
-        if (snap_borders) {
-            if (s < 0) { f = 0.f; s = 0; }
-            if (s >= src - 1) { f = 0.f; s = src - 1; }
-        }
-        auto sat_short = [](float v) {                       // saturate_cast<short>(v): cvRound (half to even) + clamp
-            long r = std::lrint(v);
-            return (int)(r < -32768 ? -32768 : (r > 32767 ? 32767 : r));
-        };
-        ofs[d] = s;
-        wts[2 * d] = sat_short((1.f - f) * 2048.f);
-        wts[2 * d + 1] = sat_short(f * 2048.f);
-    }
-}
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) return fail(VQ_ERR_OOM, "vq_resampler: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        cap = bytes;
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
+static_assert(RP_PRECISION_BITS == RS_PRECISION_BITS && RP_THREADS == RS_THREADS && RP_ROWS == RSH_ROWS && RP_SC_TILE == SC_TILE &&
+              RP_SC_CHUNK_FRAMES == SC_CHUNK_FRAMES && CV_FORM_COPY == PP_COPY && CV_FORM_HALF == PP_HALF && CV_FORM_LINEAR == PP_LINEAR,
+              "preproc_plan.h computes with the kernels' geometry");
+static_assert(RP_HX_ROW_BYTES == 64 * sizeof(uint4) && RP_HX_KW == 4, "resample_hx_kernel: one uint4 per lane and row, int kw[4] per thread");
 }  // namespace vq
 
 using namespace vq;
 
 struct vq_resampler {
+    static constexpr const char* TAG = "vq_resampler: ";
     std::mutex mu;
     hipStream_t stream = nullptr, own_stream = nullptr;
-    DevBuf src, tmp, dst, coef, acc, post;
-    // plan cache: coefficient tables on the device for the last geometry
-    int p_h = 0, p_w = 0, p_filter = 0, p_out_h = 0, p_out_w = 0;
-    Coeffs ch, cv;
-    int *d_bh = nullptr, *d_kh = nullptr, *d_bv = nullptr, *d_kv = nullptr;
+    // staged host frames | horizontal intermediate / scene partials | resized frames | statistics and verdicts | compacted survivors
+    DevBuf<uint8_t> src{TAG}, tmp{TAG}, dst{TAG}, acc{TAG}, post{TAG};
+    DevBuf<int> coef{TAG};       // the four tables of `uploaded`: d_bh | d_kh | d_bv | d_kv (CV_LINEAR: xofs | wx | yofs | wy)
+    ResampleTables tables;       // their host copy: what the plan reads
+    TableKey uploaded;
+    const int *d_bh = nullptr, *d_kh = nullptr, *d_bv = nullptr, *d_kv = nullptr;
+    bool dyn_lds_raised = false; // the horizontal kernels' dynamic-LDS limits, on this handle's device
     int64_t out_bytes = 0;
     void* out_ptr = nullptr;     // what vq_resampler_device_output hands out: dst, or post after a compaction
 };
 
 namespace {
 
-int plan(vq_resampler* r, int h, int w, int filter, int out_h, int out_w) {
-    if (r->p_h == h && r->p_w == w && r->p_filter == filter && r->p_out_h == out_h && r->p_out_w == out_w) return 0;
-    VQ_HIP(hipStreamSynchronize(r->stream));                 // earlier launches still read the old tables
-    precompute_coeffs(w, out_w, filter, r->ch);
-    precompute_coeffs(h, out_h, filter, r->cv);
-    const size_t nbh = r->ch.bounds.size(), nkh = r->ch.kk.size(), nbv = r->cv.bounds.size(), nkv = r->cv.kk.size();
-    VQ_TRY(r->coef.reserve((nbh + nkh + nbv + nkv) * sizeof(int)));
-    r->d_bh = (int*)r->coef.p; r->d_kh = r->d_bh + nbh; r->d_bv = r->d_kh + nkh; r->d_kv = r->d_bv + nbv;
-    VQ_HIP(hipMemcpyAsync(r->d_bh, r->ch.bounds.data(), nbh * 4, hipMemcpyHostToDevice, r->stream));
-    VQ_HIP(hipMemcpyAsync(r->d_kh, r->ch.kk.data(), nkh * 4, hipMemcpyHostToDevice, r->stream));
-    VQ_HIP(hipMemcpyAsync(r->d_bv, r->cv.bounds.data(), nbv * 4, hipMemcpyHostToDevice, r->stream));
-    VQ_HIP(hipMemcpyAsync(r->d_kv, r->cv.kk.data(), nkv * 4, hipMemcpyHostToDevice, r->stream));
-    VQ_HIP(hipStreamSynchronize(r->stream));                 // the host vectors may be rebuilt by the next plan
-    r->p_h = h; r->p_w = w; r->p_filter = filter; r->p_out_h = out_h; r->p_out_w = out_w;
-    return 0;
+// launch(std::integral_constant<., V>) for the V of Vs that equals v: a template argument chosen at run time, the launch written once
+template <auto... Vs, class T, class F> void dispatch(T v, F&& launch) {
+    (void)((v == Vs ? (launch(std::integral_constant<decltype(Vs), Vs>{}), true) : false) || ...);
 }
-
-int check_geometry(const char* who, int n, int h, int w, int filter, int out_h, int out_w,
-                   int crop_top, int crop_left, int crop_h, int crop_w) {
-    VQ_CHECK(n >= 0 && h > 0 && w > 0 && out_h > 0 && out_w > 0, "%s: sizes must be positive (n=%d h=%d w=%d out=%dx%d)",
-             who, n, h, w, out_h, out_w);
-    VQ_CHECK(filter == VQ_RESAMPLE_BILINEAR || filter == VQ_RESAMPLE_BICUBIC || filter == VQ_RESAMPLE_CV_LINEAR,
-             "%s: filter %d is not BILINEAR(2), BICUBIC(3) or CV_LINEAR(100)", who, filter);
-    VQ_CHECK(crop_h > 0 && crop_w > 0 && crop_top >= 0 && crop_left >= 0 && crop_top + crop_h <= out_h && crop_left + crop_w <= out_w,
-             "%s: crop %dx%d at (%d,%d) does not fit the %dx%d resized frame", who, crop_h, crop_w, crop_top, crop_left, out_h, out_w);
-    VQ_CHECK((int64_t)h * w < (int64_t)1 << 30, "%s: frame of %dx%d pixels is too large", who, h, w);
-    VQ_CHECK(n <= 65535 && crop_h <= 65535 && h <= 65535 * RSH_ROWS, "%s: at most 65535 frames per call and 65535 output rows", who);
-    return 0;
+int align16(const void* p) { return (int)((uintptr_t)p & 15); }
+const ResampleSwitches& process_switches() { static const ResampleSwitches sw = resample_switches_from_env(); return sw; }
+size_t env_bytes(const char* name, size_t dflt) {            // the per-call byte budgets: tests set them
+    if (const char* e = getenv(name)) { const long long v = atoll(e); if (v > 0) return (size_t)v; }
+    return dflt;
 }
-
-// OpenCV's INTER_LINEAR tables of the geometry on the device: d_bh = xofs, d_kh = wx, d_bv = yofs, d_kv = wy
-int plan_cv(vq_resampler* r, int h, int w, int out_h, int out_w) {
-    if (r->p_h == h && r->p_w == w && r->p_filter == VQ_RESAMPLE_CV_LINEAR && r->p_out_h == out_h && r->p_out_w == out_w) return 0;
+// a buffer that queued work may still read: wait if and only if it must move
+template <class T> int grow(vq_resampler* r, DevBuf<T>& b, size_t n) {
+    if ((int64_t)n > b.cap) VQ_HIP(hipStreamSynchronize(r->stream));
+    return b.reserve((int64_t)n);
+}
+int fetch(vq_resampler* r, void* host, const void* dev, size_t bytes) {
+    VQ_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, r->stream));
     VQ_HIP(hipStreamSynchronize(r->stream));
-    std::vector<int> xo, wx, yo, wy;
-    cv_linear_coeffs(w, out_w, true, xo, wx);
-    cv_linear_coeffs(h, out_h, false, yo, wy);
-    const size_t total = xo.size() + wx.size() + yo.size() + wy.size();
-    VQ_TRY(r->coef.reserve(total * sizeof(int)));
-    r->d_bh = (int*)r->coef.p; r->d_kh = r->d_bh + xo.size(); r->d_bv = r->d_kh + wx.size(); r->d_kv = r->d_bv + yo.size();
-    VQ_HIP(hipMemcpy(r->d_bh, xo.data(), xo.size() * 4, hipMemcpyHostToDevice));
-    VQ_HIP(hipMemcpy(r->d_kh, wx.data(), wx.size() * 4, hipMemcpyHostToDevice));
-    VQ_HIP(hipMemcpy(r->d_bv, yo.data(), yo.size() * 4, hipMemcpyHostToDevice));
-    VQ_HIP(hipMemcpy(r->d_kv, wy.data(), wy.size() * 4, hipMemcpyHostToDevice));
-    r->p_h = h; r->p_w = w; r->p_filter = VQ_RESAMPLE_CV_LINEAR; r->p_out_h = out_h; r->p_out_w = out_w;
+    return 0;
+}
+// the tables of `key` on the device and in r->tables
+int ensure_tables(vq_resampler* r, const TableKey& key) {
+    if (r->uploaded == key) return 0;
+    VQ_HIP(hipStreamSynchronize(r->stream));                 // earlier launches still read the old tables
+    r->uploaded = TableKey{};
+    build_tables(key, r->tables);
+    const std::vector<int>* part[4] = {&r->tables.ch.bounds, &r->tables.ch.kk, &r->tables.cv.bounds, &r->tables.cv.kk};
+    const int** d[4] = {&r->d_bh, &r->d_kh, &r->d_bv, &r->d_kv};
+    VQ_TRY(r->coef.reserve((int64_t)(part[0]->size() + part[1]->size() + part[2]->size() + part[3]->size())));
+    int* at = r->coef.p;
+    for (int i = 0; i < 4; at += part[i++]->size()) {
+        *d[i] = at;
+        VQ_HIP(hipMemcpyAsync(at, part[i]->data(), part[i]->size() * sizeof(int), hipMemcpyHostToDevice, r->stream));
+    }
+    VQ_HIP(hipStreamSynchronize(r->stream));                 // the host vectors are rebuilt by the next geometry
+    r->uploaded = key;
+    return 0;
+}
+int check_frames(const char* who, int n, int h, int w) {
+    VQ_CHECK((int64_t)h * w < (int64_t)1 << 30, "%s: frame of %dx%d pixels is too large", who, h, w);
+    VQ_CHECK(n <= 65535, "%s: at most 65535 frames per call", who);
+    return 0;
+}
+// one resize: the frames and the filter (the tables' key), and the window of the resized frame that is produced
+struct Geometry : TableKey { int crop_top, crop_left, crop_h, crop_w; };
+int check_geometry(const char* who, int n, const Geometry& g) {
+    VQ_CHECK(n >= 0 && g.h > 0 && g.w > 0 && g.out_h > 0 && g.out_w > 0, "%s: sizes must be positive (n=%d h=%d w=%d out=%dx%d)", who, n, g.h, g.w, g.out_h, g.out_w);
+    VQ_CHECK(g.filter == VQ_RESAMPLE_BILINEAR || g.filter == VQ_RESAMPLE_BICUBIC || g.filter == VQ_RESAMPLE_CV_LINEAR,
+             "%s: filter %d is not BILINEAR(2), BICUBIC(3) or CV_LINEAR(100)", who, g.filter);
+    VQ_CHECK(g.crop_h > 0 && g.crop_w > 0 && g.crop_top >= 0 && g.crop_left >= 0 && g.crop_top + g.crop_h <= g.out_h && g.crop_left + g.crop_w <= g.out_w,
+             "%s: crop %dx%d at (%d,%d) does not fit the %dx%d resized frame", who, g.crop_h, g.crop_w, g.crop_top, g.crop_left, g.out_h, g.out_w);
+    VQ_TRY(check_frames(who, n, g.h, g.w));
+    VQ_CHECK(g.crop_h <= 65535 && g.h <= 65535 * RSH_ROWS, "%s: at most 65535 frames per call and 65535 output rows", who);
+    return 0;
+}
+// n frames of one size: a list of host pointers, or contiguous frames at `base` on the host or on the device
+struct Frames { const uint8_t* const* list; const uint8_t* base; bool on_device; bool any() const { return list || base; } };
+int check_list(const char* who, const Frames& f, int n) {
+    if (f.list) for (int i = 0; i < n; ++i) VQ_CHECK(f.list[i], "%s: frame %d is null", who, i);
+    return 0;
+}
+// run(d_src, first, m) over the frames in slices of `slice` (device-resident frames: one slice, where they are).  Host frames are
+// staged in r->src (the caller has waited: it may move) behind `lead` frame slots the caller keeps, contiguous frames in one copy.
+// wait: the host waits after each slice, because what run() writes per slice is reused by the next.
+template <class F>
+int for_each_slice(vq_resampler* r, const Frames& f, int n, size_t frame_bytes, int slice, int lead, bool wait, F&& run) {
+    if (!f.on_device) VQ_TRY(r->src.reserve((int64_t)((size_t)(slice + lead) * frame_bytes)));
+    uint8_t* stage = f.on_device ? nullptr : r->src.p + (size_t)lead * frame_bytes;
+    auto at = [&](int i) { return f.list ? f.list[i] : f.base + (size_t)i * frame_bytes; };
+    for (int i = 0; i < n; i += slice) {
+        const int m = std::min(slice, n - i);
+        for (int a = 0, b; !f.on_device && a < m; a = b) {
+            for (b = a + 1; b < m && at(i + b) == at(i + b - 1) + frame_bytes;) ++b;
+            VQ_HIP(hipMemcpyAsync(stage + (size_t)a * frame_bytes, at(i + a), (size_t)(b - a) * frame_bytes, hipMemcpyHostToDevice, r->stream));
+        }
+        VQ_TRY(run(f.on_device ? f.base : (const uint8_t*)stage, i, m));
+        if (wait) VQ_HIP(hipStreamSynchronize(r->stream));
+    }
+    return 0;
+}
+
+// cv2.resize(frame, (out_w, out_h)) — INTER_LINEAR — of n device-resident frames; d_dst gets [n][crop_h][crop_w][3]
+int run_device_cv(vq_resampler* r, const uint8_t* d_src, int n, const Geometry& g, uint8_t* d_dst) {
+    const dim3 grid(cdiv(g.crop_w * 3, RS_THREADS), g.crop_h, n);
+    const CvForm form = cv_form(g.h, g.w, g.out_h, g.out_w, g.crop_top == 0 && g.crop_left == 0 && g.crop_h == g.h && g.crop_w == g.w);
+    if (form == CV_FORM_COPY) {
+        VQ_HIP(hipMemcpyAsync(d_dst, d_src, (size_t)n * g.h * g.w * 3, hipMemcpyDeviceToDevice, r->stream));
+    } else if (form == CV_FORM_HALF) {
+        hipLaunchKernelGGL(cv_resize_half_kernel, grid, dim3(RS_THREADS), 0, r->stream, d_src, d_dst, g.h, g.w, g.crop_top, g.crop_left,
+                           g.crop_h, g.crop_w);
+    } else {
+        VQ_TRY(ensure_tables(r, g));
+        hipLaunchKernelGGL(cv_resize_linear_kernel, grid, dim3(RS_THREADS), 0, r->stream, d_src, d_dst, r->d_bh, r->d_kh, r->d_bv,
+                           r->d_kv, g.h, g.w, g.crop_top, g.crop_left, g.crop_h, g.crop_w);
+    }
+    VQ_HIP(hipGetLastError());
     return 0;
 }
 
 // both passes for n device-resident frames; d_dst gets [n][crop_h][crop_w][3]
-// cv2.resize(frame, (out_w, out_h)) — INTER_LINEAR
-int run_device_cv(vq_resampler* r, const uint8_t* d_src, int n, int h, int w, int out_h, int out_w,
-                  int crop_top, int crop_left, int crop_h, int crop_w, uint8_t* d_dst) {
-    const dim3 grid(cdiv(crop_w * 3, RS_THREADS), crop_h, n);
-    if (out_h == h && out_w == w && crop_top == 0 && crop_left == 0 && crop_h == h && crop_w == w) {
-        VQ_HIP(hipMemcpyAsync(d_dst, d_src, (size_t)n * h * w * 3, hipMemcpyDeviceToDevice, r->stream));
-        return 0;
+int run_device(vq_resampler* r, const uint8_t* d_src, int n, const Geometry& g, uint8_t* d_dst) {
+    if (g.filter == VQ_RESAMPLE_CV_LINEAR) return run_device_cv(r, d_src, n, g, d_dst);
+    VQ_TRY(ensure_tables(r, g));
+    ResamplePlan p = plan_resample(r->tables, n, g.crop_top, g.crop_left, g.crop_h, g.crop_w, process_switches());
+    if (p.err) return fail(p.err, "%s", p.msg);
+    VQ_TRY(grow(r, r->tmp, p.tmp_bytes));                    // queued passes still use the old workspace
+    if (!r->dyn_lds_raised) {                                // per device, so per handle (under its lock)
+        const std::pair<const void*, size_t> limits[] = {{(const void*)resample_h_kernel<true>, RP_SEG_LDS_MAX}, {(const void*)resample_h_kernel<false>, RP_SEG_LDS_MAX},
+                                                         {(const void*)resample_hx_kernel<true>, RP_HX_LDS_MAX}, {(const void*)resample_hx_kernel<false>, RP_HX_LDS_MAX}};
+        for (const auto& l : limits) VQ_HIP(hipFuncSetAttribute(l.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.second));
+        r->dyn_lds_raised = true;
     }
-    if (h == 2 * out_h && w == 2 * out_w) {
-        hipLaunchKernelGGL(cv_resize_half_kernel, grid, dim3(RS_THREADS), 0, r->stream, d_src, d_dst, h, w, crop_top, crop_left,
-                           crop_h, crop_w);
-        VQ_HIP(hipGetLastError());
-        return 0;
-    }
-    VQ_TRY(plan_cv(r, h, w, out_h, out_w));
-    hipLaunchKernelGGL(cv_resize_linear_kernel, grid, dim3(RS_THREADS), 0, r->stream, d_src, d_dst, r->d_bh, r->d_kh, r->d_bv,
-                       r->d_kv, h, w, crop_top, crop_left, crop_h, crop_w);
-    VQ_HIP(hipGetLastError());
-    return 0;
-}
-
-int run_device(vq_resampler* r, const uint8_t* d_src, int n, int h, int w, int filter, int out_h, int out_w,
-               int crop_top, int crop_left, int crop_h, int crop_w, uint8_t* d_dst) {
-    if (filter == VQ_RESAMPLE_CV_LINEAR)
-        return run_device_cv(r, d_src, n, h, w, out_h, out_w, crop_top, crop_left, crop_h, crop_w, d_dst);
-    VQ_TRY(plan(r, h, w, filter, out_h, out_w));
-    const int* bv = r->cv.bounds.data();
-    const int row_first = bv[2 * crop_top];
-    const int row_last = bv[2 * (crop_top + crop_h - 1)] + bv[2 * (crop_top + crop_h - 1) + 1];
-    const int rows_needed = row_last - row_first;
-    const size_t tmp_bytes = (size_t)n * rows_needed * crop_w * 3;
-    if (tmp_bytes > r->tmp.cap) VQ_HIP(hipStreamSynchronize(r->stream));     // queued passes still use the old workspace
-    VQ_TRY(r->tmp.reserve(tmp_bytes));
-    // horizontal pass: 64 rows x `oc` output columns per workgroup; oc shrinks until the staged source span fits
-    const int* bh = r->ch.bounds.data();
-    auto span_max = [&](int oc) {                            // widest source span (pixels) of any segment
-        int m = 0;
-        for (int x0 = 0; x0 < crop_w; x0 += oc) {
-            const int xa = crop_left + x0, xb = crop_left + std::min(x0 + oc, crop_w) - 1;
-            m = std::max(m, bh[2 * xb] + bh[2 * xb + 1] - bh[2 * xa]);
-        }
-        return m;
-    };
-    int oc = 32, pitch_dw = 0, tile_pitch = 0;
-    size_t lds = 0;
-    // the row-block-major kernel (resample_hx_kernel) needs a staged row to be one wave-wide request of 16-byte loads
-    // (<= 1 KiB with its alignment slack) and a segment's weights to fit four registers per thread
-    static const bool no_hx = []() { const char* e = getenv("VQ_AMD_RSH"); return e && !strcmp(e, "seg"); }();      // A/B switch
-    bool hx = !no_hx;
-    for (int pass = 0; pass < 2; ++pass) {
-        oc = 32;
-        const int slack = hx ? 48 : 24;                      // hx: 15 bytes of alignment instead of 3
-        for (;;) {
-            pitch_dw = (span_max(oc) * 3 + slack + 3) / 4 | 1;    // + realignment and zero-weight over-read slack; odd
-            tile_pitch = (oc * 3 + 3) / 4 * 4;
-            if (((tile_pitch / 4) & 1) == 0) tile_pitch += 4;
-            lds = (size_t)RSH_ROWS * pitch_dw * 4 + (size_t)RSH_ROWS * tile_pitch + (size_t)oc * r->ch.ksize * 4;
-            // LDS per workgroup: 40 KB = four workgroups per CU for the row-block-major kernel (measured 32 / 40 / 48 / 64 KB:
-            // 0.184 / 0.161 / 0.174 / 0.184 ms per 64 1080p frames), 48 KB for the segment-major one; $VQ_AMD_RSH_LDS_KB overrides
-            static const int lds_kb = []() { const char* e = getenv("VQ_AMD_RSH_LDS_KB"); return e ? atoi(e) : 0; }();
-            const size_t lds_cap = (size_t)(lds_kb > 0 ? lds_kb : hx ? 40 : 48) * 1024;
-            const bool fits = lds <= lds_cap && (!hx || (pitch_dw * 4 <= 1024 && oc * r->ch.ksize <= 4 * RS_THREADS));
-            if (fits || oc == 1) break;
-            oc = oc > 4 ? oc - 4 : oc - 1;
-        }
-        if (!hx || (pitch_dw * 4 <= 1024 && oc * r->ch.ksize <= 4 * RS_THREADS && lds <= 96 * 1024)) break;
-        hx = false;                                          // a single output column already spans more than a request: segment-major kernel
-    }
-    VQ_CHECK(lds <= 150 * 1024, "vq_resampler: a %d -> %d pixel row needs %zu bytes of LDS per workgroup", w, out_w, lds);
-    const bool dword_store = (crop_w % 4 == 0) && (oc % 4 == 0);
-    static bool attr_set = false;
-    if (!attr_set) {
-        VQ_HIP(hipFuncSetAttribute((const void*)resample_h_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        VQ_HIP(hipFuncSetAttribute((const void*)resample_h_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        VQ_HIP(hipFuncSetAttribute((const void*)resample_hx_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        VQ_HIP(hipFuncSetAttribute((const void*)resample_hx_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        attr_set = true;
-    }
-    if (hx) {
-        // segments per workgroup: walk as many as leaves ~4+ rounds of workgroups on the chip
-        const int nseg = cdiv(crop_w, oc), yblocks = cdiv(rows_needed, RSH_ROWS);
-        static const int spw_env = []() { const char* e = getenv("VQ_AMD_RSH_SPW"); return e ? atoi(e) : 0; }();
-        int xsplit = (int)std::max<int64_t>(1, std::min<int64_t>(nseg, cdiv((int64_t)4 * 768, (int64_t)yblocks * n)));
-        int spw = spw_env > 0 ? std::min(spw_env, nseg) : cdiv(nseg, xsplit);
-        const dim3 xgrid(cdiv(nseg, spw), yblocks, n);
-        if (dword_store)
-            hipLaunchKernelGGL(resample_hx_kernel<true>, xgrid, dim3(RS_THREADS), lds, r->stream, d_src, (uint8_t*)r->tmp.p,
-                               r->d_bh, r->d_kh, r->ch.ksize, h, w, row_first, rows_needed, crop_left, crop_w, oc, pitch_dw, tile_pitch, spw);
+    uint8_t* tmp = r->tmp.p; const int ksize = r->tables.ch.ksize;
+    const dim3 hgrid(p.hgrid[0], p.hgrid[1], p.hgrid[2]);
+    dispatch<true, false>(p.dword_store, [&](auto D) {
+        constexpr bool DWORD = decltype(D)::value;
+        if (p.hx)
+            hipLaunchKernelGGL(resample_hx_kernel<DWORD>, hgrid, dim3(RS_THREADS), p.lds, r->stream, d_src, tmp, r->d_bh, r->d_kh, ksize,
+                               g.h, g.w, p.row_first, p.rows_needed, g.crop_left, g.crop_w, p.oc, p.pitch_dw, p.tile_pitch, p.spw);
         else
-            hipLaunchKernelGGL(resample_hx_kernel<false>, xgrid, dim3(RS_THREADS), lds, r->stream, d_src, (uint8_t*)r->tmp.p,
-                               r->d_bh, r->d_kh, r->ch.ksize, h, w, row_first, rows_needed, crop_left, crop_w, oc, pitch_dw, tile_pitch, spw);
-    } else {
-    const dim3 hgrid(cdiv(crop_w, oc), cdiv(rows_needed, RSH_ROWS), n);
-    if (dword_store)
-        hipLaunchKernelGGL(resample_h_kernel<true>, hgrid, dim3(RS_THREADS), lds, r->stream, d_src, (uint8_t*)r->tmp.p,
-                           r->d_bh, r->d_kh, r->ch.ksize, h, w, row_first, rows_needed, crop_left, crop_w, oc, pitch_dw, tile_pitch);
-    else
-        hipLaunchKernelGGL(resample_h_kernel<false>, hgrid, dim3(RS_THREADS), lds, r->stream, d_src, (uint8_t*)r->tmp.p,
-                           r->d_bh, r->d_kh, r->ch.ksize, h, w, row_first, rows_needed, crop_left, crop_w, oc, pitch_dw, tile_pitch);
-    }
+            hipLaunchKernelGGL(resample_h_kernel<DWORD>, hgrid, dim3(RS_THREADS), p.lds, r->stream, d_src, tmp, r->d_bh, r->d_kh, ksize,
+                               g.h, g.w, p.row_first, p.rows_needed, g.crop_left, g.crop_w, p.oc, p.pitch_dw, p.tile_pitch);
+    });
     VQ_HIP(hipGetLastError());
-    const int row_bytes = crop_w * 3;
-    if (row_bytes % 16 == 0 && ((uintptr_t)d_dst & 15) == 0 && ((uintptr_t)r->tmp.p & 15) == 0) {
-        hipLaunchKernelGGL(resample_v_kernel<16>, dim3(cdiv((row_bytes / 16) * crop_h, RS_THREADS), 1, n), dim3(RS_THREADS), 0, r->stream,
-                           (const uint8_t*)r->tmp.p, d_dst, r->d_bv, r->d_kv, r->cv.ksize, rows_needed, row_bytes, crop_top,
-                           crop_h, row_first);
-    } else if (row_bytes % 4 == 0 && ((uintptr_t)d_dst & 3) == 0) {
-        hipLaunchKernelGGL(resample_v_kernel<4>, dim3(cdiv(row_bytes / 4, RS_THREADS), crop_h, n), dim3(RS_THREADS), 0, r->stream,
-                           (const uint8_t*)r->tmp.p, d_dst, r->d_bv, r->d_kv, r->cv.ksize, rows_needed, row_bytes, crop_top,
-                           crop_h, row_first);
-    } else {
-        hipLaunchKernelGGL(resample_v_kernel<1>, dim3(cdiv(row_bytes, RS_THREADS), crop_h, n), dim3(RS_THREADS), 0, r->stream,
-                           (const uint8_t*)r->tmp.p, d_dst, r->d_bv, r->d_kv, r->cv.ksize, rows_needed, row_bytes, crop_top,
-                           crop_h, row_first);
-    }
+    plan_vertical(p, g.crop_h, n, align16(tmp), align16(d_dst));
+    dispatch<16, 4, 1>(p.vvec, [&](auto V) {
+        hipLaunchKernelGGL(resample_v_kernel<decltype(V)::value>, dim3(p.vgrid[0], p.vgrid[1], p.vgrid[2]), dim3(RS_THREADS), 0, r->stream,
+                           (const uint8_t*)tmp, d_dst, r->d_bv, r->d_kv, r->tables.cv.ksize, p.rows_needed, p.row_bytes, g.crop_top,
+                           g.crop_h, p.row_first);
+    });
     VQ_HIP(hipGetLastError());
     return 0;
 }
 
 // Scene-change partials + finalise for m device-resident frames; d_res gets [m][3] = {mse, chi, score} per pair
-// (pair i = (frame i - 1, frame i); pair 0 = (d_prev, frame 0), or zeros when d_prev is null).  Frames go through in
-// batches whose histogram partials fit SCENE_SCRATCH_BYTES: a batch's predecessor is the frame before it, so a batch
-// boundary is one more use of `prev`.  Everything is queued on the handle's stream; r->tmp holds the partials.
-// $VQ_AMD_SCENE_SCRATCH_BYTES (read per call) overrides the budget, so a test can force batches of SC_CHUNK_FRAMES.
-constexpr size_t SCENE_SCRATCH_BYTES = (size_t)256 << 20;
-
+// (pair i = (frame i - 1, frame i); pair 0 = (d_prev, frame 0), or zeros when d_prev is null).  Frames go through in batches whose
+// histogram partials fit the scratch budget ($VQ_AMD_SCENE_SCRATCH_BYTES, read per call); a batch's predecessor is the frame before it.
 int scene_run_device(vq_resampler* r, const uint8_t* d_frames, int m, int h, int w, const uint8_t* d_prev, double* d_res) {
     const int npix = h * w, tiles = cdiv(npix, SC_TILE);
     const size_t frame_bytes = (size_t)npix * 3;
-    const size_t slot_bytes = (size_t)tiles * 256 * sizeof(uint32_t);
-    size_t budget = SCENE_SCRATCH_BYTES;
-    if (const char* e = getenv("VQ_AMD_SCENE_SCRATCH_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-    const int batch = (int)std::min<size_t>((size_t)m, std::max<size_t>(SC_CHUNK_FRAMES, budget / slot_bytes / SC_CHUNK_FRAMES * SC_CHUNK_FRAMES));
-    const size_t hist_bytes = (size_t)(batch + 1) * slot_bytes, ssd_bytes = (size_t)batch * tiles * sizeof(uint32_t);
-    if (hist_bytes + ssd_bytes > r->tmp.cap) VQ_HIP(hipStreamSynchronize(r->stream));     // queued passes still use the old workspace
-    VQ_TRY(r->tmp.reserve(hist_bytes + ssd_bytes));
-    uint32_t* d_hist = (uint32_t*)r->tmp.p;
-    uint32_t* d_ssd = (uint32_t*)((uint8_t*)r->tmp.p + hist_bytes);
+    const SceneBatch sb = plan_scene_batch(m, tiles, env_bytes("VQ_AMD_SCENE_SCRATCH_BYTES", RP_SCENE_SCRATCH_BYTES));
+    VQ_TRY(grow(r, r->tmp, sb.hist_bytes + sb.ssd_bytes));   // queued passes still use the old workspace
+    uint32_t *d_hist = (uint32_t*)r->tmp.p, *d_ssd = (uint32_t*)(r->tmp.p + sb.hist_bytes);
     // 16-byte loads need every frame to start on a 16-byte boundary; anything else takes the byte-load kernel
-    const bool wide = frame_bytes % 16 == 0 && ((uintptr_t)d_frames & 15) == 0 && ((uintptr_t)d_prev & 15) == 0;
-    for (int i = 0; i < m; i += batch) {
-        const int mm = std::min(batch, m - i);
+    const bool wide = frame_bytes % 16 == 0 && align16(d_frames) == 0 && align16(d_prev) == 0;
+    for (int i = 0; i < m; i += sb.batch) {
+        const int mm = std::min(sb.batch, m - i);
         const uint8_t* f = d_frames + (size_t)i * frame_bytes;
         const uint8_t* pv = i == 0 ? d_prev : f - frame_bytes;
-        const dim3 grid(tiles, cdiv(mm, SC_CHUNK_FRAMES));
-        if (wide) hipLaunchKernelGGL(scene_partials_kernel<true>, grid, dim3(RS_THREADS), 0, r->stream, f, pv, d_hist, d_ssd, mm, npix);
-        else hipLaunchKernelGGL(scene_partials_kernel<false>, grid, dim3(RS_THREADS), 0, r->stream, f, pv, d_hist, d_ssd, mm, npix);
+        dispatch<true, false>(wide, [&](auto W) {
+            hipLaunchKernelGGL(scene_partials_kernel<decltype(W)::value>, dim3(tiles, cdiv(mm, SC_CHUNK_FRAMES)), dim3(RS_THREADS), 0,
+                               r->stream, f, pv, d_hist, d_ssd, mm, npix);
+        });
         VQ_HIP(hipGetLastError());
         hipLaunchKernelGGL(scene_finalise_kernel, dim3(mm), dim3(256), 0, r->stream, (const uint32_t*)d_hist, (const uint32_t*)d_ssd,
                            d_res + (size_t)i * 3, tiles, npix, pv ? 1 : 0);
@@ -327,54 +197,24 @@ int scene_run_device(vq_resampler* r, const uint8_t* d_frames, int m, int h, int
     return 0;
 }
 
-// ---- fused post-processing (preproc_kernels.h "fused frame post-processing") ------------------------------
-// m device-resident frames -> d_dst [m][out_h][out_w][3] and, in r->acc, the verdict's results:
-//   partials [m][n_bands][3] int64 | res: kept, sums [m][3] int64 | prefix [m] int32 | keep [m] bytes
-struct PostLayout {
-    size_t partials, res, prefix, keep, total;
-    PostLayout(int m, int nb) {
-        partials = 0;
-        res = partials + (size_t)m * nb * 3 * sizeof(long long);
-        prefix = res + (1 + (size_t)m * 3) * sizeof(long long);
-        keep = prefix + (size_t)round_up((int64_t)m * 4, 8);
-        total = keep + (size_t)round_up(m, 8);
-    }
-};
-
-template <int MODE>
-void launch_fused(vq_resampler* r, bool wide_src, const dim3 grid, size_t lds, const uint8_t* d_src, uint8_t* d_dst, long long* d_part,
-                  int h, int w, int out_h, int out_w, int band_rows, int lrows, int store_vec) {
-    if constexpr (MODE == PP_COPY) if (wide_src) {
-        hipLaunchKernelGGL((postproc_fused_kernel<MODE, true>), grid, dim3(RS_THREADS), lds, r->stream, d_src, d_dst, d_part,
-                           (const int*)r->d_bh, (const int*)r->d_kh, (const int*)r->d_bv, (const int*)r->d_kv, h, w, out_h, out_w,
-                           band_rows, lrows, store_vec);
-        return;
-    }
-    hipLaunchKernelGGL((postproc_fused_kernel<MODE, false>), grid, dim3(RS_THREADS), lds, r->stream, d_src, d_dst, d_part,
-                       (const int*)r->d_bh, (const int*)r->d_kh, (const int*)r->d_bv, (const int*)r->d_kv, h, w, out_h, out_w,
-                       band_rows, lrows, store_vec);
-}
-
-int post_run_device(vq_resampler* r, const uint8_t* d_src, int m, int h, int w, int out_h, int out_w, int quality_filter,
+// fused post-processing (preproc_kernels.h): m device-resident frames -> d_dst [m][out_h][out_w][3] and, in r->acc, the verdict's results (PostLayout)
+int post_run_device(vq_resampler* r, const uint8_t* d_src, int m, const Geometry& g, int quality_filter,
                     uint8_t* d_dst, const PostLayout& lay, int band_rows, int n_bands, int fused) {
-    uint8_t* acc = (uint8_t*)r->acc.p;
-    long long* d_part = (long long*)(acc + lay.partials);
+    const int h = g.h, w = g.w, out_h = g.out_h, out_w = g.out_w;
+    uint8_t* acc = r->acc.p; long long* d_part = (long long*)(acc + lay.partials);
     if (fused) {
-        const int mode = (out_h == h && out_w == w) ? PP_COPY : (h == 2 * out_h && w == 2 * out_w) ? PP_HALF : PP_LINEAR;
-        if (mode == PP_LINEAR) VQ_TRY(plan_cv(r, h, w, out_h, out_w));
-        const int row_bytes = out_w * 3;
-        const int lrows = std::min(band_rows, out_h) + 2;
-        const size_t lds = (size_t)pp_lds_bytes(lrows - 2, out_w);
-        const bool wide_src = row_bytes % 16 == 0 && ((uintptr_t)d_src & 15) == 0;
-        const int store_vec = (row_bytes % 16 == 0 && ((uintptr_t)d_dst & 15) == 0) ? 16 : (row_bytes % 4 == 0 && ((uintptr_t)d_dst & 3) == 0) ? 4 : 1;
-        const dim3 grid(n_bands, m);
-        if (mode == PP_COPY) launch_fused<PP_COPY>(r, wide_src, grid, lds, d_src, d_dst, d_part, h, w, out_h, out_w, band_rows, lrows, store_vec);
-        else if (mode == PP_HALF) launch_fused<PP_HALF>(r, false, grid, lds, d_src, d_dst, d_part, h, w, out_h, out_w, band_rows, lrows, store_vec);
-        else launch_fused<PP_LINEAR>(r, false, grid, lds, d_src, d_dst, d_part, h, w, out_h, out_w, band_rows, lrows, store_vec);
+        const PostFusedPlan f = plan_post_fused(h, w, out_h, out_w, band_rows, align16(d_src), align16(d_dst));
+        if (f.mode == PP_LINEAR) VQ_TRY(ensure_tables(r, g));
+        const size_t lds = (size_t)pp_lds_bytes(f.lrows - 2, out_w);
+        dispatch<PP_COPY, PP_HALF, PP_LINEAR>(f.mode, [&](auto M) { dispatch<true, false>(f.wide_src, [&](auto W) {
+            constexpr int MODE = decltype(M)::value;
+            constexpr bool WIDE = MODE == PP_COPY && decltype(W)::value;     // 16-byte source loads: copies only
+            hipLaunchKernelGGL((postproc_fused_kernel<MODE, WIDE>), dim3(n_bands, m), dim3(RS_THREADS), lds, r->stream, d_src, d_dst, d_part,
+                               r->d_bh, r->d_kh, r->d_bv, r->d_kv, h, w, out_h, out_w, band_rows, f.lrows, f.store_vec);
+        }); });
         VQ_HIP(hipGetLastError());
     } else {
-        // a row too wide for the LDS plan: the resize kernel, then frame_quality_kernel over the device buffer (one partial per frame)
-        VQ_TRY(run_device_cv(r, d_src, m, h, w, out_h, out_w, 0, 0, out_h, out_w, d_dst));
+        VQ_TRY(run_device_cv(r, d_src, m, g, d_dst));      // a row too wide for the LDS plan: resize, then frame_quality_kernel (one partial per frame)
         VQ_HIP(hipMemsetAsync(d_part, 0, (size_t)m * 3 * sizeof(long long), r->stream));
         const int wgs = std::min(cdiv((int64_t)out_h * out_w, RS_THREADS), 1024);
         hipLaunchKernelGGL(frame_quality_kernel, dim3(wgs, m), dim3(RS_THREADS), 0, r->stream, (const uint8_t*)d_dst, d_part, out_h, out_w);
@@ -386,99 +226,91 @@ int post_run_device(vq_resampler* r, const uint8_t* d_src, int m, int h, int w, 
     return 0;
 }
 
-// `list` (n host frames) or `d_frames` (n contiguous device frames): exactly one of them
-int postprocess(const char* who, vq_resampler* r, const uint8_t* const* list, const uint8_t* d_frames, int n, int h, int w,
-                int out_h, int out_w, int quality_filter, uint8_t* out, int64_t* n_kept, uint8_t* keep, int64_t* sums) {
+int postprocess(const char* who, vq_resampler* r, const Frames& f, int n, int h, int w, int out_h, int out_w, int quality_filter,
+                uint8_t* out, int64_t* n_kept, uint8_t* keep, int64_t* sums) {
     VQ_TRY(require_init());
     VQ_CHECK(r && n >= 0 && h > 0 && w > 0 && out_h >= 0 && out_w >= 0 && (out_h == 0) == (out_w == 0) && n_kept &&
-             (n == 0 || ((list || d_frames) && keep)), "%s: bad argument", who);
+             (n == 0 || (f.any() && keep)), "%s: bad argument", who);
     if (out_h == 0) { out_h = h; out_w = w; }
-    VQ_CHECK((int64_t)h * w < (int64_t)1 << 30, "%s: frame of %dx%d pixels is too large", who, h, w);
     VQ_CHECK((int64_t)out_h * out_w <= PP_MAX_PIXELS, "%s: output of %dx%d pixels is too large (at most 2^21 pixels: the integer "
              "verdict must stay inside int64)", who, out_h, out_w);
-    VQ_CHECK(n <= 65535, "%s: at most 65535 frames per call", who);
-    VQ_TRY(check_geometry(who, n, h, w, VQ_RESAMPLE_CV_LINEAR, out_h, out_w, 0, 0, out_h, out_w));
+    const Geometry g{{h, w, VQ_RESAMPLE_CV_LINEAR, out_h, out_w}, 0, 0, out_h, out_w};
+    VQ_TRY(check_geometry(who, n, g));
     *n_kept = 0;
     if (n == 0) return 0;
-    if (list) for (int i = 0; i < n; ++i) VQ_CHECK(list[i], "%s: frame %d is null", who, i);
+    VQ_TRY(check_list(who, f, n));
     std::lock_guard<std::mutex> lk(r->mu);
     const size_t frame_bytes = (size_t)h * w * 3, ob = (size_t)out_h * out_w * 3;
-    int band_rows, n_bands, fused;
-    pp_plan(out_h, out_w, &band_rows, &n_bands, &fused);
+    int band_rows, n_bands, fused; pp_plan(out_h, out_w, &band_rows, &n_bands, &fused);
     const bool need_stats = quality_filter || sums;
-    int slice = n;
-    if (list) {
-        size_t budget = (size_t)512 << 20;
-        if (const char* e = getenv("VQ_AMD_POSTPROC_SLICE_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-        slice = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / frame_bytes));
-    }
+    const int slice = f.on_device ? n : slice_frames(n, frame_bytes, env_bytes("VQ_AMD_POSTPROC_SLICE_BYTES", RP_SLICE_BYTES));
     const bool single = slice >= n;
     VQ_HIP(hipStreamSynchronize(r->stream));                 // the buffers below may move; an earlier result may still be read
-    r->out_ptr = nullptr;                                    // a call that fails half way leaves no result behind
-    r->out_bytes = 0;
-    if (list) VQ_TRY(r->src.reserve((size_t)slice * frame_bytes));
-    VQ_TRY(r->dst.reserve((size_t)slice * ob));
-    if (!single) VQ_TRY(r->post.reserve((size_t)n * ob));
+    r->out_ptr = nullptr; r->out_bytes = 0;                  // a call that fails half way leaves no result behind
+    VQ_TRY(r->dst.reserve((int64_t)((size_t)slice * ob)));
+    if (!single) VQ_TRY(r->post.reserve((int64_t)((size_t)n * ob)));
     const PostLayout lay(slice, n_bands);
-    if (need_stats) VQ_TRY(r->acc.reserve(lay.total));
+    if (need_stats) VQ_TRY(r->acc.reserve((int64_t)lay.total));
     std::vector<long long> res(1 + (size_t)slice * 3);
     int64_t kept_total = 0;
     void* result = r->dst.p;
-    for (int i = 0; i < n; i += slice) {
-        const int m = std::min(slice, n - i);
-        const uint8_t* d_src = d_frames;
-        if (list) {
-            for (int a = 0; a < m;) {                        // consecutive frames that are contiguous in host memory go up in one copy
-                int b = a + 1;
-                while (b < m && list[i + b] == list[i + b - 1] + frame_bytes) ++b;
-                VQ_HIP(hipMemcpyAsync((uint8_t*)r->src.p + (size_t)a * frame_bytes, list[i + a], (size_t)(b - a) * frame_bytes,
-                                      hipMemcpyHostToDevice, r->stream));
-                a = b;
-            }
-            d_src = (const uint8_t*)r->src.p;
-        }
-        int64_t kept = m;
+    VQ_TRY(for_each_slice(r, f, n, frame_bytes, slice, 0, true, [&](const uint8_t* d_src, int i, int m) {
         if (!need_stats) {                                   // nothing to decide: the resize alone, straight into its final place
-            uint8_t* target = single ? (uint8_t*)r->dst.p : (uint8_t*)r->post.p + (size_t)i * ob;
-            VQ_TRY(run_device_cv(r, d_src, m, h, w, out_h, out_w, 0, 0, out_h, out_w, target));
+            uint8_t* target = single ? r->dst.p : r->post.p + (size_t)i * ob;
+            VQ_TRY(run_device_cv(r, d_src, m, g, target));
             memset(keep + i, 1, (size_t)m);
             result = single ? r->dst.p : r->post.p;
+            kept_total += m;
+            return 0;
+        }
+        VQ_TRY(post_run_device(r, d_src, m, g, quality_filter, r->dst.p, lay, band_rows, n_bands, fused));
+        VQ_HIP(hipMemcpyAsync(res.data(), r->acc.p + lay.res, (1 + (size_t)m * 3) * sizeof(long long), hipMemcpyDeviceToHost, r->stream));
+        VQ_HIP(hipMemcpyAsync(keep + i, r->acc.p + lay.keep, (size_t)m, hipMemcpyDeviceToHost, r->stream));
+        VQ_HIP(hipStreamSynchronize(r->stream));             // the host needs the count to place the next slice's survivors
+        const int64_t kept = res[0];
+        if (sums) memcpy(sums + (size_t)i * 3, res.data() + 1, (size_t)m * 3 * sizeof(long long));
+        if (single && kept == m) {
+            result = r->dst.p;                               // everything kept: the resized buffer is the result
         } else {
-            VQ_TRY(post_run_device(r, d_src, m, h, w, out_h, out_w, quality_filter, (uint8_t*)r->dst.p, lay, band_rows, n_bands, fused));
-            const uint8_t* acc = (const uint8_t*)r->acc.p;
-            VQ_HIP(hipMemcpyAsync(res.data(), acc + lay.res, (1 + (size_t)m * 3) * sizeof(long long), hipMemcpyDeviceToHost, r->stream));
-            VQ_HIP(hipMemcpyAsync(keep + i, acc + lay.keep, (size_t)m, hipMemcpyDeviceToHost, r->stream));
-            VQ_HIP(hipStreamSynchronize(r->stream));         // the host needs the count to place the next slice's survivors
-            kept = res[0];
-            if (sums) memcpy(sums + (size_t)i * 3, res.data() + 1, (size_t)m * 3 * sizeof(long long));
-            if (single && kept == m) {
-                result = r->dst.p;                           // everything kept: the resized buffer is the result
-            } else {
-                if (single) VQ_TRY(r->post.reserve((size_t)kept * ob));
-                result = r->post.p;
-                if (kept > 0) {
-                    uint8_t* target = (uint8_t*)r->post.p + (size_t)kept_total * ob;
-                    const bool wide = ob % 16 == 0;          // hipMalloc'd bases are 16-byte aligned, and so is every frame slot then
-                    const dim3 grid(std::max(1, std::min(cdiv((int64_t)(wide ? ob / 16 : ob), RS_THREADS), 64)), m);
-                    if (wide) hipLaunchKernelGGL(postproc_gather_kernel<true>, grid, dim3(RS_THREADS), 0, r->stream, (const uint8_t*)r->dst.p,
-                                                 target, acc + lay.keep, (const int*)(acc + lay.prefix), ob);
-                    else hipLaunchKernelGGL(postproc_gather_kernel<false>, grid, dim3(RS_THREADS), 0, r->stream, (const uint8_t*)r->dst.p,
-                                            target, acc + lay.keep, (const int*)(acc + lay.prefix), ob);
-                    VQ_HIP(hipGetLastError());
-                }
+            if (single) VQ_TRY(grow(r, r->post, (size_t)kept * ob));
+            result = r->post.p;
+            if (kept > 0) {
+                uint8_t* target = r->post.p + (size_t)kept_total * ob;
+                const bool wide = ob % 16 == 0;              // hipMalloc'd bases are 16-byte aligned, and so is every frame slot then
+                const dim3 grid(std::max(1, std::min(cdiv((int64_t)(wide ? ob / 16 : ob), RS_THREADS), 64)), m);
+                dispatch<true, false>(wide, [&](auto W) {
+                    hipLaunchKernelGGL(postproc_gather_kernel<decltype(W)::value>, grid, dim3(RS_THREADS), 0, r->stream, (const uint8_t*)r->dst.p,
+                                       target, (const uint8_t*)(r->acc.p + lay.keep), (const int*)(r->acc.p + lay.prefix), ob);
+                });
+                VQ_HIP(hipGetLastError());
             }
         }
         kept_total += kept;
-        VQ_HIP(hipStreamSynchronize(r->stream));             // the source slice and the resized slice are reused
-    }
+        return 0;
+    }));
     r->out_ptr = result;
     r->out_bytes = (int64_t)((size_t)kept_total * ob);
-    if (out && kept_total > 0) {
-        VQ_HIP(hipMemcpyAsync(out, result, (size_t)kept_total * ob, hipMemcpyDeviceToHost, r->stream));
-        VQ_HIP(hipStreamSynchronize(r->stream));
-    }
+    if (out && kept_total > 0) VQ_TRY(fetch(r, out, result, (size_t)kept_total * ob));
     *n_kept = kept_total;
     return 0;
+}
+
+// host frames in; the result in r->dst and, with `out`, on the host
+int resize_host(const char* who, vq_resampler* r, const Frames& f, int n, const Geometry& g, uint8_t* out) {
+    VQ_TRY(require_init());
+    VQ_CHECK(r && (n <= 0 || f.any()), "%s: null argument", who);
+    VQ_TRY(check_geometry(who, n, g));
+    if (n == 0) return 0;
+    VQ_TRY(check_list(who, f, n));
+    std::lock_guard<std::mutex> lk(r->mu);
+    const size_t frame_bytes = (size_t)g.h * g.w * 3, ob_frame = (size_t)g.crop_h * g.crop_w * 3;
+    VQ_HIP(hipStreamSynchronize(r->stream));
+    VQ_TRY(r->dst.reserve((int64_t)((size_t)n * ob_frame)));
+    r->out_bytes = (int64_t)((size_t)n * ob_frame); r->out_ptr = r->dst.p;
+    VQ_TRY(for_each_slice(r, f, n, frame_bytes, slice_frames(n, frame_bytes, RP_SLICE_BYTES), 0, true, [&](const uint8_t* d_src, int i, int m) {
+        return run_device(r, d_src, m, g, r->dst.p + (size_t)i * ob_frame);
+    }));
+    return out ? fetch(r, out, r->dst.p, (size_t)n * ob_frame) : 0;
 }
 
 }  // namespace
@@ -499,9 +331,9 @@ int vq_resampler_create(vq_resampler** out) {
 int vq_resampler_destroy(vq_resampler* r) {
     if (!r) return 0;
     (void)hipStreamSynchronize(r->stream);
-    r->src.release(); r->tmp.release(); r->dst.release(); r->coef.release(); r->acc.release(); r->post.release();
-    if (r->own_stream) (void)hipStreamDestroy(r->own_stream);
-    delete r;
+    const hipStream_t own = r->own_stream;
+    delete r;                                                // frees the buffers
+    if (own) (void)hipStreamDestroy(own);
     return 0;
 }
 
@@ -515,7 +347,9 @@ int vq_resampler_set_stream(vq_resampler* r, void* hip_stream) {
 
 int vq_resampler_synchronize(vq_resampler* r) {
     VQ_CHECK(r, "vq_resampler_synchronize: null handle");
-    VQ_HIP(hipStreamSynchronize(r->stream));
+    hipStream_t s;
+    { std::lock_guard<std::mutex> lk(r->mu); s = r->stream; }    // set_stream writes it under the lock; the wait itself is outside
+    VQ_HIP(hipStreamSynchronize(s));
     return 0;
 }
 
@@ -523,64 +357,27 @@ int vq_resampler_run_u8_device(vq_resampler* r, const uint8_t* d_frames, int n, 
                                int out_h, int out_w, int crop_top, int crop_left, int crop_h, int crop_w, uint8_t* d_out) {
     VQ_TRY(require_init());
     VQ_CHECK(r && (n == 0 || d_frames), "vq_resampler_run_u8_device: null argument");
-    VQ_TRY(check_geometry("vq_resampler_run_u8_device", n, h, w, filter, out_h, out_w, crop_top, crop_left, crop_h, crop_w));
+    const Geometry g{{h, w, filter, out_h, out_w}, crop_top, crop_left, crop_h, crop_w};
+    VQ_TRY(check_geometry("vq_resampler_run_u8_device", n, g));
     if (n == 0) return 0;
     std::lock_guard<std::mutex> lk(r->mu);
     const size_t ob = (size_t)n * crop_h * crop_w * 3;
     if (!d_out) {
-        if (ob > r->dst.cap) VQ_HIP(hipStreamSynchronize(r->stream));     // a reader of the old buffer may be queued
-        VQ_TRY(r->dst.reserve(ob));
-        d_out = (uint8_t*)r->dst.p;
+        VQ_TRY(grow(r, r->dst, ob));                         // a reader of the old buffer may be queued
+        r->out_ptr = d_out = r->dst.p;
         r->out_bytes = (int64_t)ob;
-        r->out_ptr = r->dst.p;
     }
-    return run_device(r, d_frames, n, h, w, filter, out_h, out_w, crop_top, crop_left, crop_h, crop_w, d_out);
+    return run_device(r, d_frames, n, g, d_out);
 }
 
 int vq_resampler_run_u8_list(vq_resampler* r, const uint8_t* const* frames, int n, int h, int w, int filter,
                              int out_h, int out_w, int crop_top, int crop_left, int crop_h, int crop_w, uint8_t* out) {
-    VQ_TRY(require_init());
-    VQ_CHECK(r && (n == 0 || frames), "vq_resampler_run_u8_list: null argument");
-    VQ_TRY(check_geometry("vq_resampler_run_u8_list", n, h, w, filter, out_h, out_w, crop_top, crop_left, crop_h, crop_w));
-    if (n == 0) return 0;
-    for (int i = 0; i < n; ++i) VQ_CHECK(frames[i], "vq_resampler_run_u8_list: frame %d is null", i);
-    std::lock_guard<std::mutex> lk(r->mu);
-    const size_t frame_bytes = (size_t)h * w * 3, ob_frame = (size_t)crop_h * crop_w * 3;
-    VQ_HIP(hipStreamSynchronize(r->stream));
-    VQ_TRY(r->dst.reserve((size_t)n * ob_frame));
-    r->out_bytes = (int64_t)((size_t)n * ob_frame);
-    r->out_ptr = r->dst.p;
-    // frames go up in slices of <= 512 MiB so the source workspace stays bounded
-    int slice = (int)std::max<size_t>(1, ((size_t)512 << 20) / frame_bytes);
-    if (slice > n) slice = n;
-    VQ_TRY(r->src.reserve((size_t)slice * frame_bytes));
-    for (int i = 0; i < n; i += slice) {
-        const int m = std::min(slice, n - i);
-        // consecutive frames that are contiguous in host memory go up in one copy
-        for (int a = 0; a < m;) {
-            int b = a + 1;
-            while (b < m && frames[i + b] == frames[i + b - 1] + frame_bytes) ++b;
-            VQ_HIP(hipMemcpyAsync((uint8_t*)r->src.p + (size_t)a * frame_bytes, frames[i + a], (size_t)(b - a) * frame_bytes,
-                                  hipMemcpyHostToDevice, r->stream));
-            a = b;
-        }
-        VQ_TRY(run_device(r, (const uint8_t*)r->src.p, m, h, w, filter, out_h, out_w, crop_top, crop_left, crop_h, crop_w,
-                          (uint8_t*)r->dst.p + (size_t)i * ob_frame));
-        VQ_HIP(hipStreamSynchronize(r->stream));             // the source slice is reused
-    }
-    if (out) {
-        VQ_HIP(hipMemcpyAsync(out, r->dst.p, (size_t)n * ob_frame, hipMemcpyDeviceToHost, r->stream));
-        VQ_HIP(hipStreamSynchronize(r->stream));
-    }
-    return 0;
+    return resize_host("vq_resampler_run_u8_list", r, Frames{frames, nullptr, false}, n, {{h, w, filter, out_h, out_w}, crop_top, crop_left, crop_h, crop_w}, out);
 }
 
 int vq_resampler_run_u8(vq_resampler* r, const uint8_t* frames, int n, int h, int w, int filter,
                         int out_h, int out_w, int crop_top, int crop_left, int crop_h, int crop_w, uint8_t* out) {
-    VQ_CHECK(r && n >= 0 && (n == 0 || frames) && h > 0 && w > 0, "vq_resampler_run_u8: bad argument");
-    std::vector<const uint8_t*> ptrs((size_t)n);
-    for (int i = 0; i < n; ++i) ptrs[i] = frames + (size_t)i * h * w * 3;
-    return vq_resampler_run_u8_list(r, ptrs.data(), n, h, w, filter, out_h, out_w, crop_top, crop_left, crop_h, crop_w, out);
+    return resize_host("vq_resampler_run_u8", r, Frames{nullptr, frames, false}, n, {{h, w, filter, out_h, out_w}, crop_top, crop_left, crop_h, crop_w}, out);
 }
 
 int vq_resampler_device_output(vq_resampler* r, void** d_ptr, int64_t* bytes) {
@@ -608,36 +405,23 @@ int vq_frame_quality_u8(vq_resampler* r, const uint8_t* frames, int n, int h, in
                         double* mean_brightness, double* laplacian_var) {
     VQ_TRY(require_init());
     VQ_CHECK(r && n >= 0 && h > 0 && w > 0 && (n == 0 || (frames && mean_brightness && laplacian_var)), "vq_frame_quality_u8: bad argument");
-    VQ_CHECK((int64_t)h * w < (int64_t)1 << 30, "vq_frame_quality_u8: frame of %dx%d pixels is too large", h, w);
-    VQ_CHECK(n <= 65535, "vq_frame_quality_u8: at most 65535 frames per call");
+    VQ_TRY(check_frames("vq_frame_quality_u8", n, h, w));
     if (n == 0) return 0;
     std::lock_guard<std::mutex> lk(r->mu);
     const size_t frame_bytes = (size_t)h * w * 3;
     VQ_HIP(hipStreamSynchronize(r->stream));
-    VQ_TRY(r->acc.reserve((size_t)n * 3 * sizeof(long long)));
-    VQ_HIP(hipMemsetAsync(r->acc.p, 0, (size_t)n * 3 * sizeof(long long), r->stream));
-    int slice = n;
-    if (!on_device) {
-        slice = (int)std::max<size_t>(1, ((size_t)512 << 20) / frame_bytes);
-        if (slice > n) slice = n;
-        VQ_TRY(r->src.reserve((size_t)slice * frame_bytes));
-    }
+    VQ_TRY(r->acc.reserve((int64_t)((size_t)n * 3 * sizeof(long long))));
+    long long* d_acc = (long long*)r->acc.p;
+    VQ_HIP(hipMemsetAsync(d_acc, 0, (size_t)n * 3 * sizeof(long long), r->stream));
     const int wgs = std::min(cdiv((int64_t)h * w, RS_THREADS), 1024);
-    for (int i = 0; i < n; i += slice) {
-        const int m = std::min(slice, n - i);
-        const uint8_t* d = frames + (size_t)i * frame_bytes;
-        if (!on_device) {
-            VQ_HIP(hipMemcpyAsync(r->src.p, d, (size_t)m * frame_bytes, hipMemcpyHostToDevice, r->stream));
-            d = (const uint8_t*)r->src.p;
-        }
-        hipLaunchKernelGGL(frame_quality_kernel, dim3(wgs, m), dim3(RS_THREADS), 0, r->stream, d,
-                           (long long*)r->acc.p + (size_t)i * 3, h, w);
+    const int slice = on_device ? n : slice_frames(n, frame_bytes, RP_SLICE_BYTES);
+    VQ_TRY(for_each_slice(r, Frames{nullptr, frames, on_device != 0}, n, frame_bytes, slice, 0, !on_device, [&](const uint8_t* d, int i, int m) {
+        hipLaunchKernelGGL(frame_quality_kernel, dim3(wgs, m), dim3(RS_THREADS), 0, r->stream, d, d_acc + (size_t)i * 3, h, w);
         VQ_HIP(hipGetLastError());
-        if (!on_device) VQ_HIP(hipStreamSynchronize(r->stream));
-    }
+        return 0;
+    }));
     std::vector<long long> acc((size_t)n * 3);
-    VQ_HIP(hipMemcpyAsync(acc.data(), r->acc.p, acc.size() * sizeof(long long), hipMemcpyDeviceToHost, r->stream));
-    VQ_HIP(hipStreamSynchronize(r->stream));
+    VQ_TRY(fetch(r, acc.data(), d_acc, acc.size() * sizeof(long long)));
     const double npix = (double)h * w;
     for (int i = 0; i < n; ++i) {
         mean_brightness[i] = (double)acc[3 * i] / (npix * 3.0);
@@ -654,38 +438,33 @@ int vq_frame_scene_scores_u8(vq_resampler* r, const uint8_t* frames, int n, int 
     VQ_CHECK(r && n >= 0 && h > 0 && w > 0 && (n == 0 || (frames && score)), "vq_frame_scene_scores_u8: bad argument");
     VQ_CHECK((int64_t)h * w <= (int64_t)1 << 24, "vq_frame_scene_scores_u8: frame of %dx%d pixels is too large (at most 2^24 pixels: "
              "histogram counts must stay exact in float32)", h, w);
-    VQ_CHECK(n <= 65535, "vq_frame_scene_scores_u8: at most 65535 frames per call");
+    VQ_TRY(check_frames("vq_frame_scene_scores_u8", n, h, w));
     if (n == 0) return 0;
     std::lock_guard<std::mutex> lk(r->mu);
     const size_t frame_bytes = (size_t)h * w * 3;
     VQ_HIP(hipStreamSynchronize(r->stream));
-    VQ_TRY(r->acc.reserve((size_t)n * 3 * sizeof(double)));
+    VQ_TRY(r->acc.reserve((int64_t)((size_t)n * 3 * sizeof(double))));
     double* d_res = (double*)r->acc.p;
     if (on_device) {
         VQ_TRY(scene_run_device(r, frames, n, h, w, prev_frame, d_res));
     } else {
-        // host frames go up in slices; slot 0 of the staging buffer holds the frame before the slice (the caller's
-        // prev_frame, then each slice's last frame), which the device form takes as its prev
-        size_t budget = (size_t)512 << 20;
-        if (const char* e = getenv("VQ_AMD_SCENE_SLICE_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-        const int slice = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / frame_bytes));
-        VQ_TRY(r->src.reserve((size_t)(slice + 1) * frame_bytes));
-        uint8_t* stage = (uint8_t*)r->src.p;
+        // the staging buffer's leading slot holds the frame before the slice (the caller's prev_frame, then each slice's last
+        // frame, carried device to device).  No wait between slices: nothing but the staging buffer is reused.
+        const int slice = slice_frames(n, frame_bytes, env_bytes("VQ_AMD_SCENE_SLICE_BYTES", RP_SLICE_BYTES));
         bool have_prev = prev_frame != nullptr;
-        if (have_prev) VQ_HIP(hipMemcpyAsync(stage, prev_frame, frame_bytes, hipMemcpyHostToDevice, r->stream));
-        for (int i = 0; i < n; i += slice) {
-            const int m = std::min(slice, n - i);
-            VQ_HIP(hipMemcpyAsync(stage + frame_bytes, frames + (size_t)i * frame_bytes, (size_t)m * frame_bytes, hipMemcpyHostToDevice, r->stream));
-            VQ_TRY(scene_run_device(r, stage + frame_bytes, m, h, w, have_prev ? stage : nullptr, d_res + (size_t)i * 3));
+        VQ_TRY(for_each_slice(r, Frames{nullptr, frames, false}, n, frame_bytes, slice, 1, false, [&](const uint8_t* d, int i, int m) {
+            uint8_t* lead = r->src.p;
+            if (i == 0 && have_prev) VQ_HIP(hipMemcpyAsync(lead, prev_frame, frame_bytes, hipMemcpyHostToDevice, r->stream));
+            VQ_TRY(scene_run_device(r, d, m, h, w, have_prev ? lead : nullptr, d_res + (size_t)i * 3));
             if (i + m < n) {
-                VQ_HIP(hipMemcpyAsync(stage, stage + (size_t)m * frame_bytes, frame_bytes, hipMemcpyDeviceToDevice, r->stream));
+                VQ_HIP(hipMemcpyAsync(lead, d + (size_t)(m - 1) * frame_bytes, frame_bytes, hipMemcpyDeviceToDevice, r->stream));
                 have_prev = true;
             }
-        }
+            return 0;
+        }));
     }
     std::vector<double> res((size_t)n * 3);
-    VQ_HIP(hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(double), hipMemcpyDeviceToHost, r->stream));
-    VQ_HIP(hipStreamSynchronize(r->stream));
+    VQ_TRY(fetch(r, res.data(), d_res, res.size() * sizeof(double)));
     for (int i = 0; i < n; ++i) {
         if (mse) mse[i] = res[3 * (size_t)i];
         if (hist_diff) hist_diff[i] = res[3 * (size_t)i + 1];
@@ -703,17 +482,42 @@ int vq_frame_postprocess_plan(int out_h, int out_w, int* band_rows, int* n_bands
 
 int vq_frame_postprocess_u8_list(vq_resampler* r, const uint8_t* const* frames, int n, int h, int w, int out_h, int out_w,
                                  int quality_filter, uint8_t* out, int64_t* n_kept, uint8_t* keep, int64_t* sums) {
-    return postprocess("vq_frame_postprocess_u8_list", r, frames, nullptr, n, h, w, out_h, out_w, quality_filter, out, n_kept, keep, sums);
+    return postprocess("vq_frame_postprocess_u8_list", r, Frames{frames, nullptr, false}, n, h, w, out_h, out_w, quality_filter, out, n_kept, keep, sums);
 }
 
 int vq_frame_postprocess_u8(vq_resampler* r, const uint8_t* frames, int n, int h, int w, int on_device, int out_h, int out_w,
                             int quality_filter, uint8_t* out, int64_t* n_kept, uint8_t* keep, int64_t* sums) {
-    if (on_device)
-        return postprocess("vq_frame_postprocess_u8", r, nullptr, frames, n, h, w, out_h, out_w, quality_filter, out, n_kept, keep, sums);
-    VQ_CHECK(n >= 0 && n <= 65535 && h > 0 && w > 0 && (n == 0 || frames), "vq_frame_postprocess_u8: bad argument (at most 65535 frames per call)");
-    std::vector<const uint8_t*> ptrs((size_t)n);
-    for (int i = 0; i < n; ++i) ptrs[i] = frames + (size_t)i * h * w * 3;
-    return postprocess("vq_frame_postprocess_u8", r, n ? ptrs.data() : nullptr, nullptr, n, h, w, out_h, out_w, quality_filter, out, n_kept, keep, sums);
+    return postprocess("vq_frame_postprocess_u8", r, Frames{nullptr, frames, on_device != 0}, n, h, w, out_h, out_w, quality_filter, out, n_kept, keep, sums);
+}
+
+// ---- the plans as values, on a machine without a device (tests/test_preproc_plan_cpu.py) ------------------
+int vq_debug_resample_plan(int h, int w, int filter, int out_h, int out_w, int crop_top, int crop_left, int crop_h, int crop_w, int n,
+                           int tmp_align, int dst_align, int force_seg, int lds_kb, int spw, vq_resample_plan* out) {
+    VQ_CHECK(out && n >= 1 && (filter == VQ_RESAMPLE_BILINEAR || filter == VQ_RESAMPLE_BICUBIC) && tmp_align >= 0 && dst_align >= 0,
+             "vq_debug_resample_plan: a result, n >= 1, a Pillow filter and two alignments >= 0");
+    const Geometry g{{h, w, filter, out_h, out_w}, crop_top, crop_left, crop_h, crop_w};
+    VQ_TRY(check_geometry("vq_debug_resample_plan", n, g));
+    ResampleTables t;
+    build_tables(g, t);
+    ResamplePlan p = plan_resample(t, n, crop_top, crop_left, crop_h, crop_w, ResampleSwitches{force_seg != 0, lds_kb, spw});
+    if (p.err) return fail(p.err, "%s", p.msg);
+    plan_vertical(p, crop_h, n, tmp_align, dst_align);
+    *out = vq_resample_plan{p.row_first, p.rows_needed, (int64_t)p.tmp_bytes, p.hx, p.oc, p.span, p.pitch_dw, p.tile_pitch, (int64_t)p.lds,
+                            p.dword_store, p.spw, p.hgrid[0], p.hgrid[1], p.hgrid[2], t.ch.ksize, t.cv.ksize, p.row_bytes, p.vvec, p.vgrid[0],
+                            p.vgrid[1], p.vgrid[2]};
+    return 0;
+}
+
+int vq_debug_preproc_small_plans(int n, int64_t frame_bytes, int64_t slice_budget, int m, int tiles, int64_t scratch_budget,
+                                 int post_m, int post_bands, int64_t* out) {
+    VQ_CHECK(out && n >= 1 && frame_bytes >= 1 && slice_budget >= 1 && m >= 1 && tiles >= 1 && scratch_budget >= 1 && post_m >= 1 && post_bands >= 1,
+             "vq_debug_preproc_small_plans: a result and positive arguments");
+    const SceneBatch sb = plan_scene_batch(m, tiles, (size_t)scratch_budget);
+    const PostLayout lay(post_m, post_bands);
+    const int64_t v[9] = {slice_frames(n, (size_t)frame_bytes, (size_t)slice_budget), sb.batch, (int64_t)sb.hist_bytes, (int64_t)sb.ssd_bytes,
+                          (int64_t)lay.partials, (int64_t)lay.res, (int64_t)lay.prefix, (int64_t)lay.keep, (int64_t)lay.total};
+    memcpy(out, v, sizeof(v));
+    return 0;
 }
 
 }  // extern "C"

@@ -73,6 +73,23 @@ def _frames(frames) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
+def _frame_list(frames):
+    """A list of separately allocated uint8 [h, w, 3] frames of one size → (contiguous arrays, h, w)."""
+    arrs = [np.ascontiguousarray(f) for f in frames]
+    if not arrs:
+        return arrs, 0, 0
+    h, w = arrs[0].shape[:2]
+    for a in arrs:
+        if a.dtype != np.uint8 or a.shape != (h, w, 3):
+            raise ValueError(f"expected uint8 frames of one shape ({h}, {w}, 3), got {a.dtype} {a.shape}")
+    return arrs, h, w
+
+
+def _window(crop, out_h, out_w):
+    """(top, left, h, w) of the crop; default: the whole resized frame."""
+    return tuple(int(v) for v in crop) if crop is not None else (0, 0, int(out_h), int(out_w))
+
+
 class FramePreprocessor:
     def __init__(self, device: Optional[int] = None):
         self.device = _lib.init(device)
@@ -105,10 +122,10 @@ class FramePreprocessor:
         ``keep_on_device`` the device address of that array (valid until the next call on this object)."""
         a = _frames(frames)
         n, h, w = a.shape[:3]
-        top, left, ch, cw = crop if crop is not None else (0, 0, out_h, out_w)
+        top, left, ch, cw = _window(crop, out_h, out_w)
         out = None if keep_on_device else np.empty((n, ch, cw, 3), dtype=np.uint8)
         _lib.check(_lib.load().vq_resampler_run_u8(self._h, a.ctypes.data_as(c_void_p), n, h, w, int(filter), int(out_h),
-                                                   int(out_w), int(top), int(left), int(ch), int(cw),
+                                                   int(out_w), top, left, ch, cw,
                                                    out.ctypes.data_as(c_void_p) if out is not None else None))
         if out is not None:
             return out
@@ -119,27 +136,22 @@ class FramePreprocessor:
     def resize_list(self, frames, out_h: int, out_w: int, filter: int = BILINEAR,
                     crop: Optional[Tuple[int, int, int, int]] = None) -> np.ndarray:
         """:meth:`resize` for a list of separately allocated uint8 [h, w, 3] frames of one size (no stacking copy)."""
-        arrs = [np.ascontiguousarray(f) for f in frames]
+        arrs, h, w = _frame_list(frames)
         if not arrs:
             return np.empty((0, out_h, out_w, 3), np.uint8)
-        h, w = arrs[0].shape[:2]
-        for a in arrs:
-            if a.dtype != np.uint8 or a.shape != (h, w, 3):
-                raise ValueError(f"expected uint8 frames of one shape ({h}, {w}, 3), got {a.dtype} {a.shape}")
-        top, left, ch, cw = crop if crop is not None else (0, 0, out_h, out_w)
+        top, left, ch, cw = _window(crop, out_h, out_w)
         out = np.empty((len(arrs), ch, cw, 3), dtype=np.uint8)
         ptrs = (c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         _lib.check(_lib.load().vq_resampler_run_u8_list(self._h, ptrs, len(arrs), h, w, int(filter), int(out_h), int(out_w),
-                                                        int(top), int(left), int(ch), int(cw), out.ctypes.data_as(c_void_p)))
+                                                        top, left, ch, cw, out.ctypes.data_as(c_void_p)))
         return out
 
     def resize_device(self, src_ptr: int, n: int, h: int, w: int, out_h: int, out_w: int, filter: int = BILINEAR,
                       crop: Optional[Tuple[int, int, int, int]] = None, dst_ptr: Optional[int] = None) -> int:
         """Device-resident frames in, device result out; asynchronous on the handle's stream.  → device address."""
-        top, left, ch, cw = crop if crop is not None else (0, 0, out_h, out_w)
+        top, left, ch, cw = _window(crop, out_h, out_w)
         _lib.check(_lib.load().vq_resampler_run_u8_device(self._h, c_void_p(src_ptr), int(n), int(h), int(w), int(filter),
-                                                          int(out_h), int(out_w), int(top), int(left), int(ch), int(cw),
-                                                          c_void_p(dst_ptr or 0)))
+                                                          int(out_h), int(out_w), top, left, ch, cw, c_void_p(dst_ptr or 0)))
         if dst_ptr:
             return dst_ptr
         ptr = c_void_p()
@@ -198,13 +210,9 @@ class FramePreprocessor:
                          always_resize: bool = False):
         """:meth:`postprocess` for a list of separately allocated uint8 [h, w, 3] frames of one size (what sampler
         records hold; no stacking copy)."""
-        arrs = [np.ascontiguousarray(f) for f in frames]
+        arrs, h, w = _frame_list(frames)
         if not arrs:
             return np.empty((0, 0, 0, 3), np.uint8), np.zeros(0, bool), np.zeros((0, 3), np.int64)
-        h, w = arrs[0].shape[:2]
-        for f in arrs:
-            if f.dtype != np.uint8 or f.shape != (h, w, 3):
-                raise ValueError(f"expected uint8 frames of one shape ({h}, {w}, 3), got {f.dtype} {f.shape}")
         ptrs = (c_void_p * len(arrs))(*[f.ctypes.data for f in arrs])
         return self._post(lambda lib, *rest: lib.vq_frame_postprocess_u8_list(self._h, ptrs, len(arrs), h, w, *rest),
                           len(arrs), h, w, frame_size, quality_filter, keep_on_device, always_resize)
