@@ -514,6 +514,66 @@ int vq_index_summarize_groups_device(vq_index* idx, const int32_t* groups /*[n_s
 int vq_debug_summary_plan(int64_t n, int64_t largest_group, int dim, int k, int* lds_rows, int64_t* lds_bytes,
                           int* groups_wide_form, int* launches);
 
+/* Zero-shot labelling: given a vocabulary of prompts, which prompt does each row (frame) show, and what is each group (video)
+ * about.  Every search above reduces along the row axis, per query; this one reduces along the prompt axis, per row.
+ *   Inputs.  Prompts p_0 .. p_{P-1}, 1 <= P <= 4,096, fp32 [P][dim], used as given (HNSWIndex.label_rows normalises them the way
+ *   search normalises queries).  d(r, j) = the distance of prompt j to row r exactly as vq_index_search reports it:
+ *   1.0f - fp32(sum_i (double)x_r[i] * (double)p_j[i]), summed in index order (oracle/knn_oracle.c).
+ *   Row label.  L(r) = the j with the smallest (d(r, j), j): two prompts at equal distance go to the smaller index; id ranks
+ *   play no part.  best(r) = d(r, L(r)).  With max_dist (fp32; +inf: off; NaN: VQ_ERR_INVALID) a row with best(r) > max_dist is
+ *   unlabelled, L(r) = -1, and best(r) is still reported; best(r) == max_dist stays labelled (an fp32 compare).
+ *   Group tags, produced only when group_tags is not NULL (then all four group arrays are needed, and 1 <= m <= 16).  They need
+ *   valid group labels (vq_index_set_groups covering every row) and, when id ranks are set, valid ranks: refused like
+ *   vq_index_search_grouped otherwise.  votes(g, j) = the number of rows of g with L(r) = j.  The tags of g are the first
+ *   min(m, labels with votes > 0) labels by (votes descending, j ascending); tag t carries its votes and show(g, j) = the row of
+ *   g labelled j with the smallest (best(r), tie(r)), tie as vq_index_search (the row number, or the id rank): the frame that
+ *   shows the tag best.  Unused slots are -1 / 0 / -1.  Unlabelled rows vote for nothing; group_unlabelled [g] counts them.  A
+ *   label that holds no row has no tags.
+ *   Everything is integers or fp32 values the plain search defines, so the answer is unique.
+ *   Refusals (VQ_ERR_INVALID, before any work is queued, the outputs untouched): P or (with group outputs) m out of range;
+ *   NaN max_dist; group outputs without valid labels; an unknown mode; mode 2 where the fp16 path does not exist (dim not 256,
+ *   512 or 768, or rows that are not near-unit); host form only: a prompt value that is not finite (the device form documents
+ *   finite prompts as a precondition: it then still ends, by the exact path, with whatever labels NaN distances give).
+ *   An empty index returns 0 and writes nothing.  row_label and row_dist may each be NULL.
+ *   Lifetimes.  Labels and ranks are those of vq_index_set_groups / vq_index_set_id_ranks: vq_index_remove_rows compacts both
+ *   with the rows (they stay valid); vq_index_update_rows keeps them; rows added afterwards make them stale until they are set
+ *   again.  Row labels alone need neither.
+ *   How it runs (csrc/knn_label.h, DESIGN.md §4 "Zero-shot labelling").  mode 1, exact: per chunk of prompts (kept within
+ *   512 MiB of distances) the tiled fp64-chain distance kernel, then a column arg-min that carries every row's running
+ *   (distance, prompt) key across chunks.  mode 2, fp16: one pass over the fp16 matrix per range of 2,048 prompts with the
+ *   256 x 256 LDS-DMA mainloop of the clip search, rows and prompts swapped, and an epilogue that keeps every row's three
+ *   largest score keys; a row whose best key leads the second by more than 2 E + 2^-19 has a proven label and gets one exact
+ *   dot, one that leads the third so gets its two candidates re-scored exactly, any other is filed and redone over all prompts
+ *   exactly, on the device.  E = scan_eps_unit(dim) x max |row| x max |p|.  A prompt with |p|^2 outside [0.25, 4] sends the whole
+ *   call to the exact path (the host form decides that before queueing, the device form on the device).  mode 0 takes the fp16
+ *   path where it exists, the index holds at least 16,384 rows and n x P is at least 2^22 (the measured crossover: below it the
+ *   two paths tie or the exact one is ahead).  The [P][n] table never exists on the
+ *   fp16 path.  Groups: a group of at most 4,096 rows is one workgroup: an LDS histogram of the labels, m selection rounds, a
+ *   second sweep for the show rows.  A longer group is split into pieces of 4,096 rows over workgroups (a histogram per piece,
+ *   added in piece order by the group's workgroup, which runs the rounds; then the pieces' show keys, merged in piece order):
+ *   four launches for all long groups of a call, P counters per piece (at most 4 B per row of a long group), no [G][P] table.
+ *   Scratch: 12 B per row, + 8 B per row (exact) or 20 B per row and prompt range (fp16).
+ *   Cost of the device form's flagged call (a prompt norm outside [0.25, 4]): every row is scored against all prompts by one
+ *   wave per row, about 3.9e9 exact dots per second at dim 512 on one MI355X (measured through the filed rows of the probe): n
+ *   = 1M and P = 4,096 take about a second where the host form's chunked exact path takes 0.25 s.  Normalise the prompts.
+ *   The _device form takes device pointers, is asynchronous on the index's stream and reads nothing back.
+ *   vq_index_last_search_stats afterwards: [0] rows whose label the fp16 pass proved directly, [1] rows settled by the exact
+ *   re-score of their two candidates, [2] rows answered by the exact path over all prompts (mode 1: all of them).
+ *   vq_debug_label_plan (host only, near-unit rows assumed; largest_group = the rows of the longest group, 0 without group
+ *   outputs): the path (fp16_path), the exact path's chunking, the fp16 path's tiles and scratch, the split form's threshold, piece
+ *   length and the pieces of the longest group (0: it runs as one workgroup), and eps: unit rows and prompts whose best and second-best exact scores differ by more than 4 eps are
+ *   always proven directly (eps = E for norms up to 1.0001, plus half the slack). */
+int vq_index_label_rows(vq_index* idx, const float* prompts /*[P][dim]*/, int P, int mode, float max_dist,
+                        int32_t* row_label /*[n] or NULL*/, float* row_dist /*[n] or NULL*/, int m,
+                        int32_t* group_tags /*[G][m] or NULL*/, int32_t* group_votes /*[G][m]*/, int32_t* group_show_rows /*[G][m]*/,
+                        int32_t* group_unlabelled /*[G]*/);
+int vq_index_label_rows_device(vq_index* idx, const void* d_prompts_f32, int P, int mode, float max_dist, void* d_row_label_i32 /*or NULL*/,
+                               void* d_row_dist_f32 /*or NULL*/, int m, void* d_group_tags_i32 /*or NULL*/, void* d_group_votes_i32,
+                               void* d_group_show_rows_i32, void* d_group_unlabelled_i32);
+int vq_debug_label_plan(int64_t n, int dim, int P, int mode, int64_t largest_group, int* fp16_path, int* exact_chunk, int* exact_chunks,
+                        int64_t* exact_bytes, int* prompt_tiles, int* prompt_ranges, int64_t* row_tiles, int64_t* part_bytes, float* eps,
+                        int* group_split_rows, int* group_piece_rows, int64_t* largest_group_pieces);
+
 /* save / load support (hnsw.py:306-380): the stored (normalised) rows. */
 int vq_index_export(vq_index* idx, float* rows /*[size][dim]*/);
 /* Single stored rows (the reference reads `self.data[node_id]`, a dict lookup): out [n][dim] = rows row_numbers[0..n). */

@@ -14,6 +14,7 @@
 #include "knn_distinct.h"
 #include "knn_sequence.h"
 #include "knn_summary.h"
+#include "knn_label.h"
 #include "scan_plan.h"
 #include "host_buffers.h"
 #ifdef VQ_SCAN_EXPERIMENTS      // `make EXPERIMENTS=1`: the two superseded batch mainloops behind VQ_AMD_SCAN=2|4
@@ -141,6 +142,16 @@ struct vq_index {
     IdxBuf<uint64_t> d_sumk;
     IdxBuf<double> d_sumd;
     IdxBuf<int32_t> d_sumout;
+    // zero-shot labelling (knn_label.h): control words {filed rows, flag, largest |p|^2} + the filed-row list + the rows' labels
+    // and best distances (ctl [4] | filed [n_pad] | label [n_pad] | best [n_pad]); the exact path's running keys; the tile
+    // path's parts; the host form's group results
+    IdxBuf<int32_t> d_lw;
+    IdxBuf<uint64_t> d_lrun;
+    IdxBuf<uint32_t> d_lparts;
+    IdxBuf<int32_t> d_lout;
+    IdxBuf<int32_t> d_lgw;         // ... the split group form's lists, unlabelled counts and chosen labels; its pieces' histograms and show keys
+    IdxBuf<uint32_t> d_lghist;
+    IdxBuf<uint64_t> d_lgshow;
     // clip-search scratch (knn_set.h): per-group sums [2][G], candidate list / positions [2][G] + count + flag, |q_i| [m],
     // order keys [G] + the selection's block lists, candidate keys, result staging of the host form
     IdxBuf<double> d_ssum;
@@ -1426,6 +1437,147 @@ int summarize_run(vq_index* x, const char* fn, const int32_t* groups, int32_t n_
     return 0;
 }
 
+// ---- zero-shot labelling (knn_label.h) ----
+bool label_fp16_ok(const vq_index* x) { return label_fp16_dim(x->dim) && x->size >= 1 && x->near_unit; }
+
+// Everything that can refuse a labelling call before any work is queued: the mode, for group outputs stale ranks or labels,
+// and mode 2 where the tile path does not exist.
+int label_precheck(vq_index* x, const char* fn, int mode, bool groups) {
+    VQ_TRY(check_mode(fn, mode));
+    if (groups) {
+        VQ_TRY(check_ranks(x, fn));
+        VQ_TRY(check_labels(x, fn));
+    }
+    if (mode != 1) VQ_TRY(refresh_norm_range(x));
+    if (mode == 2) VQ_CHECK(label_fp16_ok(x), "%s: the fp16 path needs dim 256, 512 or 768 and near-unit rows (0.5 <= |row|^2 <= 2; rows "
+                                              "added with normalize=0 are measured); mode 1 takes any call", fn);
+    return 0;
+}
+
+int check_label_args(const char* fn, const vq_index* x, const void* prompts, int P, float max_dist, int m, bool groups, bool group_arrays) {
+    VQ_CHECK(P >= 1 && P <= LABEL_MAX_P, "%s: P %d outside [1, %d]", fn, P, LABEL_MAX_P);
+    VQ_CHECK(max_dist == max_dist, "%s: max_dist is NaN (+inf: every row is labelled)", fn);
+    if (groups) VQ_CHECK(m >= 1 && m <= LABEL_MAX_M && group_arrays, "%s: group outputs take 1 <= m <= %d and all four arrays", fn, LABEL_MAX_M);
+    VQ_TRY(require_init());
+    VQ_CHECK(x && prompts, "%s: bad argument", fn);
+    return 0;
+}
+
+// The group outputs from the rows' labels (device memory throughout).  Groups above LABEL_GROUP_SPLIT_ROWS rows take the split
+// form: their pieces are listed on the host from the labels' mirror and go up in one copy from the staging ring.
+int label_groups_run(vq_index* x, const int32_t* lab, const float* best, int P, int m, int32_t* tags, int32_t* votes, int32_t* show,
+                     int32_t* unl) {
+    const int32_t* hg = x->h_goff.data();
+    const int G = x->n_groups;
+    int64_t nl = 0, np = 0;
+    for (int g = 0; g < G; ++g) {
+        const int64_t L = (int64_t)hg[g + 1] - hg[g];
+        if (L > LABEL_GROUP_SPLIT_ROWS) { ++nl; np += cdiv(L, LABEL_GROUP_PIECE_ROWS); }
+    }
+    const TieOrder tie = x->tie();
+    Prof pr(x, I_SELECT);
+    hipLaunchKernelGGL(label_group_kernel, dim3(G), dim3(256), 0, x->stream, x->d_goff, x->d_grows, lab, best, P, m, LABEL_GROUP_SPLIT_ROWS, tie,
+                       tags, votes, show, unl);
+    if (nl) {
+        auto words = [](int64_t c) { return round_up(std::max<int64_t>(c, 1), 4); };        // 16-byte aligned regions
+        // host-built lists, one copy: piece_long [np] | piece_b [np] | piece_e [np] | long_group [nl] | long_poff [nl + 1]
+        const int64_t w_np = words(np), w_nl = words(nl), w_nl1 = words(nl + 1), w_lists = 3 * w_np + w_nl + w_nl1;
+        // behind them: punl [np] | lsel [nl][16]
+        VQ_TRY(x->d_lgw.reserve(w_lists + w_np + words(nl * LABEL_MAX_M)));
+        VQ_TRY(x->d_lghist.reserve(np * P));
+        VQ_TRY(x->d_lgshow.reserve(np * LABEL_MAX_M));
+        StageSlot* slot;
+        VQ_TRY(stage_slot(x, w_lists, &slot));
+        int32_t* h = slot->h;
+        int32_t* h_pl = h; int32_t* h_pb = h + w_np; int32_t* h_pe = h_pb + w_np; int32_t* h_lg = h_pe + w_np; int32_t* h_lp = h_lg + w_nl;
+        int64_t l = 0, q = 0;
+        for (int g = 0; g < G; ++g) {
+            const int64_t L = (int64_t)hg[g + 1] - hg[g];
+            if (L <= LABEL_GROUP_SPLIT_ROWS) continue;
+            h_lg[l] = g; h_lp[l] = (int32_t)q;
+            for (int64_t b = hg[g]; b < hg[g + 1]; b += LABEL_GROUP_PIECE_ROWS) {
+                h_pl[q] = (int32_t)l; h_pb[q] = (int32_t)b; h_pe[q] = (int32_t)std::min<int64_t>(b + LABEL_GROUP_PIECE_ROWS, hg[g + 1]);
+                ++q;
+            }
+            ++l;
+        }
+        h_lp[nl] = (int32_t)q;
+        int32_t* d = x->d_lgw;
+        VQ_HIP(hipMemcpyAsync(d, h, (size_t)w_lists * 4, hipMemcpyHostToDevice, x->stream));
+        VQ_HIP(hipEventRecord(slot->ev, x->stream));
+        LabelPieces w;
+        w.piece_long = d; w.piece_b = d + w_np; w.piece_e = d + 2 * w_np; w.long_group = d + 3 * w_np; w.long_poff = d + 3 * w_np + w_nl;
+        w.punl = d + w_lists; w.lsel = w.punl + w_np;
+        w.phist = x->d_lghist; w.pshow = (unsigned long long*)x->d_lgshow.p;
+        hipLaunchKernelGGL(label_piece_hist_kernel, dim3((unsigned)np), dim3(256), 0, x->stream, x->d_grows, lab, P, w);
+        hipLaunchKernelGGL(label_long_select_kernel, dim3((unsigned)nl), dim3(256), 0, x->stream, P, m, w, tags, votes, show, unl);
+        hipLaunchKernelGGL(label_piece_show_kernel, dim3((unsigned)np), dim3(256), 0, x->stream, x->d_grows, lab, best, tie, w);
+        hipLaunchKernelGGL(label_long_show_kernel, dim3(cdiv(nl * LABEL_MAX_M, 256)), dim3(256), 0, x->stream, (int)nl, m, tie, w, show);
+    }
+    VQ_HIP(hipGetLastError());
+    return 0;
+}
+
+// d_prompts [P][dim]; lab_out / best_out [n] or null (the call's own scratch then); tags / votes / show [G][m] and unl [G] or
+// tags null: all device memory.  force_exact: the host form found a prompt outside the fp16 bound's range.  Asynchronous on
+// the index's stream; *lab / *best: where the rows' answers are.
+int label_run(vq_index* x, const float* d_prompts, int P, int mode, bool force_exact, float max_dist, int32_t* lab_out, float* best_out,
+              int m, int32_t* tags, int32_t* votes, int32_t* show, int32_t* unl, int32_t** lab_at, float** best_at) {
+    const int64_t n = x->size;
+    const LabelPlan p = plan_label(n, x->dim, P, mode, x->near_unit, 0);
+    const int64_t n_pad = p.row_tiles * LABEL_ROW_TILE;
+    VQ_TRY(x->d_lw.reserve(4 + 3 * n_pad));
+    int32_t* ctl = x->d_lw; int32_t* filed = ctl + 4;
+    int32_t* lab = lab_out ? lab_out : filed + n_pad;
+    float* best = best_out ? best_out : (float*)(filed + 2 * n_pad);
+    if (lab_at) *lab_at = lab;
+    if (best_at) *best_at = best;
+    if (!p.fp16 || force_exact) {
+        const int64_t ld = round_up(n, 64);
+        VQ_TRY(x->d_lrun.reserve(n));
+        VQ_TRY(x->d_dist.reserve((int64_t)p.exact_chunk * ld));
+        for (int j0 = 0; j0 < P; j0 += p.exact_chunk) {
+            const int cur = std::min(p.exact_chunk, P - j0);
+            VQ_TRY(exact_dist(x, false, d_prompts + (int64_t)j0 * x->dim, cur, ld));       // always the tiled kernel
+            Prof pr(x, I_SELECT);
+            hipLaunchKernelGGL(label_colmin_kernel, dim3(grid_for(n)), dim3(256), 0, x->stream, x->d_dist, ld, n, cur, j0, j0 == 0 ? 1 : 0,
+                               j0 + cur == P ? 1 : 0, max_dist, x->d_lrun, lab, best);
+        }
+        VQ_HIP(hipGetLastError());
+        set_stats(x, STATS_HOST, 0, 0, n);
+    } else {
+        const int64_t p_pad = (int64_t)p.prompt_tiles * LABEL_PT;
+        VQ_TRY(x->d_q16.reserve(p_pad * x->dim));
+        VQ_TRY(x->d_lparts.reserve(p.part_bytes / 4));
+        VQ_TRY(ensure_gcounters(x));
+        VQ_TRY(set_dyn_lds(x, (const void*)label_tile_kernel, LABEL_LDS_BYTES));
+        VQ_HIP(hipMemsetAsync(ctl, 0, 16, x->stream));
+        VQ_HIP(hipMemsetAsync(x->d_gcounters, 0, 3 * sizeof(unsigned long long), x->stream));
+        hipLaunchKernelGGL(label_prompt_norm_kernel, dim3(P), dim3(64), 0, x->stream, d_prompts, x->dim, ctl);
+        queries_to_f16(x, d_prompts, P, p_pad);
+        {
+            Prof pr(x, I_MFMA_SCAN);
+            hipLaunchKernelGGL(label_tile_kernel, dim3((unsigned)(p.row_tiles * p.prompt_ranges)), dim3(G2_THREADS), LABEL_LDS_BYTES, x->stream,
+                               x->rows16, x->d_q16, x->dim, P, p.prompt_tiles, p.prompt_ranges, n_pad, x->d_lparts);
+        }
+        {
+            Prof pr(x, I_RESCORE);
+            hipLaunchKernelGGL(label_finalize_kernel, dim3(grid_for(n)), dim3(256), 0, x->stream, x->d_lparts, p.prompt_ranges, n_pad, n, x->rows,
+                               x->dim, d_prompts, scan_eps_unit(x->dim) * x->row_norm_max, max_dist, ctl, filed, lab, best, x->d_gcounters);
+        }
+        {
+            Prof pr(x, I_EXACT_DIST);
+            hipLaunchKernelGGL(label_redo_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n, 4), 4096)), dim3(256), 0, x->stream, x->rows, n, x->dim,
+                               d_prompts, P, max_dist, ctl, filed, lab, best, x->d_gcounters);
+        }
+        VQ_HIP(hipGetLastError());
+        VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+        set_stats(x, STATS_GCOUNTERS);
+    }
+    if (tags) VQ_TRY(label_groups_run(x, lab, best, P, m, tags, votes, show, unl));
+    return 0;
+}
+
 // ---- what the search entry points share ----
 // One argument check per shape of call.  arrays: every array the call reads or writes is there.
 int check_batch_args(const char* fn, const vq_index* x, int nq, int k, bool arrays) {
@@ -2255,6 +2407,78 @@ int vq_debug_summary_plan(int64_t n, int64_t largest_group, int dim, int k, int*
              "vq_debug_summary_plan: takes 1 <= largest_group <= n < 2^31, a dim vq_index_create takes, 1 <= k <= %d", SUM_MAX_K);
     const SummaryPlan p = sum_plan_env(largest_group, dim, k);
     *lds_rows = p.lds_rows; *lds_bytes = p.lds_bytes; *groups_wide_form = p.wide_form; *launches = p.launches;
+    return 0;
+}
+
+int vq_index_label_rows_device(vq_index* x, const void* d_prompts, int P, int mode, float max_dist, void* d_row_label, void* d_row_dist,
+                               int m, void* d_group_tags, void* d_group_votes, void* d_group_show_rows, void* d_group_unlabelled) {
+    static const char* fn = "vq_index_label_rows_device";
+    const bool groups = d_group_tags != nullptr;
+    VQ_TRY(check_label_args(fn, x, d_prompts, P, max_dist, m, groups, d_group_votes && d_group_show_rows && d_group_unlabelled));
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) {
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    VQ_TRY(label_precheck(x, fn, mode, groups));
+    return label_run(x, (const float*)d_prompts, P, mode, false, max_dist, (int32_t*)d_row_label, (float*)d_row_dist, m, (int32_t*)d_group_tags,
+                     (int32_t*)d_group_votes, (int32_t*)d_group_show_rows, (int32_t*)d_group_unlabelled, nullptr, nullptr);
+}
+
+int vq_index_label_rows(vq_index* x, const float* prompts, int P, int mode, float max_dist, int32_t* row_label, float* row_dist, int m,
+                        int32_t* group_tags, int32_t* group_votes, int32_t* group_show_rows, int32_t* group_unlabelled) {
+    static const char* fn = "vq_index_label_rows";
+    const bool groups = group_tags != nullptr;
+    VQ_TRY(check_label_args(fn, x, prompts, P, max_dist, m, groups, group_votes && group_show_rows && group_unlabelled));
+    std::lock_guard<std::mutex> lk(x->mu);
+    bool in_range = true;                                   // every |p|^2 inside what the fp16 bound covers
+    for (int j = 0; j < P; ++j) {
+        double s2 = 0.0;
+        for (int i = 0; i < x->dim; ++i) {
+            const float v = prompts[(size_t)j * x->dim + i];
+            VQ_CHECK(v - v == 0.f, "%s: prompt %d holds a value that is not finite", fn, j);
+            s2 += (double)v * v;
+        }
+        if (!(s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX)) in_range = false;
+    }
+    if (x->size == 0) {
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    VQ_TRY(label_precheck(x, fn, mode, groups));
+    const int64_t n = x->size, gm = groups ? (int64_t)x->n_groups * m : 0;
+    int32_t* d_t = nullptr;
+    if (groups) {
+        VQ_TRY(x->d_lout.reserve(3 * gm + x->n_groups));
+        d_t = x->d_lout;
+    }
+    int32_t* d_lab; float* d_best;
+    VQ_TRY(stage_queries(x, prompts, P));
+    VQ_TRY(label_run(x, x->d_q, P, mode, !in_range, max_dist, nullptr, nullptr, m, d_t, d_t + gm, d_t + 2 * gm, d_t + 3 * gm, &d_lab, &d_best));
+    if (row_label) VQ_HIP(hipMemcpyAsync(row_label, d_lab, (size_t)n * 4, hipMemcpyDeviceToHost, x->stream));
+    if (row_dist) VQ_HIP(hipMemcpyAsync(row_dist, d_best, (size_t)n * 4, hipMemcpyDeviceToHost, x->stream));
+    if (groups) {
+        VQ_HIP(hipMemcpyAsync(group_tags, d_t, (size_t)gm * 4, hipMemcpyDeviceToHost, x->stream));
+        VQ_HIP(hipMemcpyAsync(group_votes, d_t + gm, (size_t)gm * 4, hipMemcpyDeviceToHost, x->stream));
+        VQ_HIP(hipMemcpyAsync(group_show_rows, d_t + 2 * gm, (size_t)gm * 4, hipMemcpyDeviceToHost, x->stream));
+        VQ_HIP(hipMemcpyAsync(group_unlabelled, d_t + 3 * gm, (size_t)x->n_groups * 4, hipMemcpyDeviceToHost, x->stream));
+    }
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// plan_label's answer for near-unit rows; needs no device
+int vq_debug_label_plan(int64_t n, int dim, int P, int mode, int64_t largest_group, int* fp16_path, int* exact_chunk, int* exact_chunks,
+                        int64_t* exact_bytes, int* prompt_tiles, int* prompt_ranges, int64_t* row_tiles, int64_t* part_bytes, float* eps,
+                        int* group_split_rows, int* group_piece_rows, int64_t* largest_group_pieces) {
+    VQ_CHECK(fp16_path && exact_chunk && exact_chunks && exact_bytes && prompt_tiles && prompt_ranges && row_tiles && part_bytes && eps &&
+             group_split_rows && group_piece_rows && largest_group_pieces && largest_group >= 0 && largest_group <= n && n >= 1 && n < ((int64_t)1 << 31) && dim > 0 && dim % 4 == 0 && dim <= 4096 && P >= 1 && P <= LABEL_MAX_P && mode >= 0 && mode <= 2,
+             "vq_debug_label_plan: takes 0 <= largest_group <= n, 1 <= n < 2^31, a dim vq_index_create takes, 1 <= P <= %d, mode 0, 1 or 2", LABEL_MAX_P);
+    VQ_CHECK(mode != 2 || label_fp16_dim(dim), "vq_debug_label_plan: the fp16 path needs dim 256, 512 or 768");
+    const LabelPlan p = plan_label(n, dim, P, mode, true, largest_group);
+    *fp16_path = p.fp16; *exact_chunk = p.exact_chunk; *exact_chunks = p.exact_chunks; *exact_bytes = p.exact_bytes;
+    *prompt_tiles = p.prompt_tiles; *prompt_ranges = p.prompt_ranges; *row_tiles = p.row_tiles; *part_bytes = p.part_bytes; *eps = p.eps;
+    *group_split_rows = p.group_split_rows; *group_piece_rows = p.group_piece_rows; *largest_group_pieces = p.largest_group_pieces;
     return 0;
 }
 

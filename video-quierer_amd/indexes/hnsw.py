@@ -617,7 +617,8 @@ class HNSWIndex:
         return list(keys), exclude is not None
 
     def _prepare(self, queries, k: int, *, given: bool = False, group_of: GROUP_OF = None, positions: bool = False,
-                 position_of: POSITION_OF = None, flt: Optional[Tuple[List[Hashable], bool]] = None, what: str = "query"):
+                 position_of: POSITION_OF = None, flt: Optional[Tuple[List[Hashable], bool]] = None, what: str = "query",
+                 groups: bool = True):
         """The common start of the grouped, filtered, distinct, clip and sequence searches, under the lock, in the order the
         callers rely on: the queries normalised as ``search`` does (``given``: fp32 [nq][dim], used as they are), their
         dimension checked; then the answers that need no device (k <= 0, an empty index, an empty ``within``: None is
@@ -625,6 +626,7 @@ class HNSWIndex:
         labels under ``group_of``, the positions under ``position_of`` if asked for, in that order, each uploaded only when
         stale.  ``flt`` (``_filter_arg``) becomes the ascending labels of the keys the index holds (unknown keys hold no
         rows); a ``within`` that names none of them is None again, after the uploads.  Without ``flt`` nothing is excluded.
+        ``groups=False`` (a call that reads neither labels nor ranks: ``label_rows``) maps and uploads neither; its group labels are None.
         Returns (unit queries, group labels, positions or None, filter labels, exclude flag)."""
         unit = queries if given else np.ascontiguousarray(self._unit_rows(queries), dtype=np.float32)
         if unit.shape[1] != self.dimension:
@@ -632,11 +634,13 @@ class HNSWIndex:
         keys, excl = flt if flt is not None else ((), True)
         if k <= 0 or not self._ids or (not excl and not keys):
             return None
-        if not self._identity:
-            self._sync_tie_order()
-        gl = self._sync_groups(group_of)
+        gl = None
+        if groups:
+            if not self._identity:
+                self._sync_tie_order()
+            gl = self._sync_groups(group_of)
         ps = self._sync_positions(position_of) if positions else None
-        index = gl.index
+        index = gl.index if gl is not None else {}
         labels = np.array(sorted({index[key] for key in keys if key in index}), dtype=np.int32)
         if not excl and len(labels) == 0:
             return None
@@ -883,6 +887,75 @@ class HNSWIndex:
         """``summarize_groups`` for one group: ``[{'id', 'rank', 'radius', 'members'}]`` in selection order.  ``KeyError`` for a
         group the index does not hold, ``[]`` for k <= 0."""
         return self.summarize_groups([group], k, max_radius=max_radius, group_of=group_of)[group]
+
+    # -- zero-shot labelling: which prompt each row shows, what each group (video) is about --------------
+    LABEL_MAX_PROMPTS = 4096      # vq_index_label_rows: prompts per call
+    LABEL_MAX_TAGS = 16           # ... tags per group
+
+    def _label(self, prompts, mode: int, max_distance: Optional[float], top: int, group_of: GROUP_OF, given: bool = False):
+        """One device call, under the lock.  prompts: 1 .. LABEL_MAX_PROMPTS vectors (``given``: see ``_prepare``); top > 0 asks
+        for the group outputs.  None for an empty index, else (labels [n], distances [n], group labels (None without ``top``), tags, votes, show rows
+        [G][min(top, LABEL_MAX_TAGS)], unlabelled [G]); the last four None without ``top``."""
+        if len(prompts) == 0:
+            raise ValueError("labelling needs at least one prompt")
+        if len(prompts) > self.LABEL_MAX_PROMPTS:
+            raise ValueError(f"a vocabulary holds at most {self.LABEL_MAX_PROMPTS} prompts, got {len(prompts)}")
+        rho = math.inf if max_distance is None else float(max_distance)
+        if math.isnan(rho):
+            raise ValueError("max_distance must not be NaN (None: every row is labelled)")
+        m = min(int(top), self.LABEL_MAX_TAGS)
+        ready = self._prepare(prompts, 1, given=given, group_of=group_of, what="prompt", groups=m > 0)    # row labels alone need no labels or ranks
+        if ready is None:
+            return None
+        unit, gl = ready[0], ready[1]
+        n, G = len(self._ids), len(gl.keys) if m > 0 else 0
+        labels = np.empty(n, dtype=np.int32)
+        dist = np.empty(n, dtype=np.float32)
+        tags = votes = show = unl = None
+        if m > 0:
+            tags, votes, show = (np.empty((G, m), dtype=np.int32) for _ in range(3))
+            unl = np.empty(G, dtype=np.int32)
+        _lib.check(_lib.load().vq_index_label_rows(self._h, _lib.fptr(unit), unit.shape[0], int(mode), rho, _lib.i32ptr(labels),
+                                                   _lib.fptr(dist), max(m, 0), *(_lib.i32ptr(a) if m > 0 else None for a in (tags, votes, show, unl))))
+        return labels, dist, gl, tags, votes, show, unl
+
+    def label_rows(self, prompts: Sequence[np.ndarray], *, max_distance: Optional[float] = None, mode: int = MODE_AUTO):
+        """Zero-shot labels: for every stored row the prompt it is closest to.  Returns ``(labels int32 [n], distances float32
+        [n])`` in row order (the order of ``add``): ``labels[r]`` is the index into ``prompts`` with the smallest
+        ``search`` distance to row r (prompts normalised as ``search`` normalises queries; two prompts at the same distance:
+        the smaller index), ``distances[r]`` that distance.  ``max_distance``: a row farther than this from every prompt gets
+        label -1 ("none of the above"; its distance is still reported; a row exactly at ``max_distance`` keeps its label).
+        Exact in every mode; ``mode`` as ``search_mode`` (0 auto, 1 exact path, 2 fp16 path).  At most 4,096 prompts."""
+        with self.lock:
+            res = self._label(prompts, mode, max_distance, 0, None)
+        if res is None:
+            return np.empty(0, dtype=np.int32), np.empty(0, dtype=np.float32)
+        return res[0], res[1]
+
+    def _label_groups(self, prompts, top: int, group_of: GROUP_OF, max_distance: Optional[float], given: bool = False) -> Dict[Hashable, List[Dict]]:
+        """``label_groups`` under the lock (``given``: see ``_prepare``)."""
+        if int(top) <= 0:
+            raise ValueError(f"top must be >= 1, got {top}")
+        res = self._label(prompts, self.search_mode, max_distance, top, group_of, given=given)
+        if res is None:
+            return {}
+        _, dist, gl, tags, votes, show, _ = res
+        rows_of = np.bincount(gl.labels, minlength=len(gl.keys))
+        to_id = self._id_of()
+        return {key: [{"label": j, "votes": v, "share": v / int(rows_of[g]), "id": to_id(r), "distance": dist[r]}
+                      for j, v, r in zip(tags[g].tolist(), votes[g].tolist(), show[g].tolist()) if j >= 0]
+                for g, key in enumerate(gl.keys)}
+
+    def label_groups(self, prompts: Sequence[np.ndarray], top: int = 3, *, group_of: GROUP_OF = None,
+                     max_distance: Optional[float] = None) -> Dict[Hashable, List[Dict]]:
+        """What every group (video) is about, from one device call: ``{group: [{'label', 'votes', 'share', 'id', 'distance'}]}``.
+        Every row votes for its ``label_rows`` label; a group's list holds its ``top`` most voted labels (at most 16; more
+        votes first, the smaller index on equal votes; labels nobody voted for never appear).  ``votes`` is the number of the
+        group's rows with that label, ``share`` votes over ALL the group's rows (rows that ``max_distance`` leaves unlabelled
+        vote for nothing but still count here), ``id`` and ``distance`` those of the group's row that shows the label best (the
+        smallest distance, ties by id as ``search``).  ``group_of`` as ``search_grouped``."""
+        with self.lock:
+            return self._label_groups(prompts, top, group_of, max_distance)
 
     # -- sequence query: the k groups (videos) that show a list of steps in order -------------------
     SEQ_MAX_STEPS = 64            # vq_index_search_sequence: steps per call

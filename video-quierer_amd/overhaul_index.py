@@ -207,6 +207,35 @@ class SimpleVideoIndex:
             results.sort(key=lambda md: md["timestamp"])
         return results
 
+    def tag_videos(self, tag_embeddings, tags=None, top: int = 3, max_distance: Optional[float] = None) -> Dict[str, List[Dict]]:
+        """Auto-tags for every video from a vocabulary of prompts (text prompts through ``extract_text_features``):
+        ``{video_name: [{'tag', 'frames', 'share', 'timestamp', 'frame_id', 'score'}]}``, the ``top`` most voted tags of each
+        video, most voted first.  Every frame votes for the prompt it is closest to (``HNSWIndex.label_groups``: exact; each
+        prompt normalised as ``search`` normalises its query); ``frames`` is the number of the video's frames that voted for
+        the tag, ``share`` that number over all the video's frames, ``timestamp`` / ``frame_id`` / ``score`` those of the
+        frame that shows the tag best (ties between frames as ``search``).  ``tags`` names the embeddings (default: their
+        indices).  ``max_distance``: frames farther than this cosine distance from every prompt vote for nothing."""
+        embs = list(tag_embeddings)
+        if not embs:
+            raise ValueError("tag_videos needs at least one tag embedding")
+        names = list(range(len(embs))) if tags is None else list(tags)
+        if len(names) != len(embs):
+            raise ValueError(f"{len(names)} tag names for {len(embs)} embeddings")
+        if not self.embeddings:
+            return {}
+        dev = self._device(ranks=True)
+        unit = np.ascontiguousarray(np.stack([_unit_query(q) for q in embs]))
+        with dev.lock:                                # the prompts as normalised above, not normalised again
+            res = dev._label_groups(unit, top, self._group_fn, max_distance, given=True)
+        out = {}
+        for video, found in res.items():
+            out[video] = []
+            for r in found:
+                md = self.metadata[-r["id"]]
+                out[video].append({"tag": names[r["label"]], "frames": r["votes"], "share": r["share"], "timestamp": md["timestamp"],
+                                   "frame_id": md["frame_id"], "score": float(np.float32(1.0) - r["distance"])})
+        return out
+
     def save_to_disk(self, cache_path: Path):
         try:
             with open(cache_path, "wb") as f:
