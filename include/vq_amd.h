@@ -696,6 +696,28 @@ int vq_index_debug_rescore(vq_index* idx, const float* queries /*[nq][dim], host
                            const uint32_t* keys /*[nq][streams][2], host*/, int64_t capacity,
                            int32_t* ids /*[nq][k]*/, float* dist /*[nq][k]*/, int32_t* flags /*[nq]*/);
 
+/* Stage entry of the exact redo (tests/test_exact_stages.py): pass 3 of an fp16 search on flags the CALLER wrote.
+ *   vq_debug_fallback_plan: the redo's geometry for n rows, nq queries and k results, out = {fast_splits, fast_rows, splits,
+ *   rows, round_q, partial}: the row splits and rows per split of the first round (the first 64 flagged queries) and of a bulk
+ *   round, the flagged queries a bulk round takes, and the 8-byte keys of scratch that holds both rounds' per-split lists.
+ *   1 <= n < 2^31, nq >= 1, 1 <= k <= 100.  Pure host arithmetic: needs neither vq_init nor a device.
+ *   vq_index_debug_fallback: under the preconditions of vq_index_debug_rescore (dim % 64 == 0, k <= 100, a non-empty index of
+ *   near-unit rows, id ranks that cover the index or none) it uploads `ids` and `dist` [nq][k] as the answer passes 1 and 2
+ *   would have left, then `flags` [nq] (0 and 1: proven; every other value counts as 2: redo) and the queries, and makes the
+ *   two launches that end the search: the flag collection and the exact redo, through the search's own function.  Nothing
+ *   else is launched: no conversion, no scan, no re-score.  groups == NULL (n_sel = 0): the unmasked redo of
+ *   vq_index_search.  Otherwise groups / n_sel / exclude are a filter as in vq_index_search_filtered (labels set and
+ *   covering the index) and the redo is the masked one of the masked fp16 path, under the same bitmap; unlike that search
+ *   it takes any dim % 64 == 0 and any nq, since no masked scan runs.  An empty exclude list is the unmasked redo, as in the
+ *   search; a filter that allows no row is VQ_ERR_INVALID.  It waits and returns ids and dist: a flagged query's slots hold
+ *   its exact k best allowed rows by (distance, id), -1 / +inf behind the last one; every other slot holds the caller's bits
+ *   untouched.  counters = {flagged, flags == 0, flags == 1, flags counted as 2}.  The search statistics and what
+ *   vq_index_debug_read_scan_keys returns are not touched. */
+int vq_debug_fallback_plan(int64_t n, int nq, int k, int64_t* out /*[6]*/);
+int vq_index_debug_fallback(vq_index* idx, const float* queries /*[nq][dim], host*/, int nq, int k, const int32_t* flags /*[nq], host*/,
+                            const int32_t* groups, int32_t n_sel, int exclude, int32_t* ids /*[nq][k], in and out*/,
+                            float* dist /*[nq][k], in and out*/, int32_t* counters /*[4]*/);
+
 /* ------------------------------------------------------------------ frame preprocessing
  * The resize in front of the encoder, bit-identical to Pillow's 8-bit separable resample
  * (Pillow src/libImaging/Resample.c), which is what the reference runs in two places:

@@ -183,6 +183,9 @@ SIGNATURES = {
     "vq_debug_scan_row_of": (c_int64, [c_int, c_int64, c_int]),
     "vq_index_debug_rescore": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, POINTER(ctypes.c_uint32), c_int64, POINTER(c_int32),
                                        POINTER(c_float), POINTER(c_int32)]),
+    "vq_debug_fallback_plan": (c_int, [c_int64, c_int, c_int, POINTER(c_int64)]),
+    "vq_index_debug_fallback": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_int32, c_int,
+                                        POINTER(c_int32), POINTER(c_float), POINTER(c_int32)]),
     "vq_encoder_stage_frames": (c_int, [c_void_p, c_int, POINTER(c_void_p), c_int, c_int]),
     "vq_encoder_submit_staged": (c_int, [c_void_p, c_int, c_int, c_int]),
     "vq_encoder_wait_staged": (c_int, [c_void_p, c_int, POINTER(c_float)]),

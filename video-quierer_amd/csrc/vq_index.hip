@@ -418,8 +418,10 @@ FallbackPlan fallback_plan(int64_t n, int nq, int k) {
     FallbackPlan f;
     f.fast_splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_FAST_ROWS)));
     f.fast_rows = round_up(cdiv(n, f.fast_splits), FB_TILE);
+    f.fast_splits = std::max(1, cdiv(n, f.fast_rows));          // whole tiles per split can leave the last splits without a row: not launched
     f.splits = (int)std::max<int64_t>(1, std::min<int64_t>(FB_MAX_SPLITS, cdiv(n, FB_SPLIT_ROWS)));
     f.rows = round_up(cdiv(n, f.splits), FB_TILE);
+    f.splits = std::max(1, cdiv(n, f.rows));
     f.round_q = std::max<int64_t>(FB_QG, std::min<int64_t>(round_up(nq, FB_QG), ((int64_t)64 << 20) / ((int64_t)f.splits * k * 8) / FB_QG * FB_QG));
     f.partial = std::max<int64_t>(f.round_q * f.splits, (int64_t)FB_FAST_SLOTS * f.fast_splits) * k;
     return f;
@@ -1761,6 +1763,56 @@ int vq_index_debug_rescore(vq_index* x, const float* queries, int nq, int k, con
     VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
     VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
     VQ_HIP(hipMemcpyAsync(flags, x->d_flags, (size_t)nq * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// fallback_plan's answer; needs no device
+int vq_debug_fallback_plan(int64_t n, int nq, int k, int64_t* out) {
+    VQ_CHECK(out && n >= 1 && n < ((int64_t)1 << 31) && nq >= 1 && k >= 1 && k <= FB_KMAX,
+             "vq_debug_fallback_plan: the exact redo takes 1 <= n < 2^31, nq >= 1, 1 <= k <= %d", FB_KMAX);
+    const FallbackPlan f = fallback_plan(n, nq, k);
+    out[0] = f.fast_splits; out[1] = f.fast_rows; out[2] = f.splits; out[3] = f.rows; out[4] = f.round_q; out[5] = f.partial;
+    return 0;
+}
+
+// Pass 3 alone, on flags the caller wrote: collect_flags_kernel and the launch_fallback call of search_fp16, nothing in front of
+// them (no scan, no re-score: the caller's ids / dist stand in for the fast path's answer).  With a filter, the masked kernel
+// under the bitmap filter_prepare builds for the masked fp16 path.
+int vq_index_debug_fallback(vq_index* x, const float* queries, int nq, int k, const int32_t* flags, const int32_t* groups, int32_t n_sel,
+                            int exclude, int32_t* ids, float* dist, int32_t* counters) {
+    static const char* fn = "vq_index_debug_fallback";
+    VQ_TRY(check_batch_args(fn, x, nq, k, queries && flags && ids && dist && counters));
+    VQ_CHECK(nq >= 1, "%s: no query", fn);
+    VQ_CHECK(!groups ? n_sel == 0 : n_sel >= 0 && (exclude == 0 || exclude == 1), "%s: bad filter (%d labels, exclude %d)", fn, (int)n_sel, exclude);
+    std::lock_guard<std::mutex> lk(x->mu);
+    VQ_TRY(check_ranks(x, fn));
+    VQ_TRY(refresh_norm_range(x));
+    VQ_CHECK(x->dim % GEMM_BK == 0 && k <= RV_K_MAX && x->size >= 1 && x->near_unit, "%s: the fp16 search needs dim %% 64 == 0, k <= %d, "
+             "a non-empty index and near-unit rows (0.5 <= |row|^2 <= 2)", fn, RV_K_MAX);
+    const int64_t count = (int64_t)nq * k;
+    VQ_TRY(x->d_flags.reserve(nq));
+    VQ_TRY(reserve_fallback(x, nq, k));
+    VQ_TRY(reserve_id_dist(x, count));
+    GroupMask gm{};
+    bool masked = false;
+    if (groups) {
+        FilterPlan p;
+        VQ_TRY(filter_prepare(x, fn, filter_labels(x, groups, n_sel), exclude, true, &p));
+        VQ_CHECK(p.all || p.m > 0, "%s: the filter allows no row", fn);
+        masked = !p.all;                                                  // an empty exclude list: the unmasked kernel, as the search takes it
+        gm = GroupMask{x->d_group, x->d_sgroup, p.bits};
+    }
+    VQ_HIP(hipMemcpyAsync(x->d_ids, ids, (size_t)count * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_HIP(hipMemcpyAsync(x->d_out, dist, (size_t)count * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_HIP(hipMemcpyAsync(x->d_flags, flags, (size_t)nq * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_TRY(stage_queries(x, queries, nq));
+    hipLaunchKernelGGL(collect_flags_kernel, dim3(1), dim3(1024), 0, x->stream, x->d_flags, nq, x->d_slots, x->d_counters);
+    launch_fallback(x, x->d_q, nq, k, x->d_ids, x->d_out, x->d_counters, masked ? &gm : nullptr);
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(counters, x->d_counters, FB_NCOUNTERS * 4, hipMemcpyDeviceToHost, x->stream));
     VQ_HIP(hipStreamSynchronize(x->stream));
     return 0;
 }
