@@ -401,6 +401,43 @@ int vq_index_search_distinct_device(vq_index* idx, const void* d_queries_f32, in
 int vq_debug_distinct_plan(int64_t n, int nq, int k, int64_t min_gap, int mode,
                            int64_t* depth, int* producer, int* redo_slices);
 
+/* Diverse search: the k best rows such that no two results look alike — suppression in embedding space.  A static shot, an
+ * intro that sits in every episode and bit-exact re-uploads otherwise take all k slots of vq_index_search; the grouped and
+ * distinct searches suppress by position only.  No labels or positions are needed; id ranks only order L.
+ *   Definition (the order of operations is part of it).  L = the exhaustive list of all rows in vq_index_search's order ((dist,
+ *   row), or (dist, id rank) once ranks are set).  d(a, b) = 1.0f - fp32(sum_i (double)x_a[i] * (double)x_b[i]), summed in index
+ *   order: the keyframe summary's row-to-row distance, i.e. vq_index_search's distance with row b as the query; it is symmetric
+ *   bit for bit.  Walk L and keep a row r unless min_dist > 0 and an already kept row s has d(r, s) < min_dist (an fp32
+ *   compare, strict).  ids / dist [nq][k] are the first k kept rows (row numbers) and their distances to the query in L's
+ *   order; unused slots are -1 / +inf.
+ *   Consequences: min_dist = 0 is exactly vq_index_search, even with bit-exact copies in the index, whose d may be -1.2e-7 (why
+ *   the rule carries min_dist > 0); a min_dist above every pair distance (3.0f) returns one row; the answer for k is a prefix
+ *   of the answer for k' > k.  Rows that are not finite are outside the definition: such a call may return anything, but ends.
+ *   Limits: 1 <= k <= 256, min_dist >= 0 and not NaN, nq >= 1; a violation is VQ_ERR_INVALID, judged before the device is asked
+ *   for, and the message names the argument.  Stale id ranks are refused before any work is queued.  An empty index returns
+ *   every slot empty.
+ *   How it runs: the plain search fetches a prefix of L of depth D per query; a pair pass decides d(r_i, r_j) < min_dist for
+ *   the pairs i < j of each prefix (the same fp64 chain) into a bit matrix [nq][D][ceil(D / 64)] of 64-bit words; one wave per
+ *   query walks the prefix with the suppressed set across its lanes.  A row's fate depends only on rows before it in L, so k
+ *   kept rows (or D = size) prove the answer.  Queries left short are redone exactly on the device in k rounds over their
+ *   distances to all rows (sliced to 512 MiB): pick the live row with the smallest (dist, tie), then give +inf to every live
+ *   row closer than min_dist to it (row by row while at most 4 queries of a slice are filed, by exact-distance tiles beyond).  The launches queued depend on the shapes and k only; nothing is read back in between.
+ *   Depth rule: D = max(256, 8 k), capped by the size and by the producer's k limit (fp16 scan: 100, exact selection: 1024);
+ *   D = k when min_dist = 0 or k = 1.  $VQ_AMD_DIVERSE_DEPTH (tests only, read per call) replaces the rule, under the same caps.
+ *   mode is vq_index_search's and chooses only the producer of the prefix (0: the fp16 scan from 16,384 rows); the answer is
+ *   bit-identical in every mode.  The _device form takes device pointers, is asynchronous on the index's stream and reads
+ *   nothing back.  vq_index_last_search_stats afterwards: [0] queries proven on the prefix, [1] prefix entries walked (summed
+ *   over queries), [2] queries answered by the redo.
+ *   vq_debug_diverse_plan (host only, as vq_debug_distinct_plan): the depth D a call of this shape fetches, the producer (0
+ *   exact distances + selection, 1 fp16 scan), the bytes of the bit matrix (nq * D * ceil(D / 64) * 8; 0 when no pair pass
+ *   runs: min_dist = 0 or D = 1), the redo slices it queues and the kernels queued behind the plain search's own. */
+int vq_index_search_diverse(vq_index* idx, const float* queries, int nq, int k, int mode, float min_dist,
+                            int32_t* ids, float* dist);
+int vq_index_search_diverse_device(vq_index* idx, const void* d_queries_f32, int nq, int k, int mode, float min_dist,
+                                   void* d_ids_i32, void* d_dist_f32);
+int vq_debug_diverse_plan(int64_t n, int nq, int k, float min_dist, int mode,
+                          int64_t* depth, int* producer, int64_t* pair_bytes, int* redo_slices, int* launches);
+
 /* Sequence search: the k groups (videos) that show a list of steps IN ORDER — a storyboard of text prompts ("opens the door,
  * then sits down, then picks up the phone"), or "where, in which video, does this clip occur".  The clip search scores every
  * step on its own, so a video that shows the steps reversed or minutes apart scores the same; this one joins the steps along

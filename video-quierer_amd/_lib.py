@@ -140,6 +140,10 @@ SIGNATURES = {
     "vq_index_search_distinct": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, c_int64, POINTER(c_int32), POINTER(c_float)]),
     "vq_index_search_distinct_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p]),
     "vq_debug_distinct_plan": (c_int, [c_int64, c_int, c_int, c_int64, c_int, POINTER(c_int64), POINTER(c_int), POINTER(c_int)]),
+    "vq_index_search_diverse": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int, c_float, POINTER(c_int32), POINTER(c_float)]),
+    "vq_index_search_diverse_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "vq_debug_diverse_plan": (c_int, [c_int64, c_int, c_int, c_float, c_int, POINTER(c_int64), POINTER(c_int), POINTER(c_int64), POINTER(c_int),
+                              POINTER(c_int)]),
     "vq_index_search_sequence": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_int64, c_int64, POINTER(c_int32), c_int32, c_int,
                                          POINTER(c_int32), POINTER(c_float), POINTER(c_int32)]),
     "vq_index_search_sequence_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, POINTER(c_int32), c_int32, c_int,

@@ -12,6 +12,7 @@
 #include "knn_filter.h"
 #include "knn_set.h"
 #include "knn_distinct.h"
+#include "knn_diverse.h"
 #include "knn_sequence.h"
 #include "knn_summary.h"
 #include "knn_label.h"
@@ -127,6 +128,11 @@ struct vq_index {
     IdxBuf<int32_t> d_dpre;
     IdxBuf<int32_t> d_dslots;
     IdxBuf<int32_t> d_dsel;
+    // diverse search (knn_diverse.h): the prefix's pair bit matrix [nq][D][ceil(D / 64)]; the redo's chunk minima [slots][chunks];
+    // its picked rows [slots].  The prefix, the slot list and the counters are the distinct search's (d_dpre, d_dslots, d_gcounters)
+    IdxBuf<uint64_t> d_vbits;
+    IdxBuf<uint64_t> d_vpart;
+    IdxBuf<int32_t> d_vpick;
     // sequence search (knn_sequence.h): every group's rows in (position, tie) order with their positions and ties beside them
     // (order | positions | ties, [3][seq_n]), built on the host by the first sequence search after the labels, the positions or
     // the id ranks changed (seq_n = the rows it covers, 0 = none; seq_largest = the longest group).  Scratch: cost keys (carry
@@ -792,6 +798,79 @@ int search_distinct_dispatch(vq_index* x, const float* d_queries, int nq, int k,
         }
         hipLaunchKernelGGL(distinct_scatter_kernel, dim3(cap), dim3(256), 0, x->stream, sel_ids, sel_dist, k, x->d_dslots, cnt, base, cap, d_ids,
                            d_dist_out);
+    }
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+    set_stats(x, STATS_GCOUNTERS);
+    return 0;
+}
+
+// ---- diverse search (knn_diverse.h) ----
+// tests only, read per call: a prefix depth that replaces the plan's rule
+int64_t diverse_depth_override() {
+    const char* e = getenv("VQ_AMD_DIVERSE_DEPTH");
+    return e ? std::max<long long>(0, atoll(e)) : 0;
+}
+
+// The plain search at the plan's depth -> the pair pass -> the walk; the queries it files are redone exactly, slice by slice:
+// distances once, then k rounds of pick (two levels) and suppress (the tile form and the row form are both queued; the filed
+// count decides on the device which one works).  Nothing here waits for the stream.
+int search_diverse_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode, float min_dist, int32_t* d_ids, float* d_dist_out) {
+    static const char* fn = "vq_index_search_diverse";
+    VQ_TRY(check_mode(fn, mode));
+    VQ_TRY(check_ranks(x, fn));
+    const int64_t n = x->size, ld = round_up(n, 64);
+    const DiversePlan p = plan_diverse(n, nq, k, min_dist, mode, diverse_depth_override());
+    const int D = (int)p.depth, W = cdiv(D, 64);
+    const int nchunks = cdiv(n, DIV_PICK_CHUNK);
+    VQ_TRY(x->d_dpre.reserve(2 * (int64_t)nq * D));
+    VQ_TRY(x->d_dslots.reserve(nq));
+    VQ_TRY(ensure_gcounters(x));
+    if (p.pair_bytes) VQ_TRY(x->d_vbits.reserve(p.pair_bytes / 8));
+    if (p.slices) {
+        VQ_TRY(x->d_dist.reserve(p.slice_q * ld));
+        VQ_TRY(x->d_vpart.reserve(p.slice_q * nchunks));
+        VQ_TRY(x->d_vpick.reserve(p.slice_q));
+    }
+    int32_t* pre_ids = x->d_dpre;
+    float* pre_dist = (float*)(pre_ids + (int64_t)nq * D);
+    VQ_HIP(hipMemsetAsync(x->d_gcounters, 0, 3 * sizeof(unsigned long long), x->stream));
+    VQ_TRY(search_dispatch(x, d_queries, nq, D, mode, pre_ids, pre_dist));
+    if (p.pair_bytes) {
+        Prof pr(x, I_EXACT_DIST);
+        const int qmax = 32768;                                   // queries per launch (the grid's y extent)
+        for (int q0 = 0; q0 < nq; q0 += qmax)
+            hipLaunchKernelGGL(diverse_pair_kernel, dim3(W * cdiv(D, 32), std::min(qmax, nq - q0)), dim3(256), 0, x->stream, x->rows, n, x->dim,
+                               pre_ids + (int64_t)q0 * D, D, W, min_dist, x->d_vbits + (int64_t)q0 * D * W);
+    }
+    {
+        Prof pr(x, I_SELECT);
+        hipLaunchKernelGGL(diverse_walk_kernel, dim3(nq), dim3(64), 0, x->stream, pre_ids, pre_dist, D, W, n, k,
+                           p.pair_bytes ? x->d_vbits.p : nullptr, d_ids, d_dist_out, x->d_dslots, x->d_gcounters);
+    }
+    const unsigned long long* cnt = x->d_gcounters;
+    for (int sl = 0; sl < p.slices; ++sl) {
+        const int base = (int)(sl * p.slice_q), cap = (int)std::min<int64_t>(p.slice_q, nq - base);
+        {
+            Prof pr(x, I_EXACT_DIST);
+            hipLaunchKernelGGL(distinct_dist_kernel, dim3(std::min(cdiv(n, 64), DST_DIST_GRID), cdiv(cap, 32)), dim3(256), 0, x->stream, x->rows, n, x->dim, d_queries,
+                               x->d_dslots, cnt, base, cap, x->d_dist, ld);
+        }
+        for (int t = 0; t < k; ++t) {
+            {
+                Prof pr(x, I_SELECT);
+                hipLaunchKernelGGL(diverse_pick_chunk_kernel, dim3(nchunks, cap), dim3(256), 0, x->stream, x->d_dist, ld, n, x->tie(), nchunks, x->d_vpart,
+                                   cnt, base, cap);
+                hipLaunchKernelGGL(diverse_pick_kernel, dim3(cap), dim3(256), 0, x->stream, x->d_vpart, nchunks, x->tie(), t, k, x->d_dslots, cnt, base, cap,
+                                   x->d_vpick, d_ids, d_dist_out);
+            }
+            if (t + 1 == k) break;
+            Prof pr(x, I_EXACT_DIST);
+            hipLaunchKernelGGL(diverse_suppress_kernel, dim3(std::min(cdiv(n, 64), DST_DIST_GRID), cdiv(cap, 32)), dim3(256), 0, x->stream, x->rows, n, x->dim,
+                               x->d_vpick, min_dist, cnt, base, cap, x->d_dist, ld);
+            hipLaunchKernelGGL(diverse_suppress_rows_kernel, dim3(std::min(cdiv(n, SUM_THREADS), DST_DIST_GRID), std::min(cap, DIV_ROW_SLOTS)), dim3(SUM_THREADS),
+                               (size_t)x->dim * 8, x->stream, x->rows, n, x->dim, x->d_vpick, min_dist, cnt, base, cap, x->d_dist, ld);
+        }
     }
     VQ_HIP(hipGetLastError());
     VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
@@ -1607,6 +1686,15 @@ int check_distinct_args(const char* fn, const vq_index* x, int nq, int k, int64_
     return check_batch_args(fn, x, nq, k, arrays);
 }
 
+// (the arguments are judged before the library is asked for its device)
+int check_diverse_args(const char* fn, const vq_index* x, int nq, int k, float min_dist, bool arrays) {
+    VQ_CHECK(k >= 1 && k <= DIV_MAX_K, "%s: k %d outside [1, %d]", fn, k, DIV_MAX_K);
+    VQ_CHECK(min_dist == min_dist, "%s: min_dist is NaN", fn);
+    VQ_CHECK(min_dist >= 0.0f, "%s: min_dist %g is negative", fn, (double)min_dist);
+    VQ_CHECK(nq >= 1, "%s: nq %d is below 1", fn, nq);
+    return check_batch_args(fn, x, nq, k, arrays);
+}
+
 int check_sequence_args(const char* fn, const vq_index* x, int m, int k, int64_t min_gap, int64_t max_gap, const int32_t* groups,
                         int32_t n_sel, int exclude, bool arrays) {
     VQ_CHECK(m >= 1 && m <= SEQ_MAX_M && k > 0 && k <= 1024, "%s: bad argument (1 <= m <= %d, 1 <= k <= 1024)", fn, SEQ_MAX_M);
@@ -2249,6 +2337,42 @@ int vq_debug_distinct_plan(int64_t n, int nq, int k, int64_t min_gap, int mode, 
              mode >= 0 && mode <= 2, "vq_debug_distinct_plan: takes 1 <= n < 2^31, nq >= 1, 1 <= k <= 1024, min_gap >= 0, mode 0..2");
     const DistinctPlan p = plan_distinct(n, nq, k, min_gap, mode, distinct_depth_override());
     *depth = p.depth; *producer = p.producer; *redo_slices = p.slices;
+    return 0;
+}
+
+int vq_index_search_diverse_device(vq_index* x, const void* d_queries, int nq, int k, int mode, float min_dist, void* d_ids, void* d_dist) {
+    VQ_TRY(check_diverse_args("vq_index_search_diverse_device", x, nq, k, min_dist, d_queries && d_ids && d_dist));
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_ids, nullptr, (float*)d_dist);
+    return search_diverse_dispatch(x, (const float*)d_queries, nq, k, mode, min_dist, (int32_t*)d_ids, (float*)d_dist);
+}
+
+int vq_index_search_diverse(vq_index* x, const float* queries, int nq, int k, int mode, float min_dist, int32_t* ids, float* dist) {
+    static const char* fn = "vq_index_search_diverse";
+    VQ_TRY(check_diverse_args(fn, x, nq, k, min_dist, queries && ids && dist));
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    if (x->size == 0) { host_empty(count, ids, nullptr, dist); return 0; }
+    VQ_TRY(check_mode(fn, mode));                                 // refuse before staging anything
+    VQ_TRY(check_ranks(x, fn));
+    VQ_TRY(x->d_q.reserve((int64_t)nq * x->dim));
+    VQ_TRY(reserve_id_dist(x, count));
+    VQ_HIP(hipMemcpyAsync(x->d_q, queries, (size_t)nq * x->dim * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_TRY(search_diverse_dispatch(x, x->d_q, nq, k, mode, min_dist, x->d_ids, x->d_out));
+    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// plan_diverse's answer for this process's environment; needs no device
+int vq_debug_diverse_plan(int64_t n, int nq, int k, float min_dist, int mode, int64_t* depth, int* producer, int64_t* pair_bytes,
+                          int* redo_slices, int* launches) {
+    VQ_CHECK(depth && producer && pair_bytes && redo_slices && launches && n >= 1 && n < ((int64_t)1 << 31) && nq >= 1 && k >= 1 &&
+             k <= DIV_MAX_K && min_dist >= 0.0f && mode >= 0 && mode <= 2,
+             "vq_debug_diverse_plan: takes 1 <= n < 2^31, nq >= 1, 1 <= k <= %d, min_dist >= 0 (not NaN), mode 0..2", DIV_MAX_K);
+    const DiversePlan p = plan_diverse(n, nq, k, min_dist, mode, diverse_depth_override());
+    *depth = p.depth; *producer = p.producer; *pair_bytes = p.pair_bytes; *redo_slices = p.slices; *launches = p.launches;
     return 0;
 }
 

@@ -725,6 +725,45 @@ class HNSWIndex:
         return [[{"id": to_id(r), "group": keys[labels[r]], "position": int(pos[r]), **_scored(d)} for r, d in zip(rr, rd) if r >= 0]
                 for rr, rd in zip(rows.tolist(), dist)]
 
+    # -- diverse search: the k best rows, no two of them closer than min_distance to each other ------------
+    DIVERSE_MAX_K = 256
+
+    def search_diverse(self, query: np.ndarray, k: int = 5, min_distance: float = 0.05) -> List[Dict]:
+        """The k best frames that do not look alike: ``[{'id', 'distance', 'score'}]``, ``search``'s dicts.  Exactly the plain
+        search's exhaustive (distance, id) list, walked in order, with every row dropped whose cosine distance to an already
+        kept row is below ``min_distance`` (fp32, strict) — a static shot, an intro that sits in every episode or a bit-exact
+        re-upload then takes one slot, whichever video the copies sit in.  ``min_distance=0`` is ``search``; at most 256
+        results per query.  Needs neither groups nor positions."""
+        return self.search_diverse_batch([query], k, min_distance)[0]
+
+    def search_diverse_batch(self, queries: List[np.ndarray], k: int = 5, min_distance: float = 0.05) -> List[List[Dict]]:
+        """``search_diverse`` for a batch of queries, one device pass."""
+        min_dist = np.float32(min_distance)
+        if not min_dist >= 0:                                     # (NaN too)
+            raise ValueError(f"min_distance must be >= 0, got {min_distance}")
+        if len(queries) == 0:
+            return []
+        if self._empty():
+            return [[] for _ in queries]
+        with self.lock:
+            return self._diverse_many(queries, k, min_dist)
+
+    def _diverse_many(self, queries, k: int, min_dist: np.float32, given: bool = False) -> List[List[Dict]]:
+        """``given``: see ``_prepare`` (SimpleVideoIndex normalises by its own rule).  min_dist: checked."""
+        ready = self._prepare(queries, k, given=given, groups=False)
+        if ready is None:
+            return [[] for _ in queries]
+        if not self._identity:
+            self._sync_tie_order()
+        unit = ready[0]
+        nq, kk = unit.shape[0], min(int(k), len(self._ids))
+        rows = np.empty((nq, kk), dtype=np.int32)
+        dist = np.empty((nq, kk), dtype=np.float32)
+        _lib.check(_lib.load().vq_index_search_diverse(self._h, _lib.fptr(unit), nq, kk, int(self.search_mode), float(min_dist),
+                                                       _lib.i32ptr(rows), _lib.fptr(dist)))
+        to_id = self._id_of()
+        return [_hits(to_id, rr, rd) for rr, rd in zip(rows.tolist(), dist)]
+
     # -- filtered query: the plain search within, or excluding, a set of groups (videos) -------------
     def search_filtered(self, query: np.ndarray, k: int = 5, *, within: Optional[Iterable[Hashable]] = None,
                         exclude: Optional[Iterable[Hashable]] = None, group_of: GROUP_OF = None) -> List[Dict]:

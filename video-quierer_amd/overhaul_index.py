@@ -149,6 +149,25 @@ class SimpleVideoIndex:
             results.append(md)
         return results
 
+    def search_diverse(self, query_embedding: np.ndarray, k: int = 5, max_similarity: float = 0.95) -> List[Dict]:
+        """The k best frames no two of which look alike: ``search``'s exhaustive list (the same normalisation, dicts and tie
+        order), walked in order, with every frame dropped whose cosine similarity to an already kept frame is above
+        ``max_similarity`` (``HNSWIndex.search_diverse`` with ``min_dist = float32(1) - float32(max_similarity)``: exact)."""
+        if not max_similarity <= 1:                               # (NaN too)
+            raise ValueError(f"max_similarity must be <= 1, got {max_similarity}")
+        if not self.embeddings:
+            return []
+        dev = self._device(ranks=True)
+        unit = np.ascontiguousarray(_unit_query(query_embedding)[None, :])
+        with dev.lock:                                # the query as normalised above, not normalised again
+            res = dev._diverse_many(unit, k, np.float32(1) - np.float32(max_similarity), given=True)[0]
+        results = []
+        for r in res:
+            md = self.metadata[-r["id"]].copy()
+            md["score"] = float(r["score"])
+            results.append(md)
+        return results
+
     def search_storyboard(self, step_embeddings, k: int = 5, max_gap_s: float = 10.0, min_gap_s: float = 0.0) -> List[Dict]:
         """The k videos that show the steps IN ORDER (text prompts through ``extract_text_features``, or the frames of a clip):
         ``[{'video_name', 'score', 'timestamps', 'frame_ids'}]``, best first.  One frame of the video per step, each
