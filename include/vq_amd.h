@@ -611,6 +611,59 @@ int vq_debug_label_plan(int64_t n, int dim, int P, int mode, int64_t largest_gro
                         int64_t* exact_bytes, int* prompt_tiles, int* prompt_ranges, int64_t* row_tiles, int64_t* part_bytes, float* eps,
                         int* group_split_rows, int* group_piece_rows, int64_t* largest_group_pieces);
 
+/* Compound search: the k best rows that match ALL of several prompts — "a dog AND a beach, in the same frame, but NOT at night".
+ * Adding the prompt vectors ranks by the SUM of the similarities: a frame that shows one term very well and the other not at all
+ * beats a frame that shows both.  Here a frame's WORST required term decides its place.
+ *   Inputs.  Terms q_0 .. q_{m-1}, 1 <= m <= 16, fp32 [m][dim], used as given (the Python layer normalises them as `search`
+ *   normalises queries).  clause_of[j] (int32, host memory, read before the call returns) is a clause number in [0, C) or -1 for a
+ *   veto term; the clause numbers do not decrease over the non-veto terms and every value 0 .. C-1 occurs; C >= 1.  margin is
+ *   fp32; -inf and +inf are allowed.
+ *   Definition (the order of operations is part of it).  d(j, r) = the distance of term j to row r exactly as vq_index_search
+ *   reports it: fp32(1 - fp32(dot)), the dot by the index-order fp64 chain.  Clause value c_i(r) = min over the terms j of clause
+ *   i of d(j, r): any alternative satisfies the clause.  Row distance D(r) = max over the clauses i of c_i(r): every clause must
+ *   be satisfied and the worst one decides.  Both are fp32 comparisons of values the plain search defines: no new rounding.
+ *   Veto: row r is struck iff some veto term j has d(j, r) < fp32(D(r) + margin) — one fp32 addition and a strict compare.
+ *   margin = 0 strikes a frame that shows the unwanted prompt better than it shows the wanted combination (the nearest-prompt
+ *   rule of vq_index_label_rows: no calibrated threshold needed); margin = -inf strikes nothing; margin = +inf everything.
+ *   Answer: the first k rows that are not struck by (D, tie) ascending, tie as in vq_index_search (the row number, or the id rank
+ *   once vq_index_set_id_ranks is set): ids [k] row numbers, dist [k] their D; unused slots are -1 / +inf.  term_dist [k][m] (may
+ *   be NULL) holds d(j, ids[t]) for every result, +inf in unused slots: it tells which term held a frame back.  Everything is an
+ *   fp32 value the plain search defines, or an integer, so the answer is unique.
+ *   Consequences: m = 1 with one clause is vq_index_search(nq = 1) bit for bit in every mode; one clause of m terms (pure OR)
+ *   is the merge of the m plain exhaustive lists, one entry per row; repeating a term in a second clause changes nothing; a veto
+ *   term bit-equal to a term that forms a one-term clause of its own, at margin 0, keeps exactly the rows whose D that term
+ *   decides; margin = -inf with veto terms equals the call without them.
+ *   Refusals (VQ_ERR_INVALID, before any work is queued, the outputs untouched): m outside [1, 16]; k outside [1, 1024]; a
+ *   malformed clause_of (a value below -1 or >= m, a decreasing sequence, a gap in the numbering, veto terms only); NaN margin; an
+ *   unknown mode; stale id ranks, as vq_index_search refuses them; mode 2 where the fp16 path does not exist (dim not 256, 512 or
+ *   768, rows that are not near-unit, k > 100); host form only: a term value that is not finite (the device form documents finite
+ *   terms as a precondition: it then still ends, by the exact path).  An empty index returns 0 with every slot empty.
+ *   How it runs (csrc/knn_compound.h, DESIGN.md §4 "Compound search").  mode 1, exact: one tiled fp64-chain kernel writes the
+ *   [m][n] term distances (a table of its own, at most 64 MiB per million rows) and the combined row D, +inf where struck; the
+ *   plain search's exact selection runs on that row; a last kernel reads the winners' term distances from the table and empties
+ *   the slots of struck rows.  mode 2, fp16: ONE read of the fp16 matrix by the streaming scan with the terms as its 16 query
+ *   columns; the term axis is reduced per row in registers (max within a clause, min over the clauses, a conservative veto test)
+ *   before the per-stream top-2 fold, so the keys are those of one virtual query; one workgroup re-scores the best 32 .. 128 keys
+ *   exactly (m fp64 chains each, the veto decided exactly) and proves that no other row can reach the k-th survivor: every bound
+ *   + E + 2^-20 must lie below its score, E = scan_eps_unit(dim) x max |row| x max_j |q_j|.  A call that is not proven (a term
+ *   with |q|^2 outside [0.25, 4]; too many tied keys; more than four streams whose unseen rows could matter — up to four are
+ *   re-scored in full, the largest key first; a veto that leaves the pool short) is redone
+ *   by the exact path on the device behind one flag.  mode 0 takes the fp16 path where it exists, from 262,144 rows (the measured
+ *   crossover: the one-workgroup re-score costs more than the plain search's) and k <= 100.
+ *   The _device form takes device pointers for the terms and the results (clause_of stays on the host), is asynchronous on the
+ *   index's stream and reads nothing back.  vq_index_last_search_stats afterwards: [0] 1 if the fp16 path proved the answer,
+ *   [1] rows re-scored exactly, [2] 1 if the exact path answered.
+ *   vq_debug_compound_plan (host only, near-unit rows assumed, m one-term clauses): the path, the key streams of the scan, the
+ *   re-score pool (0 on the exact path), the bytes of the exact path's term table, and eps: unit rows and terms whose k-th and
+ *   (k+1)-th exact D differ by more than 4 eps are always proven when the k best rows reach the pool (eps = E for norms up to
+ *   1.0001, plus half the slack). */
+int vq_index_search_compound(vq_index* idx, const float* terms /*[m][dim]*/, int m, const int32_t* clause_of /*[m], host*/, float margin,
+                             int k, int mode, int32_t* ids /*[k]*/, float* dist /*[k]*/, float* term_dist /*[k][m] or NULL*/);
+int vq_index_search_compound_device(vq_index* idx, const void* d_terms_f32, int m, const int32_t* clause_of /*[m], host*/, float margin,
+                                    int k, int mode, void* d_ids_i32, void* d_dist_f32, void* d_term_dist_f32 /*or NULL*/);
+int vq_debug_compound_plan(int64_t n, int dim, int m, int k, int mode, int* fp16_path, int64_t* streams, int* rescore_pool,
+                           int64_t* exact_bytes, float* eps);
+
 /* save / load support (hnsw.py:306-380): the stored (normalised) rows. */
 int vq_index_export(vq_index* idx, float* rows /*[size][dim]*/);
 /* Single stored rows (the reference reads `self.data[node_id]`, a dict lookup): out [n][dim] = rows row_numbers[0..n). */

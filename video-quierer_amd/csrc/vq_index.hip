@@ -16,6 +16,7 @@
 #include "knn_sequence.h"
 #include "knn_summary.h"
 #include "knn_label.h"
+#include "knn_compound.h"
 #include "scan_plan.h"
 #include "host_buffers.h"
 #ifdef VQ_SCAN_EXPERIMENTS      // `make EXPERIMENTS=1`: the two superseded batch mainloops behind VQ_AMD_SCAN=2|4
@@ -158,6 +159,9 @@ struct vq_index {
     IdxBuf<int32_t> d_lgw;         // ... the split group form's lists, unlabelled counts and chosen labels; its pieces' histograms and show keys
     IdxBuf<uint32_t> d_lghist;
     IdxBuf<uint64_t> d_lgshow;
+    // compound search (knn_compound.h): the exact path's term table [m][ld]; the host form's term distances [k][m]
+    IdxBuf<float> d_ctab;
+    IdxBuf<float> d_cout;
     // clip-search scratch (knn_set.h): per-group sums [2][G], candidate list / positions [2][G] + count + flag, |q_i| [m],
     // order keys [G] + the selection's block lists, candidate keys, result staging of the host form
     IdxBuf<double> d_ssum;
@@ -1659,6 +1663,85 @@ int label_run(vq_index* x, const float* d_prompts, int P, int mode, bool force_e
     return 0;
 }
 
+// ---- compound search (knn_compound.h) ----
+// Everything that can refuse a compound search before any work is queued, the arguments aside: stale ranks, and mode 2 where the
+// fp16 path does not exist.
+int compound_precheck(vq_index* x, const char* fn, int k, int mode) {
+    VQ_TRY(check_ranks(x, fn));
+    if (mode != 1) VQ_TRY(refresh_norm_range(x));
+    if (mode == 2) VQ_CHECK(compound_fp16_dim(x->dim) && x->near_unit && k <= CP_K_MAX, "%s: the fp16 path needs dim 256, 512 or 768, "
+                            "k <= %d and near-unit rows (0.5 <= |row|^2 <= 2; rows added with normalize=0 are measured); mode 1 takes any call",
+                            fn, CP_K_MAX);
+    return 0;
+}
+
+// d_terms [m][dim], ids / dist [k], td [k][m] or null: all device memory.  Asynchronous on the index's stream.  force_exact: the
+// host form found a term norm the fp16 bound does not cover.
+int compound_run(vq_index* x, const float* d_terms, int m, const int32_t* clause_of, float margin, int k, int mode, bool force_exact,
+                 int32_t* ids, float* dist, float* td) {
+    const int64_t n = x->size;
+    const CompoundPlan p = plan_compound(n, x->dim, m, clause_of, k, mode, x->near_unit);
+    VQ_TRY(x->d_ctab.reserve((int64_t)m * p.ld));
+    const TieOrder tie = x->tie();
+    const bool one_wg = n <= SEL_SMALL_MAX_N;
+    // the exact path's two ends; gate = null: the call's answer, else the redo behind the call's flag
+    auto term_dists = [&](const unsigned long long* gate) {
+        Prof pr(x, I_EXACT_DIST);
+        hipLaunchKernelGGL(compound_dist_kernel, dim3(cdiv(n, 64)), dim3(256), 0, x->stream, x->rows, n, x->dim, d_terms, p.spec, margin,
+                           x->d_ctab, p.ld, x->d_dist, gate);
+    };
+    auto finish = [&](const unsigned long long* gate) {
+        Prof pr(x, I_SELECT);
+        hipLaunchKernelGGL(compound_finish_kernel, dim3(1), dim3(256), 0, x->stream, ids, dist, k, x->d_ctab, p.ld, m, td, gate);
+    };
+    if (!p.fp16 || force_exact) {
+        VQ_TRY(exact_topk(x, n, 1, k, one_wg, tie, ids, dist, [&](int, int, int64_t) { term_dists(nullptr); return 0; }));
+        finish(nullptr);
+        VQ_HIP(hipGetLastError());
+        return 0;                                           // (exact_topk has set the stats: one call answered exactly)
+    }
+    const int nchunks = cdiv(n, SEL_CHUNK);
+    VQ_TRY(x->d_q16.reserve((int64_t)CP_MAX_M * x->dim));
+    VQ_TRY(x->d_keys.reserve(p.streams * 2));
+    VQ_TRY(x->d_dist.reserve(p.ld));
+    if (!one_wg) VQ_TRY(x->d_partial.reserve((int64_t)nchunks * k));
+    VQ_TRY(ensure_gcounters(x));
+    x->last_scan.valid = false;                             // the combined keys take the plain search's buffer
+    const float eps_rows = scan_eps_unit(x->dim) * x->row_norm_max;
+    unsigned long long* gc = x->d_gcounters;
+    {
+        Prof pr(x, I_TO_F16);
+        hipLaunchKernelGGL(compound_terms_to_f16_kernel, dim3(CP_MAX_M), dim3(256), 0, x->stream, d_terms, p.lanes, x->dim, x->d_q16);
+    }
+    {
+        Prof pr(x, I_MFMA_SCAN);
+        auto scan = x->dim == 768 ? compound_scan_kernel<24> : x->dim == 512 ? compound_scan_kernel<16> : compound_scan_kernel<8>;
+        hipLaunchKernelGGL(scan, dim3(cdiv(p.streams, 4)), dim3(256), 0, x->stream, x->d_q16, x->rows16, n, p.streams, p.lanes,
+                           compound_veto_thr(eps_rows, margin), x->d_keys);
+    }
+    {
+        Prof pr(x, I_RESCORE);
+        hipLaunchKernelGGL(compound_rescore_kernel, dim3(1), dim3(256), 0, x->stream, x->d_keys, p.streams, x->rows, n, x->dim, d_terms, p.spec,
+                           margin, k, p.pool, eps_rows, ids, dist, td, gc, tie);
+    }
+    // the redo: every kernel of it leaves at once unless the re-score set the flag
+    term_dists(gc + 2);
+    {
+        Prof pr(x, I_SELECT);
+        if (one_wg) {
+            hipLaunchKernelGGL(select_small_kernel, dim3(1), dim3(256), 0, x->stream, x->d_dist, p.ld, n, k, ids, dist, tie, gc + 2, 0);
+        } else {
+            hipLaunchKernelGGL(select_chunk_kernel, dim3(1, nchunks), dim3(256), 0, x->stream, x->d_dist, p.ld, n, k, nchunks, x->d_partial, tie, gc + 2, 0);
+            hipLaunchKernelGGL(merge_topk_kernel, dim3(1), dim3(256), 0, x->stream, x->d_partial, nchunks, k, ids, dist, tie, gc + 2, 0);
+        }
+    }
+    finish(gc + 2);
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+    set_stats(x, STATS_GCOUNTERS);
+    return 0;
+}
+
 // ---- what the search entry points share ----
 // One argument check per shape of call.  arrays: every array the call reads or writes is there.
 int check_batch_args(const char* fn, const vq_index* x, int nq, int k, bool arrays) {
@@ -1711,6 +1794,28 @@ int check_summary_args(const char* fn, const vq_index* x, const int32_t* groups,
     VQ_CHECK(max_radius == max_radius, "%s: max_radius is NaN (-inf: no early stop)", fn);
     VQ_TRY(require_init());
     VQ_CHECK(x && groups && arrays, "%s: bad argument", fn);
+    return 0;
+}
+
+// (the arguments are judged before the library is asked for its device)
+int check_compound_args(const char* fn, const vq_index* x, int m, const int32_t* clause_of, float margin, int k, int mode, bool arrays) {
+    VQ_CHECK(m >= 1 && m <= CP_MAX_M, "%s: m %d outside [1, %d]", fn, m, CP_MAX_M);
+    VQ_CHECK(k >= 1 && k <= 1024, "%s: k %d outside [1, 1024]", fn, k);
+    VQ_CHECK(margin == margin, "%s: margin is NaN (-inf: the veto terms strike nothing)", fn);
+    VQ_TRY(check_mode(fn, mode));
+    VQ_CHECK(clause_of, "%s: clause_of is null", fn);
+    int next = 0;                                           // the first clause number not seen yet
+    for (int j = 0; j < m; ++j) {
+        const int c = clause_of[j];
+        if (c == -1) continue;
+        VQ_CHECK(c >= 0 && c < m, "%s: clause_of[%d] = %d is neither a clause number in [0, m) nor -1", fn, j, c);
+        VQ_CHECK(c >= next - 1, "%s: clause_of[%d] = %d after clause %d: the clause numbers must not decrease", fn, j, c, next - 1);
+        VQ_CHECK(c <= next, "%s: clause_of[%d] = %d leaves a gap: clause %d has no term", fn, j, c, next);
+        if (c == next) ++next;
+    }
+    VQ_CHECK(next >= 1, "%s: clause_of holds veto terms only: there is nothing to rank by", fn);
+    VQ_TRY(require_init());
+    VQ_CHECK(x && arrays, "%s: bad argument", fn);
     return 0;
 }
 
@@ -2655,6 +2760,67 @@ int vq_debug_label_plan(int64_t n, int dim, int P, int mode, int64_t largest_gro
     *fp16_path = p.fp16; *exact_chunk = p.exact_chunk; *exact_chunks = p.exact_chunks; *exact_bytes = p.exact_bytes;
     *prompt_tiles = p.prompt_tiles; *prompt_ranges = p.prompt_ranges; *row_tiles = p.row_tiles; *part_bytes = p.part_bytes; *eps = p.eps;
     *group_split_rows = p.group_split_rows; *group_piece_rows = p.group_piece_rows; *largest_group_pieces = p.largest_group_pieces;
+    return 0;
+}
+
+int vq_index_search_compound_device(vq_index* x, const void* d_terms, int m, const int32_t* clause_of, float margin, int k, int mode,
+                                    void* d_ids, void* d_dist, void* d_term_dist) {
+    static const char* fn = "vq_index_search_compound_device";
+    VQ_TRY(check_compound_args(fn, x, m, clause_of, margin, k, mode, d_terms && d_ids && d_dist));
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) {
+        if (d_term_dist) VQ_HIP(hipMemsetD32Async((hipDeviceptr_t)d_term_dist, 0x7f800000, (size_t)k * m, x->stream));      // +inf
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return fill_empty(x, k, (int32_t*)d_ids, nullptr, (float*)d_dist);
+    }
+    VQ_TRY(compound_precheck(x, fn, k, mode));
+    return compound_run(x, (const float*)d_terms, m, clause_of, margin, k, mode, false, (int32_t*)d_ids, (float*)d_dist, (float*)d_term_dist);
+}
+
+int vq_index_search_compound(vq_index* x, const float* terms, int m, const int32_t* clause_of, float margin, int k, int mode, int32_t* ids,
+                             float* dist, float* term_dist) {
+    static const char* fn = "vq_index_search_compound";
+    VQ_TRY(check_compound_args(fn, x, m, clause_of, margin, k, mode, terms && ids && dist));
+    std::lock_guard<std::mutex> lk(x->mu);
+    bool in_range = true;                                   // every |q|^2 inside what the fp16 bound covers
+    for (int j = 0; j < m; ++j) {
+        double s2 = 0.0;
+        for (int i = 0; i < x->dim; ++i) {
+            const float v = terms[(size_t)j * x->dim + i];
+            VQ_CHECK(v - v == 0.f, "%s: term %d holds a value that is not finite", fn, j);
+            s2 += (double)v * v;
+        }
+        if (!(s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX)) in_range = false;
+    }
+    const int64_t km = (int64_t)k * m;
+    if (x->size == 0) {
+        host_empty(k, ids, nullptr, dist);
+        if (term_dist) for (int64_t i = 0; i < km; ++i) term_dist[i] = __builtin_inff();
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    VQ_TRY(compound_precheck(x, fn, k, mode));
+    VQ_TRY(reserve_id_dist(x, k));
+    VQ_TRY(x->d_cout.reserve(km));
+    VQ_TRY(stage_queries(x, terms, m));
+    VQ_TRY(compound_run(x, x->d_q, m, clause_of, margin, k, mode, !in_range, x->d_ids, x->d_out, term_dist ? x->d_cout.p : nullptr));
+    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
+    if (term_dist) VQ_HIP(hipMemcpyAsync(term_dist, x->d_cout, (size_t)km * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// plan_compound's answer for near-unit rows; needs no device
+int vq_debug_compound_plan(int64_t n, int dim, int m, int k, int mode, int* fp16_path, int64_t* streams, int* rescore_pool,
+                           int64_t* exact_bytes, float* eps) {
+    VQ_CHECK(fp16_path && streams && rescore_pool && exact_bytes && eps && n >= 1 && n < ((int64_t)1 << 31) && dim > 0 && dim % 4 == 0 &&
+             dim <= 4096 && m >= 1 && m <= CP_MAX_M && k >= 1 && k <= 1024 && mode >= 0 && mode <= 2,
+             "vq_debug_compound_plan: takes 1 <= n < 2^31, a dim vq_index_create takes, 1 <= m <= %d, 1 <= k <= 1024, mode 0, 1 or 2", CP_MAX_M);
+    VQ_CHECK(mode != 2 || (compound_fp16_dim(dim) && k <= CP_K_MAX), "vq_debug_compound_plan: the fp16 path needs dim 256, 512 or 768 and k <= %d",
+             CP_K_MAX);
+    const CompoundPlan p = plan_compound(n, dim, m, nullptr, k, mode, true);
+    *fp16_path = p.fp16; *streams = p.streams; *rescore_pool = p.pool; *exact_bytes = p.exact_bytes; *eps = p.eps;
     return 0;
 }
 

@@ -764,6 +764,66 @@ class HNSWIndex:
         to_id = self._id_of()
         return [_hits(to_id, rr, rd) for rr, rd in zip(rows.tolist(), dist)]
 
+    # -- compound search: the k best rows that match ALL of several prompts, and none of the vetoed ones ------------
+    COMPOUND_MAX_TERMS = 16
+
+    @staticmethod
+    def _compound_terms(all_of, none_of) -> Tuple[List[np.ndarray], np.ndarray]:
+        """``all_of`` / ``none_of`` flattened into the C call's (term vectors, clause_of): an entry of ``all_of`` is one vector
+        (a clause of one term) or a sequence of vectors (alternatives: any of them satisfies the clause); the veto terms of
+        ``none_of`` follow with clause -1."""
+        terms, clause_of = [], []
+        for c, entry in enumerate(all_of):
+            if len(entry) == 0:
+                raise ValueError(f"clause {c} of all_of holds no vector")
+            alts = [entry] if np.ndim(entry[0]) == 0 else list(entry)
+            terms.extend(alts)
+            clause_of.extend([c] * len(alts))
+        if not terms:
+            raise ValueError("search_compound needs at least one vector in all_of")
+        for v in none_of:
+            terms.append(v)
+            clause_of.append(-1)
+        if len(terms) > HNSWIndex.COMPOUND_MAX_TERMS:
+            raise ValueError(f"a compound query holds at most {HNSWIndex.COMPOUND_MAX_TERMS} terms, got {len(terms)}")
+        return terms, np.array(clause_of, dtype=np.int32)
+
+    def search_compound(self, all_of, k: int = 5, *, none_of=(), margin: float = 0.0) -> List[Dict]:
+        """The k best frames that match ALL of several prompts: ``search``'s dicts plus ``'term_distances'`` (float32 [m]: the
+        frame's distance to every term, ``all_of``'s vectors in order, then ``none_of``'s — which term held the frame back).
+        An entry of ``all_of`` is one vector, or a sequence of vectors that are alternatives for that clause.  A frame's
+        distance is that of its WORST clause (the max over the clauses of the min over a clause's alternatives), so a frame
+        that shows one prompt very well and another not at all does not beat a frame that shows both — what adding the
+        prompt vectors cannot give.  A frame is struck when a ``none_of`` vector lies closer to it than that distance plus
+        ``margin`` (float32, strict): ``margin=0`` drops frames that show the unwanted prompt better than the wanted
+        combination, ``-inf`` drops nothing.  Every vector is normalised as ``search`` normalises its query; at most 16
+        vectors in all.  Exact in every mode (vq_index_search_compound)."""
+        terms, clause_of = self._compound_terms(all_of, none_of)
+        mg = np.float32(margin)
+        if mg != mg:
+            raise ValueError("margin is NaN")
+        if self._empty():
+            return []
+        with self.lock:
+            return self._compound(terms, clause_of, k, mg)
+
+    def _compound(self, terms, clause_of: np.ndarray, k: int, margin: np.float32, given: bool = False) -> List[Dict]:
+        """``given``: see ``_prepare`` (SimpleVideoIndex normalises by its own rule).  clause_of, margin: checked."""
+        ready = self._prepare(terms, k, given=given, groups=False, what="term")
+        if ready is None:
+            return []
+        if not self._identity:
+            self._sync_tie_order()
+        unit = ready[0]
+        m, kk = unit.shape[0], min(int(k), len(self._ids))
+        rows = np.empty(kk, dtype=np.int32)
+        dist = np.empty(kk, dtype=np.float32)
+        td = np.empty((kk, m), dtype=np.float32)
+        _lib.check(_lib.load().vq_index_search_compound(self._h, _lib.fptr(unit), m, _lib.i32ptr(clause_of), float(margin), kk,
+                                                        int(self.search_mode), _lib.i32ptr(rows), _lib.fptr(dist), _lib.fptr(td)))
+        to_id = self._id_of()
+        return [{"id": to_id(r), **_scored(d), "term_distances": t} for r, d, t in zip(rows.tolist(), dist, td) if r >= 0]
+
     # -- filtered query: the plain search within, or excluding, a set of groups (videos) -------------
     def search_filtered(self, query: np.ndarray, k: int = 5, *, within: Optional[Iterable[Hashable]] = None,
                         exclude: Optional[Iterable[Hashable]] = None, group_of: GROUP_OF = None) -> List[Dict]:

@@ -168,6 +168,31 @@ class SimpleVideoIndex:
             results.append(md)
         return results
 
+    def search_compound(self, all_of, k: int = 5, none_of=(), margin: float = 0.0) -> List[Dict]:
+        """The k best frames that match ALL of several prompts and none of the vetoed ones ("a dog AND a beach, NOT at night";
+        text prompts through ``extract_text_features``): ``search``'s dicts, ``'score'`` being the similarity of the frame's
+        WORST clause, plus ``'term_scores'`` (the frame's similarity to every vector: ``all_of``'s in order, then
+        ``none_of``'s).  An entry of ``all_of`` is one vector or a sequence of alternatives; a frame is dropped when a
+        ``none_of`` vector scores above the frame's score minus ``margin`` (``HNSWIndex.search_compound``: exact).  Every
+        vector is normalised as ``search`` does; ties between frames as ``search``."""
+        terms, clause_of = HNSWIndex._compound_terms(all_of, none_of)
+        mg = np.float32(margin)
+        if mg != mg:
+            raise ValueError("margin is NaN")
+        if not self.embeddings or k <= 0:
+            return []
+        dev = self._device(ranks=True)
+        unit = np.ascontiguousarray(np.stack([_unit_query(q) for q in terms]))
+        with dev.lock:                                # the terms as normalised above, not normalised again
+            res = dev._compound(unit, clause_of, k, mg, given=True)
+        results = []
+        for r in res:
+            md = self.metadata[-r["id"]].copy()
+            md["score"] = float(r["score"])
+            md["term_scores"] = [float(np.float32(1.0) - d) for d in r["term_distances"]]
+            results.append(md)
+        return results
+
     def search_storyboard(self, step_embeddings, k: int = 5, max_gap_s: float = 10.0, min_gap_s: float = 0.0) -> List[Dict]:
         """The k videos that show the steps IN ORDER (text prompts through ``extract_text_features``, or the frames of a clip):
         ``[{'video_name', 'score', 'timestamps', 'frame_ids'}]``, best first.  One frame of the video per step, each
