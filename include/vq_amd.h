@@ -611,6 +611,60 @@ int vq_debug_label_plan(int64_t n, int dim, int P, int mode, int64_t largest_gro
                         int64_t* exact_bytes, int* prompt_tiles, int* prompt_ranges, int64_t* row_tiles, int64_t* part_bytes, float* eps,
                         int* group_split_rows, int* group_piece_rows, int64_t* largest_group_pieces);
 
+/* Library clustering: exact spherical k-means over ALL stored rows; what organises a library nobody has queried yet (the themes
+ * of an archive with a poster frame each, material that recurs across videos, a vocabulary for vq_index_label_rows).  The result
+ * is a pure function of the rows, the initial centroids and the id ranks: every floating-point operation and its order are part
+ * of this definition, and the tests compare bits with a numpy restatement (tests/cluster_ref.py).
+ *   Inputs.  P clusters, 1 <= P <= min(4,096, n).  max_iter, 1 <= max_iter <= 1,000.  mode as vq_index_label_rows.  The initial
+ *   centroids C_1 come in exactly one of two ways: init, fp32 [P][dim], used as given; or init_rows, int32 [P], C_1[j] = stored
+ *   row init_rows[j] (gathered on the device; the same row may be named twice).
+ *   Iteration t = 1, 2, ...
+ *   1. Assign.  (L_t, best_t) = the row labels and distances of vq_index_label_rows(C_t, max_dist = +inf): its definition
+ *      applies, the tie rule included (of two centroids at the same distance the smaller j wins).
+ *   2. Stop.  changed[t-1] = the number of rows with L_t != L_{t-1}; changed[0] = n.  The host form stops when t > 1 and
+ *      changed[t-1] == 0, or when t == max_iter.
+ *   3. Update to C_{t+1}.  For cluster j let R_j be its rows in ascending row number, cnt_j = |R_j|.  R_j is cut into pieces of
+ *      1,024 consecutive entries (the last one may be shorter).  piece_sum[i] = the fp64 sum of (double)x_r[i] over the piece's
+ *      rows, added one after another in list order, starting from 0.0.  s_j[i] = the pieces' sums added in piece order, starting
+ *      from 0.0.  m_j[i] = fp32(s_j[i] / (double)cnt_j).  n2_j = the fp64 sum over i = 0 .. dim-1, in index order, starting
+ *      from 0.0, of (double)m_j[i] * (double)m_j[i] (products of two fp32 values are exact in fp64: a fused multiply-add gives
+ *      the same sum).  C_{t+1}[j][i] = fp32((double)m_j[i] / sqrt(n2_j)).  If cnt_j == 0 or n2_j == 0, C_{t+1}[j] = C_t[j], bit
+ *      for bit.  Every operation is an IEEE fp64 add, divide or square root (round to nearest even), or an exact product.
+ *   Result, with T = the last t reached: centroids = C_T [P][dim]; row_label = L_T and row_dist = best_T [n] (either may be
+ *   NULL); counts[j] = cnt_j under L_T; show_rows[j] = the row of cluster j with the smallest (best_T, tie), tie as
+ *   vq_index_search (the row number, or the id rank), -1 for a cluster without rows; *iterations = T; changed[0 .. T-1] (NULL:
+ *   not wanted; the array holds max_iter entries, those from T on are not written).  The labels are always the assignment TO THE
+ *   RETURNED centroids: vq_index_label_rows(centroids) reproduces row_label and row_dist bit for bit.
+ *   The _device form takes device pointers (d_init or d_init_rows, the other NULL; d_init may be d_centroids itself) and runs
+ *   exactly `iters` assignments and iters - 1 updates: no convergence test, nothing read back, asynchronous on the index's
+ *   stream.  Past a fixed point every further iteration reproduces the same bits (the update is a pure function of L), so it
+ *   agrees with the host form whenever iters >= the host form's *iterations.  Its init_rows entries cannot be checked without
+ *   reading them back: entries in [0, n) are a precondition (the gather clamps others into range).
+ *   Refused (VQ_ERR_INVALID, before any work is queued, no output touched): P or max_iter / iters out of range; both or neither of
+ *   init / init_rows; an init_rows entry outside [0, n) (host form); an init value that is not finite (host form); an unknown
+ *   mode, or mode 2 where vq_index_label_rows refuses it; stale id ranks.  An empty index returns 0 and writes nothing.
+ *   vq_index_last_search_stats afterwards holds the three label classes of the LAST assignment.
+ *   How it runs (csrc/knn_cluster.h, DESIGN.md §4 "Library clustering").  The assignment is the label call's run, unchanged.
+ *   The rows are then listed by label in ascending row order (a stable counting sort over blocks of 1,024 rows: integers only);
+ *   the same pass counts the changed rows, and the host form reads that one mapped word per iteration.  One workgroup per piece
+ *   sums its rows' columns in fp64 (a thread owns four columns; no floating-point atomics anywhere: the order is the
+ *   definition), one workgroup per cluster adds the pieces in order and finishes the centroid in place.  The show rows are a
+ *   64-bit minimum per cluster over the list, after the last assignment only.  The piece sums are accounted under the profile
+ *   class exact_dist_f64chain, the finish under normalize_rows, the list and the show rows under select_topk (VQ_IDX_NCLASS
+ *   stays 7).
+ *   vq_debug_cluster_plan (host only): the piece length (1,024), the piece kernel's grid max_pieces = floor(n / 1,024) +
+ *   min(P, n) (a bound on sum_j ceil(cnt_j / 1,024): workgroups beyond a list's pieces leave at once), the counting sort's blocks
+ *   ceil(n / 1,024) and its table (blocks x P x 4 bytes), the pieces' sums (max_pieces x dim x 8 bytes), all scratch, the piece
+ *   kernel's threads (dim / 4 rounded up to whole waves) and the launches of one iteration, the assignment aside. */
+int vq_index_cluster(vq_index* idx, const float* init /*[P][dim] or NULL*/, const int32_t* init_rows /*[P] or NULL*/, int P, int max_iter,
+                     int mode, float* centroids /*[P][dim]*/, int32_t* row_label /*[n] or NULL*/, float* row_dist /*[n] or NULL*/,
+                     int32_t* counts /*[P]*/, int32_t* show_rows /*[P]*/, int* iterations, int32_t* changed /*[max_iter] or NULL*/);
+int vq_index_cluster_device(vq_index* idx, const void* d_init_f32 /*or NULL*/, const void* d_init_rows_i32 /*or NULL*/, int P, int iters,
+                            int mode, void* d_centroids_f32, void* d_row_label_i32 /*or NULL*/, void* d_row_dist_f32 /*or NULL*/,
+                            void* d_counts_i32, void* d_show_rows_i32);
+int vq_debug_cluster_plan(int64_t n, int dim, int P, int* piece_rows, int64_t* max_pieces, int64_t* list_blocks, int64_t* table_bytes,
+                          int64_t* sum_bytes, int64_t* scratch_bytes, int* piece_threads, int* launches);
+
 /* Compound search: the k best rows that match ALL of several prompts — "a dog AND a beach, in the same frame, but NOT at night".
  * Adding the prompt vectors ranks by the SUM of the similarities: a frame that shows one term very well and the other not at all
  * beats a frame that shows both.  Here a frame's WORST required term decides its place.
@@ -785,6 +839,13 @@ int64_t vq_debug_scan_row_of(int layout, int64_t stream, int local);
 int vq_index_debug_rescore(vq_index* idx, const float* queries /*[nq][dim], host*/, int nq, int k,
                            const uint32_t* keys /*[nq][streams][2], host*/, int64_t capacity,
                            int32_t* ids /*[nq][k]*/, float* dist /*[nq][k]*/, int32_t* flags /*[nq]*/);
+
+/* Stage entry of the clustering update (tests/test_cluster.py): the update step of vq_index_cluster alone, on labels the CALLER
+ * wrote.  labels [n] (host, each in [0, P), VQ_ERR_INVALID otherwise; a non-empty index) take the place of an assignment;
+ * centroids_in [P][dim] are C_t.  It builds the by-label list and runs the piece sums and the finish, the launches of the loop
+ * through its own functions, waits, and returns C_{t+1} and the clusters' row counts.  The search statistics are not touched. */
+int vq_index_debug_cluster_update(vq_index* idx, const int32_t* labels /*[n], host*/, int P, const float* centroids_in /*[P][dim], host*/,
+                                  float* centroids_out /*[P][dim]*/, int32_t* counts /*[P]*/);
 
 /* Stage entry of the exact redo (tests/test_exact_stages.py): pass 3 of an fp16 search on flags the CALLER wrote.
  *   vq_debug_fallback_plan: the redo's geometry for n rows, nq queries and k results, out = {fast_splits, fast_rows, splits,

@@ -161,6 +161,12 @@ SIGNATURES = {
     "vq_debug_label_plan": (c_int, [c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int64),
                                     POINTER(c_int), POINTER(c_int), POINTER(c_int64), POINTER(c_int64), POINTER(c_float), POINTER(c_int),
                                     POINTER(c_int), POINTER(c_int64)]),
+    "vq_index_cluster": (c_int, [c_void_p, POINTER(c_float), POINTER(c_int32), c_int, c_int, c_int, POINTER(c_float), POINTER(c_int32),
+                                 POINTER(c_float), POINTER(c_int32), POINTER(c_int32), POINTER(c_int), POINTER(c_int32)]),
+    "vq_index_cluster_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vq_debug_cluster_plan": (c_int, [c_int64, c_int, c_int, POINTER(c_int), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
+                                      POINTER(c_int64), POINTER(c_int64), POINTER(c_int), POINTER(c_int)]),
+    "vq_index_debug_cluster_update": (c_int, [c_void_p, POINTER(c_int32), c_int, POINTER(c_float), POINTER(c_float), POINTER(c_int32)]),
     "vq_index_search_compound": (c_int, [c_void_p, POINTER(c_float), c_int, POINTER(c_int32), c_float, c_int, c_int, POINTER(c_int32),
                                          POINTER(c_float), POINTER(c_float)]),
     "vq_index_search_compound_device": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int32), c_float, c_int, c_int, c_void_p, c_void_p,

@@ -17,6 +17,7 @@
 #include "knn_summary.h"
 #include "knn_label.h"
 #include "knn_compound.h"
+#include "knn_cluster.h"
 #include "scan_plan.h"
 #include "host_buffers.h"
 #ifdef VQ_SCAN_EXPERIMENTS      // `make EXPERIMENTS=1`: the two superseded batch mainloops behind VQ_AMD_SCAN=2|4
@@ -159,6 +160,15 @@ struct vq_index {
     IdxBuf<int32_t> d_lgw;         // ... the split group form's lists, unlabelled counts and chosen labels; its pieces' histograms and show keys
     IdxBuf<uint32_t> d_lghist;
     IdxBuf<uint64_t> d_lgshow;
+    // library clustering (knn_cluster.h): control words | previous labels | labels | distances | by-label row list [n each] |
+    // counts | list offsets | piece offsets | counts and show rows of the host form [P + 1 each]; the blocks' label counts
+    // [blocks][P]; the pieces' fp64 sums [pieces][dim]; the clusters' show keys [P]; the host form's changed counts (mapped:
+    // cluster_scan_kernel writes one per iteration, the host reads it after its wait)
+    IdxBuf<int32_t> d_clw;
+    IdxBuf<uint32_t> d_cltab;
+    IdxBuf<double> d_clsum;
+    IdxBuf<uint64_t> d_clkey;
+    PinnedBuf<int32_t> h_clchanged{true};
     // compound search (knn_compound.h): the exact path's term table [m][ld]; the host form's term distances [k][m]
     IdxBuf<float> d_ctab;
     IdxBuf<float> d_cout;
@@ -1663,6 +1673,102 @@ int label_run(vq_index* x, const float* d_prompts, int P, int mode, bool force_e
     return 0;
 }
 
+// ---- library clustering (knn_cluster.h) ----
+static_assert(CL_MAX_P == LABEL_MAX_P, "knn_cluster.h: a cluster is a prompt of the label call");
+
+struct ClusterBufs {
+    int32_t* ctl; int32_t* prev; int32_t* lab; float* best; int32_t* list; int32_t* cnt; int32_t* off; int32_t* poff;
+    int32_t* counts; int32_t* show;      // the host form's results
+    ClusterPlan plan;
+};
+
+int cluster_reserve(vq_index* x, int P, ClusterBufs* b) {
+    const int64_t n = x->size, nw = round_up(n, 4), pw = round_up((int64_t)P + 1, 4);
+    b->plan = plan_cluster(n, x->dim, P);
+    VQ_TRY(x->d_clw.reserve(CL_CTL_WORDS + 4 * nw + 5 * pw));
+    VQ_TRY(x->d_cltab.reserve(b->plan.blocks * P));
+    VQ_TRY(x->d_clsum.reserve(b->plan.max_pieces * x->dim));
+    VQ_TRY(x->d_clkey.reserve(P));
+    int32_t* w = x->d_clw;
+    b->ctl = w; b->prev = w + CL_CTL_WORDS; b->lab = b->prev + nw; b->best = (float*)(b->lab + nw); b->list = b->lab + 2 * nw;
+    b->cnt = b->list + nw; b->off = b->cnt + pw; b->poff = b->off + pw; b->counts = b->poff + pw; b->show = b->counts + pw;
+    VQ_HIP(hipMemsetAsync(b->ctl, 0, CL_CTL_WORDS * 4, x->stream));
+    return 0;
+}
+
+// The by-label row list of lab [n], its offsets and pieces; counts_out / changed_out (device addresses) or null.
+void cluster_list(vq_index* x, const ClusterBufs& b, const int32_t* lab, int P, bool first, int32_t* counts_out, int32_t* changed_out) {
+    const int64_t n = x->size;
+    Prof pr(x, I_SELECT);
+    hipLaunchKernelGGL(cluster_hist_kernel, dim3((unsigned)b.plan.blocks), dim3(256), 0, x->stream, lab, b.prev, n, P, first ? 1 : 0, x->d_cltab, b.ctl);
+    hipLaunchKernelGGL(cluster_prefix_kernel, dim3(cdiv(P, 256)), dim3(256), 0, x->stream, x->d_cltab, b.plan.blocks, P, b.cnt);
+    hipLaunchKernelGGL(cluster_scan_kernel, dim3(1), dim3(1024), 0, x->stream, b.cnt, P, b.off, b.poff, (unsigned long long*)x->d_clkey.p, counts_out,
+                       b.ctl, changed_out);
+    hipLaunchKernelGGL(cluster_scatter_kernel, dim3((unsigned)b.plan.blocks), dim3(256), 0, x->stream, lab, n, P, x->d_cltab, b.off, b.list);
+}
+
+// C [P][dim] <- the update of the list's clusters, in place.  The pieces' sums are accounted under exact_dist_f64chain (fp64
+// chains over the master), the finish under normalize_rows.
+void cluster_update(vq_index* x, const ClusterBufs& b, int P, float* C) {
+    {
+        Prof pr(x, I_EXACT_DIST);
+        hipLaunchKernelGGL(cluster_piece_kernel, dim3((unsigned)b.plan.max_pieces), dim3(b.plan.piece_threads), 0, x->stream, x->rows, x->dim, P, b.list,
+                           b.off, b.poff, b.ctl, x->d_clsum);
+    }
+    Prof pr(x, I_NORMALIZE);
+    hipLaunchKernelGGL(cluster_finish_kernel, dim3(P), dim3(256), 0, x->stream, x->d_clsum, x->dim, b.off, b.poff, C);
+}
+
+void cluster_show(vq_index* x, const ClusterBufs& b, int P, const float* best, int32_t* show) {
+    const TieOrder tie = x->tie();
+    Prof pr(x, I_SELECT);
+    hipLaunchKernelGGL(cluster_show_kernel, dim3((unsigned)b.plan.max_pieces), dim3(256), 0, x->stream, b.list, b.off, b.poff, P, b.ctl, best, tie,
+                       (unsigned long long*)x->d_clkey.p);
+    hipLaunchKernelGGL(cluster_show_rows_kernel, dim3(cdiv(P, 256)), dim3(256), 0, x->stream, (const unsigned long long*)x->d_clkey.p, P, tie, show);
+}
+
+// Everything that can refuse a clustering call before any work is queued, the arguments aside: stale ranks (the show rows'
+// ties), the mode, mode 2 where the label call refuses it.
+int cluster_precheck(vq_index* x, const char* fn, int mode) {
+    VQ_TRY(check_ranks(x, fn));
+    return label_precheck(x, fn, mode, false);
+}
+
+int check_cluster_args(const char* fn, const vq_index* x, const void* init, const void* init_rows, int P, int iters, bool outputs) {
+    VQ_CHECK(P >= 1 && P <= CL_MAX_P, "%s: P %d outside [1, %d]", fn, P, CL_MAX_P);
+    VQ_CHECK(iters >= 1 && iters <= CL_MAX_ITER, "%s: %d iterations outside [1, %d]", fn, iters, CL_MAX_ITER);
+    VQ_CHECK((init != nullptr) != (init_rows != nullptr), "%s: give exactly one of init and init_rows", fn);
+    VQ_TRY(require_init());
+    VQ_CHECK(x && outputs, "%s: bad argument", fn);
+    return 0;
+}
+
+// C [P][dim] holds C_1 (device memory) and ends as C_T.  The host form (h_changed != null: the mapped counters) waits for the
+// stream once per iteration and stops at a fixed point; the device form runs `iters` assignments and reads nothing back.
+// lab / best: where the rows' answers go (the caller's arrays or the call's scratch).  *T: the iterations run.
+int cluster_run(vq_index* x, const ClusterBufs& b, float* C, int P, int iters, int mode, bool force_exact, int32_t* lab, float* best,
+                int32_t* counts, int32_t* show, int32_t* changed, int* T) {
+    const bool host = changed != nullptr;
+    const float inf = __builtin_inff();
+    int t = 1;
+    for (;; ++t) {
+        VQ_TRY(label_run(x, C, P, mode, force_exact, inf, lab, best, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        cluster_list(x, b, lab, P, t == 1, counts, host ? x->h_clchanged.dev + (t - 1) : nullptr);
+        VQ_HIP(hipGetLastError());
+        if (host) {
+            VQ_HIP(hipStreamSynchronize(x->stream));
+            changed[t - 1] = x->h_clchanged[t - 1];
+            if (t > 1 && changed[t - 1] == 0) break;
+        }
+        if (t == iters) break;
+        cluster_update(x, b, P, C);
+    }
+    cluster_show(x, b, P, best, show);
+    VQ_HIP(hipGetLastError());
+    *T = t;
+    return 0;
+}
+
 // ---- compound search (knn_compound.h) ----
 // Everything that can refuse a compound search before any work is queued, the arguments aside: stale ranks, and mode 2 where the
 // fp16 path does not exist.
@@ -2760,6 +2866,126 @@ int vq_debug_label_plan(int64_t n, int dim, int P, int mode, int64_t largest_gro
     *fp16_path = p.fp16; *exact_chunk = p.exact_chunk; *exact_chunks = p.exact_chunks; *exact_bytes = p.exact_bytes;
     *prompt_tiles = p.prompt_tiles; *prompt_ranges = p.prompt_ranges; *row_tiles = p.row_tiles; *part_bytes = p.part_bytes; *eps = p.eps;
     *group_split_rows = p.group_split_rows; *group_piece_rows = p.group_piece_rows; *largest_group_pieces = p.largest_group_pieces;
+    return 0;
+}
+
+int vq_index_cluster_device(vq_index* x, const void* d_init, const void* d_init_rows, int P, int iters, int mode, void* d_centroids,
+                            void* d_row_label, void* d_row_dist, void* d_counts, void* d_show_rows) {
+    static const char* fn = "vq_index_cluster_device";
+    VQ_TRY(check_cluster_args(fn, x, d_init, d_init_rows, P, iters, d_centroids && d_counts && d_show_rows));
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) {
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    VQ_CHECK(P <= x->size, "%s: %d clusters for an index of %lld rows", fn, P, (long long)x->size);
+    VQ_TRY(cluster_precheck(x, fn, mode));
+    ClusterBufs b;
+    VQ_TRY(cluster_reserve(x, P, &b));
+    float* C = (float*)d_centroids;
+    if (d_init) {
+        if (d_init != d_centroids) VQ_HIP(hipMemcpyAsync(C, d_init, (size_t)P * x->dim * 4, hipMemcpyDeviceToDevice, x->stream));
+    } else {
+        hipLaunchKernelGGL(cluster_gather_kernel, dim3(P), dim3(256), 0, x->stream, x->rows, x->size, x->dim, (const int32_t*)d_init_rows, C);
+    }
+    int T;
+    return cluster_run(x, b, C, P, iters, mode, false, d_row_label ? (int32_t*)d_row_label : b.lab, d_row_dist ? (float*)d_row_dist : b.best,
+                       (int32_t*)d_counts, (int32_t*)d_show_rows, nullptr, &T);
+}
+
+int vq_index_cluster(vq_index* x, const float* init, const int32_t* init_rows, int P, int max_iter, int mode, float* centroids,
+                     int32_t* row_label, float* row_dist, int32_t* counts, int32_t* show_rows, int* iterations, int32_t* changed) {
+    static const char* fn = "vq_index_cluster";
+    VQ_TRY(check_cluster_args(fn, x, init, init_rows, P, max_iter, centroids && counts && show_rows && iterations));
+    std::lock_guard<std::mutex> lk(x->mu);
+    bool in_range = true;                                   // every |c|^2 inside what the fp16 bound covers
+    if (init) {
+        for (int j = 0; j < P; ++j) {
+            double s2 = 0.0;
+            for (int i = 0; i < x->dim; ++i) {
+                const float v = init[(size_t)j * x->dim + i];
+                VQ_CHECK(v - v == 0.f, "%s: initial centroid %d holds a value that is not finite", fn, j);
+                s2 += (double)v * v;
+            }
+            if (!(s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX)) in_range = false;
+        }
+    }
+    if (x->size == 0) {
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    const int64_t n = x->size;
+    VQ_CHECK(P <= n, "%s: %d clusters for an index of %lld rows", fn, P, (long long)n);
+    if (init_rows)
+        for (int j = 0; j < P; ++j)
+            VQ_CHECK(init_rows[j] >= 0 && init_rows[j] < n, "%s: init_rows[%d] = %d outside [0, %lld)", fn, j, (int)init_rows[j], (long long)n);
+    VQ_TRY(cluster_precheck(x, fn, mode));
+    ClusterBufs b;
+    VQ_TRY(cluster_reserve(x, P, &b));
+    if (x->h_clchanged.cap < max_iter) {                    // (the device form never writes there: nothing in flight uses it)
+        VQ_HIP(hipStreamSynchronize(x->stream));
+        VQ_TRY(x->h_clchanged.reserve(max_iter, CL_MAX_ITER));
+    }
+    const int64_t words = (int64_t)P * x->dim;
+    if (init) {
+        VQ_TRY(stage_queries(x, init, P));                  // the centroids live in d_q, as the label call's prompts do
+    } else {
+        VQ_TRY(x->d_q.reserve(words));
+        StageSlot* slot;
+        VQ_TRY(stage_slot(x, P, &slot));
+        std::memcpy(slot->h, init_rows, (size_t)P * 4);
+        VQ_HIP(hipMemcpyAsync(b.show, slot->h.p, (size_t)P * 4, hipMemcpyHostToDevice, x->stream));      // (free until the show rows are written)
+        VQ_HIP(hipEventRecord(slot->ev, x->stream));
+        hipLaunchKernelGGL(cluster_gather_kernel, dim3(P), dim3(256), 0, x->stream, x->rows, n, x->dim, b.show, x->d_q);
+    }
+    std::vector<int32_t> ch((size_t)max_iter);
+    int T = 0;
+    VQ_TRY(cluster_run(x, b, x->d_q, P, max_iter, mode, !in_range, b.lab, b.best, b.counts, b.show, ch.data(), &T));
+    VQ_HIP(hipMemcpyAsync(centroids, x->d_q, (size_t)words * 4, hipMemcpyDeviceToHost, x->stream));
+    if (row_label) VQ_HIP(hipMemcpyAsync(row_label, b.lab, (size_t)n * 4, hipMemcpyDeviceToHost, x->stream));
+    if (row_dist) VQ_HIP(hipMemcpyAsync(row_dist, b.best, (size_t)n * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(counts, b.counts, (size_t)P * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(show_rows, b.show, (size_t)P * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    *iterations = T;
+    if (changed) std::copy(ch.begin(), ch.begin() + T, changed);
+    return 0;
+}
+
+// The update alone, on labels the caller writes (tests/test_cluster.py): centroids_out = the update of centroids_in under
+// labels [n] (each in [0, P)), counts [P] the clusters' rows.
+int vq_index_debug_cluster_update(vq_index* x, const int32_t* labels, int P, const float* centroids_in, float* centroids_out, int32_t* counts) {
+    static const char* fn = "vq_index_debug_cluster_update";
+    VQ_CHECK(P >= 1 && P <= CL_MAX_P, "%s: P %d outside [1, %d]", fn, P, CL_MAX_P);
+    VQ_TRY(require_init());
+    VQ_CHECK(x && labels && centroids_in && centroids_out && counts, "%s: bad argument", fn);
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t n = x->size;
+    VQ_CHECK(n >= 1, "%s: the index is empty", fn);
+    for (int64_t r = 0; r < n; ++r) VQ_CHECK(labels[r] >= 0 && labels[r] < P, "%s: labels[%lld] = %d outside [0, %d)", fn, (long long)r, (int)labels[r], P);
+    ClusterBufs b;
+    VQ_TRY(cluster_reserve(x, P, &b));
+    VQ_TRY(stage_queries(x, centroids_in, P));
+    StreamDrain drain{x->stream};                           // `labels` is the caller's pageable memory
+    VQ_HIP(hipMemcpyAsync(b.lab, labels, (size_t)n * 4, hipMemcpyHostToDevice, x->stream));
+    cluster_list(x, b, b.lab, P, true, b.counts, nullptr);
+    cluster_update(x, b, P, x->d_q);
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(centroids_out, x->d_q, (size_t)P * x->dim * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(counts, b.counts, (size_t)P * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// plan_cluster's answer; needs no device
+int vq_debug_cluster_plan(int64_t n, int dim, int P, int* piece_rows, int64_t* max_pieces, int64_t* list_blocks, int64_t* table_bytes,
+                          int64_t* sum_bytes, int64_t* scratch_bytes, int* piece_threads, int* launches) {
+    VQ_CHECK(piece_rows && max_pieces && list_blocks && table_bytes && sum_bytes && scratch_bytes && piece_threads && launches && n >= 1 &&
+             n < ((int64_t)1 << 31) && dim > 0 && dim % 4 == 0 && dim <= 4096 && P >= 1 && P <= CL_MAX_P && P <= n,
+             "vq_debug_cluster_plan: takes 1 <= n < 2^31, a dim vq_index_create takes, 1 <= P <= min(%d, n)", CL_MAX_P);
+    const ClusterPlan p = plan_cluster(n, dim, P);
+    *piece_rows = p.piece_rows; *max_pieces = p.max_pieces; *list_blocks = p.blocks; *table_bytes = p.table_bytes; *sum_bytes = p.sum_bytes;
+    *scratch_bytes = p.scratch_bytes; *piece_threads = p.piece_threads; *launches = p.launches;
     return 0;
 }
 

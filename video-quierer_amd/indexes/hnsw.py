@@ -1056,6 +1056,70 @@ class HNSWIndex:
         with self.lock:
             return self._label_groups(prompts, top, group_of, max_distance)
 
+    # -- library clustering: the themes of everything stored, nobody's query needed ----------------------
+    CLUSTER_MAX = 4096            # vq_index_cluster: clusters per call
+    CLUSTER_MAX_ITER = 1000       # ... iterations
+
+    def _cluster(self, k: int, max_iter: int, init, seed, mode: int, given: bool = False):
+        """One device call, under the lock.  None for an empty index, else (centroids [k][dim], labels [n], distances [n],
+        counts [k], show rows [k], iterations, changed [iterations])."""
+        k, max_iter = int(k), int(max_iter)
+        if not 1 <= k <= self.CLUSTER_MAX:
+            raise ValueError(f"k must be in [1, {self.CLUSTER_MAX}], got {k}")
+        if not 1 <= max_iter <= self.CLUSTER_MAX_ITER:
+            raise ValueError(f"max_iter must be in [1, {self.CLUSTER_MAX_ITER}], got {max_iter}")
+        if self._empty():
+            return None
+        n = len(self._ids)
+        if k > n:
+            raise ValueError(f"{k} clusters for an index of {n} rows")
+        unit = rows = None
+        if init is None:
+            rows = np.sort(np.random.default_rng(seed).choice(n, k, replace=False)).astype(np.int32)
+        else:
+            unit = init if given else np.ascontiguousarray(self._unit_rows(init), dtype=np.float32)
+            if unit.shape != (k, self.dimension):
+                raise ValueError(f"init must hold {k} vectors of dimension {self.dimension}, got shape {unit.shape}")
+        if not self._identity:
+            self._sync_tie_order()                # the show rows' ties follow the ids, as `search` orders them
+        centroids = np.empty((k, self.dimension), dtype=np.float32)
+        labels, counts, show = np.empty(n, dtype=np.int32), np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int32)
+        dist = np.empty(n, dtype=np.float32)
+        changed = np.zeros(max_iter, dtype=np.int32)
+        iterations = ctypes.c_int(0)
+        _lib.check(_lib.load().vq_index_cluster(self._h, _lib.fptr(unit) if unit is not None else None,
+                                                _lib.i32ptr(rows) if rows is not None else None, k, max_iter, int(mode), _lib.fptr(centroids),
+                                                _lib.i32ptr(labels), _lib.fptr(dist), _lib.i32ptr(counts), _lib.i32ptr(show),
+                                                ctypes.byref(iterations), _lib.i32ptr(changed)))
+        return centroids, labels, dist, counts, show, iterations.value, changed[:iterations.value]
+
+    def cluster(self, k: int, *, max_iter: int = 25, init=None, seed=0, mode: int = MODE_AUTO) -> Dict:
+        """Spherical k-means over every stored row, exact and reproducible: the same rows, ``k``, ``init`` / ``seed`` give the
+        same bits on every run (the device sums in a fixed order; include/vq_amd.h vq_index_cluster has the definition).
+        ``init``: k start vectors (normalised as ``search`` normalises queries); None: k distinct stored rows drawn by
+        ``np.random.default_rng(seed)``, in ascending row order.  Every iteration assigns each row to its closest centroid
+        (``label_rows``' rule: equal distances go to the smaller cluster number) and moves each centroid to the normalised
+        mean of its rows; a cluster that loses all its rows keeps its centroid.  It stops when no row changes cluster, or
+        after ``max_iter`` assignments.  Returns ``{'centroids' float32 [k][dim], 'labels' int32 [n], 'distances' float32 [n],
+        'clusters', 'iterations', 'converged', 'changed'}``: labels and distances are ``label_rows(centroids)`` in row order;
+        ``clusters[j]`` is ``{'cluster': j, 'size', 'id', 'distance', 'score'}`` with the row closest to the centroid (ties by id
+        as ``search``; ``id`` None for an empty cluster); ``changed[t]`` the rows that changed cluster in assignment t + 1 (all
+        of them in the first); ``converged``: the last assignment changed nothing.  ``mode`` as ``label_rows``.  At most 4,096
+        clusters, at most as many as rows.  An empty index: no clusters."""
+        with self.lock:
+            res = self._cluster(k, max_iter, init, seed, mode)
+        if res is None:
+            return {"centroids": np.empty((0, self.dimension), dtype=np.float32), "labels": np.empty(0, dtype=np.int32),
+                    "distances": np.empty(0, dtype=np.float32), "clusters": [], "iterations": 0, "converged": True, "changed": []}
+        centroids, labels, dist, counts, show, iterations, changed = res
+        to_id = self._id_of()
+        clusters = [{"cluster": j, "size": c, "id": to_id(r), **_scored(dist[r])} if r >= 0 else
+                    {"cluster": j, "size": c, "id": None, "distance": None, "score": None}
+                    for j, (c, r) in enumerate(zip(counts.tolist(), show.tolist()))]
+        changed = changed.tolist()
+        return {"centroids": centroids, "labels": labels, "distances": dist, "clusters": clusters, "iterations": iterations,
+                "converged": iterations > 1 and changed[-1] == 0, "changed": changed}
+
     # -- sequence query: the k groups (videos) that show a list of steps in order -------------------
     SEQ_MAX_STEPS = 64            # vq_index_search_sequence: steps per call
 

@@ -280,6 +280,37 @@ class SimpleVideoIndex:
                                    "frame_id": md["frame_id"], "score": float(np.float32(1.0) - r["distance"])})
         return out
 
+    def topics(self, k: int, top_videos: int = 3, **kw) -> List[Dict]:
+        """The ``k`` themes of the whole library, nobody's prompts needed (a browse page: a poster frame per theme):
+        ``[{'topic', 'video_name', 'timestamp', 'frame_id', 'score', 'size', 'share', 'videos'}]``, one entry per non-empty
+        cluster of ``HNSWIndex.cluster(k, **kw)`` (exact spherical k-means over all frames; ``seed``, ``max_iter``, ``init``
+        pass through), the largest first (equal sizes: the smaller cluster number).  ``video_name`` / ``timestamp`` /
+        ``frame_id`` / ``score`` are those of the frame closest to the theme's centre, ``size`` its frames, ``share`` that
+        over all frames, ``videos`` the ``top_videos`` videos with the most frames in it as ``{'video_name', 'frames'}``
+        (more frames first, then library order).  The per-video counts are ``tag_videos``' vote on the final centres, which
+        labels every frame as the clustering did; a video enters a theme's list when the theme is among its 16 most voted."""
+        if int(top_videos) < 0:
+            raise ValueError(f"top_videos must be >= 0, got {top_videos}")
+        if not self.embeddings:
+            return []
+        dev = self._device(ranks=True)
+        with dev.lock:                                # one lock for both calls: the same rows; the centres as returned, not normalised again
+            res = dev.cluster(k, **kw)
+            tagged = dev._label_groups(res["centroids"], dev.LABEL_MAX_TAGS, self._group_fn, None, given=True)
+        votes: Dict[int, List] = {}
+        for video, found in tagged.items():
+            for r in found:
+                votes.setdefault(r["label"], []).append((video, r["votes"]))
+        n = len(self.embeddings)
+        out = []
+        for c in sorted((c for c in res["clusters"] if c["size"] > 0), key=lambda c: (-c["size"], c["cluster"])):
+            md = self.metadata[-c["id"]]
+            best = sorted(votes.get(c["cluster"], []), key=lambda vv: -vv[1])[:int(top_videos)]          # stable: library order on equal counts
+            out.append({"topic": c["cluster"], "video_name": md["video_name"], "timestamp": md["timestamp"], "frame_id": md["frame_id"],
+                        "score": float(c["score"]), "size": c["size"], "share": c["size"] / n,
+                        "videos": [{"video_name": v, "frames": f} for v, f in best]})
+        return out
+
     def save_to_disk(self, cache_path: Path):
         try:
             with open(cache_path, "wb") as f:
