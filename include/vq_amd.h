@@ -665,6 +665,69 @@ int vq_index_cluster_device(vq_index* idx, const void* d_init_f32 /*or NULL*/, c
 int vq_debug_cluster_plan(int64_t n, int dim, int P, int* piece_rows, int64_t* max_pieces, int64_t* list_blocks, int64_t* table_bytes,
                           int64_t* sum_bytes, int64_t* scratch_bytes, int* piece_threads, int* launches);
 
+/* Chapter segmentation: where does a video change subject?  Each listed group (video), walked in time order, is cut into at
+ * most k contiguous runs of frames (chapters) so that the frames of a run point the same way: the optimal contiguous
+ * k-segmentation under the cost below, by a dynamic programme over a table of pair costs.  The timeline counterpart of the
+ * keyframe summary (a thumbnail strip) and of vq_index_cluster (themes across the library).
+ *   For one group g (vq_index_set_groups) with L >= 1 rows, let r_0 .. r_{L-1} be its rows in ascending (position, tie) order,
+ *   positions as vq_index_set_positions gave them, tie(r) = the row number, or the id rank once ranks are set: the order
+ *   vq_index_search_sequence walks.  Parameters k, penalty (fp32), max_len (int64, 0 = none); W = L when max_len = 0, else
+ *   min(L, max_len): the longest run allowed.  The order of the operations is part of the definition:
+ *   1. Prefix sums.  P_0[i] = 0.0, P_{t+1}[i] = P_t[i] + (double)x_{r_t}[i]: ONE fp64 chain per column along the order (not a
+ *      blocked or tree scan).
+ *   2. Cost of the run [a, b), 0 <= a < b <= L, b - a <= W.  u[i] = (float)(P_b[i] - P_a[i]): one fp64 subtraction, rounded to
+ *      fp32.  V = the fp64 chain over i in index order of (double)u[i] * (double)u[i], from 0.0.  cost(a, b) = (double)(b - a) -
+ *      sqrt(V).  (The products of two fp32 values are exact in fp64, so contraction to fma cannot change a bit.)  Its meaning:
+ *      the number of frames times the mean cosine distance of the run's frames to the run's mean direction (for unit rows).
+ *   3. Dynamic programme.  E_0(0) = 0.0.  For c = 1 .. K, K = min(k, L), and b = c .. L: E_c(b) = E_{c-1}(a*) + cost(a*, b), one
+ *      fp64 addition (for c = 1 too), a* = the admissible a with the smallest (E_{c-1}(a) + cost(a, b), a); admissible:
+ *      max(c - 1, b - W) <= a < b and E_{c-1}(a) defined.  E_c(b) is undefined when no a is admissible.
+ *   4. Number of chapters.  F(c) = E_c(L) + (double)c * (double)penalty (the product is exact).  kappa = the smallest c in 1 .. K
+ *      with E_c(L) defined and the smallest F.  No defined E_c(L) (k * W < L): kappa = 0, every slot of the group is empty.
+ *   5. Chapters.  The a* followed back from (kappa, L) give chapter t = [a_t, b_t), t = 0 .. kappa - 1 in time order: first =
+ *      r_{a_t} and last = r_{b_t - 1} (full-index row numbers), len = b_t - a_t, spread = (float)(cost(a_t, b_t) / (double)len),
+ *      show = the row of the chapter with the smallest (1.0f - (float)chain_i((double)x_r[i] * (double)u[i]), tie(r)), u the
+ *      chapter's own u: the keyframe summary's seed rule with the chapter as the video.  Per group count = kappa and mean_spread =
+ *      (float)(E_kappa(L) / (double)L) (+inf when kappa = 0).  Unused slots are -1 / -1 / 0 / +inf / -1.
+ *   Consequences: k = 1 returns the whole video as one chapter; penalty = 0 asks for the best split into at most k parts (more
+ *   parts never cost more, up to rounding); a huge penalty returns one chapter; max_len >= L is the same as none; a group's
+ *   answer does not depend on any other group.  Rows that are not finite are outside the definition: such a call may return
+ *   anything, but it ends (every loop is bounded by the shapes, and every minimum is taken over integer keys).
+ *   groups [n_sel]: labels in host memory; duplicates are allowed, each entry is answered on its own ([n_sel] and [n_sel][k]
+ *   outputs; show_out and mean_spread_out may be NULL).  A label outside [0, n_groups) is VQ_ERR_INVALID; a label that holds no
+ *   row gives empty slots.  Limits, judged before the device is asked for, else VQ_ERR_INVALID naming the argument: n_sel >= 1,
+ *   1 <= k <= 64, penalty >= 0 and not NaN, max_len >= 0.  A listed group with L * W > 2^26 pairs is refused with VQ_ERR_INVALID
+ *   naming the label: the work is quadratic in the run length, so this is a stated bound (8,192 frames without max_len; any
+ *   length with max_len <= 2^26 / L).  Stale or missing labels, positions or id ranks are refused before any work is queued, with
+ *   vq_index_search_sequence's lifetime rules.  An empty index returns every slot empty.
+ *   How it runs (csrc/knn_segment.h): exact only.  The listed groups are taken in list order in batches whose band tables
+ *   (L x W x 8 B per group) stay within 512 MiB, and whose prefix rows ((L + 1) x dim x 8 B) do; per batch four launches: the
+ *   prefix kernel (a workgroup per group, a thread per four columns), the pair-cost kernel (a workgroup per 64 x 64 tile of
+ *   (a, b) pairs inside the band, all groups of the batch in one grid, prefix rows staged through LDS 32 columns at a time, each
+ *   pair's chain owned by one thread) writing cost[b - 1][b - a - 1], the DP kernel (a workgroup per group, E as order-preserving
+ *   keys in LDS up to 4,096 rows and in global memory above, back-pointers [K][L + 1] int32 in scratch, the same workgroup picks
+ *   kappa and walks back) and the show kernel (a workgroup per group and slot; not queued when show_out is NULL).  One more
+ *   launch writes the counters.  The launches depend on the group sizes (known on the host) and the arguments only.  No
+ *   floating-point atomics, no global atomics, no waiting of one workgroup on another.  They are accounted under the existing
+ *   profile class exact_dist_f64chain (VQ_IDX_NCLASS stays 7).
+ *   The _device form takes device results, is asynchronous on the index's stream (once the (position, tie) order is on the
+ *   device, as for vq_index_search_sequence) and reads nothing back.
+ *   vq_index_last_search_stats afterwards: [0] listed groups that got at least one chapter, [1] pairs costed, [2] group batches.
+ *   $VQ_AMD_SEG_COST_BYTES (tests only, read per call) replaces the 512 MiB; $VQ_AMD_SEG_LDS_ROWS (tests only, read per call, at
+ *   most 4,096) lowers the DP's LDS row limit.
+ *   vq_debug_segment_plan (host only, as vq_debug_summary_plan): for listed groups of lengths[0 .. n_sel) rows in list order — the
+ *   batches, the largest batch's table bytes, the DP's LDS row limit and dynamic LDS bytes, global_form = 1 when the longest
+ *   listed group keeps E in global memory, the launches a call with show_out queues, and the pairs it costs. */
+int vq_index_segment_groups(vq_index* idx, const int32_t* groups /*[n_sel]*/, int32_t n_sel, int k, float penalty, int64_t max_len,
+                            int32_t* count_out /*[n_sel]*/, int32_t* first_out /*[n_sel][k]*/, int32_t* last_out /*[n_sel][k]*/,
+                            int32_t* len_out /*[n_sel][k]*/, float* spread_out /*[n_sel][k]*/, int32_t* show_out /*[n_sel][k] or NULL*/,
+                            float* mean_spread_out /*[n_sel] or NULL*/);
+int vq_index_segment_groups_device(vq_index* idx, const int32_t* groups /*[n_sel], host*/, int32_t n_sel, int k, float penalty,
+                                   int64_t max_len, void* d_count_i32, void* d_first_i32, void* d_last_i32, void* d_len_i32,
+                                   void* d_spread_f32, void* d_show_i32 /*or NULL*/, void* d_mean_spread_f32 /*or NULL*/);
+int vq_debug_segment_plan(const int64_t* lengths /*[n_sel]*/, int32_t n_sel, int dim, int k, int64_t max_len, int* batches,
+                          int64_t* table_bytes, int* lds_rows, int64_t* lds_bytes, int* global_form, int* launches, int64_t* pairs);
+
 /* Compound search: the k best rows that match ALL of several prompts — "a dog AND a beach, in the same frame, but NOT at night".
  * Adding the prompt vectors ranks by the SUM of the similarities: a frame that shows one term very well and the other not at all
  * beats a frame that shows both.  Here a frame's WORST required term decides its place.

@@ -154,6 +154,12 @@ SIGNATURES = {
                                           POINTER(c_int32)]),
     "vq_index_summarize_groups_device": (c_int, [c_void_p, POINTER(c_int32), c_int32, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "vq_debug_summary_plan": (c_int, [c_int64, c_int64, c_int, c_int, POINTER(c_int), POINTER(c_int64), POINTER(c_int), POINTER(c_int)]),
+    "vq_index_segment_groups": (c_int, [c_void_p, POINTER(c_int32), c_int32, c_int, c_float, c_int64, POINTER(c_int32), POINTER(c_int32),
+                                        POINTER(c_int32), POINTER(c_int32), POINTER(c_float), POINTER(c_int32), POINTER(c_float)]),
+    "vq_index_segment_groups_device": (c_int, [c_void_p, POINTER(c_int32), c_int32, c_int, c_float, c_int64, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vq_debug_segment_plan": (c_int, [POINTER(c_int64), c_int32, c_int, c_int, c_int64, POINTER(c_int), POINTER(c_int64), POINTER(c_int),
+                                      POINTER(c_int64), POINTER(c_int), POINTER(c_int), POINTER(c_int64)]),
     "vq_index_label_rows": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_float, POINTER(c_int32), POINTER(c_float), c_int,
                                     POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "vq_index_label_rows_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p,

@@ -15,6 +15,7 @@
 #include "knn_diverse.h"
 #include "knn_sequence.h"
 #include "knn_summary.h"
+#include "knn_segment.h"
 #include "knn_label.h"
 #include "knn_compound.h"
 #include "knn_cluster.h"
@@ -150,6 +151,12 @@ struct vq_index {
     IdxBuf<uint64_t> d_sumk;
     IdxBuf<double> d_sumd;
     IdxBuf<int32_t> d_sumout;
+    // chapter segmentation (knn_segment.h): the call's entries, the chapters' cuts and a batch's back-pointers; a batch's prefix
+    // rows and band tables; its global-form E keys; the host form's results
+    IdxBuf<int32_t> d_segw;
+    IdxBuf<double> d_segd;
+    IdxBuf<uint64_t> d_sege;
+    IdxBuf<int32_t> d_segout;
     // zero-shot labelling (knn_label.h): control words {filed rows, flag, largest |p|^2} + the filed-row list + the rows' labels
     // and best distances (ctl [4] | filed [n_pad] | label [n_pad] | best [n_pad]); the exact path's running keys; the tile
     // path's parts; the host form's group results
@@ -1524,6 +1531,107 @@ int summarize_run(vq_index* x, const char* fn, const int32_t* groups, int32_t n_
             hipLaunchKernelGGL(sum_wide_members_kernel, ge, th, 0, x->stream, w, k, rows_out, radius_out, members_out, kap);
         }
         hipLaunchKernelGGL(sum_stats_kernel, dim3(1), dim3(256), 0, x->stream, kap, n_sel, (unsigned long long)(n_sel - nw), (unsigned long long)nw,
+                           x->d_gcounters);
+    }
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+    set_stats(x, STATS_GCOUNTERS);
+    return 0;
+}
+
+// ---- chapter segmentation (knn_segment.h) ----
+SegmentPlan seg_plan_env(const int64_t* lengths, int32_t n_sel, int dim, int k, int64_t max_len, bool show) {
+    return plan_segment(lengths, n_sel, dim, k, max_len, show, seq_env("VQ_AMD_SEG_COST_BYTES"), seq_env("VQ_AMD_SEG_LDS_ROWS"));   // tests only, read per call
+}
+
+// a group whose band table alone would pass the stated bound is refused: the work is quadratic
+int seg_check_pairs(const char* fn, int32_t label, int64_t L, int64_t max_len) {
+    const int64_t W = seg_run_limit(L, max_len);
+    VQ_CHECK(L * W <= SEG_MAX_PAIRS, "%s: group %d holds %lld rows: %lld x %lld (rows x longest run) is more than 2^26 pairs; pass a smaller max_len",
+             fn, (int)label, (long long)L, (long long)L, (long long)W);
+    return 0;
+}
+
+// Everything that can refuse a segmentation before any work is queued.  len [n_sel]: the listed groups' rows.
+int seg_precheck(vq_index* x, const char* fn, const int32_t* groups, int32_t n_sel, int k, int64_t max_len, std::vector<int64_t>* len) {
+    VQ_TRY(check_ranks(x, fn));
+    VQ_TRY(check_labels(x, fn));
+    VQ_TRY(check_positions(x, fn));
+    VQ_CHECK((int64_t)n_sel * k < ((int64_t)1 << 31), "%s: n_sel x k = %lld slots, 2^31 or more", fn, (long long)n_sel * k);
+    len->resize((size_t)n_sel);
+    for (int32_t i = 0; i < n_sel; ++i) {
+        VQ_CHECK(groups[i] >= 0 && groups[i] < x->n_groups, "%s: group %d outside [0, %d)", fn, (int)groups[i], (int)x->n_groups);
+        (*len)[(size_t)i] = (int64_t)x->h_goff[(size_t)groups[i] + 1] - x->h_goff[(size_t)groups[i]];
+        VQ_TRY(seg_check_pairs(fn, groups[i], (*len)[(size_t)i], max_len));
+    }
+    return 0;
+}
+
+// groups [n_sel]: host, checked, with their lengths.  Outputs: device; show / mean may be null.  Asynchronous on the index's stream
+// once the (position, tie) order is on the device.  Per batch of listed groups: prefix rows, band table, DP, show rows.
+int segment_run(vq_index* x, const char* fn, const int32_t* groups, int32_t n_sel, const std::vector<int64_t>& len, int k, float penalty,
+                int64_t max_len, int32_t* count, int32_t* first, int32_t* last, int32_t* lens, float* spread, int32_t* show, float* mean) {
+    const int dim = x->dim;
+    const SegmentPlan p = seg_plan_env(len.data(), n_sel, dim, k, max_len, show != nullptr);
+    VQ_CHECK(p.tiles < ((int64_t)1 << 31) && p.prefix_rows < ((int64_t)1 << 31), "%s: a batch of %lld tiles and %lld prefix rows is too large",
+             fn, (long long)p.tiles, (long long)p.prefix_rows);
+    VQ_TRY(seq_order_prepare(x));
+    // words: the entries of every batch, each batch closed by one more | cuts [n_sel][k][2] | a batch's back-pointers
+    const int64_t n_ent = (int64_t)n_sel + p.batches;
+    const int64_t w_ent = round_up(n_ent * SEG_ENTRY_WORDS, 4), w_cuts = round_up((int64_t)2 * n_sel * k, 4);
+    VQ_TRY(x->d_segw.reserve(w_ent + w_cuts + p.bp_words));
+    VQ_TRY(x->d_segd.reserve(p.prefix_rows * dim + p.table_bytes / 8));
+    if (p.e_words) VQ_TRY(x->d_sege.reserve(p.e_words));
+    VQ_TRY(ensure_gcounters(x));
+    VQ_TRY(set_dyn_lds(x, (const void*)seg_dp_kernel, (size_t)p.lds_bytes));
+    StageSlot* slot;
+    VQ_TRY(stage_slot(x, w_ent, &slot));
+    SegEntry* he = (SegEntry*)(int32_t*)slot->h;
+    int64_t e = 0;
+    int32_t b0 = 0;
+    for (int bi = 0; bi < p.batches; ++bi) {
+        const int32_t end = p.batch_end[(size_t)bi];
+        SegEntry run{};                                                 // the running offsets; closes the batch
+        for (int32_t i = b0; i < end; ++i, ++e) {
+            const int64_t L = len[(size_t)i], W = seg_run_limit(L, max_len);
+            he[e] = run;
+            he[e].group = groups[i]; he[e].L = (int32_t)L; he[e].W = (int32_t)W; he[e].slot = i;
+            he[e].band = L ? seg_band(L, W) : 1;
+            run.toff += L * W; run.bpoff += std::min<int64_t>(k, L) * (L + 1); run.prow += (int32_t)(L + 1);
+            if (L > p.lds_rows) run.eoff += 2 * (L + 1);
+            if (L) run.tile0 += seg_tiles_b(L) * seg_band(L, W);
+        }
+        he[e++] = run;
+        b0 = end;
+    }
+    int32_t* d = x->d_segw;
+    VQ_HIP(hipMemcpyAsync(d, he, (size_t)n_ent * sizeof(SegEntry), hipMemcpyHostToDevice, x->stream));
+    VQ_HIP(hipEventRecord(slot->ev, x->stream));
+    const SegEntry* ent = (const SegEntry*)d;
+    int32_t* cuts = d + w_ent;
+    int32_t* bp = cuts + w_cuts;
+    double* P = x->d_segd;
+    double* tab = P + p.prefix_rows * dim;
+    const int32_t* sorder = x->d_seq;
+    const TieOrder tie = x->tie();
+    {
+        Prof pr(x, I_EXACT_DIST);
+        e = 0; b0 = 0;
+        for (int bi = 0; bi < p.batches; ++bi) {
+            const int32_t end = p.batch_end[(size_t)bi], nb = end - b0;
+            const int32_t tiles = he[e + nb].tile0;
+            const SegEntry* be = ent + e;
+            hipLaunchKernelGGL(seg_prefix_kernel, dim3(nb), dim3((unsigned)round_up(dim / 4, 64)), 0, x->stream, x->rows, dim, x->d_goff, sorder, be, P);
+            if (tiles)
+                hipLaunchKernelGGL(seg_pair_kernel, dim3((unsigned)tiles), dim3(SEG_PAIR_THREADS), 0, x->stream, be, nb, P, dim, tab);
+            hipLaunchKernelGGL(seg_dp_kernel, dim3(nb), dim3(SEG_DP_THREADS), (size_t)p.lds_bytes, x->stream, be, tab, bp, x->d_sege.p, x->d_goff, sorder,
+                               k, penalty, p.lds_rows, (int)(p.lds_bytes / 16), count, first, last, lens, spread, mean, cuts);
+            if (show)
+                hipLaunchKernelGGL(seg_show_kernel, dim3((unsigned)((int64_t)nb * k)), dim3(SEG_SHOW_THREADS), 0, x->stream, x->rows, dim, x->d_goff, sorder,
+                                   be, P, cuts, k, tie, show);
+            e += nb + 1; b0 = end;
+        }
+        hipLaunchKernelGGL(seg_stats_kernel, dim3(1), dim3(256), 0, x->stream, count, n_sel, (unsigned long long)p.pairs, (unsigned long long)p.batches,
                            x->d_gcounters);
     }
     VQ_HIP(hipGetLastError());
@@ -3047,6 +3155,95 @@ int vq_debug_compound_plan(int64_t n, int dim, int m, int k, int mode, int* fp16
              CP_K_MAX);
     const CompoundPlan p = plan_compound(n, dim, m, nullptr, k, mode, true);
     *fp16_path = p.fp16; *streams = p.streams; *rescore_pool = p.pool; *exact_bytes = p.exact_bytes; *eps = p.eps;
+    return 0;
+}
+
+// (the arguments are judged before the library is asked for its device)
+static int check_segment_args(const char* fn, const vq_index* x, const int32_t* groups, int32_t n_sel, int k, float penalty, int64_t max_len,
+                              bool arrays) {
+    VQ_CHECK(n_sel >= 1, "%s: n_sel %d: at least one group must be listed", fn, (int)n_sel);
+    VQ_CHECK(k >= 1 && k <= SEG_MAX_K, "%s: k %d outside [1, %d]", fn, k, SEG_MAX_K);
+    VQ_CHECK(penalty == penalty && penalty >= 0.0f, "%s: penalty must be >= 0 and not NaN", fn);
+    VQ_CHECK(max_len >= 0, "%s: max_len %lld is negative (0: no limit)", fn, (long long)max_len);
+    VQ_TRY(require_init());
+    VQ_CHECK(x && groups && arrays, "%s: bad argument", fn);
+    return 0;
+}
+
+int vq_index_segment_groups_device(vq_index* x, const int32_t* groups, int32_t n_sel, int k, float penalty, int64_t max_len, void* d_count_out,
+                                   void* d_first_out, void* d_last_out, void* d_len_out, void* d_spread_out, void* d_show_out,
+                                   void* d_mean_spread_out) {
+    static const char* fn = "vq_index_segment_groups_device";
+    VQ_TRY(check_segment_args(fn, x, groups, n_sel, k, penalty, max_len, d_count_out && d_first_out && d_last_out && d_len_out && d_spread_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) {
+        const int64_t slots = (int64_t)n_sel * k;
+        fill_no_result(x, (int32_t*)d_first_out, (float*)d_spread_out, slots);
+        fill_no_result(x, (int32_t*)d_last_out, (float*)d_spread_out, slots);
+        if (d_show_out) fill_no_result(x, (int32_t*)d_show_out, (float*)d_spread_out, slots);
+        if (d_mean_spread_out) fill_no_result(x, (int32_t*)d_first_out, (float*)d_mean_spread_out, n_sel);
+        VQ_HIP(hipMemsetAsync(d_len_out, 0, (size_t)slots * 4, x->stream));
+        VQ_HIP(hipMemsetAsync(d_count_out, 0, (size_t)n_sel * 4, x->stream));
+        VQ_HIP(hipGetLastError());
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    std::vector<int64_t> len;
+    VQ_TRY(seg_precheck(x, fn, groups, n_sel, k, max_len, &len));
+    return segment_run(x, fn, groups, n_sel, len, k, penalty, max_len, (int32_t*)d_count_out, (int32_t*)d_first_out, (int32_t*)d_last_out,
+                       (int32_t*)d_len_out, (float*)d_spread_out, (int32_t*)d_show_out, (float*)d_mean_spread_out);
+}
+
+int vq_index_segment_groups(vq_index* x, const int32_t* groups, int32_t n_sel, int k, float penalty, int64_t max_len, int32_t* count_out,
+                            int32_t* first_out, int32_t* last_out, int32_t* len_out, float* spread_out, int32_t* show_out, float* mean_spread_out) {
+    static const char* fn = "vq_index_segment_groups";
+    VQ_TRY(check_segment_args(fn, x, groups, n_sel, k, penalty, max_len, count_out && first_out && last_out && len_out && spread_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t slots = (int64_t)n_sel * k;
+    if (x->size == 0) {
+        host_empty(slots, first_out, last_out, spread_out);
+        std::fill(len_out, len_out + slots, 0);
+        std::fill(count_out, count_out + n_sel, 0);
+        if (show_out) std::fill(show_out, show_out + slots, -1);
+        if (mean_spread_out) std::fill(mean_spread_out, mean_spread_out + n_sel, __builtin_inff());
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    std::vector<int64_t> len;
+    VQ_TRY(seg_precheck(x, fn, groups, n_sel, k, max_len, &len));
+    // count [n_sel] | mean [n_sel] | first | last | len | show | spread [slots] each
+    VQ_TRY(x->d_segout.reserve(2 * (int64_t)n_sel + 5 * slots));
+    int32_t* d_count = x->d_segout; float* d_mean = (float*)(d_count + n_sel);
+    int32_t* d_first = d_count + 2 * (int64_t)n_sel; int32_t* d_last = d_first + slots; int32_t* d_len = d_last + slots; int32_t* d_show = d_len + slots;
+    float* d_spread = (float*)(d_show + slots);
+    VQ_TRY(segment_run(x, fn, groups, n_sel, len, k, penalty, max_len, d_count, d_first, d_last, d_len, d_spread, show_out ? d_show : nullptr,
+                       mean_spread_out ? d_mean : nullptr));
+    auto back = [&](void* dst, const void* src, int64_t words) { return hipMemcpyAsync(dst, src, (size_t)words * 4, hipMemcpyDeviceToHost, x->stream); };
+    VQ_HIP(back(count_out, d_count, n_sel));
+    VQ_HIP(back(first_out, d_first, slots));
+    VQ_HIP(back(last_out, d_last, slots));
+    VQ_HIP(back(len_out, d_len, slots));
+    VQ_HIP(back(spread_out, d_spread, slots));
+    if (show_out) VQ_HIP(back(show_out, d_show, slots));
+    if (mean_spread_out) VQ_HIP(back(mean_spread_out, d_mean, n_sel));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// plan_segment's answer for this process's environment; needs no device
+int vq_debug_segment_plan(const int64_t* lengths, int32_t n_sel, int dim, int k, int64_t max_len, int* batches, int64_t* table_bytes, int* lds_rows,
+                          int64_t* lds_bytes, int* global_form, int* launches, int64_t* pairs) {
+    static const char* fn = "vq_debug_segment_plan";
+    VQ_CHECK(lengths && batches && table_bytes && lds_rows && lds_bytes && global_form && launches && pairs && n_sel >= 1 && dim > 0 &&
+             dim % 4 == 0 && dim <= 4096 && k >= 1 && k <= SEG_MAX_K && max_len >= 0,
+             "%s: takes n_sel >= 1 group lengths, a dim vq_index_create takes, 1 <= k <= %d, max_len >= 0", fn, SEG_MAX_K);
+    for (int32_t i = 0; i < n_sel; ++i) {
+        VQ_CHECK(lengths[i] >= 0 && lengths[i] < ((int64_t)1 << 31), "%s: lengths[%d] = %lld outside [0, 2^31)", fn, (int)i, (long long)lengths[i]);
+        VQ_TRY(seg_check_pairs(fn, i, lengths[i], max_len));
+    }
+    const SegmentPlan p = seg_plan_env(lengths, n_sel, dim, k, max_len, true);
+    *batches = p.batches; *table_bytes = p.table_bytes; *lds_rows = p.lds_rows; *lds_bytes = p.lds_bytes; *global_form = p.global_form;
+    *launches = p.launches; *pairs = p.pairs;
     return 0;
 }
 

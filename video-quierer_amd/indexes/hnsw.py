@@ -987,6 +987,59 @@ class HNSWIndex:
         group the index does not hold, ``[]`` for k <= 0."""
         return self.summarize_groups([group], k, max_radius=max_radius, group_of=group_of)[group]
 
+    # -- chapter segmentation: each group (video) cut into at most k coherent runs of frames -------------------------
+    SEGMENT_MAX_K = 64            # vq_index_segment_groups: chapters per group
+
+    def _segment(self, labels: List[int], k: int, penalty: float, max_len: Optional[int], group_of: GROUP_OF, position_of: POSITION_OF):
+        """labels: dense labels of the host's labels under ``group_of`` (at least one), k >= 1, the index not empty; under the
+        lock.  One device call -> (count [n], first, last, frames, spread, show: each [n][min(k, SEGMENT_MAX_K)])."""
+        pen, cap = float(penalty), 0 if max_len is None else int(max_len)
+        if not pen >= 0:                                          # (NaN too)
+            raise ValueError(f"penalty must be >= 0, got {penalty}")
+        if max_len is not None and cap < 1:
+            raise ValueError(f"max_len must be >= 1 (None: no limit), got {max_len}")
+        self._prepare(np.empty((0, self.dimension), dtype=np.float32), k, given=True, group_of=group_of, positions=True,
+                      position_of=position_of, what="index")
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        kk = min(int(k), self.SEGMENT_MAX_K)
+        count = np.empty(len(lab), dtype=np.int32)
+        first, last, frames, show = (np.empty((len(lab), kk), dtype=np.int32) for _ in range(4))
+        spread = np.empty((len(lab), kk), dtype=np.float32)
+        _lib.check(_lib.load().vq_index_segment_groups(self._h, _lib.i32ptr(lab), len(lab), kk, pen, cap, _lib.i32ptr(count), _lib.i32ptr(first),
+                                                       _lib.i32ptr(last), _lib.i32ptr(frames), _lib.fptr(spread), _lib.i32ptr(show), None))
+        return count, first, last, frames, spread, show
+
+    def segment_groups(self, groups: Optional[Iterable[Hashable]] = None, k: int = 8, *, penalty: float = 0.0, max_len: Optional[int] = None,
+                       group_of: GROUP_OF = None, position_of: POSITION_OF = None) -> Dict[Hashable, List[Dict]]:
+        """Chapters: each listed group (default: every group the index holds), walked by (position, id), cut into at most k
+        contiguous runs of rows that point the same way, from one device call: ``{group: [{'first', 'last', 'frames', 'spread',
+        'show'}]}``, each list in time order.  The cut is the optimal one (a dynamic programme over all contiguous runs) for
+        the cost "rows of the run times their mean cosine distance to the run's mean direction", summed over the runs, plus
+        ``penalty`` per chapter: ``penalty=0`` gives the best split into at most k parts, a larger one fewer chapters.
+        ``first`` / ``last`` are the ids of a chapter's first and last row, ``frames`` its number of rows, ``spread`` that mean
+        distance (float32), ``show`` the id of the row most like the chapter as a whole.  ``max_len`` caps the rows of a
+        chapter (a group that k chapters of that length cannot cover returns ``[]``).  ``group_of`` as ``search_grouped``,
+        ``position_of`` as ``search_distinct``; a key the index does not hold raises ``KeyError`` before any device work; a key
+        named twice is answered once.  At most 64 chapters per group; a group of more than 8,192 rows needs ``max_len``."""
+        with self.lock:
+            gl = self._group_labels(group_of)
+            gl.extend()
+            keys = list(gl.keys) if groups is None else list(dict.fromkeys(groups))
+            labels = [gl.index[key] for key in keys]                 # KeyError: before any device work
+            if k <= 0 or not keys:
+                return {key: [] for key in keys}
+            count, first, last, frames, spread, show = self._segment(labels, k, penalty, max_len, group_of, position_of)
+            to_id = self._id_of()
+            return {key: [{"first": to_id(a), "last": to_id(b), "frames": n, "spread": d, "show": to_id(s)}
+                          for a, b, n, d, s in zip(fa[:c], la[:c], na[:c], da[:c], sa[:c])]
+                    for key, c, fa, la, na, da, sa in zip(keys, count.tolist(), first.tolist(), last.tolist(), frames.tolist(), spread, show.tolist())}
+
+    def segment_group(self, group: Hashable, k: int = 8, *, penalty: float = 0.0, max_len: Optional[int] = None, group_of: GROUP_OF = None,
+                      position_of: POSITION_OF = None) -> List[Dict]:
+        """``segment_groups`` for one group: ``[{'first', 'last', 'frames', 'spread', 'show'}]`` in time order.  ``KeyError`` for a
+        group the index does not hold, ``[]`` for k <= 0."""
+        return self.segment_groups([group], k, penalty=penalty, max_len=max_len, group_of=group_of, position_of=position_of)[group]
+
     # -- zero-shot labelling: which prompt each row shows, what each group (video) is about --------------
     LABEL_MAX_PROMPTS = 4096      # vq_index_label_rows: prompts per call
     LABEL_MAX_TAGS = 16           # ... tags per group

@@ -311,6 +311,21 @@ class SimpleVideoIndex:
                         "videos": [{"video_name": v, "frames": f} for v, f in best]})
         return out
 
+    def video_chapters(self, video_name: str, k: int = 8, penalty: float = 0.0, max_frames: Optional[int] = None) -> List[Dict]:
+        """Where ``video_name`` changes subject: at most k chapters in time order, ``[{'start', 'end', 'frames', 'spread',
+        'poster'}]``.  ``start`` / ``end`` are the timestamps of a chapter's first and last frame, ``frames`` its number of
+        frames, ``spread`` the mean cosine distance of its frames to its mean direction, ``poster`` ``search``'s metadata dict
+        ``{'video_name', 'timestamp', 'frame_id'}`` of the frame most like the chapter as a whole.  ``HNSWIndex.segment_group``
+        on the embeddings as stored: the optimal contiguous split, exact; ``penalty`` per chapter gives fewer chapters,
+        ``max_frames`` caps a chapter's length.  Positions are ``round(timestamp * 1000)`` ms, groups the video names, ties
+        between frames as ``search``.  ``KeyError`` for an unknown video."""
+        if not self.embeddings:
+            raise KeyError(video_name)
+        res = self._device(ranks=True).segment_group(video_name, k, penalty=penalty, max_len=max_frames, group_of=self._group_fn,
+                                                      position_of=self._pos_fn)
+        return [{"start": self.metadata[-r["first"]]["timestamp"], "end": self.metadata[-r["last"]]["timestamp"], "frames": r["frames"],
+                 "spread": float(r["spread"]), "poster": self.metadata[-r["show"]].copy()} for r in res]
+
     def save_to_disk(self, cache_path: Path):
         try:
             with open(cache_path, "wb") as f:
