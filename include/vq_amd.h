@@ -728,6 +728,72 @@ int vq_index_segment_groups_device(vq_index* idx, const int32_t* groups /*[n_sel
 int vq_debug_segment_plan(const int64_t* lengths /*[n_sel]*/, int32_t n_sel, int dim, int k, int64_t max_len, int* batches,
                           int64_t* table_bytes, int* lds_rows, int64_t* lds_bytes, int* global_form, int* launches, int64_t* pairs);
 
+/* Shared-footage search: the k groups (videos) that contain the same footage as a clip, and where — a re-upload, a trailer cut
+ * from a film, an intro that opens every episode, a news clip reused in a compilation.  vq_index_search_set is blind to order
+ * and reports no span; vq_index_search_sequence takes 64 steps, forces one frame per step and dilutes a partial overlap;
+ * vq_index_search_diverse suppresses copies.  This call thresholds the similarity of the WHOLE clip against the WHOLE library
+ * and reads diagonal runs off the bits.
+ *   Inputs.  Queries q_0 .. q_{m-1} in time order, fp32 [m][dim], used as given (the Python layer normalises them as `search`
+ *   does), 1 <= m <= 4096.  max_dist fp32, not NaN (+inf and -inf are allowed).  min_len >= 1, max_miss >= 0, 1 <= k <= 1024.
+ *   mode as in vq_index_search_set.  groups / n_sel / exclude: the filter of vq_index_search_set in host memory, with both of
+ *   its empty-list cases (n_sel = 0, exclude = 1: unfiltered; n_sel = 0, exclude = 0: every slot empty).
+ *   Hit.  d(i, r) = the distance of q_i to row r exactly as vq_index_search reports it: fp32 of the fixed-order fp64 chain.
+ *   hit(i, r) holds iff d(i, r) <= max_dist, compared in fp32: inclusive, and a NaN distance never hits.
+ *   Runs.  For an allowed group g with rows b_0 .. b_{L-1} in ascending (position, tie) order — the order
+ *   vq_index_search_sequence walks — diagonal delta, -(m-1) <= delta <= L-1, is the cells (i, i + delta) with both indices in
+ *   range, taken by ascending i.  The diagonal is cut at every stretch of more than max_miss consecutive non-hits and each piece
+ *   is trimmed to its first and last hit; each non-empty piece is a RUN with s = its first i, span = last i - first i + 1 and
+ *   hits = the hit cells in it.  Runs with hits < min_len are dropped.
+ *   Best run of a group: the run with the smallest (-hits, span, delta, s), all integers.  A group with no run never appears.
+ *   Answer: the first min(k, groups with a run) allowed groups by (-hits, span, label).  Per slot: group, hits, span, q_first =
+ *   s, row_first and row_last = the full-index row numbers of b_{s + delta} and of the last hit cell's row, mean_dist = fp32 of
+ *   (the fp64 chain sum of (double)d(i, b_{i + delta}) over the run's hit cells in ascending i) / (double)hits.  Unused slots are
+ *   -1 / 0 / 0 / -1 / -1 / -1 / +inf.
+ *   Consequences: max_dist = +inf on finite rows makes every cell hit, so the best run of g has hits = span = min(m, L) on the
+ *   smallest delta among the diagonals of that length: delta = min(0, L - m); max_dist = -inf returns nothing; m = 1 with min_len =
+ *   1 returns exactly the allowed groups whose vq_index_search_grouped best distance is <= max_dist, in label order.
+ *   Limits, judged before the device is asked for anything, else VQ_ERR_INVALID naming the argument: the ranges above, and
+ *   m x ceil(n / 32) x 4 B <= 512 MiB for the bit table (m = 4,096 at a million rows: a stated bound, like the segmentation's
+ *   pair bound; a longer clip goes in pieces).  Stale or missing labels, positions or id ranks are refused with
+ *   vq_index_search_sequence's lifetime rules; mode 2 where the tile path does not exist (dim not 256, 512 or 768, rows that are
+ *   not near-unit) is refused too.  An empty index returns every slot empty.
+ *   How it runs (csrc/knn_match.h, DESIGN.md §4 "Shared footage").  The answer is a function of the hit bits alone, so both
+ *   paths fill one bit table [m][ceil(n / 32)] and share everything behind it.  mode 1, exact: per chunk of queries the plain
+ *   search's exact distances [chunk][n] (within 512 MiB) and a kernel that packs d <= max_dist 32 rows to a word.  mode 2, tile
+ *   path: the 256-query x 2,048-row workgroup of the clip search's fp16 pass over the fp16 matrix, whose epilogue classifies
+ *   every score against T = 1 - max_dist: above T + E_i + slack a sure hit, below T - E_i - slack a sure miss (E_i =
+ *   scan_eps_unit(dim) x max|row| x |q_i|, slack 2^-19), otherwise the pair (i, r) is appended to a filed list (64-bit integer
+ *   cursor, 16M pairs); whole bit words leave by plain stores and no [m][n] score table exists; a second kernel decides every
+ *   filed pair by the exact chain and sets its bit by an integer atomicOr.  A query with |q|^2 outside [0.25, 4] (or not finite)
+ *   or a filed list that overflows sets the call's flag to 2 and the exact chain then rewrites the whole table on the device
+ *   (the host form sees such a query before it queues anything and takes the chunked exact path, reporting the same flag).
+ *   mode 0 takes the tile path where it exists from 16,384 rows and 32 clip frames.  Then one thread per diagonal of every
+ *   allowed group walks its bits through the (position, tie) order and the group's best run is kept as one 64-bit integer key
+ *   (a workgroup reduction, then an integer atomicMin per group); a small kernel builds each group's (-hits, span, label) key,
+ *   the clip search's selection takes the k smallest, and one workgroup per winner recomputes its hit cells' distances by the
+ *   chain for mean_dist.  No floating-point atomics, no waiting of one workgroup on another, every loop bounded by the shapes;
+ *   the launches depend on the shapes and the arguments only.  Accounted under the existing profile classes (VQ_IDX_NCLASS
+ *   stays 7): the tile kernel under scan_f16_mfma_top2, the run pass under sequence_dp.
+ *   The _device form takes device queries and results, is asynchronous on the index's stream (once the (position, tie) order is
+ *   on the device, as for vq_index_search_sequence) and reads nothing back.
+ *   vq_index_last_search_stats afterwards: [0] groups with a run, [1] pairs filed (0 on the exact path and for a flagged call),
+ *   [2] the flag (0, or 2 when the exact chain answered a tile-path call).
+ *   $VQ_AMD_MATCH_FILED_CAP (tests only, read per call) lowers the filed list's capacity.
+ *   vq_debug_match_plan (host only, near-unit rows assumed, as vq_debug_segment_plan): the path, the bit table's bytes (above the
+ *   bound: VQ_ERR_INVALID), the exact path's query chunks, the tile path's query tiles, row ranges and workgroups, the filed
+ *   capacity, the bits the run key uses (at most 63), the run pass's workgroups and the kernels a call queues. */
+int vq_index_match_runs(vq_index* idx, const float* queries /*[m][dim]*/, int m, int k, float max_dist, int min_len, int max_miss, int mode,
+                        const int32_t* groups, int32_t n_sel, int exclude,
+                        int32_t* groups_out /*[k]*/, int32_t* hits_out /*[k]*/, int32_t* span_out /*[k]*/, int32_t* q_first_out /*[k]*/,
+                        int32_t* row_first_out /*[k]*/, int32_t* row_last_out /*[k]*/, float* mean_dist_out /*[k]*/);
+int vq_index_match_runs_device(vq_index* idx, const void* d_queries_f32, int m, int k, float max_dist, int min_len, int max_miss, int mode,
+                               const int32_t* groups, int32_t n_sel, int exclude,
+                               void* d_groups_i32, void* d_hits_i32, void* d_span_i32, void* d_q_first_i32, void* d_row_first_i32,
+                               void* d_row_last_i32, void* d_mean_dist_f32);
+int vq_debug_match_plan(int64_t n, int64_t n_groups, int dim, int m, int mode, int* fp16_path, int64_t* bits_bytes, int* exact_chunk,
+                        int* exact_chunks, int* q_tiles, int* ranges, int64_t* tile_grid, int64_t* filed_cap, int* key_bits,
+                        int64_t* run_blocks, int* launches);
+
 /* Compound search: the k best rows that match ALL of several prompts — "a dog AND a beach, in the same frame, but NOT at night".
  * Adding the prompt vectors ranks by the SUM of the similarities: a frame that shows one term very well and the other not at all
  * beats a frame that shows both.  Here a frame's WORST required term decides its place.

@@ -19,6 +19,7 @@
 #include "knn_label.h"
 #include "knn_compound.h"
 #include "knn_cluster.h"
+#include "knn_match.h"
 #include "scan_plan.h"
 #include "host_buffers.h"
 #ifdef VQ_SCAN_EXPERIMENTS      // `make EXPERIMENTS=1`: the two superseded batch mainloops behind VQ_AMD_SCAN=2|4
@@ -179,6 +180,14 @@ struct vq_index {
     // compound search (knn_compound.h): the exact path's term table [m][ld]; the host form's term distances [k][m]
     IdxBuf<float> d_ctab;
     IdxBuf<float> d_cout;
+    // shared-footage search (knn_match.h): the hit-bit table [m][ceil(n / 32)]; the filed (query, row) pairs; control words
+    // (cursor, flag) + the groups' best-run keys [G]; the queries' threshold half-widths [m] + the selection's unused distances
+    // [k]; the host form's results [7][k]
+    IdxBuf<uint32_t> d_mbits;
+    IdxBuf<uint64_t> d_mfiled;
+    IdxBuf<uint64_t> d_mw;
+    IdxBuf<float> d_mqe;
+    IdxBuf<int32_t> d_mout;
     // clip-search scratch (knn_set.h): per-group sums [2][G], candidate list / positions [2][G] + count + flag, |q_i| [m],
     // order keys [G] + the selection's block lists, candidate keys, result staging of the host form
     IdxBuf<double> d_ssum;
@@ -1956,6 +1965,134 @@ int compound_run(vq_index* x, const float* d_terms, int m, const int32_t* clause
     return 0;
 }
 
+// ---- shared-footage search (knn_match.h) ----
+bool match_fp16_ok(const vq_index* x) { return match_fp16_dim(x->dim) && x->size >= 1 && x->near_unit; }
+
+MatchPlan match_plan_env(int64_t n, int64_t n_groups, int dim, int m, int mode, bool near_unit) {
+    return plan_match(n, n_groups, dim, m, mode, near_unit, seq_env("VQ_AMD_MATCH_FILED_CAP"));      // tests only, read per call
+}
+
+// the bit table's stated bound
+int match_check_bits(const char* fn, int m, int64_t n) {
+    const int64_t bytes = (int64_t)m * ((std::max<int64_t>(n, 1) + 31) / 32) * 4;
+    VQ_CHECK(bytes <= MATCH_BITS_BYTES, "%s: m = %d frames against %lld rows need a bit table of %lld bytes; m x ceil(n / 32) x 4 B must stay "
+             "within %lld (send the clip in pieces)", fn, m, (long long)n, (long long)bytes, (long long)MATCH_BITS_BYTES);
+    return 0;
+}
+
+// Everything that can refuse a shared-footage search before any work is queued.
+int match_precheck(vq_index* x, const char* fn, int m, int mode, const FilterLabels& f) {
+    VQ_TRY(match_check_bits(fn, m, x->size));
+    VQ_TRY(seq_precheck(x, fn, f));
+    if (mode != 1) VQ_TRY(refresh_norm_range(x));
+    if (mode == 2) VQ_CHECK(match_fp16_ok(x), "%s: the tile path needs dim 256, 512 or 768 and near-unit rows (0.5 <= |row|^2 <= 2; rows "
+                                              "added with normalize=0 are measured); mode 1 takes any call", fn);
+    return 0;
+}
+
+// the seven result arrays of a call [k] each, device memory
+struct MatchOut { int32_t* group; int32_t* hits; int32_t* span; int32_t* q_first; int32_t* row_first; int32_t* row_last; float* mean; };
+
+// every slot empty
+int match_fill_empty(vq_index* x, int k, const MatchOut& o) {
+    fill_no_result(x, o.group, o.mean, k);
+    hipLaunchKernelGGL(match_score_kernel, dim3(k), dim3(256), 0, x->stream, o.group, nullptr, MatchKey{0, 1}, 1, nullptr, 0, nullptr, x->dim, nullptr,
+                       nullptr, nullptr, o.hits, o.span, o.q_first, o.row_first, o.row_last, o.mean);
+    VQ_HIP(hipGetLastError());
+    set_stats(x, STATS_HOST, 0, 0, 0);
+    return 0;
+}
+
+// d_queries [m][dim] and the results: device memory.  force_exact: the host form found a query outside the fp16 bound's range.
+// Asynchronous on the index's stream once the (position, tie) order is on the device.
+int match_run(vq_index* x, const char* fn, const float* d_queries, int m, int k, float max_dist, int min_len, int max_miss, int mode,
+              bool force_exact, const FilterLabels& f, int exclude, const MatchOut& o) {
+    FilterPlan fp;
+    VQ_TRY(filter_prepare(x, fn, f, exclude, true, &fp));
+    if (!fp.all && fp.m == 0) return match_fill_empty(x, k, o);         // nothing allowed
+    VQ_TRY(seq_order_prepare(x));
+    const uint32_t* allow = fp.all ? nullptr : fp.bits;
+    const int64_t n = x->size, ld = round_up(n, 64);
+    const int G = x->n_groups;
+    const int nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK);
+    const MatchPlan p = match_plan_env(n, G, x->dim, m, mode, x->near_unit);
+    const bool tile = p.fp16 && !force_exact;
+    const int64_t W = p.words;
+    const unsigned long long cap = (unsigned long long)p.filed_cap;
+    const MatchKey key{p.key_m_bits, p.key_d_bits};
+    VQ_TRY(x->d_mbits.reserve((int64_t)m * W));
+    VQ_TRY(x->d_mw.reserve(2 + (int64_t)G));
+    VQ_TRY(x->d_mqe.reserve((int64_t)m + k));
+    VQ_TRY(x->d_sekey.reserve((int64_t)G + (int64_t)nblocks * kl));
+    VQ_TRY(ensure_gcounters(x));
+    MatchCtl* ctl = (MatchCtl*)x->d_mw.p;
+    unsigned long long* gkey = (unsigned long long*)(x->d_mw.p + 2);
+    float* qe = x->d_mqe; float* sel_dist = qe + m;                      // (the selection writes a distance per slot: unused here)
+    uint64_t* ekey = x->d_sekey; uint64_t* partial = ekey + G;
+    uint32_t* bits = x->d_mbits;
+    const int32_t* sorder = x->d_seq;
+    VQ_HIP(hipMemsetAsync(ctl, 0, sizeof(MatchCtl), x->stream));
+    VQ_HIP(hipMemsetAsync(gkey, 0xff, (size_t)G * 8, x->stream));
+    if (!tile) {
+        VQ_TRY(x->d_dist.reserve((int64_t)p.exact_chunk * ld));
+        for (int q0 = 0; q0 < m; q0 += p.exact_chunk) {
+            const int cur = std::min(p.exact_chunk, m - q0);
+            VQ_TRY(exact_dist(x, false, d_queries + (int64_t)q0 * x->dim, cur, ld));       // always the tiled kernel
+            Prof pr(x, I_SELECT);
+            hipLaunchKernelGGL(match_threshold_kernel<true>, dim3(cdiv(n, 256), cur), dim3(256), 0, x->stream, x->d_dist, ld, x->rows, n, x->dim,
+                               nullptr, max_dist, bits + (int64_t)q0 * W, W, nullptr);
+        }
+    } else {
+        const int64_t q_pad = (int64_t)p.q_tiles * SCAN2_QT;
+        VQ_TRY(x->d_q16.reserve(q_pad * x->dim));
+        VQ_TRY(x->d_mfiled.reserve(std::min<int64_t>(p.filed_cap, (int64_t)m * n)));
+        VQ_TRY(set_dyn_lds(x, (const void*)match_tile_kernel, MATCH_LDS_BYTES));
+        const float T = (float)(1.0 - (double)max_dist);
+        {
+            Prof pr(x, I_RESCORE);
+            hipLaunchKernelGGL(match_query_norm_kernel, dim3(m), dim3(64), 0, x->stream, d_queries, x->dim, scan_eps_unit(x->dim) * x->row_norm_max, qe, ctl);
+        }
+        queries_to_f16(x, d_queries, m, q_pad);
+        {
+            Prof pr(x, I_MFMA_SCAN);
+            hipLaunchKernelGGL(match_tile_kernel, dim3((unsigned)p.tile_grid), dim3(G2_THREADS), MATCH_LDS_BYTES, x->stream, x->d_q16, x->rows16, x->dim, n,
+                               p.q_tiles, p.ranges, cdiv(p.ranges, 4), m, T, qe, bits, W, ctl, (unsigned long long*)x->d_mfiled.p, cap);
+        }
+        {
+            Prof pr(x, I_RESCORE);
+            hipLaunchKernelGGL(match_patch_kernel, dim3(grid_for(std::min<int64_t>(p.filed_cap, (int64_t)m * n))), dim3(256), 0, x->stream, x->rows, x->dim,
+                               d_queries, max_dist, ctl, (const unsigned long long*)x->d_mfiled.p, cap, bits, W);
+        }
+        {
+            Prof pr(x, I_EXACT_DIST);                        // the redo: leaves at once unless the flag is 2
+            hipLaunchKernelGGL(match_threshold_kernel<false>, dim3(cdiv(n, 256), m), dim3(256), 0, x->stream, nullptr, 0, x->rows, n, x->dim, d_queries,
+                               max_dist, bits, W, ctl);
+        }
+    }
+    {
+        Prof pr(x, I_SEQ_DP);
+        hipLaunchKernelGGL(match_run_kernel, dim3((unsigned)p.run_blocks), dim3(MATCH_RUN_THREADS), 0, x->stream, bits, W, m, x->d_goff, sorder, G,
+                           p.diagonals, min_len, max_miss, key, allow, gkey);
+    }
+    {
+        Prof pr(x, I_SELECT);
+        hipLaunchKernelGGL(match_final_kernel, dim3(nblocks), dim3(256), 0, x->stream, gkey, G, key, ekey);
+        hipLaunchKernelGGL(set_select_block_kernel, dim3(nblocks), dim3(256), 0, x->stream, ekey, G, kl, partial);
+        hipLaunchKernelGGL(set_select_merge_kernel, dim3(1), dim3(256), 0, x->stream, partial, (int64_t)nblocks * kl, k, o.group, sel_dist, nullptr,
+                           nullptr);
+    }
+    {
+        Prof pr(x, I_EXACT_DIST);
+        hipLaunchKernelGGL(match_score_kernel, dim3(k), dim3(256), 0, x->stream, o.group, gkey, key, m, bits, W, x->rows, x->dim, d_queries, x->d_goff,
+                           sorder, o.hits, o.span, o.q_first, o.row_first, o.row_last, o.mean);
+    }
+    hipLaunchKernelGGL(match_stats_kernel, dim3(1), dim3(256), 0, x->stream, ekey, G, ctl, cap, p.fp16 && force_exact ? 1 : 0, x->d_gcounters);
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+    set_stats(x, STATS_GCOUNTERS);
+    return 0;
+}
+
 // ---- what the search entry points share ----
 // One argument check per shape of call.  arrays: every array the call reads or writes is there.
 int check_batch_args(const char* fn, const vq_index* x, int nq, int k, bool arrays) {
@@ -1999,6 +2136,21 @@ int check_sequence_args(const char* fn, const vq_index* x, int m, int k, int64_t
              (long long)min_gap, (long long)max_gap);
     VQ_TRY(require_init());
     VQ_CHECK(x && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) && arrays, "%s: bad argument", fn);
+    return 0;
+}
+
+// (the arguments are judged before the library is asked for its device)
+int check_match_args(const char* fn, const vq_index* x, int m, int k, float max_dist, int min_len, int max_miss, int mode,
+                     const int32_t* groups, int32_t n_sel, int exclude, bool arrays) {
+    VQ_CHECK(m >= 1 && m <= MATCH_MAX_M, "%s: m %d outside [1, %d]", fn, m, MATCH_MAX_M);
+    VQ_CHECK(k >= 1 && k <= 1024, "%s: k %d outside [1, 1024]", fn, k);
+    VQ_CHECK(max_dist == max_dist, "%s: max_dist is NaN (+inf: every cell hits)", fn);
+    VQ_CHECK(min_len >= 1, "%s: min_len %d is below 1", fn, min_len);
+    VQ_CHECK(max_miss >= 0, "%s: max_miss %d is negative", fn, max_miss);
+    VQ_TRY(check_mode(fn, mode));
+    VQ_CHECK(n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1), "%s: bad filter (n_sel >= 0, exclude 0 or 1)", fn);
+    VQ_TRY(require_init());
+    VQ_CHECK(x && arrays, "%s: bad argument", fn);
     return 0;
 }
 
@@ -3244,6 +3396,73 @@ int vq_debug_segment_plan(const int64_t* lengths, int32_t n_sel, int dim, int k,
     const SegmentPlan p = seg_plan_env(lengths, n_sel, dim, k, max_len, true);
     *batches = p.batches; *table_bytes = p.table_bytes; *lds_rows = p.lds_rows; *lds_bytes = p.lds_bytes; *global_form = p.global_form;
     *launches = p.launches; *pairs = p.pairs;
+    return 0;
+}
+
+int vq_index_match_runs_device(vq_index* x, const void* d_queries, int m, int k, float max_dist, int min_len, int max_miss, int mode,
+                               const int32_t* groups, int32_t n_sel, int exclude, void* d_groups_out, void* d_hits_out, void* d_span_out,
+                               void* d_q_first_out, void* d_row_first_out, void* d_row_last_out, void* d_mean_dist_out) {
+    static const char* fn = "vq_index_match_runs_device";
+    VQ_TRY(check_match_args(fn, x, m, k, max_dist, min_len, max_miss, mode, groups, n_sel, exclude,
+                            d_queries && d_groups_out && d_hits_out && d_span_out && d_q_first_out && d_row_first_out && d_row_last_out && d_mean_dist_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    const MatchOut o{(int32_t*)d_groups_out, (int32_t*)d_hits_out, (int32_t*)d_span_out, (int32_t*)d_q_first_out, (int32_t*)d_row_first_out,
+                     (int32_t*)d_row_last_out, (float*)d_mean_dist_out};
+    if (x->size == 0) return match_fill_empty(x, k, o);
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(match_precheck(x, fn, m, mode, f));
+    return match_run(x, fn, (const float*)d_queries, m, k, max_dist, min_len, max_miss, mode, false, f, exclude, o);
+}
+
+int vq_index_match_runs(vq_index* x, const float* queries, int m, int k, float max_dist, int min_len, int max_miss, int mode,
+                        const int32_t* groups, int32_t n_sel, int exclude, int32_t* groups_out, int32_t* hits_out, int32_t* span_out,
+                        int32_t* q_first_out, int32_t* row_first_out, int32_t* row_last_out, float* mean_dist_out) {
+    static const char* fn = "vq_index_match_runs";
+    VQ_TRY(check_match_args(fn, x, m, k, max_dist, min_len, max_miss, mode, groups, n_sel, exclude,
+                            queries && groups_out && hits_out && span_out && q_first_out && row_first_out && row_last_out && mean_dist_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) {
+        for (int j = 0; j < k; ++j) {
+            groups_out[j] = -1; hits_out[j] = 0; span_out[j] = 0; q_first_out[j] = -1; row_first_out[j] = -1; row_last_out[j] = -1;
+            mean_dist_out[j] = __builtin_inff();
+        }
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(match_precheck(x, fn, m, mode, f));
+    bool in_range = true;                                   // every |q|^2 inside what the fp16 bound covers (the sum as the device takes it
+    for (int i = 0; i < m && in_range; ++i) {               // matters only at the range's very edge, where either path is exact)
+        double s2 = 0.0;
+        for (int c = 0; c < x->dim; ++c) s2 += (double)queries[(size_t)i * x->dim + c] * queries[(size_t)i * x->dim + c];
+        in_range = s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX;
+    }
+    VQ_TRY(x->d_mout.reserve(7 * (int64_t)k));
+    int32_t* d = x->d_mout;
+    const MatchOut o{d, d + k, d + 2 * k, d + 3 * k, d + 4 * k, d + 5 * k, (float*)(d + 6 * k)};
+    VQ_TRY(stage_queries(x, queries, m));
+    VQ_TRY(match_run(x, fn, x->d_q, m, k, max_dist, min_len, max_miss, mode, !in_range, f, exclude, o));
+    void* const host[7] = {groups_out, hits_out, span_out, q_first_out, row_first_out, row_last_out, mean_dist_out};
+    for (int a = 0; a < 7; ++a) VQ_HIP(hipMemcpyAsync(host[a], d + (int64_t)a * k, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// plan_match's answer for near-unit rows and this process's environment; needs no device
+int vq_debug_match_plan(int64_t n, int64_t n_groups, int dim, int m, int mode, int* fp16_path, int64_t* bits_bytes, int* exact_chunk,
+                        int* exact_chunks, int* q_tiles, int* ranges, int64_t* tile_grid, int64_t* filed_cap, int* key_bits,
+                        int64_t* run_blocks, int* launches) {
+    static const char* fn = "vq_debug_match_plan";
+    VQ_CHECK(fp16_path && bits_bytes && exact_chunk && exact_chunks && q_tiles && ranges && tile_grid && filed_cap && key_bits && run_blocks &&
+             launches && n >= 1 && n < ((int64_t)1 << 31) && n_groups >= 1 && n_groups <= n && dim > 0 && dim % 4 == 0 && dim <= 4096 &&
+             m >= 1 && m <= MATCH_MAX_M && mode >= 0 && mode <= 2,
+             "%s: takes 1 <= n_groups <= n < 2^31, a dim vq_index_create takes, 1 <= m <= %d, mode 0, 1 or 2", fn, MATCH_MAX_M);
+    VQ_CHECK(mode != 2 || match_fp16_dim(dim), "%s: the tile path needs dim 256, 512 or 768", fn);
+    VQ_TRY(match_check_bits(fn, m, n));
+    const MatchPlan p = match_plan_env(n, n_groups, dim, m, mode, true);
+    *fp16_path = p.fp16; *bits_bytes = p.bits_bytes; *exact_chunk = p.exact_chunk; *exact_chunks = p.exact_chunks; *q_tiles = p.q_tiles;
+    *ranges = p.ranges; *tile_grid = p.tile_grid; *filed_cap = p.filed_cap; *key_bits = 3 * p.key_m_bits + p.key_d_bits;
+    *run_blocks = p.run_blocks; *launches = p.launches;
     return 0;
 }
 

@@ -1223,6 +1223,97 @@ class HNSWIndex:
         with self.lock:
             return self._search_sequence(steps, k, lo, min(hi, 2 ** 62), flt, group_of, position_of)
 
+    # -- shared footage: the k groups (videos) that reuse a run of a clip's frames, and where -------
+    MATCH_MAX_FRAMES = 4096       # vq_index_match_runs: clip frames per call
+
+    @staticmethod
+    def _match_args(max_distance, min_len, max_miss) -> Tuple[np.float32, int, int]:
+        md = np.float32(max_distance)
+        if md != md:
+            raise ValueError("max_distance is NaN")
+        if int(min_len) < 1 or int(max_miss) < 0:
+            raise ValueError(f"shared runs need min_len >= 1 and max_miss >= 0, got min_len={min_len}, max_miss={max_miss}")
+        return md, int(min_len), min(int(max_miss), 2 ** 31 - 1)
+
+    def _shared_runs(self, frames, k: int, max_dist: np.float32, min_len: int, max_miss: int, flt, group_of, position_of,
+                     given: bool = False) -> List[Dict]:
+        """frames: 1 to MATCH_MAX_FRAMES of them, in time order (``given``: see ``_prepare``).  flt: ``_filter_arg``'s."""
+        ready = self._prepare(frames, k, given=given, group_of=group_of, positions=True, position_of=position_of, flt=flt, what="frame")
+        if ready is None:
+            return []
+        unit, gl, ps, labels, excl = ready
+        m, kk = unit.shape[0], min(int(k), len(gl.keys), 1024)
+        ints = np.empty((6, kk), dtype=np.int32)              # group, hits, span, q_first, row_first, row_last
+        mean = np.empty(kk, dtype=np.float32)
+        _lib.check(_lib.load().vq_index_match_runs(self._h, _lib.fptr(unit), m, kk, max_dist, min_len, max_miss, int(self.search_mode),
+                                                   _lib.i32ptr(labels), len(labels), int(excl), *(_lib.i32ptr(ints[a]) for a in range(6)),
+                                                   _lib.fptr(mean)))
+        keys, pos, to_id = gl.keys, ps.values, self._id_of()
+        out = []
+        for (g, hits, span, q_first, first, last), d in zip(ints.T.tolist(), mean):
+            if g < 0:
+                break
+            out.append({"group": keys[g], "hits": hits, "span": span, "query_first": q_first, "first": to_id(first), "last": to_id(last),
+                        "positions": (int(pos[first]), int(pos[last])), **_scored(d)})
+        return out
+
+    def shared_runs(self, frames: Sequence[np.ndarray], k: int = 5, *, max_distance: float, min_len: int = 3, max_miss: int = 0,
+                    within: Optional[Iterable[Hashable]] = None, exclude: Optional[Iterable[Hashable]] = None,
+                    group_of: GROUP_OF = None, position_of: POSITION_OF = None) -> List[Dict]:
+        """The k GROUPS (videos) that contain the same footage as the clip ``frames`` (in time order), and where:
+        ``[{'group', 'hits', 'span', 'query_first', 'first', 'last', 'positions', 'distance', 'score'}]``.  Clip frame i HITS a
+        stored frame when their distance (the clip normalised as ``search`` does) is at most ``max_distance``.  A video's
+        frames are taken in (position, id) order; a run is a stretch of hits along one diagonal — clip frame i against the
+        video's frame i + offset — that no gap of more than ``max_miss`` misses interrupts, trimmed to its first and last hit,
+        with at least ``min_len`` hits.  Per video its best run (most hits, then the shortest span, the smallest offset, the
+        earliest start): ``hits``, ``span`` (clip frames from its first to its last hit), ``query_first`` (the clip frame it
+        starts at), ``first`` / ``last`` (node ids of the video's frames at its ends) and their ``positions``, ``distance`` the
+        mean distance over the hits, ``score = float32(1) - distance``.  Videos come back by (most hits, shortest span, order
+        in which the groups first appeared in the index); a video without a run does not appear.  ``group_of`` / ``within`` /
+        ``exclude`` as ``search_grouped``, ``position_of`` as ``search_distinct``.  At most 4,096 frames and 1,024 results;
+        the clip times the index's rows is bounded (4,096 frames against a million rows)."""
+        flt = self._filter_arg(within, exclude)
+        if len(frames) == 0:
+            raise ValueError("shared_runs needs at least one frame")
+        if len(frames) > self.MATCH_MAX_FRAMES:
+            raise ValueError(f"a clip holds at most {self.MATCH_MAX_FRAMES} frames, got {len(frames)}")
+        md, lo, miss = self._match_args(max_distance, min_len, max_miss)
+        if self._empty() or k <= 0:
+            return []
+        with self.lock:
+            return self._shared_runs(frames, k, md, lo, miss, flt, group_of, position_of)
+
+    def shared_runs_of(self, group: Hashable, k: int = 5, *, max_distance: float, min_len: int = 3, max_miss: int = 0,
+                       within: Optional[Iterable[Hashable]] = None, group_of: GROUP_OF = None,
+                       position_of: POSITION_OF = None) -> List[Dict]:
+        """"Which videos reuse footage of this one": ``shared_runs`` with the stored rows of ``group``, in (position, id) order,
+        as the clip and ``group`` itself excluded; ``within`` restricts the answer to those groups.  ``KeyError`` for a group
+        the index does not hold, ``ValueError`` for a group of more than 4,096 rows."""
+        if within is not None:
+            within = self._filter_arg(within, None)[0]
+        md, lo, miss = self._match_args(max_distance, min_len, max_miss)
+        with self.lock:
+            rn = self._group_rows(group, group_of)
+            if rn is None:
+                raise KeyError(group)
+            if len(rn) > self.MATCH_MAX_FRAMES:
+                raise ValueError(f"group {group!r} holds {len(rn)} rows; a clip holds at most {self.MATCH_MAX_FRAMES}")
+            if k <= 0:
+                return []
+            flt = ([key for key in within if key != group], False) if within is not None else ([group], True)
+            if not flt[1] and not flt[0]:
+                return []
+            self._positions = _Positions.current(self._positions, frame_of if position_of is None else position_of, self._ids)
+            self._positions.extend()
+            pos, ids = self._positions.values, self._ids
+            try:
+                rn = np.array(sorted(rn.tolist(), key=lambda r: (int(pos[r]), ids[r])), dtype=np.int64)
+            except TypeError:                                 # ids without a total order: rows at one position stay in row order
+                rn = np.array(sorted(rn.tolist(), key=lambda r: int(pos[r])), dtype=np.int64)
+            unit = np.empty((len(rn), self.dimension), dtype=np.float32)
+            _lib.check(_lib.load().vq_index_read_rows(self._h, _lib.i64ptr(rn), len(rn), _lib.fptr(unit)))
+            return self._shared_runs(unit, k, md, lo, miss, flt, group_of, position_of, given=True)
+
     def synchronize(self) -> None:
         _lib.check(_lib.load().vq_index_synchronize(self._h))
 

@@ -232,6 +232,35 @@ class SimpleVideoIndex:
         res = self._device(ranks=True).similar_groups(video_name, k, group_of=self._group_fn, keyframes=keyframes)
         return [{"video_name": r["group"], "score": float(r["score"])} for r in res]
 
+    def find_reuse(self, video_name: str, k: int = 5, min_similarity: float = 0.9, min_seconds: float = 3.0, max_miss: int = 1) -> List[Dict]:
+        """The k indexed videos that contain footage of ``video_name`` (a re-upload, a trailer, a shared intro, a reused news
+        clip), itself excluded, and where: ``[{'video_name', 'frames', 'score', 'start', 'end', 'query_start', 'query_end'}]``,
+        the longest match first.  A frame of ``video_name`` matches a frame of another video when their cosine similarity is
+        at least ``min_similarity``; a match is a stretch in which frame after frame of the one video matches frame after
+        frame of the other, with at most ``max_miss`` consecutive frames in between that do not (``HNSWIndex.shared_runs_of``
+        on the embeddings as stored: exact).  ``frames`` is the number of matching frames, ``score`` their mean similarity,
+        ``start`` / ``end`` the timestamps of the match in the found video, ``query_start`` / ``query_end`` in ``video_name``.
+        A match needs at least ``min_seconds`` of ``video_name``'s own frame interval worth of matching frames (at least one).
+        Frames are taken in timestamp order (``round(timestamp * 1000)`` ms), ties between frames as ``search``.  ``KeyError``
+        for an unknown video, ``ValueError`` for a video of more than 4,096 frames."""
+        if not min_similarity <= 1:                               # (NaN too)
+            raise ValueError(f"min_similarity must be <= 1, got {min_similarity}")
+        if min_seconds < 0 or int(max_miss) < 0:
+            raise ValueError(f"min_seconds and max_miss must be >= 0, got {min_seconds}, {max_miss}")
+        stamps = sorted(md["timestamp"] for md in self.metadata if md.get("video_name") == video_name)
+        if not stamps:
+            raise KeyError(video_name)
+        interval = (stamps[-1] - stamps[0]) / (len(stamps) - 1) if len(stamps) > 1 and stamps[-1] > stamps[0] else 1.0
+        min_len = max(1, int(math.ceil(min_seconds / interval - 1e-9)))
+        res = self._device(ranks=True).shared_runs_of(video_name, k, max_distance=np.float32(1) - np.float32(min_similarity), min_len=min_len,
+                                                      max_miss=max_miss, group_of=self._group_fn, position_of=self._pos_fn)
+        out = []
+        for r in res:
+            first, last = self.metadata[-r["first"]], self.metadata[-r["last"]]
+            out.append({"video_name": r["group"], "frames": r["hits"], "score": float(r["score"]), "start": first["timestamp"],
+                        "end": last["timestamp"], "query_start": stamps[r["query_first"]], "query_end": stamps[r["query_first"] + r["span"] - 1]})
+        return out
+
     def video_summary(self, video_name: str, k: int = 5, max_radius: Optional[float] = None, chronological: bool = False) -> List[Dict]:
         """The k frames that show what is in ``video_name`` (a poster frame and a thumbnail strip): ``search``'s metadata dicts
         ``{'video_name', 'timestamp', 'frame_id'}`` plus ``'rank'`` (selection order: rank 0 is the frame most like the video as
