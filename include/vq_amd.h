@@ -493,6 +493,70 @@ int vq_index_search_sequence_device(vq_index* idx, const void* d_steps_f32, int 
 int vq_debug_sequence_plan(int64_t n, int64_t largest_group, int m, int k, int* step_chunks, int* lds_rows, int* groups_global_form,
                            int64_t* lds_bytes, int* chain_table, int* chain_slices);
 
+/* Span search: per query, the k groups (videos) with the best TIME SPAN — "where in the video does X happen, from when to
+ * when?".  Every other search answers with frames or whole videos; a retrieved moment is a start and an end.
+ *   Queries q_0 .. q_{nq-1} [nq][dim], used as given, 1 <= nq <= 64.  max_dist tau (fp32; NaN is VQ_ERR_INVALID).  max_gap and
+ *   max_span: int64 in position units (vq_index_set_positions), both >= 0 (negative: VQ_ERR_INVALID); values >= 2^32 behave as
+ *   2^32 — positions are 32-bit, so that means "no limit".  1 <= k <= 1024.
+ *   Gain of a row: d(i, r) = the distance of q_i to row r exactly as vq_index_search reports it (fp32 of the fixed-order fp64
+ *   chain); tie(r) = the row number, or the id rank once ranks are set.  w(i, r) = (int64) rint(((double)tau - (double)d(i, r))
+ *   * 2^24), rounded to nearest, ties to even, then kept within +-2^31 (a NaN distance takes -2^31).  The fp64 subtraction of
+ *   two fp32 values and the scaling by 2^24 are exact, so for distances and tau of ordinary size |w| <= 2^27, and every sum below
+ *   is exact in int64.  Integer gains are the point: sums of integers are associative, so a parallel scan in any order gives
+ *   the bits of the sequential walk.
+ *   Span: s_0 .. s_{L-1} are the rows of group g in (position, tie) order.  A span is an index range [a, b], 0 <= a <= b < L,
+ *   with pos(s_{j+1}) - pos(s_j) <= max_gap for every a <= j < b and pos(s_b) - pos(s_a) <= max_span (differences in 64-bit).
+ *   Its mass S(a, b) = the sum of w(i, s_j) over j in a..b.  The group's span for query i is the admissible span with S > 0 that
+ *   comes first under: largest S; then shortest b - a + 1; then smallest a.  A group with no admissible span of positive mass
+ *   has no result for that query and never appears.  The peak is the row of the span with the smallest (d(i, r), tie(r)).
+ *   Result per query: D(g) = fp32(-(double)S * 2^-24); the first min(k, allowed groups with a span) groups by (D, label)
+ *   ascending.  groups_out [nq][k] int32, dist_out [nq][k] fp32 (D), mass_out [nq][k] int64 or NULL, len_out [nq][k] int32 (the
+ *   rows in the span) or NULL, rows_out [nq][k][3] int32 (full-index row numbers of the start, the end and the peak) or NULL.
+ *   Unused slots hold -1 / +inf / 0 / 0 / -1.
+ *   groups / n_sel / exclude: the host-memory filter of vq_index_search_sequence, with the same two empty-list cases.  Stale or
+ *   missing labels, positions or id ranks are refused before any work is queued, as the sequence search refuses them.
+ *   Consequences: a group's span does not depend on other groups or on other queries of the call.  max_span = 0 with distinct
+ *   positions inside every group: every span is one row, and the groups, their order and their peak rows are those of
+ *   vq_index_search_grouped restricted to groups whose best distance is below tau (S = w of that row).  tau so large that every
+ *   gain is positive, both limits unlimited: every allowed group's span is all of its rows and S the plain sum.  tau below
+ *   every distance: every slot is empty.  Rows whose d equals tau exactly have zero gain and never sit at an end of a returned
+ *   span.
+ *   How it runs (csrc/knn_span.h): exact only, no mode.  Per chunk of queries the plain search's exact distances [chunk][n]
+ *   (chunks keep them within 512 MiB), then one workgroup per (allowed group, query) walks the group's rows in the sequence
+ *   search's (position, tie) order (built by the first sequence or span search after the labels, the positions or the id ranks
+ *   changed; that one call waits for the stream once).  One pass over 256-row tiles builds the exclusive int64 prefix sums
+ *   P[0..L] of the gains, for every end b the first admissible start lo(b) (the larger of a max-scan over the indices behind a
+ *   gap above max_gap and a binary search over the sorted positions for max_span) and the prefix minimum of P.  The best start
+ *   for b is the index in [lo(b), b] with the smallest P, ties to the largest index: the prefix minimum where lo(b) = 0,
+ *   otherwise a range minimum that reads at most 126 + L / 64 entries (64-row block minima, built only when some range needs
+ *   them).  The candidates (P[b+1] - P[a(b)], length, a(b)) are reduced over b under the order above.  Groups of at most
+ *   4,096 rows keep the arrays in LDS (20 B per row); longer groups run the same arithmetic over global arrays (20 B per row
+ *   of the index, only then) with one more level of minima (at most 252 + L / 4096 reads), one workgroup per group that takes
+ *   the chunk's queries one after the other.  Each (query, group) files its (D, label) key and (a, b); the clip search's
+ *   selection takes the k smallest per query; one workgroup per winner then sums the span's gains again (integers: the same
+ *   mass) and finds the peak.  No floating-point arithmetic behind the gain, no global atomics, workgroup barriers only; the
+ *   launches queued depend on the shapes only.  Accounted under the existing profile classes (the span kernels under
+ *   sequence_dp; VQ_IDX_NCLASS stays 7).
+ *   The _device form takes device queries and results, is asynchronous on the index's stream and reads nothing back.
+ *   vq_index_last_search_stats afterwards: [0] the (query, group) pairs that hold a span, [1] the allowed groups run by the
+ *   global form, [2] the query chunks.
+ *   $VQ_AMD_SPAN_LDS_ROWS (the LDS form's row limit, at most 4,096) and $VQ_AMD_SPAN_DIST_BYTES (the distance budget): tests
+ *   only, read per call.
+ *   vq_debug_span_plan (host only, as vq_debug_sequence_plan): for n rows in n_groups groups whose longest holds largest_group
+ *   rows and nq queries — the query chunks, the LDS form's row limit and the dynamic LDS bytes of a group of that many rows
+ *   (capped by largest_group), groups_global_form = 1 when the longest group (so at least one) takes the global form, and the
+ *   bytes of the global form's scratch (0 without it). */
+int vq_index_search_spans(vq_index* idx, const float* queries /*[nq][dim]*/, int nq, int k, float max_dist, int64_t max_gap,
+                          int64_t max_span, const int32_t* groups, int32_t n_sel, int exclude,
+                          int32_t* groups_out /*[nq][k]*/, float* dist_out /*[nq][k]*/, int64_t* mass_out /*[nq][k] or NULL*/,
+                          int32_t* len_out /*[nq][k] or NULL*/, int32_t* rows_out /*[nq][k][3] or NULL*/);
+int vq_index_search_spans_device(vq_index* idx, const void* d_queries_f32, int nq, int k, float max_dist, int64_t max_gap,
+                                 int64_t max_span, const int32_t* groups, int32_t n_sel, int exclude,
+                                 void* d_groups_i32, void* d_dist_f32, void* d_mass_i64 /*or NULL*/, void* d_len_i32 /*or NULL*/,
+                                 void* d_rows_i32 /*or NULL*/);
+int vq_debug_span_plan(int64_t n, int64_t n_groups, int64_t largest_group, int nq, int* query_chunks, int* lds_rows,
+                       int64_t* lds_bytes, int* groups_global_form, int64_t* scratch_bytes);
+
 /* Keyframe summary: the k most representative rows of each listed group (video) — the poster frame and thumbnail strip of a
  * video, the few frames that stand in for a long one (as the query set of vq_index_search_set, say).  An iterative
  * farthest-point (greedy k-centre) pass per group: its covering radius is within a factor 2 of the best possible for every k,

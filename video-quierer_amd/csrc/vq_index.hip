@@ -14,6 +14,7 @@
 #include "knn_distinct.h"
 #include "knn_diverse.h"
 #include "knn_sequence.h"
+#include "knn_span.h"
 #include "knn_summary.h"
 #include "knn_segment.h"
 #include "knn_label.h"
@@ -146,6 +147,11 @@ struct vq_index {
     IdxBuf<int32_t> d_seqw;
     IdxBuf<int32_t> d_seqbp;
     IdxBuf<int32_t> d_seqout;
+    // span search (knn_span.h): words (each chunk's spans (a, b) [chunk][G][2] | the global form's lo | pm | minima [3][n]), the
+    // global form's prefix sums [n + G], the host form's results (masses first: 8-byte aligned)
+    IdxBuf<int32_t> d_spanw;
+    IdxBuf<int64_t> d_spanp;
+    IdxBuf<int64_t> d_spanout;
     // keyframe summary (knn_summary.h): the call's lists, keyframe counts and the wide form's per-row / per-block words; the
     // blocks' packed maxima; the mean's block sums and the widened mean directions; the host form's results
     IdxBuf<int32_t> d_sumw;
@@ -1448,6 +1454,99 @@ int search_sequence_run(vq_index* x, const char* fn, const float* d_steps, int m
     return 0;
 }
 
+// ---- span search (knn_span.h) ----
+// tests only, read per call: the LDS form's row limit and the distance budget in bytes
+SpanPlan span_plan_env(int64_t n, int64_t n_groups, int64_t largest_group, int nq) {
+    return plan_spans(n, n_groups, largest_group, nq, seq_env("VQ_AMD_SPAN_LDS_ROWS"), seq_env("VQ_AMD_SPAN_DIST_BYTES"));
+}
+
+// the optional outputs of a span search: device memory, each [nq][k] ([nq][k][3] for rows) or null
+struct SpanOut { int64_t* mass; int32_t* len; int32_t* rows; };
+
+// a device form's answer with no span in any slot
+int span_fill_empty(vq_index* x, int64_t count, int32_t* g_out, float* d_out, const SpanOut& o) {
+    VQ_TRY(fill_empty(x, count, g_out, nullptr, d_out));
+    if (o.mass) VQ_HIP(hipMemsetAsync(o.mass, 0, (size_t)count * 8, x->stream));
+    if (o.len) VQ_HIP(hipMemsetAsync(o.len, 0, (size_t)count * 4, x->stream));
+    if (o.rows) VQ_HIP(hipMemsetAsync(o.rows, 0xff, (size_t)count * 12, x->stream));
+    return 0;
+}
+
+// d_queries [nq][dim], g_out / d_out [nq][k], o: all device memory.  Asynchronous on the index's stream once the (position, tie)
+// order is on the device.
+int search_spans_run(vq_index* x, const char* fn, const float* d_queries, int nq, int k, float tau, int64_t max_gap, int64_t max_span,
+                     const FilterLabels& f, int exclude, int32_t* g_out, float* d_out, const SpanOut& o) {
+    FilterPlan fp;
+    VQ_TRY(filter_prepare(x, fn, f, exclude, true, &fp));
+    if (!fp.all && fp.m == 0) {                             // nothing allowed: every slot empty
+        VQ_TRY(span_fill_empty(x, (int64_t)nq * k, g_out, d_out, o));
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    VQ_TRY(seq_order_prepare(x));
+    const uint32_t* allow = fp.all ? nullptr : fp.bits;
+    const int64_t n = x->size, ld = round_up(n, 64);
+    const int G = x->n_groups;
+    const int nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK);
+    const SpanPlan p = span_plan_env(n, G, x->seq_largest, nq);
+    // positions are 32-bit: a limit of 2^32 or more behaves as 2^32 ("none"), and the differences stay far inside 64 bits
+    const int64_t cap = (int64_t)1 << 32;
+    max_gap = std::min(max_gap, cap); max_span = std::min(max_span, cap);
+    // the allowed groups the global form runs (the host mirror of goff and the sorted filter list)
+    int64_t global_groups = 0;
+    if (p.global_form) {
+        size_t si = 0;
+        for (int32_t g = 0; g < G; ++g) {
+            while (si < f.sel.size() && f.sel[si] < g) ++si;
+            const bool listed = si < f.sel.size() && f.sel[si] == g;
+            if ((exclude ? !listed : listed) && x->h_goff[(size_t)g + 1] - x->h_goff[(size_t)g] > p.lds_rows) ++global_groups;
+        }
+    }
+    const int64_t pairs = (int64_t)p.chunk_queries * G;
+    VQ_TRY(x->d_dist.reserve((int64_t)p.chunk_queries * ld));
+    VQ_TRY(x->d_sekey.reserve(pairs + (int64_t)nblocks * kl));
+    VQ_TRY(x->d_spanw.reserve(2 * pairs + (p.global_form ? 3 * n : 0)));
+    if (p.global_form) VQ_TRY(x->d_spanp.reserve(n + G));
+    VQ_TRY(ensure_gcounters(x));
+    VQ_TRY(set_dyn_lds(x, (const void*)span_lds_kernel, (size_t)p.lds_bytes));
+    const int32_t* sorder = x->d_seq; const int32_t* spos = sorder + n; const int32_t* stie = spos + n;
+    uint64_t* ekey = x->d_sekey; uint64_t* partial = ekey + pairs;
+    int32_t* ab = x->d_spanw; int32_t* work = ab + 2 * pairs;
+    const bool finish = o.mass || o.len || o.rows;
+    for (int q0 = 0; q0 < nq; q0 += p.chunk_queries) {
+        const int cur = std::min(p.chunk_queries, nq - q0);
+        const int64_t at = (int64_t)q0 * k;
+        VQ_TRY(exact_dist(x, false, d_queries + (int64_t)q0 * x->dim, cur, ld));       // always the tiled kernel
+        {
+            Prof pr(x, I_SEQ_DP);
+            hipLaunchKernelGGL(span_lds_kernel, dim3(G, cur), dim3(SPAN_THREADS), (size_t)p.lds_bytes, x->stream, x->d_dist, ld, x->d_goff, sorder,
+                               spos, p.lds_rows, p.lds_alloc_rows, tau, max_gap, max_span, G, allow, ekey, ab);
+            if (p.global_form)
+                hipLaunchKernelGGL(span_global_kernel, dim3(G), dim3(SPAN_THREADS), 0, x->stream, x->d_dist, ld, cur, x->d_goff, sorder, spos,
+                                   p.lds_rows, tau, max_gap, max_span, G, allow, x->d_spanp.p, work, n, ekey, ab);
+        }
+        {
+            Prof pr(x, I_SELECT);
+            for (int q = 0; q < cur; ++q) {
+                hipLaunchKernelGGL(set_select_block_kernel, dim3(nblocks), dim3(256), 0, x->stream, ekey + (int64_t)q * G, G, kl, partial);
+                hipLaunchKernelGGL(set_select_merge_kernel, dim3(1), dim3(256), 0, x->stream, partial, (int64_t)nblocks * kl, k,
+                                   g_out + at + (int64_t)q * k, d_out + at + (int64_t)q * k, nullptr, nullptr);
+            }
+            hipLaunchKernelGGL(span_stats_kernel, dim3(1), dim3(256), 0, x->stream, ekey, (int64_t)cur * G, q0 == 0 ? 1 : 0,
+                               (unsigned long long)global_groups, (unsigned long long)p.query_chunks, x->d_gcounters);
+        }
+        if (finish) {
+            Prof pr(x, I_SEQ_DP);
+            hipLaunchKernelGGL(span_finish_kernel, dim3(k, cur), dim3(SPAN_THREADS), 0, x->stream, x->d_dist, ld, g_out + at, k, x->d_goff, sorder,
+                               stie, tau, G, ab, o.mass ? o.mass + at : nullptr, o.len ? o.len + at : nullptr, o.rows ? o.rows + 3 * at : nullptr);
+        }
+    }
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+    set_stats(x, STATS_GCOUNTERS);
+    return 0;
+}
+
 // ---- keyframe summary (knn_summary.h) ----
 SummaryPlan sum_plan_env(int64_t largest_group, int dim, int k) {
     return plan_summary(largest_group, dim, k, seq_env("VQ_AMD_SUM_LDS_ROWS"));      // tests only, read per call
@@ -2136,6 +2235,20 @@ int check_sequence_args(const char* fn, const vq_index* x, int m, int k, int64_t
              (long long)min_gap, (long long)max_gap);
     VQ_TRY(require_init());
     VQ_CHECK(x && n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1) && arrays, "%s: bad argument", fn);
+    return 0;
+}
+
+// (the arguments are judged before the library is asked for its device)
+int check_span_args(const char* fn, const vq_index* x, int nq, int k, float max_dist, int64_t max_gap, int64_t max_span,
+                    const int32_t* groups, int32_t n_sel, int exclude, bool arrays) {
+    VQ_CHECK(nq >= 1 && nq <= SPAN_MAX_Q, "%s: nq %d outside [1, %d]", fn, nq, SPAN_MAX_Q);
+    VQ_CHECK(k >= 1 && k <= 1024, "%s: k %d outside [1, 1024]", fn, k);
+    VQ_CHECK(max_dist == max_dist, "%s: max_dist is NaN", fn);
+    VQ_CHECK(max_gap >= 0 && max_span >= 0, "%s: max_gap %lld or max_span %lld is negative", fn, (long long)max_gap, (long long)max_span);
+    VQ_CHECK(n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1), "%s: bad filter (n_sel >= 0, exclude 0 or 1)", fn);
+    VQ_CHECK(arrays, "%s: a required array is null", fn);
+    VQ_TRY(require_init());
+    VQ_CHECK(x, "%s: bad argument", fn);
     return 0;
 }
 
@@ -2991,6 +3104,68 @@ int vq_index_search_sequence(vq_index* x, const float* steps, int m, int k, int6
     VQ_HIP(hipMemcpyAsync(dist_out, d_d, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
     if (chain_rows) VQ_HIP(hipMemcpyAsync(chain_rows, d_c, (size_t)nc * 4, hipMemcpyDeviceToHost, x->stream));
     VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+int vq_index_search_spans_device(vq_index* x, const void* d_queries, int nq, int k, float max_dist, int64_t max_gap, int64_t max_span,
+                                 const int32_t* groups, int32_t n_sel, int exclude, void* d_groups_out, void* d_dist_out, void* d_mass_out,
+                                 void* d_len_out, void* d_rows_out) {
+    static const char* fn = "vq_index_search_spans_device";
+    VQ_TRY(check_span_args(fn, x, nq, k, max_dist, max_gap, max_span, groups, n_sel, exclude, d_queries && d_groups_out && d_dist_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    const SpanOut o{(int64_t*)d_mass_out, (int32_t*)d_len_out, (int32_t*)d_rows_out};
+    if (x->size == 0) {
+        VQ_TRY(span_fill_empty(x, (int64_t)nq * k, (int32_t*)d_groups_out, (float*)d_dist_out, o));
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(seq_precheck(x, fn, f));
+    return search_spans_run(x, fn, (const float*)d_queries, nq, k, max_dist, max_gap, max_span, f, exclude, (int32_t*)d_groups_out,
+                            (float*)d_dist_out, o);
+}
+
+int vq_index_search_spans(vq_index* x, const float* queries, int nq, int k, float max_dist, int64_t max_gap, int64_t max_span,
+                          const int32_t* groups, int32_t n_sel, int exclude, int32_t* groups_out, float* dist_out, int64_t* mass_out,
+                          int32_t* len_out, int32_t* rows_out) {
+    static const char* fn = "vq_index_search_spans";
+    VQ_TRY(check_span_args(fn, x, nq, k, max_dist, max_gap, max_span, groups, n_sel, exclude, queries && groups_out && dist_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    if (x->size == 0) {
+        host_empty(count, groups_out, nullptr, dist_out);
+        if (mass_out) std::fill(mass_out, mass_out + count, (int64_t)0);
+        if (len_out) std::fill(len_out, len_out + count, 0);
+        if (rows_out) std::fill(rows_out, rows_out + 3 * count, -1);
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(seq_precheck(x, fn, f));
+    VQ_TRY(x->d_spanout.reserve(4 * count));                    // masses [count] int64 | groups | distances | lengths | rows [3] (int32)
+    int64_t* d_m = x->d_spanout; int32_t* d_g = (int32_t*)(d_m + count); float* d_d = (float*)(d_g + count);
+    int32_t* d_l = d_g + 2 * count; int32_t* d_r = d_g + 3 * count;
+    const SpanOut o{mass_out ? d_m : nullptr, len_out ? d_l : nullptr, rows_out ? d_r : nullptr};
+    VQ_TRY(stage_queries(x, queries, nq));
+    VQ_TRY(search_spans_run(x, fn, x->d_q, nq, k, max_dist, max_gap, max_span, f, exclude, d_g, d_d, o));
+    VQ_HIP(hipMemcpyAsync(groups_out, d_g, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(dist_out, d_d, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    if (mass_out) VQ_HIP(hipMemcpyAsync(mass_out, d_m, (size_t)count * 8, hipMemcpyDeviceToHost, x->stream));
+    if (len_out) VQ_HIP(hipMemcpyAsync(len_out, d_l, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    if (rows_out) VQ_HIP(hipMemcpyAsync(rows_out, d_r, (size_t)count * 12, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// plan_spans' answer for this process's environment; needs no device
+int vq_debug_span_plan(int64_t n, int64_t n_groups, int64_t largest_group, int nq, int* query_chunks, int* lds_rows, int64_t* lds_bytes,
+                       int* groups_global_form, int64_t* scratch_bytes) {
+    VQ_CHECK(query_chunks && lds_rows && lds_bytes && groups_global_form && scratch_bytes && n >= 1 && n < ((int64_t)1 << 31) &&
+             n_groups >= 1 && n_groups <= n && largest_group >= 1 && largest_group <= n && nq >= 1 && nq <= SPAN_MAX_Q,
+             "vq_debug_span_plan: takes 1 <= largest_group <= n < 2^31, 1 <= n_groups <= n, 1 <= nq <= %d", SPAN_MAX_Q);
+    const SpanPlan p = span_plan_env(n, n_groups, largest_group, nq);
+    *query_chunks = p.query_chunks; *lds_rows = p.lds_rows; *lds_bytes = p.lds_bytes; *groups_global_form = p.global_form;
+    *scratch_bytes = p.scratch_bytes;
     return 0;
 }
 

@@ -1223,8 +1223,90 @@ class HNSWIndex:
         with self.lock:
             return self._search_sequence(steps, k, lo, min(hi, 2 ** 62), flt, group_of, position_of)
 
+    # -- span query: the k groups (videos) with the best time span for a query, from where to where ----
+    SPAN_MAX_QUERIES = 64         # vq_index_search_spans: queries per call
+    SPAN_NO_LIMIT = 2 ** 40       # what None means for max_gap / max_span (positions are 32-bit)
+
+    @staticmethod
+    def _span_args(max_distance, max_gap, max_span) -> Tuple[np.float32, int, int]:
+        tau = np.float32(max_distance)
+        if tau != tau:
+            raise ValueError("max_distance is NaN")
+        gap = HNSWIndex.SPAN_NO_LIMIT if max_gap is None else int(max_gap)
+        span = HNSWIndex.SPAN_NO_LIMIT if max_span is None else int(max_span)
+        if gap < 0 or span < 0:
+            raise ValueError(f"max_gap and max_span must be >= 0 (None: no limit), got max_gap={max_gap}, max_span={max_span}")
+        return tau, min(gap, 2 ** 62), min(span, 2 ** 62)
+
+    def _search_spans(self, queries, k: int, tau: np.float32, max_gap: int, max_span: int, flt, group_of, position_of,
+                      given: bool = False) -> List[List[Dict]]:
+        """queries: 1 to SPAN_MAX_QUERIES of them (``given``: see ``_prepare``).  flt: ``_filter_arg``'s.  tau and limits: checked."""
+        ready = self._prepare(queries, k, given=given, group_of=group_of, positions=True, position_of=position_of, flt=flt)
+        if ready is None:
+            return [[] for _ in queries]
+        unit, gl, ps, labels, excl = ready
+        nq, kk = unit.shape[0], min(int(k), len(gl.keys), 1024)
+        groups = np.empty((nq, kk), dtype=np.int32)
+        dist = np.empty((nq, kk), dtype=np.float32)
+        mass = np.empty((nq, kk), dtype=np.int64)
+        length = np.empty((nq, kk), dtype=np.int32)
+        rows = np.empty((nq, kk, 3), dtype=np.int32)
+        _lib.check(_lib.load().vq_index_search_spans(self._h, _lib.fptr(unit), nq, kk, float(tau), max_gap, max_span, _lib.i32ptr(labels),
+                                                     len(labels), int(excl), _lib.i32ptr(groups), _lib.fptr(dist),
+                                                     mass.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _lib.i32ptr(length),
+                                                     _lib.i32ptr(rows)))
+        keys, pos, to_id = gl.keys, ps.values, self._id_of()
+        out = []
+        for gq, mq, lq, rq in zip(groups.tolist(), mass.tolist(), length.tolist(), rows.tolist()):
+            res = []
+            for g, s, n, (a, b, p) in zip(gq, mq, lq, rq):
+                if g < 0:
+                    break
+                m = s * 2.0 ** -24                              # (exact: |s| < 2^53)
+                res.append({"group": keys[g], "mass": m, "frames": n, "start_id": to_id(a), "end_id": to_id(b), "peak_id": to_id(p),
+                            "start": int(pos[a]), "end": int(pos[b]), "score": 1.0 - (float(tau) - m / n)})
+            out.append(res)
+        return out
+
+    def search_spans(self, query: np.ndarray, k: int = 5, *, max_distance: float, max_gap: Optional[int] = None,
+                     max_span: Optional[int] = None, within: Optional[Iterable[Hashable]] = None,
+                     exclude: Optional[Iterable[Hashable]] = None, group_of: GROUP_OF = None,
+                     position_of: POSITION_OF = None) -> List[Dict]:
+        """The k GROUPS (videos) with the best TIME SPAN for one query — "where does it happen, from when to when":
+        ``[{'group', 'mass', 'frames', 'start_id', 'end_id', 'peak_id', 'start', 'end', 'score'}]``.  Every row gains
+        ``max_distance - distance`` (the query normalised as ``search`` does; the gain is kept as an integer multiple of
+        2^-24), so rows closer than ``max_distance`` add to a span and rows farther away cost it.  A span is a run of
+        consecutive rows of one group in position order in which neighbours lie at most ``max_gap`` positions apart and the
+        first and the last at most ``max_span`` (``None``: no limit); a group answers with its span of the largest summed gain
+        (``mass``; then the shortest, then the earliest), and groups without a span of positive mass do not appear.  Groups
+        come back by mass, largest first (ties: the order in which the groups first appeared in the index).  ``frames`` is the
+        number of rows in the span, ``start`` / ``end`` the positions of its first and last row (``start_id`` / ``end_id``),
+        ``peak_id`` its best single row (ties by id, as ``search``); ``score`` = ``1 - (max_distance - mass / frames)`` is the
+        mean similarity over the span, good to the gain's rounding.  ``max_span=0`` on distinct positions is
+        ``search_grouped`` below ``max_distance``.  ``group_of`` / ``within`` / ``exclude`` as ``search_grouped``,
+        ``position_of`` as ``search_distinct`` (timestamps in ms with limits in ms alike).  At most 1,024 results."""
+        return self.search_spans_batch([query], k, max_distance=max_distance, max_gap=max_gap, max_span=max_span, within=within,
+                                       exclude=exclude, group_of=group_of, position_of=position_of)[0]
+
+    def search_spans_batch(self, queries: Sequence[np.ndarray], k: int = 5, *, max_distance: float, max_gap: Optional[int] = None,
+                           max_span: Optional[int] = None, within: Optional[Iterable[Hashable]] = None,
+                           exclude: Optional[Iterable[Hashable]] = None, group_of: GROUP_OF = None,
+                           position_of: POSITION_OF = None) -> List[List[Dict]]:
+        """``search_spans`` for a batch of at most 64 queries, one device pass; a group's span for one query does not depend on
+        the other queries."""
+        flt = self._filter_arg(within, exclude)
+        tau, gap, span = self._span_args(max_distance, max_gap, max_span)
+        if len(queries) > self.SPAN_MAX_QUERIES:
+            raise ValueError(f"a span search takes at most {self.SPAN_MAX_QUERIES} queries, got {len(queries)}")
+        if len(queries) == 0:
+            return []
+        if self._empty() or k <= 0:
+            return [[] for _ in queries]
+        with self.lock:
+            return self._search_spans(queries, k, tau, gap, span, flt, group_of, position_of)
+
     # -- shared footage: the k groups (videos) that reuse a run of a clip's frames, and where -------
-    MATCH_MAX_FRAMES = 4096       # vq_index_match_runs: clip frames per call
+    MATCH_MAX_FRAMES = 4096      # vq_index_match_runs: clip frames per call
 
     @staticmethod
     def _match_args(max_distance, min_len, max_miss) -> Tuple[np.float32, int, int]:

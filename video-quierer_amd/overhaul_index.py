@@ -220,6 +220,36 @@ class SimpleVideoIndex:
                  "timestamps": [self.metadata[-i]["timestamp"] for i in r["chain"]],
                  "frame_ids": [self.metadata[-i]["frame_id"] for i in r["chain"]]} for r in res]
 
+    def search_spans(self, query_embedding: np.ndarray, k: int = 5, min_similarity: float = 0.25, max_gap_s: Optional[float] = None,
+                     max_len_s: Optional[float] = None) -> List[Dict]:
+        """Where in which video does the query happen, from when to when: ``[{'video_name', 'start', 'end', 'peak', 'frames',
+        'score', 'mass'}]``, the k videos with the best time span, best first.  A frame adds its similarity above
+        ``min_similarity`` to a span and costs it what it lacks; a span is a run of consecutive frames of one video, neighbours
+        at most ``max_gap_s`` seconds apart and the whole at most ``max_len_s`` long (``None``: no limit), and a video answers
+        with its span of the largest sum (``mass``; ``HNSWIndex.search_spans`` with ``max_distance = float32(1) -
+        float32(min_similarity)``: exact).  ``start`` / ``end`` / ``peak`` are the timestamps in seconds of the span's first,
+        last and best frame, ``frames`` the number of frames in it, ``score`` their mean similarity.  The query is normalised
+        as ``search`` does; positions are ``round(timestamp * 1000)`` ms, the limits ``floor(x * 1000)`` ms, groups the video
+        names; ties between frames as ``search``."""
+        tau = np.float32(1) - np.float32(min_similarity)
+        if tau != tau:
+            raise ValueError("min_similarity is NaN")
+        for name, x in (("max_gap_s", max_gap_s), ("max_len_s", max_len_s)):
+            if x is not None and not x >= 0:                      # (NaN too)
+                raise ValueError(f"{name} must be >= 0 or None, got {x}")
+        gap = None if max_gap_s is None else int(math.floor(max_gap_s * 1000))
+        span = None if max_len_s is None else int(math.floor(max_len_s * 1000))
+        tau, gap, span = HNSWIndex._span_args(tau, gap, span)
+        if not self.embeddings or k <= 0:
+            return []
+        dev = self._device(ranks=True)
+        unit = np.ascontiguousarray(_unit_query(query_embedding)[None, :])
+        with dev.lock:                                # the query as normalised above, not normalised again
+            res = dev._search_spans(unit, k, tau, gap, span, None, self._group_fn, self._pos_fn, given=True)[0]
+        stamp = lambda i: self.metadata[-i]["timestamp"]
+        return [{"video_name": r["group"], "start": stamp(r["start_id"]), "end": stamp(r["end_id"]), "peak": stamp(r["peak_id"]),
+                 "frames": r["frames"], "score": r["score"], "mass": r["mass"]} for r in res]
+
     def similar_videos(self, video_name: str, k: int = 5, keyframes: Optional[int] = None) -> List[Dict]:
         """The k indexed videos most similar to ``video_name``, itself excluded: ``[{'video_name', 'score'}]``, best first.
         Every stored frame of the video takes its best match in the other video; ``score`` is the mean of those cosine
