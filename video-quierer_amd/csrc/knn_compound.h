@@ -109,19 +109,18 @@ struct CompoundPlan {
     CompoundLanes lanes;
 };
 
-static inline bool compound_fp16_dim(int dim) { return dim == 256 || dim == 512 || dim == 768; }
 static inline int compound_pool(int k) { return k <= 20 ? 32 : k <= 40 ? 64 : k <= 64 ? 80 : CP_MAX_C; }
 
 // clause_of is well-formed (check_compound_args) or null (vq_debug_compound_plan: m terms of one-term clauses)
 static inline CompoundPlan plan_compound(int64_t n, int dim, int m, const int32_t* clause_of, int k, int mode, bool near_unit) {
     CompoundPlan p;
-    const bool ok = compound_fp16_dim(dim) && near_unit && k <= CP_K_MAX && n >= 1;
+    const bool ok = scan_fp16_dim(dim) && near_unit && k <= CP_K_MAX && n >= 1;
     p.fp16 = mode == 2 ? ok : mode == 0 && ok && n >= CP_FP16_MIN_ROWS;
     p.streams = (n + 127) / 128;
     p.pool = p.fp16 ? compound_pool(k) : 0;
     p.ld = (n + 63) / 64 * 64;
     p.exact_bytes = (int64_t)m * p.ld * 4;
-    p.eps = compound_fp16_dim(dim) ? scan_eps_unit(dim) * 1.0001f * 1.0001f + 0.5f * CP_SLACK : 0.f;
+    p.eps = scan_fp16_dim(dim) ? scan_eps_unit(dim) * 1.0001f * 1.0001f + 0.5f * CP_SLACK : 0.f;
     p.spec.m = m; p.spec.clauses = 0;
     for (int j = 0; j < CP_MAX_M; ++j) {
         p.spec.clause[j] = j < m ? (int8_t)(clause_of ? clause_of[j] : j) : (int8_t)-1;

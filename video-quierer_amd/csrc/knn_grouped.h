@@ -90,7 +90,7 @@ void group_block_topk_kernel(const float* __restrict__ dist, int64_t ld, const f
                 const int r = POS ? i : grows[i];
                 float d;
                 if constexpr (FROM_DIST) d = dist[(int64_t)q * ld + r];
-                else d = 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(rows + (size_t)r * dim, qv, dim) : exact_dot_chain(rows + (size_t)r * dim, qv, dim));
+                else d = exact_row_dist(rows + (size_t)r * dim, qv, dim);
                 const uint64_t key = dist_key(d, tie_of(tie, r));
                 best = key < best ? key : best;
             }

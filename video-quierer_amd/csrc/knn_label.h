@@ -18,7 +18,7 @@
 //
 // Tile path (mode 2): the ROWS take the place the queries have in set_group_max_kernel (knn_set.h) and the PROMPTS the place
 // of its streamed rows: a workgroup holds one 256-row tile of the fp16 matrix and streams up to eight 256-prompt tiles past it
-// through the same four-phase LDS-DMA mainloop (gemm_mfma256.h), one continuous K loop.  Wave (wr, wc) owns rows 128 wr .. +127
+// through the same streamed mainloop (scan_stream256.h), one continuous K loop.  Wave (wr, wc) owns rows 128 wr .. +127
 // and prompts 64 wc .. +63 of every prompt tile; a lane holds, for each of its 8 rows, scores of 16 prompts per tile.  So the
 // reduction over the prompt axis runs along the lane's own registers, tile after tile, and needs no exchange until the range
 // is done: per row the lane keeps k1 >= k2 >= f, the three largest keys it has seen.  A key is the order-preserving word of
@@ -64,7 +64,7 @@
 #pragma once
 #include "vq_common.h"
 #include "gemm_mfma.h"
-#include "gemm_mfma256.h"
+#include "scan_stream256.h"
 #include "knn_kernels.h"
 #include "knn_scan_f16.h"
 #include "knn_grouped.h"
@@ -105,12 +105,10 @@ struct LabelPlan {
     int64_t largest_group_pieces;   // pieces of the longest group (0: it runs as one workgroup)
 };
 
-inline bool label_fp16_dim(int dim) { return dim == 256 || dim == 512 || dim == 768; }
-
 // near_unit: the index's rows are (knn_kernels.h row_norm_range_kernel); mode 2 is refused by the caller when !fp16 below.
 inline LabelPlan plan_label(int64_t n, int dim, int P, int mode, bool near_unit, int64_t largest_group) {
     LabelPlan p;
-    const bool ok = label_fp16_dim(dim) && near_unit && n >= 1;
+    const bool ok = scan_fp16_dim(dim) && near_unit && n >= 1;
     p.fp16 = (mode == 2 && ok) || (mode == 0 && ok && n >= LABEL_AUTO_MIN_ROWS && n * P >= LABEL_AUTO_MIN_WORK) ? 1 : 0;
     const int64_t ld = round_up(std::max<int64_t>(n, 1), 64);
     int64_t c = std::max<int64_t>(1, std::min<int64_t>(P, LABEL_DIST_WORDS / ld));
@@ -123,7 +121,7 @@ inline LabelPlan plan_label(int64_t n, int dim, int P, int mode, bool near_unit,
     p.row_tiles = (n + LABEL_ROW_TILE - 1) / LABEL_ROW_TILE;
     p.part_bytes = (int64_t)p.prompt_ranges * LABEL_PART_WORDS * p.row_tiles * LABEL_ROW_TILE * 4;
     // the bound for |row| <= 1.0001 (what normalised rows measure) and |p| <= 1.0001, with the slack's half
-    p.eps = label_fp16_dim(dim) ? scan_eps_unit(dim) * 1.0001f * 1.0001f + 0.5f * LABEL_SLACK : 0.f;
+    p.eps = scan_fp16_dim(dim) ? scan_eps_unit(dim) * 1.0001f * 1.0001f + 0.5f * LABEL_SLACK : 0.f;
     p.group_split_rows = LABEL_GROUP_SPLIT_ROWS;
     p.group_piece_rows = LABEL_GROUP_PIECE_ROWS;
     p.largest_group_pieces = largest_group > LABEL_GROUP_SPLIT_ROWS ? (largest_group + LABEL_GROUP_PIECE_ROWS - 1) / LABEL_GROUP_PIECE_ROWS : 0;
@@ -155,16 +153,11 @@ void label_colmin_kernel(const float* __restrict__ dist, int64_t ld, int64_t n, 
 // ---- tile path: ctl = {filed rows, flag, bits of the largest |p|^2} (zeroed by the caller); one wave per prompt ----
 __global__ __launch_bounds__(64)
 void label_prompt_norm_kernel(const float* __restrict__ prompts, int dim, int32_t* __restrict__ ctl) {
-    const int j = blockIdx.x, lane = threadIdx.x;
-    const float* pv = prompts + (size_t)j * dim;
-    float s2 = 0.f;
-    for (int i = lane; i < dim; i += 64) s2 += pv[i] * pv[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o);
-    if (lane == 0) {
-        if (!(s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX)) ctl[1] = 2;      // outside what the fp16 bound covers (NaN included)
+    const int j = blockIdx.x;
+    wave_query_norm2(prompts + (size_t)j * dim, dim, [&](float s2, bool covered) {
+        if (!covered) ctl[1] = 2;
         else atomicMax((uint32_t*)ctl + 2, __builtin_bit_cast(uint32_t, s2));   // positive floats order like their bits
-    }
+    });
 }
 
 __device__ __forceinline__ float label_key_score(uint32_t key) { return key_score(key & ~127u); }
@@ -181,14 +174,10 @@ __device__ __forceinline__ void label_insert(uint32_t key, int32_t j, uint32_t& 
 __global__ __launch_bounds__(G2_THREADS, 2)
 void label_tile_kernel(const uint16_t* __restrict__ X16, const uint16_t* __restrict__ P16, int dim, int P, int p_tiles, int p_ranges,
                        int64_t n_pad, uint32_t* __restrict__ parts) {
-    typedef mfma_op<true> op;
-    typedef op::frag frag;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 2, wc = wave & 3;
+    const Stream256Lane ln = stream256_lane();
+    const int wr = ln.wr, wc = ln.wc, frow = ln.frow, fgrp = ln.fgrp;
 
     const int64_t rtile = blockIdx.x / p_ranges;
     const int range = blockIdx.x - (int)rtile * p_ranges;
@@ -196,79 +185,13 @@ void label_tile_kernel(const uint16_t* __restrict__ X16, const uint16_t* __restr
     const int j00 = range * (LABEL_RANGE_TILES * LABEL_PT);          // first prompt
     const int nt = min(LABEL_RANGE_TILES, p_tiles - range * LABEL_RANGE_TILES);   // prompt tiles of this range (>= 1)
 
-    const int srow = lane >> 3, sslot = lane & 7;
-    const uint16_t* a_src[2];
-    const uint16_t* w_src[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = (wave * 2 + i) * 8 + srow;
-        const int chunk = sslot ^ ((row >> 1) & 7);
-        a_src[i] = X16 + (size_t)(m0 + row) * dim + chunk * 8;
-        w_src[i] = P16 + (size_t)(j00 + row) * dim + chunk * 8;
-    }
-    const size_t half_rows = (size_t)128 * dim;
-    const int piece_off = wave * 2048;
-    const int nk = dim / G2_BK;                          // K-tiles per prompt tile (even: dim % 128 == 0)
-    const int total = nt * nk;                           // flattened K-tiles
-
-    auto stage = [&](int buf, int which, int kt) __attribute__((always_inline)) {
-        char* dst = smem + buf * G2_BUF + which * G2_HALF + piece_off;
-        const int t = kt / nk, kk = kt - t * nk;
-        if (which < 2) {
-            const size_t off = (which ? half_rows : 0) + (size_t)kk * G2_BK;
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(a_src[0] + off), (lds_void_t*)(dst), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(a_src[1] + off), (lds_void_t*)(dst + 1024), 16, 0, 0);
-        } else {
-            const size_t off = (size_t)t * 256 * dim + ((which & 1) ? half_rows : 0) + (size_t)kk * G2_BK;
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(w_src[0] + off), (lds_void_t*)(dst), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(w_src[1] + off), (lds_void_t*)(dst + 1024), 16, 0, 0);
-        }
-    };
-
-    const int frow = lane & 15, fgrp = lane >> 4;
-    const int fx = (frow >> 1) & 7;
-    const int slot[2] = {((0 + fgrp) ^ fx) * 16, ((4 + fgrp) ^ fx) * 16};
-    const int a_base = wr * G2_HALF + frow * 128;
-    const int w_base = 2 * G2_HALF + (wc >> 1) * G2_HALF + ((wc & 1) * 64 + frow) * 128;
-
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    frag af[4][2], wf[2][2];
     uint32_t k1[8], k2[8], fl[8];                        // per row block mi: the lane's three largest keys so far
 #pragma unroll
     for (int i = 0; i < 8; ++i) { k1[i] = 0u; k2[i] = 0u; fl[i] = 0u; }
     const int jlane = j00 + wc * 64 + 4 * fgrp;          // the lane's prompt of (t, ni, r): jlane + t * 256 + ni * 16 + r
 
-    auto load_a = [&](const char* buf, int hm) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-                af[i][ks] = *(const frag*)(buf + a_base + (hm * 4 + i) * 2048 + slot[ks]);
-    };
-    auto load_w = [&](const char* buf, int hn) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-                wf[j][ks] = *(const frag*)(buf + w_base + (hn * 2 + j) * 2048 + slot[ks]);
-    };
-    auto mfma_quadrant = [&](int hm, int hn) __attribute__((always_inline)) {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[hm * 4 + i][hn * 2 + j] = op::run(wf[j][ks], af[i][ks], acc[hm * 4 + i][hn * 2 + j]);
-        __builtin_amdgcn_s_setprio(0);
-    };
     // Fold quadrant (hm, hn) of prompt tile t into the rows' running keys and clear it.
-    auto fold = [&](int hm, int hn, int t) __attribute__((always_inline)) {
+    auto fold = [&](f32x4 (&acc)[8][4], int hm, int hn, int t) __attribute__((always_inline)) {
         const bool ragged = j00 + (t + 1) * LABEL_PT > P;             // uniform: the tile holds pad prompts
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -290,67 +213,12 @@ void label_tile_kernel(const uint16_t* __restrict__ X16, const uint16_t* __restr
             }
         }
     };
-    auto barrier = [&]() __attribute__((always_inline)) {
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
+    stream256_run(smem, ln, X16 + (size_t)m0 * dim, P16 + (size_t)j00 * dim, dim, nt, fold);
 
-    // One K-tile: the four phases, hazards and waits of gemm_tn256_kernel.  `last` = final K-tile of a prompt tile: each
-    // quadrant is folded in the read half of the phase after its last MFMAs; the fourth quadrant's fold lands in phase 1 of
-    // the next K-tile (`fold_prev`).
-    auto tile = [&](int kt, int bufi, bool last, bool fold_prev, int t) __attribute__((always_inline)) {
-        const char* buf = smem + bufi * G2_BUF;
-        const bool next = kt + 1 < total, next2 = kt + 2 < total;
-        if (fold_prev) fold(1, 0, t - 1);
-        load_a(buf, 0); load_w(buf, 0);
-        if (next) stage(bufi ^ 1, 1, kt + 1);
-        barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        mfma_quadrant(0, 0);
-        barrier();
-        if (last) fold(0, 0, t);
-        load_w(buf, 1);
-        if (next) stage(bufi ^ 1, 2, kt + 1);
-        barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        mfma_quadrant(0, 1);
-        barrier();
-        if (last) fold(0, 1, t);
-        load_a(buf, 1);
-        if (next) stage(bufi ^ 1, 3, kt + 1);
-        barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        mfma_quadrant(1, 1);
-        barrier();
-        if (last) fold(1, 1, t);
-        load_w(buf, 0);
-        if (next2) { stage(bufi, 0, kt + 2); asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
-        else       { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        mfma_quadrant(1, 0);
-        barrier();
-    };
-
-    stage(0, 0, 0); stage(0, 1, 0); stage(0, 2, 0); stage(0, 3, 0);
-    if (total > 1) { stage(1, 0, 1); asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
-    else           { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    barrier();
-
-    if (wr == 1) barrier();
-    int kk = 0, t = 0;
-    for (int kt = 0; kt < total; kt += 2) {
-        tile(kt, 0, false, kk == 0 && t > 0, t);
-        ++kk;
-        tile(kt + 1, 1, kk + 1 == nk, false, t);
-        if (++kk == nk) { kk = 0; ++t; }
-    }
-    fold(1, 0, nt - 1);
-    if (wr == 0) barrier();
-
-    // ---- merge: every wave is past its last LDS read and every LDS-DMA has landed (vmcnt(0) in the last K-tile) ----
-    barrier();
+    // ---- merge: behind this barrier every wave is past its last LDS read; every LDS-DMA has landed (scan_stream256.h) ----
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
     uint32_t* const lw = (uint32_t*)smem;
     {
         uint32_t* part = lw + (wc * 4 + fgrp) * LABEL_PART_STRIDE + wr * 128 + frow;
@@ -380,10 +248,6 @@ void label_tile_kernel(const uint16_t* __restrict__ X16, const uint16_t* __restr
     }
 }
 
-__device__ __forceinline__ float label_exact_dist(const float* __restrict__ row, const float* __restrict__ p, int dim) {
-    return 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(row, p, dim) : exact_dot_chain(row, p, dim));
-}
-
 // ---- tile path: per row, the ranges' parts in order -> proven / re-scored / filed.  counters {proven, re-scored, filed}. ----
 __global__ __launch_bounds__(256)
 void label_finalize_kernel(const uint32_t* __restrict__ parts, int p_ranges, int64_t n_pad, int64_t n, const float* __restrict__ rows, int dim,
@@ -408,13 +272,13 @@ void label_finalize_kernel(const uint32_t* __restrict__ parts, int p_ranges, int
             const float s1 = label_key_score(K1);
             const float* rv = rows + (size_t)r * dim;
             if (K2 == 0u || s1 - label_key_score(K2) > T) {
-                const float d = label_exact_dist(rv, prompts + (size_t)J1 * dim, dim);
+                const float d = exact_row_dist(rv, prompts + (size_t)J1 * dim, dim);
                 lab[r] = d > max_dist ? -1 : J1;
                 best[r] = d;
                 state = 0;
             } else if (F == 0u || s1 - label_key_score(F) > T) {
-                const float d1 = label_exact_dist(rv, prompts + (size_t)J1 * dim, dim);
-                const float d2 = label_exact_dist(rv, prompts + (size_t)J2 * dim, dim);
+                const float d1 = exact_row_dist(rv, prompts + (size_t)J1 * dim, dim);
+                const float d2 = exact_row_dist(rv, prompts + (size_t)J2 * dim, dim);
                 const bool second = dist_key(d2, (uint32_t)J2) < dist_key(d1, (uint32_t)J1);
                 const float d = second ? d2 : d1;
                 lab[r] = d > max_dist ? -1 : (second ? J2 : J1);
@@ -447,7 +311,7 @@ void label_redo_kernel(const float* __restrict__ rows, int64_t n, int dim, const
         const float* rv = rows + (size_t)r * dim;
         uint64_t key = ~0ull;
         for (int j = lane; j < P; j += 64) {
-            const uint64_t k = dist_key(label_exact_dist(rv, prompts + (size_t)j * dim, dim), (uint32_t)j);
+            const uint64_t k = dist_key(exact_row_dist(rv, prompts + (size_t)j * dim, dim), (uint32_t)j);
             key = k < key ? k : key;
         }
 #pragma unroll

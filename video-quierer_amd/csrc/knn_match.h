@@ -25,8 +25,8 @@
 // as consecutive rows, one or two words.  Row-major ([r][m / 32]) would make the same 64 reads hit 64 different rows' words.
 // It also suits the writer: the quadrant a wave finishes in the tile kernel is 64 queries x 32 rows, exactly one word per query.
 //
-// Tile path.  The workgroup, staging, phases and waits are set_group_max_kernel's (knn_set.h; gemm_mfma256.h explains the
-// schedule): queries on the A side, 2,048-row ranges of the fp16 matrix streamed past them in one continuous K loop.  A lane of
+// Tile path.  The workgroup and the workgroup order are set_group_max_kernel's (knn_set.h), the mainloop is the shared one
+// (scan_stream256.h): queries on the A side, 2,048-row ranges of the fp16 matrix streamed past them in one continuous K loop.  A lane of
 // wave (wr, wc) holds, for query m0 + 128 wr + 16 mi + (lane & 15), the scores of rows 64 wc + 16 ni + 4 (lane >> 4) + r of the
 // row tile; a finished quadrant (hm, hn) is 4 query blocks x rows 64 wc + 32 hn .. + 31: the four lanes lane & 15 = const hold
 // the 32 bits of one word between them, 8 each.  They are OR-ed across the four 16-lane rows by two permlane swaps and lane
@@ -62,7 +62,7 @@
 #pragma once
 #include "vq_common.h"
 #include "gemm_mfma.h"
-#include "gemm_mfma256.h"
+#include "scan_stream256.h"
 #include "knn_kernels.h"
 #include "knn_scan_f16.h"
 #include "knn_grouped.h"
@@ -101,14 +101,13 @@ struct MatchPlan {
     int launches;          // kernels a call queues (memsets and copies not counted)
 };
 
-inline bool match_fp16_dim(int dim) { return dim == 256 || dim == 512 || dim == 768; }
 inline int match_bits_of(int64_t v) { int b = 0; while (v > 0) { ++b; v >>= 1; } return b; }
 
 // near_unit: the index's rows are (knn_kernels.h row_norm_range_kernel); mode 2 is refused by the caller when !fp16 below.
 // filed_cap_override > 0 (tests) lowers the capacity.
 inline MatchPlan plan_match(int64_t n, int64_t n_groups, int dim, int m, int mode, bool near_unit, int64_t filed_cap_override) {
     MatchPlan p;
-    const bool ok = match_fp16_dim(dim) && near_unit && n >= 1;
+    const bool ok = scan_fp16_dim(dim) && near_unit && n >= 1;
     p.fp16 = (mode == 2 && ok) || (mode == 0 && ok && n >= MATCH_AUTO_MIN_ROWS && m >= MATCH_AUTO_MIN_M) ? 1 : 0;
     p.words = (std::max<int64_t>(n, 1) + 31) / 32;
     p.bits_bytes = (int64_t)m * p.words * 4;
@@ -137,10 +136,6 @@ inline MatchPlan plan_match(int64_t n, int64_t n_groups, int dim, int m, int mod
 // control words of a call: the filed list's cursor (64-bit), then the flag
 struct MatchCtl { unsigned long long cursor; int32_t flag; int32_t pad; };
 
-__device__ __forceinline__ float match_exact_dist(const float* __restrict__ row, const float* __restrict__ q, int dim) {
-    return 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(row, q, dim) : exact_dot_chain(row, q, dim));
-}
-
 // ---- exact path: hit bits of `cur` queries (grid.y) over all rows, 256 rows per workgroup, two words per wave.  bits /
 // queries / dist: at the chunk's first query.  gate != null: only a call flagged 2 does anything. ----
 template <bool FROM_DIST>
@@ -155,7 +150,7 @@ void match_threshold_kernel(const float* __restrict__ dist, int64_t ld, const fl
     if (r < n) {
         float d;
         if constexpr (FROM_DIST) d = dist[(int64_t)i * ld + r];
-        else d = match_exact_dist(rows + (size_t)r * dim, queries + (size_t)i * dim, dim);
+        else d = exact_row_dist(rows + (size_t)r * dim, queries + (size_t)i * dim, dim);
         hit = d <= max_dist;                                   // inclusive; a NaN distance never hits
     }
     const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
@@ -171,16 +166,11 @@ void match_threshold_kernel(const float* __restrict__ dist, int64_t ld, const fl
 __global__ __launch_bounds__(64)
 void match_query_norm_kernel(const float* __restrict__ queries, int dim, float eps_rows, float* __restrict__ qe /*[m]*/,
                              MatchCtl* __restrict__ ctl) {
-    const int q = blockIdx.x, lane = threadIdx.x;
-    const float* qv = queries + (size_t)q * dim;
-    float s2 = 0.f;
-    for (int i = lane; i < dim; i += 64) s2 += qv[i] * qv[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o);
-    if (lane == 0) {
+    const int q = blockIdx.x;
+    wave_query_norm2(queries + (size_t)q * dim, dim, [&](float s2, bool covered) {
         qe[q] = eps_rows * sqrtf(s2) + MATCH_SLACK;
-        if (!(s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX)) ctl->flag = 2;      // outside what the fp16 bound covers (NaN included)
-    }
+        if (!covered) ctl->flag = 2;
+    });
 }
 
 // OR across the four 16-lane rows of a wave (lane ^ 16, lane ^ 32), the result in every lane: rows4_sum's two swaps on bits
@@ -193,28 +183,22 @@ __device__ __forceinline__ uint32_t rows4_or(uint32_t x) {
 }
 
 // ---- tile path: hit bits of a 256-query tile over a 2,048-row range per workgroup (SCAN2_QT, SCAN2_RANGE: 8 row tiles, one
-// continuous K loop); workgroup order, staging, phases and waits are set_group_max_kernel's.  Q16 [q_tiles * 256][dim] (pad
+// continuous K loop: scan_stream256.h); the workgroup order is set_group_max_kernel's.  Q16 [q_tiles * 256][dim] (pad
 // queries zero), X16 the index's fp16 copy (whole ranges allocated).  T = fp32(1 - max_dist), qe [nq_real]. ----
 __global__ __launch_bounds__(G2_THREADS, 2)
 void match_tile_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __restrict__ X16, int dim, int64_t n, int q_tiles, int n_ranges,
                        int range_groups, int nq_real, float T, const float* __restrict__ qe, uint32_t* __restrict__ bits, int64_t W,
                        MatchCtl* __restrict__ ctl, unsigned long long* __restrict__ filed, unsigned long long cap) {
-    typedef mfma_op<true> op;
-    typedef op::frag frag;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int skip_s;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 2, wc = wave & 3;
+    const Stream256Lane ln = stream256_lane();
+    const int wr = ln.wr, wc = ln.wc, frow = ln.frow, fgrp = ln.fgrp;
 
-    const int wg = xcd_remap(blockIdx.x, gridDim.x);
-    const int blk = wg >> 5, inner = wg & 31;
-    const int rg = blk % range_groups, qg = blk / range_groups;
-    const int range = rg * 4 + (inner >> 3);
-    const int qtile = qg * 8 + (inner & 7);
-    if (range >= n_ranges || qtile >= q_tiles) return;   // whole workgroup leaves before any barrier
+    int range, qtile;
+    if (!scan2_block_tile(range_groups, n_ranges, q_tiles, range, qtile)) return;   // whole workgroup leaves before any barrier
     const int m0 = qtile * SCAN2_QT;
     const int64_t n0 = (int64_t)range * SCAN2_RANGE;
 
@@ -227,76 +211,10 @@ void match_tile_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __restr
     __syncthreads();
     if (skip_s == 2) return;
 
-    const int srow = lane >> 3, sslot = lane & 7;
-    const uint16_t* a_src[2];
-    const uint16_t* w_src[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = (wave * 2 + i) * 8 + srow;
-        const int chunk = sslot ^ ((row >> 1) & 7);
-        a_src[i] = Q16 + (size_t)(m0 + row) * dim + chunk * 8;
-        w_src[i] = X16 + (size_t)(n0 + row) * dim + chunk * 8;
-    }
-    const size_t half_rows = (size_t)128 * dim;
-    const int piece_off = wave * 2048;
-    const int nk = dim / G2_BK;                          // K-tiles per row tile (even: dim % 128 == 0)
-    const int total = 8 * nk;                            // flattened K-tiles
-
-    auto stage = [&](int buf, int which, int kt) __attribute__((always_inline)) {
-        char* dst = smem + buf * G2_BUF + which * G2_HALF + piece_off;
-        const int t = kt / nk, kk = kt - t * nk;
-        if (which < 2) {
-            const size_t off = (which ? half_rows : 0) + (size_t)kk * G2_BK;
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(a_src[0] + off), (lds_void_t*)(dst), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(a_src[1] + off), (lds_void_t*)(dst + 1024), 16, 0, 0);
-        } else {
-            const size_t off = (size_t)t * 256 * dim + ((which & 1) ? half_rows : 0) + (size_t)kk * G2_BK;
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(w_src[0] + off), (lds_void_t*)(dst), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(w_src[1] + off), (lds_void_t*)(dst + 1024), 16, 0, 0);
-        }
-    };
-
-    const int frow = lane & 15, fgrp = lane >> 4;
-    const int fx = (frow >> 1) & 7;
-    const int slot[2] = {((0 + fgrp) ^ fx) * 16, ((4 + fgrp) ^ fx) * 16};
-    const int a_base = wr * G2_HALF + frow * 128;
-    const int w_base = 2 * G2_HALF + (wc >> 1) * G2_HALF + ((wc & 1) * 64 + frow) * 128;
-
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    frag af[4][2], wf[2][2];
     const int qbase = m0 + wr * 128 + frow;              // the lane's query of block mi: qbase + 16 mi
 
-    auto load_a = [&](const char* buf, int hm) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-                af[i][ks] = *(const frag*)(buf + a_base + (hm * 4 + i) * 2048 + slot[ks]);
-    };
-    auto load_w = [&](const char* buf, int hn) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-                wf[j][ks] = *(const frag*)(buf + w_base + (hn * 2 + j) * 2048 + slot[ks]);
-    };
-    auto mfma_quadrant = [&](int hm, int hn) __attribute__((always_inline)) {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[hm * 4 + i][hn * 2 + j] = op::run(wf[j][ks], af[i][ks], acc[hm * 4 + i][hn * 2 + j]);
-        __builtin_amdgcn_s_setprio(0);
-    };
     // the undecided cells of the lane's 8 scores of (query block mi, quadrant column hn): |score - T| <= e, the row exists
-    auto undecided = [&](int mi, int hn, float ei, uint32_t live) __attribute__((always_inline)) -> uint32_t {
+    auto undecided = [&](const f32x4 (&acc)[8][4], int mi, int hn, float ei, uint32_t live) __attribute__((always_inline)) -> uint32_t {
         uint32_t un = 0u;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -309,12 +227,12 @@ void match_tile_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __restr
     };
     // The undecided cells of a quadrant go to the filed list: one cursor atomic for the wave, then plain stores.  Entered by whole
     // waves (the caller's test is a ballot) and it contains no barrier of the mainloop.  Rare: it recomputes what it files.
-    auto file = [&](int hm, int hn, int64_t rbase, uint32_t live) __attribute__((always_inline)) {
+    auto file = [&](const f32x4 (&acc)[8][4], int hm, int hn, int64_t rbase, uint32_t live) __attribute__((always_inline)) {
         const bool up = __atomic_load_n(&ctl->flag, __ATOMIC_RELAXED) == 2;
         if (__builtin_amdgcn_ballot_w64(up) != 0) return;      // the redo answers the call: leave the cursor alone
         int cnt = 0;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) cnt += __builtin_popcount(undecided(hm * 4 + i, hn, es[wr * 128 + frow + 16 * (hm * 4 + i)], live));
+        for (int i = 0; i < 4; ++i) cnt += __builtin_popcount(undecided(acc, hm * 4 + i, hn, es[wr * 128 + frow + 16 * (hm * 4 + i)], live));
         int incl = cnt;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -330,7 +248,7 @@ void match_tile_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __restr
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int mi = hm * 4 + i;
-            uint32_t u = undecided(mi, hn, es[wr * 128 + frow + 16 * mi], live);
+            uint32_t u = undecided(acc, mi, hn, es[wr * 128 + frow + 16 * mi], live);
             const unsigned long long q = (unsigned long long)(qbase + 16 * mi);
             while (u) {
                 const int bp = __builtin_ctz(u);
@@ -341,7 +259,7 @@ void match_tile_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __restr
         }
     };
     // Classify quadrant (hm, hn) of row tile t, store its 64 words, file what is undecided, and clear it.
-    auto fold = [&](int hm, int hn, int t) __attribute__((always_inline)) {
+    auto fold = [&](f32x4 (&acc)[8][4], int hm, int hn, int t) __attribute__((always_inline)) {
         const int64_t rbase = n0 + (int64_t)t * 256 + wc * 64 + hn * 32;       // first row of the wave's word (wave-uniform)
         const int64_t left = n - rbase;                                        // rows of it that exist
         const uint32_t live = left >= 32 ? 0xffffffffu : (left <= 0 ? 0u : ((1u << (int)left) - 1u));
@@ -358,77 +276,20 @@ void match_tile_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __restr
                     sure |= (acc[mi][hn * 2 + j][r] - T > ei ? 1u : 0u) << (j * 16 + 4 * fgrp + r);
             const uint32_t word = rows4_or(qbase + 16 * mi < nq_real ? sure & live : 0u);
             mine = fgrp == i ? word : mine;                                    // lane group i stores the word of query block i
-            any |= undecided(mi, hn, ei, live);
+            any |= undecided(acc, mi, hn, ei, live);
         }
         const int q = qbase + 16 * (hm * 4 + fgrp);
         const int64_t w = rbase >> 5;
         if (q < nq_real && w < W) bits[(size_t)q * W + w] = mine;
-        if (__builtin_amdgcn_ballot_w64(any != 0u) != 0) file(hm, hn, rbase, live);
+        if (__builtin_amdgcn_ballot_w64(any != 0u) != 0) file(acc, hm, hn, rbase, live);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             acc[hm * 4 + i][hn * 2] = f32x4{0.f, 0.f, 0.f, 0.f};
             acc[hm * 4 + i][hn * 2 + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     };
-    auto barrier = [&]() __attribute__((always_inline)) {
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-
-    // One K-tile: the four phases, hazards and waits of gemm_tn256_kernel.  `last` = final K-tile of a row tile: each
-    // quadrant is folded in the read half of the phase after its last MFMAs; the fourth quadrant's fold lands in phase 1 of
-    // the next K-tile (`fold_prev`).  The fold's stores and its rare atomic only add to vmcnt ahead of the DMA the counted
-    // wait leaves in flight (they are issued before it), so the wait retires them with the older half-tiles.
-    auto tile = [&](int kt, int bufi, bool last, bool fold_prev, int t) __attribute__((always_inline)) {
-        const char* buf = smem + bufi * G2_BUF;
-        const bool next = kt + 1 < total, next2 = kt + 2 < total;
-        if (fold_prev) fold(1, 0, t - 1);
-        load_a(buf, 0); load_w(buf, 0);
-        if (next) stage(bufi ^ 1, 1, kt + 1);
-        barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        mfma_quadrant(0, 0);
-        barrier();
-        if (last) fold(0, 0, t);
-        load_w(buf, 1);
-        if (next) stage(bufi ^ 1, 2, kt + 1);
-        barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        mfma_quadrant(0, 1);
-        barrier();
-        if (last) fold(0, 1, t);
-        load_a(buf, 1);
-        if (next) stage(bufi ^ 1, 3, kt + 1);
-        barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        mfma_quadrant(1, 1);
-        barrier();
-        if (last) fold(1, 1, t);
-        load_w(buf, 0);
-        if (next2) { stage(bufi, 0, kt + 2); asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
-        else       { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        mfma_quadrant(1, 0);
-        barrier();
-    };
-
-    stage(0, 0, 0); stage(0, 1, 0); stage(0, 2, 0); stage(0, 3, 0);
-    if (total > 1) { stage(1, 0, 1); asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
-    else           { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    barrier();
-
-    if (wr == 1) barrier();
-    int kk = 0, t = 0;
-    for (int kt = 0; kt < total; kt += 2) {
-        tile(kt, 0, false, kk == 0 && t > 0, t);
-        ++kk;
-        tile(kt + 1, 1, kk + 1 == nk, false, t);
-        if (++kk == nk) { kk = 0; ++t; }
-    }
-    fold(1, 0, 7);
-    if (wr == 0) barrier();
+    // (the stores and the rare atomic sit ahead of the mainloop's counted wait: scan_stream256.h says why that is safe)
+    stream256_run(smem, ln, Q16 + (size_t)m0 * dim, X16 + (size_t)n0 * dim, dim, 8, fold);
 }
 
 // ---- tile path: every filed pair by the exact chain; a hit sets its bit.  One lane per pair: a chain is one fixed-order sum. ----
@@ -441,7 +302,7 @@ void match_patch_kernel(const float* __restrict__ rows, int dim, const float* __
     for (unsigned long long p = (unsigned long long)blockIdx.x * 256 + threadIdx.x; p < count; p += (unsigned long long)gridDim.x * 256) {
         const unsigned long long pair = filed[p];
         const uint32_t i = (uint32_t)(pair >> 32), r = (uint32_t)pair;
-        const float d = match_exact_dist(rows + (size_t)r * dim, queries + (size_t)i * dim, dim);
+        const float d = exact_row_dist(rows + (size_t)r * dim, queries + (size_t)i * dim, dim);
         if (d <= max_dist) atomicOr(bits + (size_t)i * W + (r >> 5), 1u << (r & 31));
     }
 }
@@ -568,7 +429,7 @@ void match_score_kernel(const int32_t* __restrict__ groups_out, const unsigned l
         const int i = s + c;
         const uint32_t r = (uint32_t)ord[i];
         const bool hit = (bits[(size_t)i * W + (r >> 5)] >> (r & 31)) & 1u;
-        cell[c] = hit ? match_exact_dist(rows + (size_t)r * dim, queries + (size_t)i * dim, dim) : __builtin_nanf("");
+        cell[c] = hit ? exact_row_dist(rows + (size_t)r * dim, queries + (size_t)i * dim, dim) : __builtin_nanf("");
     }
     __syncthreads();
     if (tid == 0) {

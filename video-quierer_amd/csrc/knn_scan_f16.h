@@ -62,6 +62,21 @@ static inline float scan_eps_unit(int dim) {
     return (float)(e * 1.02);
 }
 
+// the dimensions the 256-wide tile scans (clip search, labelling, compound and shared-footage search) take on their fp16 paths
+inline bool scan_fp16_dim(int dim) { return dim == 256 || dim == 512 || dim == 768; }
+
+// One wave of 64 per query vector v: |v|^2 (the order of the additions is part of the result) and whether the bound above
+// covers a query of that norm (NaN: it does not) go to lane 0's store(s2, covered).  The body of the tile scans' norm kernels.
+template <class Store>
+__device__ __forceinline__ void wave_query_norm2(const float* __restrict__ v, int dim, Store&& store) {
+    const int lane = threadIdx.x;
+    float s2 = 0.f;
+    for (int i = lane; i < dim; i += 64) s2 += v[i] * v[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o);
+    if (lane == 0) store(s2, s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX);
+}
+
 // Key layout of the batch scans: [group of 16 queries][stream][16 queries][2 keys].  A scan lane group writes the
 // 128 bytes of (stream, 16 queries) at once, and the re-score workgroup of a query group walks its streams through
 // CONTIGUOUS memory (stream-major [stream][q_pad] made every one of its reads a 64-128 byte piece of a different
@@ -206,6 +221,23 @@ void scan_f16_top2_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __re
 constexpr int SCAN2_QT = 256;
 constexpr int SCAN2_RANGE = 2048;
 
+// Workgroup -> (row range, query tile) of a grid of cdiv(ranges, 4) * cdiv(query tiles, 8) * 32 workgroups; false: the
+// workgroup has neither (it leaves before any barrier).  Measured with the plain "query tile fastest" order: 55 % of the L2
+// requests missed (47 GB from beyond L2 for a 1 GB matrix: every workgroup re-reads its own 256 KB query tile once per row
+// tile and 32 distinct query tiles do not fit a 4 MiB L2), and the DMA ring is too shallow to cover Infinity-Cache latency.
+// So the 32 workgroups an XCD runs at a time form a 4 (ranges) x 8 (query tiles) block: they walk their ranges in step,
+// which makes the live set 4 row tiles + 8 query tiles = 3 MiB, every row tile is fetched once per 8 workgroups and the 8
+// query tiles stay L2-resident; blocks advance range-group fastest so those query tiles are reused by the next block too.
+// (scan5_f16_top2_kernel's order, knn_scan_fold.h, has a block shape of its own.)
+__device__ __forceinline__ bool scan2_block_tile(int range_groups, int n_ranges, int q_tiles, int& range, int& qtile) {
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
+    const int blk = wg >> 5, inner = wg & 31;
+    const int rg = blk % range_groups, qg = blk / range_groups;
+    range = rg * 4 + (inner >> 3);
+    qtile = qg * 8 + (inner & 7);
+    return range < n_ranges && qtile < q_tiles;
+}
+
 __host__ __device__ inline int64_t scan2_row_of(int64_t stream, int local) {
     const int64_t range = stream >> 4;
     const int wc = (int)(stream >> 2) & 3, g = (int)stream & 3;
@@ -268,6 +300,11 @@ __device__ __forceinline__ float exact_dot_chain(const float* __restrict__ row, 
         acc += (double)a.w * (double)b.w;
     }
     return (float)acc;
+}
+
+// the reported distance of (row, query): the chain (either form: the same additions in the same order), one subtraction
+__device__ __forceinline__ float exact_row_dist(const float* __restrict__ row, const float* __restrict__ q, int dim) {
+    return 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(row, q, dim) : exact_dot_chain(row, q, dim));
 }
 
 // keys carry the sign of the score, so compare them as floats; ties and the
@@ -921,7 +958,7 @@ void rescore_verify_small_kernel_t(const uint32_t* __restrict__ keys, int64_t st
             const int which = i / SCAN_STREAM_ROWS, local = i - which * SCAN_STREAM_ROWS;
             const int64_t r = scan3_row_of(resc_stream[which], local);
             int row = -1; float d = __builtin_inff();
-            if (r < n_valid) { row = (int)r; d = 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(rows + (size_t)r * dim, qv, dim) : exact_dot_chain(rows + (size_t)r * dim, qv, dim)); }   // _pf: eight 16-byte loads in flight per thread (a stream rescan was ~35 us of one-load-per-step round trips)
+            if (r < n_valid) { row = (int)r; d = exact_row_dist(rows + (size_t)r * dim, qv, dim); }   // _pf: eight 16-byte loads in flight per thread (a stream rescan was ~35 us of one-load-per-step round trips)
             cand_row[C + i] = row; cand_dist[C + i] = d;
         }
     }

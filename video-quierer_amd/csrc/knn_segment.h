@@ -350,7 +350,7 @@ void seg_show_kernel(const float* __restrict__ rows, int dim, const int32_t* __r
     for (int p = a + tid; p < b; p += SEG_SHOW_THREADS) {
         const int r = so[p];
         const float* x = rows + (size_t)r * dim;
-        const float d = 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(x, u, dim) : exact_dot_chain(x, u, dim));
+        const float d = exact_row_dist(x, u, dim);
         const uint64_t kk = dist_key(d, tie_of(tie, r));
         key = kk < key ? kk : key;
     }

@@ -139,10 +139,6 @@ __device__ __forceinline__ void seq_wave_min(uint64_t& key, uint64_t& ti) {
     }
 }
 
-__device__ __forceinline__ float seq_row_dist(const float* rows, int dim, const float* qv, int r) {
-    return 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(rows + (size_t)r * dim, qv, dim) : exact_dot_chain(rows + (size_t)r * dim, qv, dim));
-}
-
 // One group of L rows, one workgroup of SEQ_THREADS: steps j0 .. j0 + steps - 1 of the DP.  pos / tie / row [L]: the group in
 // (position, tie) order; lo / hi [L], bmin [cdiv(L, 64)] (SUPER: [L], the superblock minima behind the block minima; L >= 2),
 // c0 / c1 [L]: working arrays (LDS or global).  Step 0 fills the costs
@@ -157,7 +153,7 @@ __device__ __forceinline__ void seq_dp_group(const int32_t* pos, const uint32_t*
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     auto d_of = [&](int j, int r) -> double {
         if constexpr (FROM_DIST) return (double)dist[(int64_t)(j - j0) * ld + r];
-        else return (double)seq_row_dist(rows, dim, queries + (size_t)j * dim, r);
+        else return (double)exact_row_dist(rows + (size_t)r * dim, queries + (size_t)j * dim, dim);
     };
     int wide = 0;
     for (int i = tid; i < L; i += SEQ_THREADS) {

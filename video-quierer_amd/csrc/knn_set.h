@@ -17,8 +17,8 @@
 //
 // fp16 path (mode 2):
 //   1. set_group_max_kernel: gbest[i][g] = the order-preserving key of the largest fp16 score of query i over group g, for a
-//      whole tile of 256 queries per pass over the matrix — the 256 x 256 four-phase LDS-DMA mainloop of gemm_mfma256.h over
-//      2048-row ranges (geometry: knn_scan_f16.h) with a group-max epilogue where a batch scan folds its top-2.  Wave (wr, wc) owns 64 rows of every 256-row tile,
+//      whole tile of 256 queries per pass over the matrix — the streamed 256 x 256 mainloop of scan_stream256.h over
+//      2048-row ranges (geometry: knn_scan_f16.h) with a group-max fold.  Wave (wr, wc) owns 64 rows of every 256-row tile,
 //      all inside one 128-row stream: when stream_group says those rows share a label, the epilogue is a register maximum per
 //      query column and ONE atomicMax per (wave, row tile, query); otherwise it reads the 8 row labels of its quadrant and
 //      issues at most one atomicMax per (query, run of equal labels); where a lane's 8 rows hold more than two runs (scattered
@@ -51,6 +51,7 @@
 #include "vq_common.h"
 #include "gemm_mfma.h"
 #include "gemm_mfma256.h"
+#include "scan_stream256.h"
 #include "knn_kernels.h"
 #include "knn_scan_f16.h"
 #include "knn_grouped.h"
@@ -62,9 +63,13 @@ constexpr int64_t SET_KEY_BUDGET = (int64_t)16 << 20; // candidate (group, query
 constexpr float SET_SLACK = 1.0f / 524288;            // 2^-19 >= 5 * 2^-22 (derivation above)
 
 // ---- fp16 pass 1: group-max over a 256-query tile.  A workgroup covers 256 queries x 2048 rows (SCAN2_QT, SCAN2_RANGE: 8 row
-// tiles, one continuous K loop); staging, phases and waits are gemm_tn256_kernel's (gemm_mfma256.h); a finished quadrant (4 query
-// blocks x 2 row blocks of 16) is folded into group maxima.  stream_group / group_of cover
-// `streams` = cdiv(n, 128) streams; row tiles past them score nothing.  MASK: disallowed groups never reach gbest. ----
+// tiles, one continuous K loop); a finished quadrant (4 query blocks x 2 row blocks of 16) is folded into group maxima.
+// The K loop is stream256_run's (scan_stream256.h: staging, phases, waits and the hazard argument are written there), kept here
+// as the kernel's OWN COPY: called through stream256_run, with the row tile's label handed over by a per-tile hook, the kernel
+// kept its instruction counts and registers but ran 0.1-0.8 % slower than this copy at m = 64 and 256, repeatably and outside
+// the copy's run-to-run spread (profiles/stream256_mainloop/ab.txt), and the margin was not found.  A change to the schedule
+// is made in scan_stream256.h first and repeated here.  stream_group / group_of cover `streams` = cdiv(n, 128) streams; row
+// tiles past them score nothing.  MASK: disallowed groups never reach gbest. ----
 template <bool MASK>
 __global__ __launch_bounds__(G2_THREADS, 2)
 void set_group_max_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __restrict__ X16, int dim, int64_t streams,
@@ -80,12 +85,8 @@ void set_group_max_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __re
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
 
-    const int wg = xcd_remap(blockIdx.x, gridDim.x);
-    const int blk = wg >> 5, inner = wg & 31;
-    const int rg = blk % range_groups, qg = blk / range_groups;
-    const int range = rg * 4 + (inner >> 3);
-    const int qtile = qg * 8 + (inner & 7);
-    if (range >= n_ranges || qtile >= q_tiles) return;   // whole workgroup leaves before any barrier
+    int range, qtile;
+    if (!scan2_block_tile(range_groups, n_ranges, q_tiles, range, qtile)) return;   // whole workgroup leaves before any barrier
     const int m0 = qtile * SCAN2_QT;
     const int64_t n0 = (int64_t)range * SCAN2_RANGE;
 
@@ -260,9 +261,9 @@ void set_group_max_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __re
     };
 
     int sg_cur = -2, sg_prev = -2;
-    // One K-tile: the four phases, hazards and waits of gemm_tn256_kernel.  `last` = final K-tile of a row tile: each
-    // quadrant is folded in the read half of the phase after its last MFMAs; the fourth quadrant's fold lands in phase 1 of
-    // the next K-tile (`fold_prev`).
+    // One K-tile of stream256_run's schedule (scan_stream256.h has the phases, hazards and waits), with the row tile's label
+    // handed to its folds: `last` = final K-tile of a row tile, the fourth quadrant's fold lands in phase 1 of the next
+    // K-tile (`fold_prev`).
     auto tile = [&](int kt, int bufi, bool last, bool fold_prev, int t) __attribute__((always_inline)) {
         const char* buf = smem + bufi * G2_BUF;
         const bool next = kt + 1 < total, next2 = kt + 2 < total;
@@ -318,16 +319,11 @@ void set_group_max_kernel(const uint16_t* __restrict__ Q16, const uint16_t* __re
 // ---- |q_i| and the |q|^2 range test: one wave per query ----
 __global__ __launch_bounds__(64)
 void set_query_norm_kernel(const float* __restrict__ queries, int dim, float* __restrict__ qn /*[m]*/, int32_t* __restrict__ flag) {
-    const int q = blockIdx.x, lane = threadIdx.x;
-    const float* qv = queries + (size_t)q * dim;
-    float s2 = 0.f;
-    for (int i = lane; i < dim; i += 64) s2 += qv[i] * qv[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o);
-    if (lane == 0) {
+    const int q = blockIdx.x;
+    wave_query_norm2(queries + (size_t)q * dim, dim, [&](float s2, bool covered) {
         qn[q] = sqrtf(s2);
-        if (!(s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX)) *flag = 2;      // outside what the fp16 bound covers (NaN included)
-    }
+        if (!covered) *flag = 2;
+    });
 }
 
 // ---- sum16[g] (+)= the chunk's fp16 group maxima, i ascending; a group no row reached (key 0: disallowed) adds nothing ----
@@ -437,7 +433,7 @@ void set_cand_keys_kernel(const float* __restrict__ rows, int dim, const float* 
             const int g = cand[c], e = goff[g + 1];
             for (int i = goff[g] + ls; i < e; i += lpg) {
                 const int r = grows[i];
-                const float d = 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(rows + (size_t)r * dim, qv, dim) : exact_dot_chain(rows + (size_t)r * dim, qv, dim));
+                const float d = exact_row_dist(rows + (size_t)r * dim, qv, dim);
                 const uint64_t key = dist_key(d, tie_of(tie, r));
                 best = key < best ? key : best;
             }
@@ -487,7 +483,7 @@ void set_group_min_kernel(const float* __restrict__ dist, int64_t ld, const floa
                 const int r = grows[i];
                 float d;
                 if constexpr (FROM_DIST) d = dist[(int64_t)q * ld + r];
-                else d = 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(rows + (size_t)r * dim, qv, dim) : exact_dot_chain(rows + (size_t)r * dim, qv, dim));
+                else d = exact_row_dist(rows + (size_t)r * dim, qv, dim);
                 const uint64_t key = dist_key(d, tie_of(tie, r));
                 best = key < best ? key : best;
             }
@@ -588,7 +584,7 @@ void set_match_rows_kernel(const int32_t* __restrict__ groups_out, int m, const 
             const int e = goff[g + 1];
             for (int p = goff[g] + lane; p < e; p += 64) {
                 const int r = grows[p];
-                const float d = 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(rows + (size_t)r * dim, qv, dim) : exact_dot_chain(rows + (size_t)r * dim, qv, dim));
+                const float d = exact_row_dist(rows + (size_t)r * dim, qv, dim);
                 const uint64_t key = dist_key(d, tie_of(tie, r));
                 best = key < best ? key : best;
             }

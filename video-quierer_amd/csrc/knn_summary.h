@@ -98,9 +98,11 @@ __device__ __forceinline__ float exact_dot_chain(const float* __restrict__ row, 
     }
     return (float)acc;
 }
+__device__ __forceinline__ float exact_row_dist(const float* __restrict__ row, const double* __restrict__ q, int dim) {
+    return 1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(row, q, dim) : exact_dot_chain(row, q, dim));
+}
 __device__ __forceinline__ uint32_t sum_row_key(const float* rows, int dim, const double* cq, int r) {
-    const float* x = rows + (size_t)r * dim;
-    return sum_key(1.0f - ((dim & 31) == 0 ? exact_dot_chain_pf(x, cq, dim) : exact_dot_chain(x, cq, dim)));
+    return sum_key(exact_row_dist(rows + (size_t)r * dim, cq, dim));
 }
 
 // the workgroup's largest v, in every thread (two barriers: red [4] may still be read from the round before)

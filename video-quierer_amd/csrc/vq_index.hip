@@ -1187,7 +1187,7 @@ int host_results(vq_index* x, int64_t bytes) {          // h_res holds at least 
 }
 
 // ---- clip search (knn_set.h) ----
-bool set_fp16_ok(const vq_index* x) { return (x->dim == 256 || x->dim == 512 || x->dim == 768) && x->size >= 1 && x->near_unit; }
+bool set_fp16_ok(const vq_index* x) { return scan_fp16_dim(x->dim) && x->size >= 1 && x->near_unit; }
 
 // Everything that can refuse a clip search before any work is queued: the mode, stale ranks or labels, the filter's labels, and
 // mode 2 where the fp16 path does not exist.
@@ -1749,7 +1749,7 @@ int segment_run(vq_index* x, const char* fn, const int32_t* groups, int32_t n_se
 }
 
 // ---- zero-shot labelling (knn_label.h) ----
-bool label_fp16_ok(const vq_index* x) { return label_fp16_dim(x->dim) && x->size >= 1 && x->near_unit; }
+bool label_fp16_ok(const vq_index* x) { return scan_fp16_dim(x->dim) && x->size >= 1 && x->near_unit; }
 
 // Everything that can refuse a labelling call before any work is queued: the mode, for group outputs stale ranks or labels,
 // and mode 2 where the tile path does not exist.
@@ -1991,7 +1991,7 @@ int cluster_run(vq_index* x, const ClusterBufs& b, float* C, int P, int iters, i
 int compound_precheck(vq_index* x, const char* fn, int k, int mode) {
     VQ_TRY(check_ranks(x, fn));
     if (mode != 1) VQ_TRY(refresh_norm_range(x));
-    if (mode == 2) VQ_CHECK(compound_fp16_dim(x->dim) && x->near_unit && k <= CP_K_MAX, "%s: the fp16 path needs dim 256, 512 or 768, "
+    if (mode == 2) VQ_CHECK(scan_fp16_dim(x->dim) && x->near_unit && k <= CP_K_MAX, "%s: the fp16 path needs dim 256, 512 or 768, "
                             "k <= %d and near-unit rows (0.5 <= |row|^2 <= 2; rows added with normalize=0 are measured); mode 1 takes any call",
                             fn, CP_K_MAX);
     return 0;
@@ -2065,7 +2065,7 @@ int compound_run(vq_index* x, const float* d_terms, int m, const int32_t* clause
 }
 
 // ---- shared-footage search (knn_match.h) ----
-bool match_fp16_ok(const vq_index* x) { return match_fp16_dim(x->dim) && x->size >= 1 && x->near_unit; }
+bool match_fp16_ok(const vq_index* x) { return scan_fp16_dim(x->dim) && x->size >= 1 && x->near_unit; }
 
 MatchPlan match_plan_env(int64_t n, int64_t n_groups, int dim, int m, int mode, bool near_unit) {
     return plan_match(n, n_groups, dim, m, mode, near_unit, seq_env("VQ_AMD_MATCH_FILED_CAP"));      // tests only, read per call
@@ -3296,7 +3296,7 @@ int vq_debug_label_plan(int64_t n, int dim, int P, int mode, int64_t largest_gro
     VQ_CHECK(fp16_path && exact_chunk && exact_chunks && exact_bytes && prompt_tiles && prompt_ranges && row_tiles && part_bytes && eps &&
              group_split_rows && group_piece_rows && largest_group_pieces && largest_group >= 0 && largest_group <= n && n >= 1 && n < ((int64_t)1 << 31) && dim > 0 && dim % 4 == 0 && dim <= 4096 && P >= 1 && P <= LABEL_MAX_P && mode >= 0 && mode <= 2,
              "vq_debug_label_plan: takes 0 <= largest_group <= n, 1 <= n < 2^31, a dim vq_index_create takes, 1 <= P <= %d, mode 0, 1 or 2", LABEL_MAX_P);
-    VQ_CHECK(mode != 2 || label_fp16_dim(dim), "vq_debug_label_plan: the fp16 path needs dim 256, 512 or 768");
+    VQ_CHECK(mode != 2 || scan_fp16_dim(dim), "vq_debug_label_plan: the fp16 path needs dim 256, 512 or 768");
     const LabelPlan p = plan_label(n, dim, P, mode, true, largest_group);
     *fp16_path = p.fp16; *exact_chunk = p.exact_chunk; *exact_chunks = p.exact_chunks; *exact_bytes = p.exact_bytes;
     *prompt_tiles = p.prompt_tiles; *prompt_ranges = p.prompt_ranges; *row_tiles = p.row_tiles; *part_bytes = p.part_bytes; *eps = p.eps;
@@ -3478,7 +3478,7 @@ int vq_debug_compound_plan(int64_t n, int dim, int m, int k, int mode, int* fp16
     VQ_CHECK(fp16_path && streams && rescore_pool && exact_bytes && eps && n >= 1 && n < ((int64_t)1 << 31) && dim > 0 && dim % 4 == 0 &&
              dim <= 4096 && m >= 1 && m <= CP_MAX_M && k >= 1 && k <= 1024 && mode >= 0 && mode <= 2,
              "vq_debug_compound_plan: takes 1 <= n < 2^31, a dim vq_index_create takes, 1 <= m <= %d, 1 <= k <= 1024, mode 0, 1 or 2", CP_MAX_M);
-    VQ_CHECK(mode != 2 || (compound_fp16_dim(dim) && k <= CP_K_MAX), "vq_debug_compound_plan: the fp16 path needs dim 256, 512 or 768 and k <= %d",
+    VQ_CHECK(mode != 2 || (scan_fp16_dim(dim) && k <= CP_K_MAX), "vq_debug_compound_plan: the fp16 path needs dim 256, 512 or 768 and k <= %d",
              CP_K_MAX);
     const CompoundPlan p = plan_compound(n, dim, m, nullptr, k, mode, true);
     *fp16_path = p.fp16; *streams = p.streams; *rescore_pool = p.pool; *exact_bytes = p.exact_bytes; *eps = p.eps;
@@ -3632,7 +3632,7 @@ int vq_debug_match_plan(int64_t n, int64_t n_groups, int dim, int m, int mode, i
              launches && n >= 1 && n < ((int64_t)1 << 31) && n_groups >= 1 && n_groups <= n && dim > 0 && dim % 4 == 0 && dim <= 4096 &&
              m >= 1 && m <= MATCH_MAX_M && mode >= 0 && mode <= 2,
              "%s: takes 1 <= n_groups <= n < 2^31, a dim vq_index_create takes, 1 <= m <= %d, mode 0, 1 or 2", fn, MATCH_MAX_M);
-    VQ_CHECK(mode != 2 || match_fp16_dim(dim), "%s: the tile path needs dim 256, 512 or 768", fn);
+    VQ_CHECK(mode != 2 || scan_fp16_dim(dim), "%s: the tile path needs dim 256, 512 or 768", fn);
     VQ_TRY(match_check_bits(fn, m, n));
     const MatchPlan p = match_plan_env(n, n_groups, dim, m, mode, true);
     *fp16_path = p.fp16; *bits_bytes = p.bits_bytes; *exact_chunk = p.exact_chunk; *exact_chunks = p.exact_chunks; *q_tiles = p.q_tiles;
