@@ -858,6 +858,38 @@ int vq_debug_match_plan(int64_t n, int64_t n_groups, int dim, int m, int mode, i
                         int* exact_chunks, int* q_tiles, int* ranges, int64_t* tile_grid, int64_t* filed_cap, int* key_bits,
                         int64_t* run_blocks, int* launches);
 
+/* Library neighbours: for every asked row of the index its k nearest stored rows among the rows that are not "the same" as it.
+ * Every other search starts from a query the caller brings; this one answers the library's questions about itself (which frames
+ * also exist in another video, which videos are related, "more like this frame, elsewhere") from one table.
+ *   Inputs.  rows: m row numbers in host memory (read before the call returns), in any order, repeats allowed: every entry gets
+ *   its line; NULL = every row in row order, and m must then be the index's size.  An entry outside [0, size) is VQ_ERR_INVALID.
+ *   m = 0 is a no-op.
+ *   Eligible set of an asked row r.  exclude = 0: S(r) = { c : c != r }.  exclude = 1: S(r) = { c : group(c) != group(r) }, which
+ *   needs current labels (vq_index_set_groups): stale or missing labels are VQ_ERR_INVALID before anything is queued, as in the
+ *   grouped search.
+ *   Result.  Line r of ids / dist [m][k] holds the first min(k, |S(r)|) rows of S(r) by (d(r, c), tie(c)) ascending, where
+ *   d(r, c) = fp32(1 - fp32(dot(row_c, row_r))) by the fixed-order fp64 chain of vq_index_search with the stored fp32 master of
+ *   row r as the query, used as given, and tie(c) is the row number, or the id rank once vq_index_set_id_ranks was called.
+ *   Unused slots are -1 / +inf.  So with exclude = 1 line r is bit for bit what vq_index_search_filtered(query = master row r,
+ *   groups = {group(r)}, exclude = 1) returns, and with exclude = 0 it is vq_index_search(row r, k + 1) with r struck out.
+ *   Modes follow vq_index_search.  1: exact, 1 <= k <= 1024.  2: fp16 tile scan with the matrix on both sides (per-pair mask),
+ *   exact re-score with proof, exact redo on the device for the rows the proof leaves open; k <= 100; refused with
+ *   VQ_ERR_INVALID unless dim is 256, 512 or 768 and the rows are near-unit.  0: the library's choice (mode 2 from 16,384 stored
+ *   rows and 64 asked rows, when mode 2 would be accepted).
+ *   The _device form takes device result pointers (rows stays host memory) and is asynchronous on the index's stream.
+ *   vq_index_last_search_stats afterwards reports [0] rows proven on the fp16 path, [1] rows of [0] that needed stream rescans,
+ *   [2] rows answered exactly.
+ *   $VQ_AMD_NEIGHBORS_CHUNK (tests only, read per call) replaces the number of asked rows per chunk, rounded up to 256.
+ *   vq_debug_neighbors_plan: the plan for near-unit rows, pure arithmetic, no device: chunk_rows asked rows per chunk (whole
+ *   256-row tiles within the key budget on the fp16 path, within 512 MiB of distances on the exact path), the chunk count, the
+ *   bytes of keys per chunk (0 on the exact path), the re-score kernel's candidate pool (0: 32 candidates, k <= 20; 1: 80, k <= 64; 2: 128,
+ *   k <= 100; four rows per workgroup, up to 8, 8 and 6 stream rescans per row) and eps: rows whose k-th and (k+1)-th eligible scores differ by more than 4 eps are proven. */
+int vq_index_neighbors(vq_index* idx, const int64_t* rows, int64_t m, int k, int exclude, int mode, int32_t* ids, float* dist);
+int vq_index_neighbors_device(vq_index* idx, const int64_t* rows, int64_t m, int k, int exclude, int mode, void* d_ids_i32,
+                              void* d_dist_f32);
+int vq_debug_neighbors_plan(int64_t n, int dim, int64_t m, int k, int exclude, int mode, int* fp16_path, int64_t* chunk_rows,
+                            int64_t* chunks, int64_t* key_bytes, int* rescore_kind, float* eps);
+
 /* Compound search: the k best rows that match ALL of several prompts — "a dog AND a beach, in the same frame, but NOT at night".
  * Adding the prompt vectors ranks by the SUM of the similarities: a frame that shows one term very well and the other not at all
  * beats a frame that shows both.  Here a frame's WORST required term decides its place.

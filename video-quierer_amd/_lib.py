@@ -174,6 +174,10 @@ SIGNATURES = {
     "vq_debug_match_plan": (c_int, [c_int64, c_int64, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int64), POINTER(c_int), POINTER(c_int),
                                     POINTER(c_int), POINTER(c_int), POINTER(c_int64), POINTER(c_int64), POINTER(c_int), POINTER(c_int64),
                                     POINTER(c_int)]),
+    "vq_index_neighbors": (c_int, [c_void_p, POINTER(c_int64), c_int64, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_float)]),
+    "vq_index_neighbors_device": (c_int, [c_void_p, POINTER(c_int64), c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vq_debug_neighbors_plan": (c_int, [c_int64, c_int, c_int64, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int64), POINTER(c_int64),
+                                        POINTER(c_int64), POINTER(c_int), POINTER(c_float)]),
     "vq_index_label_rows": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_float, POINTER(c_int32), POINTER(c_float), c_int,
                                     POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "vq_index_label_rows_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p,

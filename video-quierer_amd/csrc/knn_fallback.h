@@ -60,13 +60,14 @@ void collect_flags_kernel(const int32_t* __restrict__ flags, int nq, int32_t* __
 }
 
 // MASK (filtered search): rows whose group is disallowed never join a list.  MASK = false compiles to the unfiltered kernel.
-template <bool MASK = false>
+// Elig (vq_common.h; library neighbours): rows not eligible for a query never join THAT query's list; EligAll changes nothing.
+template <bool MASK = false, class Elig = EligAll>
 __global__ __launch_bounds__(FB_TILE)
 void exact_fallback_kernel(const float* __restrict__ rows, int64_t n, int dim,
                            const float* __restrict__ queries, const int32_t* __restrict__ slots,
                            const int32_t* __restrict__ counters, int slot_base, int slot_cap, int k,
                            int64_t rows_per_split, uint64_t* __restrict__ partial /*[slot_cap][splits][k]*/, const TieOrder tie,
-                           const GroupMask mask = {}) {
+                           const GroupMask mask = {}, const Elig elig = Elig{}) {
     const int count = min(counters[0] - slot_base, slot_cap);          // flagged queries of this round (uniform)
     if (count <= 0) return;
     __shared__ float xs[FB_TILE][FB_PANEL + 1];
@@ -141,7 +142,7 @@ void exact_fallback_kernel(const float* __restrict__ rows, int64_t n, int dim,
             for (int j = 0; j < FB_QG; ++j) {
                 if (qidx[j] < 0) continue;                                           // block-uniform
                 const uint64_t key = dist_key(1.0f - (float)acc[j], my_tie);
-                const bool in = row_ok && key < best[cur_s[j]][j][k - 1];
+                const bool in = row_ok && elig(qidx[j], row) && key < best[cur_s[j]][j][k - 1];
                 const unsigned long long mask = __ballot(in);
                 if (mask == 0) continue;                                             // wave-uniform
                 const int lane = tid & 63;

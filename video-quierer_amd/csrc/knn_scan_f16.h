@@ -314,7 +314,12 @@ __device__ __forceinline__ float exact_row_dist(const float* __restrict__ row, c
 // (video_search_system.py:297), and a proof needs the (C+1)-th key at least a bound's width below the k-th exact score, i.e.
 // C well above k: with C = 32, k in (20, 32] sent nearly every query to the exact fallback.  layout 3 = the streaming scan's
 // query-major keys (small batches with k > RV_K_SMALL come here instead of rescore_verify_small_kernel).
-template <int QPW, int KEEP, int C>
+// Elig (vq_common.h): which (query, row) pairs exist at all.  A scan that masked pairs left keys over eligible rows only, so every
+// bound above is one over eligible rows; the kernel itself meets rows the scan did not hand it in two places — a candidate whose
+// key is the masked sentinel, and the rows of a re-scanned stream — and drops the ineligible ones there.  EligAll is the
+// unfiltered kernel.  RESC: streams re-scored in full per query before the query is flagged (the pool in LDS grows by 128 rows
+// each): 4 everywhere but the library neighbours, whose candidates come in runs of adjacent rows (knn_neighbors.h).
+template <int QPW, int KEEP, int C, class Elig = EligAll, int RESC = RV_RESCAN_MAX>
 __global__ __launch_bounds__(256)
 void rescore_verify_kernel_t(const uint32_t* __restrict__ keys, int64_t streams, int64_t q_pad,
                            const float* __restrict__ rows, int64_t n_valid, int dim,
@@ -322,8 +327,8 @@ void rescore_verify_kernel_t(const uint32_t* __restrict__ keys, int64_t streams,
                            int32_t* __restrict__ out_ids, float* __restrict__ out_dist,
                            int32_t* __restrict__ flags, int layout /*1: scan_f16_top2, 2: the 256 x 2048 scans (scan2_row_of), 3: scan3_f16_top2 streams*/,
                            float eps_rows /* scan_eps_unit(dim) x the largest |row| in the index */,
-                           const TieOrder tie /* (distance, id) order of the result: vq_common.h */) {
-    constexpr int SHARES = 256 / QPW, TPQ = 256 / QPW, POOL = C + RV_RESCAN_MAX * SCAN_STREAM_ROWS;
+                           const TieOrder tie /* (distance, id) order of the result: vq_common.h */, const Elig elig = Elig{}) {
+    constexpr int SHARES = 256 / QPW, TPQ = 256 / QPW, POOL = C + RESC * SCAN_STREAM_ROWS;
     __shared__ float kept_v[QPW][SHARES * KEEP];      // kept key values (with packed index bits)
     __shared__ int kept_s[QPW][SHARES * KEEP];        // stream*2 + which (0: 1st key, 1: 2nd key)
     __shared__ float share_floor[QPW][SHARES];           // upper bound of what a share dropped
@@ -333,7 +338,7 @@ void rescore_verify_kernel_t(const uint32_t* __restrict__ keys, int64_t streams,
     __shared__ int cand_src[QPW][C];
     __shared__ int pool_n[QPW];
     __shared__ float bound_rest[QPW];                       // (C+1)-th kept key
-    __shared__ int resc_stream[QPW][RV_RESCAN_MAX];
+    __shared__ int resc_stream[QPW][RESC];
     __shared__ int resc_n[QPW];
     __shared__ int state[QPW];
     __shared__ float qn2[QPW][SHARES];                   // partial |q|^2 (the bound scales with |q|)
@@ -493,7 +498,7 @@ void rescore_verify_kernel_t(const uint32_t* __restrict__ keys, int64_t streams,
             const uint32_t kb = __builtin_bit_cast(uint32_t, cand_key[ql][c]);
             const int64_t r = layout == 3 ? scan3_row_of(src >> 1, (int)(kb & 127u))
                             : layout == 2 ? scan2_row_of(src >> 1, (int)(kb & 127u)) : scan_row_of(src >> 1, (int)(kb & 127u));
-            if (r < n_valid) { row = (int)r; d = 1.0f - exact_dot_chain_pf(rows + (size_t)r * dim, qv, dim); }
+            if (r < n_valid && elig(q, r)) { row = (int)r; d = 1.0f - exact_dot_chain_pf(rows + (size_t)r * dim, qv, dim); }
         }
         cand_row[ql][c] = row; cand_dist[ql][c] = d;
     }
@@ -539,7 +544,7 @@ void rescore_verify_kernel_t(const uint32_t* __restrict__ keys, int64_t streams,
                 // a stream whose 2nd key is among the candidates hides rows bounded only by that key
                 for (int c = 0; c < C; ++c) {
                     if ((cand_src[qq][c] & 1) && cand_key[qq][c] + SCAN_EPS >= sk) {
-                        if (resc_n[qq] < RV_RESCAN_MAX) resc_stream[qq][resc_n[qq]++] = cand_src[qq][c] >> 1;
+                        if (resc_n[qq] < RESC) resc_stream[qq][resc_n[qq]++] = cand_src[qq][c] >> 1;
                         else st = 2;
                     }
                 }
@@ -565,7 +570,7 @@ void rescore_verify_kernel_t(const uint32_t* __restrict__ keys, int64_t streams,
             const int64_t r = layout == 3 ? scan3_row_of(resc_stream[qq][which], local)
                             : layout == 2 ? scan2_row_of(resc_stream[qq][which], local) : scan_row_of(resc_stream[qq][which], local);
             int row = -1; float d = __builtin_inff();
-            if (r < n_valid) { row = (int)r; d = 1.0f - exact_dot_chain_pf(rows + (size_t)r * dim, qv2, dim); }
+            if (r < n_valid && elig(q0 + qq, r)) { row = (int)r; d = 1.0f - exact_dot_chain_pf(rows + (size_t)r * dim, qv2, dim); }
             cand_row[qq][C + i] = row; cand_dist[qq][C + i] = d;
         }
         if (tid == 0) pool_n[qq] = C + nres * SCAN_STREAM_ROWS;

@@ -85,6 +85,18 @@ struct GroupMask {
 };
 __device__ __forceinline__ bool group_allowed(const uint32_t* bits, int32_t g) { return g >= 0 && ((bits[g >> 5] >> (g & 31)) & 1u); }
 
+// Eligibility of a (query, row) pair in the re-score kernels (knn_scan_f16.h) and the exact redo (knn_fallback.h), a template
+// parameter of both.  EligAll: every pair; it compiles to the kernels as they were.  EligTag (library neighbours, knn_neighbors.h):
+// a pair is struck when the two tags are equal — the row's tag is its label (rtag) or, with rtag null, its row number.
+struct EligAll {
+    __device__ __forceinline__ bool operator()(int, int64_t) const { return true; }
+};
+struct EligTag {
+    const int32_t* qtag;   // [queries of the launch]
+    const int32_t* rtag;   // [n] or null
+    __device__ __forceinline__ bool operator()(int q, int64_t row) const { return (rtag ? rtag[row] : (int32_t)row) != qtag[q]; }
+};
+
 struct TieOrder {
     const int32_t* rank;   // [n] rank of row r
     const int32_t* row;    // [n] row of rank t

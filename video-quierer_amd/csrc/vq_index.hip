@@ -21,6 +21,7 @@
 #include "knn_compound.h"
 #include "knn_cluster.h"
 #include "knn_match.h"
+#include "knn_neighbors.h"
 #include "scan_plan.h"
 #include "host_buffers.h"
 #ifdef VQ_SCAN_EXPERIMENTS      // `make EXPERIMENTS=1`: the two superseded batch mainloops behind VQ_AMD_SCAN=2|4
@@ -194,6 +195,12 @@ struct vq_index {
     IdxBuf<uint64_t> d_mw;
     IdxBuf<float> d_mqe;
     IdxBuf<int32_t> d_mout;
+    // library neighbours (knn_neighbors.h): the call's row list; a chunk's tags; a chunk's gathered fp32 masters (row-list calls;
+    // their fp16 copies go to d_q16).  Keys, flags, the redo's scratch and the counters are the fp16 search's and the grouped
+    // search's (d_keys, d_flags, d_slots, d_counters, d_fb_partial; totals in d_gcounters)
+    IdxBuf<int32_t> d_nbrows;
+    IdxBuf<int32_t> d_nbtag;
+    IdxBuf<float> d_nbq;
     // clip-search scratch (knn_set.h): per-group sums [2][G], candidate list / positions [2][G] + count + flag, |q_i| [m],
     // order keys [G] + the selection's block lists, candidate keys, result staging of the host form
     IdxBuf<double> d_ssum;
@@ -374,6 +381,7 @@ int check_positions(const vq_index* x, const char* fn) {
 // mode 0 (auto): the fp16 scans pay once the matrix is large enough to amortise their fixed costs
 constexpr int64_t FP16_AUTO_MIN_ROWS = 16384;
 static_assert(DST_FP16_MIN_ROWS == FP16_AUTO_MIN_ROWS, "knn_distinct.h: the auto mode's threshold");
+static_assert(NB_FP16_MIN_ROWS == FP16_AUTO_MIN_ROWS, "knn_neighbors.h: the auto mode's threshold");
 
 void fill_no_result(vq_index* x, int32_t* ids, float* dist, int64_t count) {
     hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, ids, dist, count);
@@ -489,20 +497,22 @@ int reserve_fallback(vq_index* x, int nq, int k) {
 
 // The exact redo of the queries whose proof did not close (knn_fallback.h), sized from the device-side flagged count.
 // mask (filtered search): the masked kernel, which lists allowed rows only
+// elig (library neighbours): the per-query eligibility of knn_fallback.h's second template parameter
+template <class Elig = EligAll>
 void launch_fallback(vq_index* x, const float* d_queries, int nq, int k, int32_t* d_ids, float* d_dist_out, const int32_t* counters,
-                     const GroupMask* mask = nullptr) {
-    auto fb = mask ? exact_fallback_kernel<true> : exact_fallback_kernel<false>;
+                     const GroupMask* mask = nullptr, const Elig elig = Elig{}) {
+    auto fb = mask ? exact_fallback_kernel<true, Elig> : exact_fallback_kernel<false, Elig>;
     const GroupMask gm = mask ? *mask : GroupMask{};
     const int64_t n = x->size;
     const FallbackPlan f = fallback_plan(n, nq, k);
     Prof p(x, I_EXACT_DIST);
     hipLaunchKernelGGL(fb, dim3(f.fast_splits, 1), dim3(FB_TILE), 0, x->stream, x->rows, n, x->dim,
-                       d_queries, x->d_slots, counters, 0, FB_FAST_SLOTS, k, f.fast_rows, x->d_fb_partial, x->tie(), gm);
+                       d_queries, x->d_slots, counters, 0, FB_FAST_SLOTS, k, f.fast_rows, x->d_fb_partial, x->tie(), gm, elig);
     hipLaunchKernelGGL(fallback_merge_kernel, dim3(FB_FAST_SLOTS), dim3(256), 0, x->stream, x->d_fb_partial, f.fast_splits, k, x->d_slots,
                        counters, 0, FB_FAST_SLOTS, d_ids, d_dist_out, x->tie());
     for (int64_t base = FB_FAST_SLOTS; base < nq; base += f.round_q) {
         hipLaunchKernelGGL(fb, dim3(f.splits, FB_SLOT_LANES), dim3(FB_TILE), 0, x->stream, x->rows, n, x->dim,
-                           d_queries, x->d_slots, counters, (int)base, (int)f.round_q, k, f.rows, x->d_fb_partial, x->tie(), gm);
+                           d_queries, x->d_slots, counters, (int)base, (int)f.round_q, k, f.rows, x->d_fb_partial, x->tie(), gm, elig);
         hipLaunchKernelGGL(fallback_merge_kernel, dim3(64), dim3(256), 0, x->stream, x->d_fb_partial, f.splits, k, x->d_slots,
                            counters, (int)base, (int)f.round_q, d_ids, d_dist_out, x->tie());
     }
@@ -600,7 +610,7 @@ int launch_rescore(vq_index* x, const ScanPlan& p, const float* qp, int cur, int
                            eps_rows, p.rescore_files_flags ? x->d_slots.p : nullptr, p.rescore_files_flags ? counters : nullptr, x->tie());
     else
         hipLaunchKernelGGL(batch, grid, dim3(256), 0, x->stream, x->d_keys, p.streams, qpad, x->rows, n, x->dim, qp, cur, k, ids, dist, flags, p.layout,
-                           eps_rows, x->tie());
+                           eps_rows, x->tie(), EligAll{});
     return 0;
 }
 
@@ -2192,6 +2202,122 @@ int match_run(vq_index* x, const char* fn, const float* d_queries, int m, int k,
     return 0;
 }
 
+// ---- library neighbours (knn_neighbors.h) ----
+// $VQ_AMD_NEIGHBORS_CHUNK (tests): asked rows per chunk, read per call
+int64_t neighbors_chunk_override() {
+    const char* e = getenv("VQ_AMD_NEIGHBORS_CHUNK");
+    return e ? std::max<int64_t>(0, atoll(e)) : 0;
+}
+
+// Refusals, before anything is queued; then the plan.
+int neighbors_precheck(vq_index* x, const char* fn, const int64_t* rows, int64_t m, int k, int exclude, int mode, NeighborsPlan* p) {
+    VQ_TRY(check_mode(fn, mode));
+    VQ_TRY(check_ranks(x, fn));
+    if (exclude) VQ_TRY(check_labels(x, fn));
+    VQ_CHECK(rows || m == x->size, "%s: rows = NULL asks for every row: m must be the index's size %lld, not %lld", fn, (long long)x->size, (long long)m);
+    if (rows)
+        for (int64_t i = 0; i < m; ++i)
+            VQ_CHECK(rows[i] >= 0 && rows[i] < x->size, "%s: rows[%lld] = %lld, the index holds rows 0 .. %lld", fn, (long long)i, (long long)rows[i],
+                     (long long)x->size - 1);
+    if (mode != 1) VQ_TRY(refresh_norm_range(x));
+    *p = plan_neighbors(x->size, x->dim, m, k, mode, x->near_unit, neighbors_chunk_override());
+    if (mode == 2) VQ_CHECK(p->fp16, "%s: the fp16 path needs dim 256, 512 or 768, k <= %d and near-unit rows (0.5 <= |row|^2 <= 2; rows added "
+                                     "with normalize=0 are measured)", fn, RV_K_MAX);
+    return 0;
+}
+
+// rows: host memory or null (every row); d_ids / d_out [m][k] device memory.  Asynchronous on the index's stream.
+int neighbors_run(vq_index* x, const int64_t* rows, int64_t m, int k, int exclude, const NeighborsPlan& p, int32_t* d_ids, float* d_out) {
+    const int64_t n = x->size;
+    const int dim = x->dim;
+    const int32_t* group_of = exclude ? x->d_group.p : nullptr;
+    const int32_t* list = nullptr;
+    if (rows) {                                          // the row list goes up through a pinned staging slot, like the filter lists
+        VQ_TRY(x->d_nbrows.reserve(m));
+        StageSlot* slot;
+        VQ_TRY(stage_slot(x, m, &slot));
+        int32_t* h = slot->h;
+        for (int64_t i = 0; i < m; ++i) h[i] = (int32_t)rows[i];
+        VQ_HIP(hipMemcpyAsync(x->d_nbrows, h, (size_t)m * 4, hipMemcpyHostToDevice, x->stream));
+        VQ_HIP(hipEventRecord(slot->ev, x->stream));
+        list = x->d_nbrows;
+        VQ_TRY(x->d_nbq.reserve(p.chunk_rows * dim));
+    }
+    VQ_TRY(x->d_nbtag.reserve(p.chunk_rows));
+    const EligTag elig{x->d_nbtag, group_of};
+    auto rescore = rescore_verify_kernel_t<NB_RESCORE_QPW, RV_KEEP, RV_C, EligTag, NB_RESCAN>;
+    if (p.fp16) {
+        if (rows) VQ_TRY(x->d_q16.reserve(p.chunk_rows * dim));
+        VQ_TRY(x->d_keys.reserve(p.streams * p.chunk_rows * 2));
+        VQ_TRY(x->d_flags.reserve(p.chunk_rows));
+        VQ_TRY(reserve_fallback(x, (int)p.chunk_rows, k));
+        VQ_TRY(ensure_gcounters(x));
+        VQ_HIP(hipMemsetAsync(x->d_gcounters, 0, 3 * sizeof(unsigned long long), x->stream));
+        VQ_TRY(set_dyn_lds(x, (const void*)neighbors_tile_kernel, NB_LDS_BYTES));
+        if (p.rescore == RESCORE_LARGE4) rescore = rescore_verify_kernel_t<NB_RESCORE_QPW, RVL_KEEP, RVL_C, EligTag, NB_RESCAN>;
+        if (p.rescore == RESCORE_XLARGE4) rescore = rescore_verify_kernel_t<NB_RESCORE_QPW, RVX_KEEP, RVX_C, EligTag, NB_RESCAN_XL>;
+        x->last_scan.valid = false;                      // d_keys is taken
+    }
+    const float eps_rows = scan_eps_unit(dim) * x->row_norm_max;
+    const int rb = 2;                                    // 4 ranges x 8 resident tiles per block of 32 workgroups (knn_scan_fold.h)
+    const int range_groups = (p.ranges + (1 << rb) - 1) >> rb;
+    const bool one_wg = n <= SEL_SMALL_MAX_N && k <= 256;
+    for (int64_t q0 = 0; q0 < m; q0 += p.chunk_rows) {
+        const int cur = (int)std::min<int64_t>(p.chunk_rows, m - q0);
+        const int64_t qpad = round_up(cur, NB_ROW_TILE);
+        const int qt = (int)(qpad / NB_ROW_TILE);
+        int32_t* ids0 = d_ids + q0 * k;
+        float* out0 = d_out + q0 * k;
+        {
+            Prof pr(x, I_TO_F16);
+            hipLaunchKernelGGL(neighbors_prepare_kernel, dim3((unsigned)std::min<int64_t>(cdiv(qpad, 4), 4096)), dim3(256), 0, x->stream, list, q0, cur,
+                               qpad, group_of, x->rows.p, x->rows16.p, dim, x->d_nbtag.p, x->d_nbq.p, p.fp16 && rows ? x->d_q16.p : nullptr);
+        }
+        const float* qp = rows ? x->d_nbq.p : x->rows + q0 * dim;           // the re-score's and the redo's queries: the fp32 masters
+        if (!p.fp16) {
+            VQ_TRY(exact_topk(x, n, cur, k, one_wg, x->tie(), ids0, out0, [&](int s0, int c, int64_t ld) {
+                VQ_TRY(exact_dist(x, false, qp + (int64_t)s0 * dim, c, ld));
+                Prof pr(x, I_SELECT);
+                hipLaunchKernelGGL(neighbors_strike_kernel, dim3(c), dim3(256), 0, x->stream, x->d_dist.p, ld, x->d_nbtag + s0,
+                                   exclude ? x->d_goff : nullptr, exclude ? x->d_grows : nullptr);
+                return 0;
+            }));
+            Prof pr(x, I_SELECT);
+            hipLaunchKernelGGL(neighbors_fix_kernel, dim3(grid_for((int64_t)cur * k)), dim3(256), 0, x->stream, ids0, out0, (int64_t)cur * k);
+            continue;
+        }
+        const uint16_t* a16 = rows ? x->d_q16.p : x->rows16 + q0 * dim;     // every row: the scan copy itself is the resident operand
+        {
+            Prof pr(x, I_MFMA_SCAN);
+            const int qb = 32 >> rb;
+            hipLaunchKernelGGL(neighbors_tile_kernel, dim3(range_groups * ((qt + qb - 1) / qb) * 32), dim3(G2_THREADS), NB_LDS_BYTES, x->stream, a16,
+                               x->d_nbtag.p, x->rows16.p, group_of, dim, n, cur, qt, p.ranges, range_groups, x->d_keys.p, rb);
+        }
+        {
+            Prof pr(x, I_RESCORE);
+            hipLaunchKernelGGL(rescore, dim3(cdiv(cur, p.rescore_qpw)), dim3(256), 0, x->stream, x->d_keys.p, p.streams, qpad, x->rows.p, n, dim, qp, cur, k,
+                               ids0, out0, x->d_flags.p, 2, eps_rows, x->tie(), elig);
+        }
+        // the rows the proof left open are redone exactly under the same eligibility, sized on the device (search_fp16 says how)
+        hipLaunchKernelGGL(collect_flags_kernel, dim3(1), dim3(1024), 0, x->stream, x->d_flags.p, cur, x->d_slots.p, x->d_counters.p);
+        launch_fallback(x, qp, cur, k, ids0, out0, x->d_counters.p, nullptr, elig);
+        hipLaunchKernelGGL(neighbors_stats_kernel, dim3(1), dim3(64), 0, x->stream, x->d_counters.p, x->d_gcounters.p);
+        VQ_HIP(hipGetLastError());
+    }
+    VQ_HIP(hipGetLastError());
+    if (!p.fp16) { set_stats(x, STATS_HOST, 0, 0, m); return 0; }
+    VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+    set_stats(x, STATS_GCOUNTERS);
+    return 0;
+}
+
+int check_neighbors_args(const char* fn, const vq_index* x, int64_t m, int k, int exclude, int mode, bool arrays) {
+    VQ_TRY(require_init());
+    VQ_CHECK(x && m >= 0 && m < ((int64_t)1 << 31) && (exclude == 0 || exclude == 1) && (m == 0 || arrays), "%s: bad argument", fn);
+    VQ_CHECK(k >= 1 && k <= (mode == 2 ? RV_K_MAX : NB_K_EXACT_MAX), "%s: k = %d, takes 1 <= k <= %d (mode 2: %d)", fn, k, NB_K_EXACT_MAX, RV_K_MAX);
+    return 0;
+}
+
 // ---- what the search entry points share ----
 // One argument check per shape of call.  arrays: every array the call reads or writes is there.
 int check_batch_args(const char* fn, const vq_index* x, int nq, int k, bool arrays) {
@@ -3638,6 +3764,46 @@ int vq_debug_match_plan(int64_t n, int64_t n_groups, int dim, int m, int mode, i
     *fp16_path = p.fp16; *bits_bytes = p.bits_bytes; *exact_chunk = p.exact_chunk; *exact_chunks = p.exact_chunks; *q_tiles = p.q_tiles;
     *ranges = p.ranges; *tile_grid = p.tile_grid; *filed_cap = p.filed_cap; *key_bits = 3 * p.key_m_bits + p.key_d_bits;
     *run_blocks = p.run_blocks; *launches = p.launches;
+    return 0;
+}
+
+int vq_index_neighbors_device(vq_index* x, const int64_t* rows, int64_t m, int k, int exclude, int mode, void* d_ids, void* d_dist) {
+    static const char* fn = "vq_index_neighbors_device";
+    VQ_TRY(check_neighbors_args(fn, x, m, k, exclude, mode, d_ids && d_dist));
+    std::lock_guard<std::mutex> lk(x->mu);
+    NeighborsPlan p;
+    VQ_TRY(neighbors_precheck(x, fn, rows, m, k, exclude, mode, &p));
+    if (m == 0) return 0;
+    return neighbors_run(x, rows, m, k, exclude, p, (int32_t*)d_ids, (float*)d_dist);
+}
+
+int vq_index_neighbors(vq_index* x, const int64_t* rows, int64_t m, int k, int exclude, int mode, int32_t* ids, float* dist) {
+    static const char* fn = "vq_index_neighbors";
+    VQ_TRY(check_neighbors_args(fn, x, m, k, exclude, mode, ids && dist));
+    std::lock_guard<std::mutex> lk(x->mu);
+    NeighborsPlan p;
+    VQ_TRY(neighbors_precheck(x, fn, rows, m, k, exclude, mode, &p));
+    if (m == 0) return 0;
+    const int64_t count = m * k;
+    VQ_TRY(reserve_id_dist(x, count));
+    VQ_TRY(neighbors_run(x, rows, m, k, exclude, p, x->d_ids, x->d_out));
+    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return 0;
+}
+
+// plan_neighbors' answer for near-unit rows; needs no device
+int vq_debug_neighbors_plan(int64_t n, int dim, int64_t m, int k, int exclude, int mode, int* fp16_path, int64_t* chunk_rows, int64_t* chunks,
+                            int64_t* key_bytes, int* rescore_kind, float* eps) {
+    static const char* fn = "vq_debug_neighbors_plan";
+    VQ_CHECK(fp16_path && chunk_rows && chunks && key_bytes && rescore_kind && eps && n >= 1 && n < ((int64_t)1 << 31) && dim > 0 && dim % 4 == 0 &&
+             dim <= 4096 && m >= 1 && m < ((int64_t)1 << 31) && (exclude == 0 || exclude == 1) && mode >= 0 && mode <= 2,
+             "%s: takes 1 <= n < 2^31, a dim vq_index_create takes, 1 <= m < 2^31, exclude 0 or 1, mode 0, 1 or 2", fn);
+    VQ_CHECK(k >= 1 && k <= (mode == 2 ? RV_K_MAX : NB_K_EXACT_MAX), "%s: k = %d, takes 1 <= k <= %d (mode 2: %d)", fn, k, NB_K_EXACT_MAX, RV_K_MAX);
+    VQ_CHECK(mode != 2 || scan_fp16_dim(dim), "%s: the fp16 path needs dim 256, 512 or 768", fn);
+    const NeighborsPlan p = plan_neighbors(n, dim, m, k, mode, true, neighbors_chunk_override());
+    *fp16_path = p.fp16; *chunk_rows = p.chunk_rows; *chunks = p.chunks; *key_bytes = p.key_bytes; *rescore_kind = p.rescore; *eps = p.eps;
     return 0;
 }
 

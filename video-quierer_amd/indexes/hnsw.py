@@ -1396,6 +1396,60 @@ class HNSWIndex:
             _lib.check(_lib.load().vq_index_read_rows(self._h, _lib.i64ptr(rn), len(rn), _lib.fptr(unit)))
             return self._shared_runs(unit, k, md, lo, miss, flt, group_of, position_of, given=True)
 
+    # -- library neighbours: every stored row's nearest rows elsewhere ------------------------
+    NEIGHBORS_MAX_K = 1024
+
+    def _neighbors(self, rows: Optional[np.ndarray], k: int, other_groups: bool, group_of: GROUP_OF, mode: int):
+        """One device call, under the lock.  rows: int64 row numbers, or None for every row.  (rows int32 [m][k], distances
+        float32 [m][k]); unused slots -1 / inf."""
+        k = int(k)
+        if not 1 <= k <= self.NEIGHBORS_MAX_K:
+            raise ValueError(f"k must be in 1 .. {self.NEIGHBORS_MAX_K}, got {k}")
+        if int(mode) not in (MODE_AUTO, 1, 2):
+            raise ValueError(f"mode {mode} unknown (0 auto, 1 exact path, 2 fp16 path)")
+        m = len(self._ids) if rows is None else len(rows)
+        out_rows = np.full((m, k), -1, dtype=np.int32)
+        out_dist = np.full((m, k), np.inf, dtype=np.float32)
+        if m == 0 or self._empty():
+            return out_rows, out_dist
+        if not self._identity:
+            self._sync_tie_order()
+        if other_groups:
+            self._sync_groups(group_of)
+        _lib.check(_lib.load().vq_index_neighbors(self._h, None if rows is None else _lib.i64ptr(rows), m, k, 1 if other_groups else 0,
+                                                  int(mode), _lib.i32ptr(out_rows), _lib.fptr(out_dist)))
+        return out_rows, out_dist
+
+    def _rows_of_ids(self, ids: Iterable[Hashable]) -> np.ndarray:
+        try:
+            return np.array([self._row_of[i] for i in ids], dtype=np.int64)
+        except KeyError as e:
+            raise KeyError(f"id {e.args[0]!r} is not in the index") from None
+
+    def neighbors(self, k: int = 5, *, ids: Optional[Iterable[Hashable]] = None, other_groups: bool = False,
+                  group_of: GROUP_OF = None, mode: int = MODE_AUTO) -> Tuple[np.ndarray, np.ndarray]:
+        """The library's neighbour table: for every stored row (``ids=None``, in add order) or for the rows of ``ids`` (in
+        their order; repeats allowed) the ``k`` nearest OTHER stored rows.  ``other_groups=False``: every row but the row
+        itself.  ``other_groups=True``: only rows of other groups (videos, under ``group_of``, default ``video_of``) — "where
+        else does this frame appear".  Returns ``(rows int32 [m][k], distances float32 [m][k])`` in ROW numbers (``index._ids[r]``
+        is the id), nearest first by ``search``'s (distance, id) order (ids without a common order: equal distances in row
+        order); a row with fewer than ``k`` eligible rows has -1 / inf in its unused slots.  The distances are ``search``'s, bit
+        for bit: line r is what ``search_filtered(stored row r, k, exclude=[group of r])`` (or ``search(row r, k + 1)`` without
+        r) returns.  Exact in every mode; ``mode`` as ``search_mode`` (2 takes k <= 100).  ``KeyError`` for an unknown id."""
+        with self.lock:
+            rows = None if ids is None else self._rows_of_ids(ids)
+            return self._neighbors(rows, k, other_groups, group_of, mode)
+
+    def neighbors_of(self, node_id: Hashable, k: int = 5, *, other_groups: bool = False, group_of: GROUP_OF = None) -> List[Dict]:
+        """"More like this frame": the ``k`` nearest other stored rows of one stored id (``other_groups``: of other videos only),
+        as ``search`` returns them: ``[{'id', 'distance', 'score'}]``.  ``KeyError`` for an unknown id."""
+        with self.lock:
+            rows = self._rows_of_ids([node_id])
+            if k <= 0:
+                return []
+            out_rows, out_dist = self._neighbors(rows, k, other_groups, group_of, self.search_mode)
+            return _hits(self._id_of(), out_rows[0].tolist(), out_dist[0])
+
     def synchronize(self) -> None:
         _lib.check(_lib.load().vq_index_synchronize(self._h))
 

@@ -291,6 +291,59 @@ class SimpleVideoIndex:
                         "end": last["timestamp"], "query_start": stamps[r["query_first"]], "query_end": stamps[r["query_first"] + r["span"] - 1]})
         return out
 
+    def _other_video_neighbors(self, per_frame: int):
+        """The library's neighbour table: for every stored frame its ``per_frame`` nearest frames of OTHER videos
+        (``HNSWIndex.neighbors(other_groups=True)`` on the embeddings as stored: exact, ties between frames as ``search``).
+        (rows int32 [n][per_frame], distances float32 [n][per_frame]); row r is frame r of ``metadata``."""
+        return self._device(ranks=True).neighbors(per_frame, other_groups=True, group_of=self._group_fn)
+
+    def related_videos(self, k: int = 5, per_frame: int = 3) -> Dict[str, List[Dict]]:
+        """For every indexed video the k other videos its frames land in most: each frame votes for the videos of its
+        ``per_frame`` nearest frames of other videos.  ``{video_name: [{'video_name', 'votes', 'share', 'score'}]}`` with
+        ``votes`` the number of (frame, neighbour) pairs that landed in that video, ``share`` = votes over the video's filled
+        neighbour slots, ``score`` the mean cosine similarity of those pairs; ordered by votes descending, then mean distance
+        ascending, then name.  One neighbour table over the whole library (exact)."""
+        if k <= 0 or per_frame <= 0:
+            raise ValueError(f"k and per_frame must be at least 1, got {k}, {per_frame}")
+        if not self.embeddings:
+            return {}
+        rows, dist = self._other_video_neighbors(int(per_frame))
+        names = [md["video_name"] for md in self.metadata]
+        tally: Dict[str, Dict[str, List]] = {}
+        filled: Dict[str, int] = {}
+        for r, (rr, dd) in enumerate(zip(rows.tolist(), dist.tolist())):
+            mine = tally.setdefault(names[r], {})
+            for c, d in zip(rr, dd):
+                if c < 0:
+                    continue
+                filled[names[r]] = filled.get(names[r], 0) + 1
+                cell = mine.setdefault(names[c], [0, 0.0])
+                cell[0] += 1
+                cell[1] += d
+        out = {}
+        for name, mine in tally.items():
+            order = sorted(mine.items(), key=lambda kv: (-kv[1][0], kv[1][1] / kv[1][0], kv[0]))[:k]
+            out[name] = [{"video_name": other, "votes": v, "share": v / filled[name], "score": 1.0 - s / v} for other, (v, s) in order]
+        return out
+
+    def duplicate_frames(self, min_similarity: float = 0.97) -> List[Dict]:
+        """Every frame whose nearest frame of another video is at least ``min_similarity`` similar (cosine):
+        ``[{'video_name', 'timestamp', 'other_video', 'other_timestamp', 'score'}]`` in frame order.  The same neighbour
+        table as ``related_videos`` at one neighbour per frame (exact)."""
+        if not min_similarity <= 1:                               # (NaN too)
+            raise ValueError(f"min_similarity must be <= 1, got {min_similarity}")
+        if not self.embeddings:
+            return []
+        rows, dist = self._other_video_neighbors(1)
+        out = []
+        for r in np.flatnonzero(rows[:, 0] >= 0).tolist():
+            score = np.float32(1.0) - dist[r, 0]
+            if score >= min_similarity:
+                a, b = self.metadata[r], self.metadata[int(rows[r, 0])]
+                out.append({"video_name": a["video_name"], "timestamp": a["timestamp"], "other_video": b["video_name"],
+                            "other_timestamp": b["timestamp"], "score": float(score)})
+        return out
+
     def video_summary(self, video_name: str, k: int = 5, max_radius: Optional[float] = None, chronological: bool = False) -> List[Dict]:
         """The k frames that show what is in ``video_name`` (a poster frame and a thumbnail strip): ``search``'s metadata dicts
         ``{'video_name', 'timestamp', 'frame_id'}`` plus ``'rank'`` (selection order: rank 0 is the frame most like the video as
