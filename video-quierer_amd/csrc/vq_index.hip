@@ -97,8 +97,8 @@ struct vq_index {
     IdxBuf<float> d_q;             // queries [nq][dim]
     IdxBuf<float> d_dist;          // exact distances
     IdxBuf<uint64_t> d_partial;    // per-chunk top-k keys
-    IdxBuf<int32_t> d_ids;         // host forms: device results
-    IdxBuf<float> d_out;
+    IdxBuf<char> d_res;            // a host form's results until they are copied back, laid out by outs_place: one call at a time
+                                   // holds the lock and ends with a stream wait, so one block serves every family
     IdxBuf<float> d_upd;           // vq_index_update_rows: staged rows [n][dim] + their row numbers behind them;
                                    // vq_index_remove_rows: one chunk of moved rows
     IdxBuf<int32_t> d_rmw;         // vq_index_remove_rows: row maps, prefix sums, rebuilt ranks / labels (words)
@@ -126,7 +126,6 @@ struct vq_index {
     IdxBuf<uint64_t> d_gkeys;      // best [qc][CAND] (fp16 path), per-block lists (exact path / redo)
     IdxBuf<uint64_t> d_gpart;
     IdxBuf<unsigned long long> d_gcounters; PinnedBuf<unsigned long long> h_gcounters;
-    IdxBuf<int32_t> d_gout;        // vq_index_search_grouped: device results [3][nq][k]
     // positions (vq_index_set_positions): one int32 per row; pos_n = the rows they cover (0 = none set).  A distinct search with
     // pos_n != size is refused.  Distinct-search scratch (knn_distinct.h): the plain search's answer at the plan's depth
     // (ids | distances), the filed queries' slot list, the redo's selection (ids | distances); its counters are d_gcounters
@@ -142,36 +141,31 @@ struct vq_index {
     // sequence search (knn_sequence.h): every group's rows in (position, tie) order with their positions and ties beside them
     // (order | positions | ties, [3][seq_n]), built on the host by the first sequence search after the labels, the positions or
     // the id ranks changed (seq_n = the rows it covers, 0 = none; seq_largest = the longest group).  Scratch: cost keys (carry
-    // [n] | two working arrays [2][n]), words (lo | hi | block minima [3][n] | end rows [G]), back-pointers, the host form's results
+    // [n] | two working arrays [2][n]), words (lo | hi | block minima [3][n] | end rows [G]), back-pointers
     IdxBuf<int32_t> d_seq; int64_t seq_n = 0; int64_t seq_largest = 0;
     IdxBuf<uint64_t> d_seqc;
     IdxBuf<int32_t> d_seqw;
     IdxBuf<int32_t> d_seqbp;
-    IdxBuf<int32_t> d_seqout;
     // span search (knn_span.h): words (each chunk's spans (a, b) [chunk][G][2] | the global form's lo | pm | minima [3][n]), the
-    // global form's prefix sums [n + G], the host form's results (masses first: 8-byte aligned)
+    // global form's prefix sums [n + G]
     IdxBuf<int32_t> d_spanw;
     IdxBuf<int64_t> d_spanp;
-    IdxBuf<int64_t> d_spanout;
     // keyframe summary (knn_summary.h): the call's lists, keyframe counts and the wide form's per-row / per-block words; the
-    // blocks' packed maxima; the mean's block sums and the widened mean directions; the host form's results
+    // blocks' packed maxima; the mean's block sums and the widened mean directions
     IdxBuf<int32_t> d_sumw;
     IdxBuf<uint64_t> d_sumk;
     IdxBuf<double> d_sumd;
-    IdxBuf<int32_t> d_sumout;
     // chapter segmentation (knn_segment.h): the call's entries, the chapters' cuts and a batch's back-pointers; a batch's prefix
-    // rows and band tables; its global-form E keys; the host form's results
+    // rows and band tables; its global-form E keys
     IdxBuf<int32_t> d_segw;
     IdxBuf<double> d_segd;
     IdxBuf<uint64_t> d_sege;
-    IdxBuf<int32_t> d_segout;
     // zero-shot labelling (knn_label.h): control words {filed rows, flag, largest |p|^2} + the filed-row list + the rows' labels
     // and best distances (ctl [4] | filed [n_pad] | label [n_pad] | best [n_pad]); the exact path's running keys; the tile
-    // path's parts; the host form's group results
+    // path's parts
     IdxBuf<int32_t> d_lw;
     IdxBuf<uint64_t> d_lrun;
     IdxBuf<uint32_t> d_lparts;
-    IdxBuf<int32_t> d_lout;
     IdxBuf<int32_t> d_lgw;         // ... the split group form's lists, unlabelled counts and chosen labels; its pieces' histograms and show keys
     IdxBuf<uint32_t> d_lghist;
     IdxBuf<uint64_t> d_lgshow;
@@ -184,17 +178,14 @@ struct vq_index {
     IdxBuf<double> d_clsum;
     IdxBuf<uint64_t> d_clkey;
     PinnedBuf<int32_t> h_clchanged{true};
-    // compound search (knn_compound.h): the exact path's term table [m][ld]; the host form's term distances [k][m]
+    // compound search (knn_compound.h): the exact path's term table [m][ld]
     IdxBuf<float> d_ctab;
-    IdxBuf<float> d_cout;
     // shared-footage search (knn_match.h): the hit-bit table [m][ceil(n / 32)]; the filed (query, row) pairs; control words
-    // (cursor, flag) + the groups' best-run keys [G]; the queries' threshold half-widths [m] + the selection's unused distances
-    // [k]; the host form's results [7][k]
+    // (cursor, flag) + the groups' best-run keys [G]; the queries' threshold half-widths [m] + the selection's unused distances [k]
     IdxBuf<uint32_t> d_mbits;
     IdxBuf<uint64_t> d_mfiled;
     IdxBuf<uint64_t> d_mw;
     IdxBuf<float> d_mqe;
-    IdxBuf<int32_t> d_mout;
     // library neighbours (knn_neighbors.h): the call's row list; a chunk's tags; a chunk's gathered fp32 masters (row-list calls;
     // their fp16 copies go to d_q16).  Keys, flags, the redo's scratch and the counters are the fp16 search's and the grouped
     // search's (d_keys, d_flags, d_slots, d_counters, d_fb_partial; totals in d_gcounters)
@@ -202,13 +193,12 @@ struct vq_index {
     IdxBuf<int32_t> d_nbtag;
     IdxBuf<float> d_nbq;
     // clip-search scratch (knn_set.h): per-group sums [2][G], candidate list / positions [2][G] + count + flag, |q_i| [m],
-    // order keys [G] + the selection's block lists, candidate keys, result staging of the host form
+    // order keys [G] + the selection's block lists, candidate keys
     IdxBuf<double> d_ssum;
     IdxBuf<int32_t> d_scand;
     IdxBuf<float> d_sqn;
     IdxBuf<uint64_t> d_sekey;
     IdxBuf<uint64_t> d_sckeys;
-    IdxBuf<int32_t> d_sout;
     // fp16 scan scratch
     IdxBuf<uint16_t> d_q16;
     IdxBuf<uint32_t> d_keys;
@@ -383,15 +373,129 @@ constexpr int64_t FP16_AUTO_MIN_ROWS = 16384;
 static_assert(DST_FP16_MIN_ROWS == FP16_AUTO_MIN_ROWS, "knn_distinct.h: the auto mode's threshold");
 static_assert(NB_FP16_MIN_ROWS == FP16_AUTO_MIN_ROWS, "knn_neighbors.h: the auto mode's threshold");
 
-void fill_no_result(vq_index* x, int32_t* ids, float* dist, int64_t count) {
-    hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, ids, dist, count);
+// device memory with no result in any slot (b: the grouped forms' second id array, or null), where a search of a non-empty
+// index finds nothing to look at (an empty filter; a peer's empty shard)
+int fill_empty(vq_index* x, int64_t count, int32_t* a, int32_t* b, float* dist) {
+    hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, a, dist, count);
+    if (b) hipLaunchKernelGGL(fill_no_result_kernel, dim3(cdiv(count, 256)), dim3(256), 0, x->stream, b, dist, count);
+    VQ_HIP(hipGetLastError());
+    return 0;
 }
 
-// a device form's answer with no result in any slot (b: the grouped forms' second id array, or null)
-int fill_empty(vq_index* x, int64_t count, int32_t* a, int32_t* b, float* dist) {
-    fill_no_result(x, a, dist, count);
-    if (b) fill_no_result(x, b, dist, count);
-    VQ_HIP(hipGetLastError());
+// ---- a family's outputs (host_buffers.h: OutField, Outs) ----
+// Both forms of a family run one call sequence; the form says where its arrays are and how the queries reach the device.
+enum Form {
+    ON_DEVICE,         // the _device form: queries and outputs are device memory, nothing is copied, nothing waits
+    HOST_PINNED,       // a host form whose queries go up through the pinned staging buffer
+    HOST_PAGEABLE,     // a host form whose queries go up straight from the caller's memory
+};
+
+// device memory <- the field's empty value, on the stream (a 64-bit empty value repeats its 32-bit half: only zero is in use)
+int out_fill_stream(vq_index* x, void* p, const OutField& f) {
+    if (p && f.count) VQ_HIP(hipMemsetD32Async((hipDeviceptr_t)p, (int)(uint32_t)f.empty, f.bytes() / 4, x->stream));
+    return 0;
+}
+
+// The answer of an empty index: every field that was asked for holds its empty value, written on the host (host forms) or on
+// the stream (device forms).  The statistics read zero.
+int outs_empty(vq_index* x, Form form, const Outs& o) {
+    for (int i = 0; i < o.n; ++i) {
+        if (!o.f[i].dst) continue;
+        if (form == ON_DEVICE) VQ_TRY(out_fill_stream(x, o.f[i].dst, o.f[i]));
+        else out_fill_host(o.f[i].dst, o.f[i]);
+    }
+    set_stats(x, STATS_HOST, 0, 0, 0);
+    return 0;
+}
+
+// ... and of a run that finds nothing to look at (a filter that allows no row): the placed fields, on the stream
+int outs_empty_placed(vq_index* x, const Outs& o) {
+    for (int i = 0; i < o.n; ++i) VQ_TRY(out_fill_stream(x, o.f[i].dev, o.f[i]));
+    return 0;
+}
+
+int host_results(vq_index* x, int64_t bytes) {          // h_res holds at least `bytes` (pinned + mapped; the stream is idle when it is replaced)
+    if (bytes <= x->h_res.cap) return 0;
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    return x->h_res.reserve(bytes, 64 << 10);
+}
+
+// Where the run writes each field.  Device forms: the caller's arrays.  Host forms: pieces of d_res (outs_layout), except for
+// owned fields, whose `dev` the family sets itself; a field that was not asked for keeps dev = null.
+int outs_place(vq_index* x, Form form, Outs* o) {
+    if (form == ON_DEVICE) {
+        for (int i = 0; i < o->n; ++i) o->f[i].dev = o->f[i].dst;
+        return 0;
+    }
+    int64_t off[OUT_MAX_FIELDS];
+    const int64_t bytes = outs_layout(*o, off);
+    VQ_TRY(x->d_res.reserve(bytes));
+    if (o->how != COPY_TO_CALLER) VQ_TRY(host_results(x, bytes));
+    for (int i = 0; i < o->n; ++i)
+        if (off[i] >= 0) o->f[i].dev = x->d_res.p + off[i];
+    return 0;
+}
+
+// Host forms: every field that was asked for, from where the run wrote it to the caller's array, in list order; then the call's
+// one wait.  Device forms: nothing.
+int outs_return(vq_index* x, Form form, const Outs& o) {
+    if (form == ON_DEVICE) return 0;
+    auto pinned = [&](const OutField& f) { return x->h_res.p + ((char*)f.dev - x->d_res.p); };
+    if (o.how == COPY_PINNED_BLOCK) {
+        int64_t off[OUT_MAX_FIELDS];
+        VQ_HIP(hipMemcpyAsync(x->h_res, x->d_res, (size_t)outs_layout(o, off), hipMemcpyDeviceToHost, x->stream));
+    } else {
+        for (int i = 0; i < o.n; ++i)
+            if (o.f[i].dst)
+                VQ_HIP(hipMemcpyAsync(o.how == COPY_TO_CALLER ? o.f[i].dst : pinned(o.f[i]), o.f[i].dev, o.f[i].bytes(), hipMemcpyDeviceToHost, x->stream));
+    }
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    if (o.how != COPY_TO_CALLER)
+        for (int i = 0; i < o.n; ++i)
+            if (o.f[i].dst) std::memcpy(o.f[i].dst, pinned(o.f[i]), o.f[i].bytes());
+    return 0;
+}
+
+// A host form's queries [nq][dim] -> d_q, by the form's route: through the pinned staging buffer (vq_index_search's fast path,
+// the filtered searches and every family from the clip search on, the two debug passes, the cluster update), or straight from
+// the caller's pageable memory (the plain search's large batches, the grouped, distinct and diverse searches).  Each form keeps
+// the route it was written with: on large batches the runtime stages a pageable copy itself, in pieces, and which route wins
+// there has not been measured, so the two are not merged here.
+int stage_queries(vq_index* x, const float* queries, int nq, Form route = HOST_PINNED) {
+    const int64_t count = (int64_t)nq * x->dim;
+    VQ_TRY(x->d_q.reserve(count));
+    if (route == HOST_PINNED) {
+        VQ_TRY(x->h_q.reserve(count, (64 << 10) / 4));
+        std::memcpy(x->h_q, queries, (size_t)count * 4);
+        queries = x->h_q;
+    }
+    VQ_HIP(hipMemcpyAsync(x->d_q, queries, (size_t)count * 4, hipMemcpyHostToDevice, x->stream));
+    return 0;
+}
+
+// What the two forms of a family share behind their refusals: the queries get to the device (or are there), the outputs get
+// their places, `run(d_queries)` queues the work, the host form's results come back.
+template <class Run>
+int run_form(vq_index* x, Form form, const float* queries, int nq, Outs* o, Run run) {
+    if (form != ON_DEVICE && queries) VQ_TRY(stage_queries(x, queries, nq, form));       // (a family without queries passes null)
+    VQ_TRY(outs_place(x, form, o));
+    VQ_TRY(run(form == ON_DEVICE ? queries : x->d_q.p));
+    return outs_return(x, form, *o);
+}
+
+// Host forms: is every |q|^2 of q [count][dim] inside what the fp16 bound covers?  what (a query's name in the message) set:
+// a value that is not finite is refused.  what null: nothing is refused, and such a query simply reads as out of range.
+int queries_in_range(const char* fn, const char* what, const float* q, int count, int dim, bool* in_range) {
+    *in_range = true;
+    for (int j = 0; j < count; ++j) {
+        double s2 = 0.0;
+        for (int i = 0; i < dim; ++i) {
+            const float v = q[(size_t)j * dim + i];
+            if (what) VQ_CHECK(v - v == 0.f, "%s: %s %d holds a value that is not finite", fn, what, j);
+            s2 += (double)v * v;
+        }
+        if (!(s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX)) *in_range = false;
+    }
     return 0;
 }
 
@@ -1146,13 +1250,6 @@ bool filter_use_fp16(const vq_index* x, int nq, int k, int mode, int64_t m) {
     return filter_fp16_ok(x, nq, k) && x->size >= FP16_AUTO_MIN_ROWS && m * den >= x->size;
 }
 
-// S is empty: no result for any query
-int filter_fill_empty(vq_index* x, int nq, int k, int32_t* a, int32_t* b, float* dist) {
-    VQ_TRY(fill_empty(x, (int64_t)nq * k, a, b, dist));
-    set_stats(x, STATS_HOST, 0, 0, nq);
-    return 0;
-}
-
 int search_filtered_dispatch(vq_index* x, const float* d_queries, int nq, int k, int mode, const int32_t* sel, int32_t n_sel, int exclude,
                              int32_t* d_ids, float* d_dist) {
     static const char* fn = "vq_index_search_filtered";
@@ -1162,7 +1259,10 @@ int search_filtered_dispatch(vq_index* x, const float* d_queries, int nq, int k,
     const bool fp16 = filter_use_fp16(x, nq, k, mode, f.allowed_rows(x, exclude));
     FilterPlan p;
     VQ_TRY(filter_prepare(x, fn, f, exclude, fp16, &p));
-    if (p.m == 0) return filter_fill_empty(x, nq, k, d_ids, nullptr, d_dist);
+    if (p.m == 0) {                                         // S is empty: no result for any query
+        set_stats(x, STATS_HOST, 0, 0, nq);
+        return fill_empty(x, (int64_t)nq * k, d_ids, nullptr, d_dist);
+    }
     return fp16 ? search_filtered_fp16(x, d_queries, nq, k, p, d_ids, d_dist) : search_filtered_gather(x, d_queries, nq, k, p, d_ids, d_dist);
 }
 
@@ -1175,25 +1275,12 @@ int search_grouped_filtered_dispatch(vq_index* x, const float* d_queries, int nq
     const bool fp16 = filter_use_fp16(x, nq, k, mode, f.allowed_rows(x, exclude));
     FilterPlan p;
     VQ_TRY(filter_prepare(x, fn, f, exclude, fp16, &p));
-    if (p.m == 0) return filter_fill_empty(x, nq, k, groups, rows_out, dist);
+    if (p.m == 0) {
+        set_stats(x, STATS_HOST, 0, 0, nq);
+        return fill_empty(x, (int64_t)nq * k, groups, rows_out, dist);
+    }
     return fp16 ? search_grouped_fp16(x, d_queries, nq, k, groups, rows_out, dist, p.bits, p.nA)
                 : search_grouped_filtered_gather(x, d_queries, nq, k, p, groups, rows_out, dist);
-}
-
-// Host forms (vq_index_search's fast path, the filtered and clip searches): the queries go up from pinned staging; all but the clip search take their results through h_res.
-int stage_queries(vq_index* x, const float* queries, int nq) {
-    const int64_t count = (int64_t)nq * x->dim;
-    VQ_TRY(x->d_q.reserve(count));
-    VQ_TRY(x->h_q.reserve(count, (64 << 10) / 4));
-    std::memcpy(x->h_q, queries, (size_t)count * 4);
-    VQ_HIP(hipMemcpyAsync(x->d_q, x->h_q, (size_t)count * 4, hipMemcpyHostToDevice, x->stream));
-    return 0;
-}
-
-int host_results(vq_index* x, int64_t bytes) {          // h_res holds at least `bytes` (pinned + mapped; the stream is idle when it is replaced)
-    if (bytes <= x->h_res.cap) return 0;
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return x->h_res.reserve(bytes, 64 << 10);
 }
 
 // ---- clip search (knn_set.h) ----
@@ -1212,14 +1299,16 @@ int set_precheck(vq_index* x, const char* fn, int mode, const FilterLabels& f) {
     return 0;
 }
 
-// d_queries [m][dim], g_out / d_out [k], match [k][m] or null: all device memory.  Asynchronous on the index's stream.
+// d_queries [m][dim]; o: groups / distances [k], match rows [k][m] or not asked for, placed in device memory.  Asynchronous on
+// the index's stream.
 int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, int k, int mode, const FilterLabels& f, int exclude,
-                   int32_t* g_out, float* d_out, int32_t* match) {
+                   const Outs& o) {
+    int32_t* const g_out = o.dev<int32_t>(0); float* const d_out = o.dev<float>(1); int32_t* const match = o.dev<int32_t>(2);
     FilterPlan p;
     VQ_TRY(filter_prepare(x, fn, f, exclude, true, &p));
     if (!p.all && p.m == 0) {                               // nothing allowed: every slot empty
-        if (match) VQ_HIP(hipMemsetAsync(match, 0xff, (size_t)k * m * 4, x->stream));
-        return filter_fill_empty(x, 1, k, g_out, nullptr, d_out);
+        set_stats(x, STATS_HOST, 0, 0, 1);
+        return outs_empty_placed(x, o);
     }
     const uint32_t* allow = p.all ? nullptr : p.bits;
     const int64_t n = x->size, ld = round_up(n, 64);
@@ -1386,17 +1475,16 @@ int seq_precheck(vq_index* x, const char* fn, const FilterLabels& f) {
     return check_label_range(x, fn, f);
 }
 
-// d_steps [m][dim], g_out / d_out [k], chain [k][m] or null: all device memory.  Asynchronous on the index's stream once the
-// (position, tie) order is on the device.
+// d_steps [m][dim]; o: groups / distances [k], chain rows [k][m] or not asked for, placed in device memory.  Asynchronous on
+// the index's stream once the (position, tie) order is on the device.
 int search_sequence_run(vq_index* x, const char* fn, const float* d_steps, int m, int k, int64_t min_gap, int64_t max_gap,
-                        const FilterLabels& f, int exclude, int32_t* g_out, float* d_out, int32_t* chain) {
+                        const FilterLabels& f, int exclude, const Outs& o) {
+    int32_t* const g_out = o.dev<int32_t>(0); float* const d_out = o.dev<float>(1); int32_t* const chain = o.dev<int32_t>(2);
     FilterPlan fp;
     VQ_TRY(filter_prepare(x, fn, f, exclude, true, &fp));
     if (!fp.all && fp.m == 0) {                             // nothing allowed: every slot empty
-        if (chain) VQ_HIP(hipMemsetAsync(chain, 0xff, (size_t)k * m * 4, x->stream));
-        VQ_TRY(fill_empty(x, k, g_out, nullptr, d_out));
         set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
+        return outs_empty_placed(x, o);
     }
     VQ_TRY(seq_order_prepare(x));
     const uint32_t* allow = fp.all ? nullptr : fp.bits;
@@ -1470,28 +1558,17 @@ SpanPlan span_plan_env(int64_t n, int64_t n_groups, int64_t largest_group, int n
     return plan_spans(n, n_groups, largest_group, nq, seq_env("VQ_AMD_SPAN_LDS_ROWS"), seq_env("VQ_AMD_SPAN_DIST_BYTES"));
 }
 
-// the optional outputs of a span search: device memory, each [nq][k] ([nq][k][3] for rows) or null
-struct SpanOut { int64_t* mass; int32_t* len; int32_t* rows; };
-
-// a device form's answer with no span in any slot
-int span_fill_empty(vq_index* x, int64_t count, int32_t* g_out, float* d_out, const SpanOut& o) {
-    VQ_TRY(fill_empty(x, count, g_out, nullptr, d_out));
-    if (o.mass) VQ_HIP(hipMemsetAsync(o.mass, 0, (size_t)count * 8, x->stream));
-    if (o.len) VQ_HIP(hipMemsetAsync(o.len, 0, (size_t)count * 4, x->stream));
-    if (o.rows) VQ_HIP(hipMemsetAsync(o.rows, 0xff, (size_t)count * 12, x->stream));
-    return 0;
-}
-
-// d_queries [nq][dim], g_out / d_out [nq][k], o: all device memory.  Asynchronous on the index's stream once the (position, tie)
-// order is on the device.
+// d_queries [nq][dim]; o: groups / distances [nq][k], then masses, lengths [nq][k] and rows [nq][k][3], each or not asked for,
+// placed in device memory.  Asynchronous on the index's stream once the (position, tie) order is on the device.
 int search_spans_run(vq_index* x, const char* fn, const float* d_queries, int nq, int k, float tau, int64_t max_gap, int64_t max_span,
-                     const FilterLabels& f, int exclude, int32_t* g_out, float* d_out, const SpanOut& o) {
+                     const FilterLabels& f, int exclude, const Outs& o) {
+    int32_t* const g_out = o.dev<int32_t>(0); float* const d_out = o.dev<float>(1);
+    int64_t* const mass = o.dev<int64_t>(2); int32_t* const len = o.dev<int32_t>(3); int32_t* const rows = o.dev<int32_t>(4);
     FilterPlan fp;
     VQ_TRY(filter_prepare(x, fn, f, exclude, true, &fp));
     if (!fp.all && fp.m == 0) {                             // nothing allowed: every slot empty
-        VQ_TRY(span_fill_empty(x, (int64_t)nq * k, g_out, d_out, o));
         set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
+        return outs_empty_placed(x, o);
     }
     VQ_TRY(seq_order_prepare(x));
     const uint32_t* allow = fp.all ? nullptr : fp.bits;
@@ -1522,7 +1599,7 @@ int search_spans_run(vq_index* x, const char* fn, const float* d_queries, int nq
     const int32_t* sorder = x->d_seq; const int32_t* spos = sorder + n; const int32_t* stie = spos + n;
     uint64_t* ekey = x->d_sekey; uint64_t* partial = ekey + pairs;
     int32_t* ab = x->d_spanw; int32_t* work = ab + 2 * pairs;
-    const bool finish = o.mass || o.len || o.rows;
+    const bool finish = mass || len || rows;
     for (int q0 = 0; q0 < nq; q0 += p.chunk_queries) {
         const int cur = std::min(p.chunk_queries, nq - q0);
         const int64_t at = (int64_t)q0 * k;
@@ -1548,7 +1625,7 @@ int search_spans_run(vq_index* x, const char* fn, const float* d_queries, int nq
         if (finish) {
             Prof pr(x, I_SEQ_DP);
             hipLaunchKernelGGL(span_finish_kernel, dim3(k, cur), dim3(SPAN_THREADS), 0, x->stream, x->d_dist, ld, g_out + at, k, x->d_goff, sorder,
-                               stie, tau, G, ab, o.mass ? o.mass + at : nullptr, o.len ? o.len + at : nullptr, o.rows ? o.rows + 3 * at : nullptr);
+                               stie, tau, G, ab, mass ? mass + at : nullptr, len ? len + at : nullptr, rows ? rows + 3 * at : nullptr);
         }
     }
     VQ_HIP(hipGetLastError());
@@ -2099,26 +2176,19 @@ int match_precheck(vq_index* x, const char* fn, int m, int mode, const FilterLab
     return 0;
 }
 
-// the seven result arrays of a call [k] each, device memory
-struct MatchOut { int32_t* group; int32_t* hits; int32_t* span; int32_t* q_first; int32_t* row_first; int32_t* row_last; float* mean; };
-
-// every slot empty
-int match_fill_empty(vq_index* x, int k, const MatchOut& o) {
-    fill_no_result(x, o.group, o.mean, k);
-    hipLaunchKernelGGL(match_score_kernel, dim3(k), dim3(256), 0, x->stream, o.group, nullptr, MatchKey{0, 1}, 1, nullptr, 0, nullptr, x->dim, nullptr,
-                       nullptr, nullptr, o.hits, o.span, o.q_first, o.row_first, o.row_last, o.mean);
-    VQ_HIP(hipGetLastError());
-    set_stats(x, STATS_HOST, 0, 0, 0);
-    return 0;
-}
-
-// d_queries [m][dim] and the results: device memory.  force_exact: the host form found a query outside the fp16 bound's range.
-// Asynchronous on the index's stream once the (position, tie) order is on the device.
+// d_queries [m][dim]; o: the seven result arrays [k] each (match_outs), placed in device memory.  force_exact: the host form found
+// a query outside the fp16 bound's range.  Asynchronous on the index's stream once the (position, tie) order is on the device.
 int match_run(vq_index* x, const char* fn, const float* d_queries, int m, int k, float max_dist, int min_len, int max_miss, int mode,
-              bool force_exact, const FilterLabels& f, int exclude, const MatchOut& o) {
+              bool force_exact, const FilterLabels& f, int exclude, const Outs& o) {
+    int32_t* const group = o.dev<int32_t>(0); int32_t* const hits = o.dev<int32_t>(1); int32_t* const span = o.dev<int32_t>(2);
+    int32_t* const q_first = o.dev<int32_t>(3); int32_t* const row_first = o.dev<int32_t>(4); int32_t* const row_last = o.dev<int32_t>(5);
+    float* const mean = o.dev<float>(6);
     FilterPlan fp;
     VQ_TRY(filter_prepare(x, fn, f, exclude, true, &fp));
-    if (!fp.all && fp.m == 0) return match_fill_empty(x, k, o);         // nothing allowed
+    if (!fp.all && fp.m == 0) {                             // nothing allowed: every slot empty
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return outs_empty_placed(x, o);
+    }
     VQ_TRY(seq_order_prepare(x));
     const uint32_t* allow = fp.all ? nullptr : fp.bits;
     const int64_t n = x->size, ld = round_up(n, 64);
@@ -2187,13 +2257,13 @@ int match_run(vq_index* x, const char* fn, const float* d_queries, int m, int k,
         Prof pr(x, I_SELECT);
         hipLaunchKernelGGL(match_final_kernel, dim3(nblocks), dim3(256), 0, x->stream, gkey, G, key, ekey);
         hipLaunchKernelGGL(set_select_block_kernel, dim3(nblocks), dim3(256), 0, x->stream, ekey, G, kl, partial);
-        hipLaunchKernelGGL(set_select_merge_kernel, dim3(1), dim3(256), 0, x->stream, partial, (int64_t)nblocks * kl, k, o.group, sel_dist, nullptr,
+        hipLaunchKernelGGL(set_select_merge_kernel, dim3(1), dim3(256), 0, x->stream, partial, (int64_t)nblocks * kl, k, group, sel_dist, nullptr,
                            nullptr);
     }
     {
         Prof pr(x, I_EXACT_DIST);
-        hipLaunchKernelGGL(match_score_kernel, dim3(k), dim3(256), 0, x->stream, o.group, gkey, key, m, bits, W, x->rows, x->dim, d_queries, x->d_goff,
-                           sorder, o.hits, o.span, o.q_first, o.row_first, o.row_last, o.mean);
+        hipLaunchKernelGGL(match_score_kernel, dim3(k), dim3(256), 0, x->stream, group, gkey, key, m, bits, W, x->rows, x->dim, d_queries, x->d_goff,
+                           sorder, hits, span, q_first, row_first, row_last, mean);
     }
     hipLaunchKernelGGL(match_stats_kernel, dim3(1), dim3(256), 0, x->stream, ekey, G, ctl, cap, p.fp16 && force_exact ? 1 : 0, x->d_gcounters);
     VQ_HIP(hipGetLastError());
@@ -2424,15 +2494,334 @@ int check_compound_args(const char* fn, const vq_index* x, int m, const int32_t*
     return 0;
 }
 
-// a host form's answer from an empty index: no candidates (hnsw.py:243-244 returns []); b: the grouped forms' second id array, or null
-void host_empty(int64_t count, int32_t* a, int32_t* b, float* dist) {
-    for (int64_t i = 0; i < count; ++i) { a[i] = -1; if (b) b[i] = -1; dist[i] = __builtin_inff(); }
+// (the arguments are judged before the library is asked for its device)
+int check_segment_args(const char* fn, const vq_index* x, const int32_t* groups, int32_t n_sel, int k, float penalty, int64_t max_len, bool arrays) {
+    VQ_CHECK(n_sel >= 1, "%s: n_sel %d: at least one group must be listed", fn, (int)n_sel);
+    VQ_CHECK(k >= 1 && k <= SEG_MAX_K, "%s: k %d outside [1, %d]", fn, k, SEG_MAX_K);
+    VQ_CHECK(penalty == penalty && penalty >= 0.0f, "%s: penalty must be >= 0 and not NaN", fn);
+    VQ_CHECK(max_len >= 0, "%s: max_len %lld is negative (0: no limit)", fn, (long long)max_len);
+    VQ_TRY(require_init());
+    VQ_CHECK(x && groups && arrays, "%s: bad argument", fn);
+    return 0;
 }
 
-// device results of the plain host forms: ids and distances [count] each
-int reserve_id_dist(vq_index* x, int64_t count) {
-    VQ_TRY(x->d_ids.reserve(count));
-    return x->d_out.reserve(count);
+// ---- the families' call sequences ----
+// One function per family, run by both of its entry points: the argument check, the lock, the empty index's answer (no
+// candidates: hnsw.py:243-244 returns []), the filter's labels, the family's precheck, the run.  The entry points say where the
+// arrays are (Form) and nothing else; what only a host form does is marked `host`.  The output lists name each array's empty value.
+OutField out_ids(void* p, int64_t count) { return {p, count, 4, OUT_NONE}; }                    // rows or groups: -1
+OutField out_dist(void* p, int64_t count) { return {p, count, 4, OUT_INF}; }                    // distances: +inf
+OutField out_zero(void* p, int64_t count, int width = 4) { return {p, count, width, OUT_ZERO}; }  // counts, lengths, masses
+OutField out_owned(void* p, int64_t count) { return {p, count, 4, OUT_ZERO, true}; }             // copied back from memory the call names
+
+// vq_index_search's small calls — the reference caller's (one query, k * 2 results: video_search_system.py:297) and small
+// batches: the query goes up from pinned staging, the kernels write ids | distances straight into pinned, device-mapped host
+// memory, and the ONE wait below is the only host/device round trip — no copy-back commands, no fallback launches unless a
+// query was flagged.  (Larger results: scattered 4-byte stores across PCIe lose to one copy.)
+bool host_fast_fits(const vq_index* x, int nq, int k) {
+    static const bool host_fast = !(getenv("VQ_AMD_HOST_FAST") && atoi(getenv("VQ_AMD_HOST_FAST")) == 0);      // A/B switch
+    return host_fast && (int64_t)nq * x->dim * 4 <= ((int64_t)256 << 10) && (int64_t)nq * k * 8 <= ((int64_t)16 << 10);
+}
+int search_host_fast(vq_index* x, const float* queries, int nq, int k, int mode, int32_t* ids, float* dist) {
+    const int64_t count = (int64_t)nq * k;
+    VQ_TRY(host_results(x, count * 8));
+    VQ_TRY(stage_queries(x, queries, nq));
+    int32_t* r_ids = (int32_t*)x->h_res.dev;
+    float* r_dist = (float*)(x->h_res.dev + count * 4);
+    VQ_TRY(search_dispatch(x, x->d_q, nq, k, mode, r_ids, r_dist, true));
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    if (x->stats_at == STATS_DEFERRED) {
+        stats_from_counters(x);
+        if (x->h_counters[0] > 0) {                      // some proof did not close: the exact redo, then one more wait
+            launch_fallback(x, x->d_q, nq, k, r_ids, r_dist, x->h_counters.dev);
+            VQ_HIP(hipGetLastError());
+            VQ_HIP(hipStreamSynchronize(x->stream));
+        }
+    }
+    std::memcpy(ids, x->h_res, (size_t)count * 4);
+    std::memcpy(dist, x->h_res + count * 4, (size_t)count * 4);
+    return 0;
+}
+
+int search_call(vq_index* x, const char* fn, Form form, const void* queries, int nq, int k, int mode, void* ids, void* dist) {
+    VQ_TRY(check_batch_args(fn, x, nq, k, queries && ids && dist));
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    Outs o{2, {out_ids(ids, count), out_dist(dist, count)}};
+    if (x->size == 0) return outs_empty(x, form, o);
+    if (form != ON_DEVICE && host_fast_fits(x, nq, k)) return search_host_fast(x, (const float*)queries, nq, k, mode, (int32_t*)ids, (float*)dist);
+    return run_form(x, form, (const float*)queries, nq, &o, [&](const float* dq) {
+        return search_dispatch(x, dq, nq, k, mode, o.dev<int32_t>(0), o.dev<float>(1));
+    });
+}
+
+int grouped_call(vq_index* x, const char* fn, Form form, const void* queries, int nq, int k, int mode, void* groups, void* rows, void* dist) {
+    VQ_TRY(check_batch_args(fn, x, nq, k, queries && groups && rows && dist));
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    Outs o{3, {out_ids(groups, count), out_ids(rows, count), out_dist(dist, count)}};
+    if (x->size == 0) return outs_empty(x, form, o);
+    return run_form(x, form, (const float*)queries, nq, &o, [&](const float* dq) {
+        return search_grouped_dispatch(x, dq, nq, k, mode, o.dev<int32_t>(0), o.dev<int32_t>(1), o.dev<float>(2));
+    });
+}
+
+int distinct_call(vq_index* x, const char* fn, Form form, const void* queries, int nq, int k, int mode, int64_t min_gap, void* ids, void* dist) {
+    VQ_TRY(check_distinct_args(fn, x, nq, k, min_gap, queries && ids && dist));
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    Outs o{2, {out_ids(ids, count), out_dist(dist, count)}};
+    if (x->size == 0) return outs_empty(x, form, o);
+    return run_form(x, form, (const float*)queries, nq, &o, [&](const float* dq) {
+        return search_distinct_dispatch(x, dq, nq, k, mode, min_gap, o.dev<int32_t>(0), o.dev<float>(1));
+    });
+}
+
+int diverse_call(vq_index* x, const char* fn, Form form, const void* queries, int nq, int k, int mode, float min_dist, void* ids, void* dist) {
+    const bool host = form != ON_DEVICE;
+    VQ_TRY(check_diverse_args(fn, x, nq, k, min_dist, queries && ids && dist));
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    Outs o{2, {out_ids(ids, count), out_dist(dist, count)}};
+    if (x->size == 0) return outs_empty(x, form, o);
+    if (host) {                                             // refuse before staging anything
+        VQ_TRY(check_mode(fn, mode));
+        VQ_TRY(check_ranks(x, fn));
+    }
+    return run_form(x, form, (const float*)queries, nq, &o, [&](const float* dq) {
+        return search_diverse_dispatch(x, dq, nq, k, mode, min_dist, o.dev<int32_t>(0), o.dev<float>(1));
+    });
+}
+
+// the two filtered searches: their host forms' results come back through the pinned buffer
+int filtered_call(vq_index* x, const char* fn, Form form, const void* queries, int nq, int k, int mode, const int32_t* groups, int32_t n_sel,
+                  int exclude, void* ids, void* dist) {
+    const bool host = form != ON_DEVICE;
+    VQ_TRY(check_filtered_args(fn, x, nq, k, groups, n_sel, exclude, queries && ids && dist));
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    Outs o{2, {out_ids(ids, count), out_dist(dist, count)}, COPY_PINNED_FIELDS};
+    if (x->size == 0) return outs_empty(x, form, o);
+    if (host) VQ_TRY(filter_precheck(x, fn, nq, k, mode, n_sel, exclude));      // refuse before staging anything
+    return run_form(x, form, (const float*)queries, nq, &o, [&](const float* dq) {
+        return search_filtered_dispatch(x, dq, nq, k, mode, groups, n_sel, exclude, o.dev<int32_t>(0), o.dev<float>(1));
+    });
+}
+
+int grouped_filtered_call(vq_index* x, const char* fn, Form form, const void* queries, int nq, int k, int mode, const int32_t* groups,
+                          int32_t n_sel, int exclude, void* groups_out, void* rows, void* dist) {
+    const bool host = form != ON_DEVICE;
+    VQ_TRY(check_filtered_args(fn, x, nq, k, groups, n_sel, exclude, queries && groups_out && rows && dist));
+    if (nq == 0) return 0;
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    Outs o{3, {out_ids(groups_out, count), out_ids(rows, count), out_dist(dist, count)}, COPY_PINNED_BLOCK};
+    if (x->size == 0) return outs_empty(x, form, o);
+    if (host) VQ_TRY(filter_precheck(x, fn, nq, k, mode, n_sel, exclude));      // refuse before staging anything
+    return run_form(x, form, (const float*)queries, nq, &o, [&](const float* dq) {
+        return search_grouped_filtered_dispatch(x, dq, nq, k, mode, groups, n_sel, exclude, o.dev<int32_t>(0), o.dev<int32_t>(1), o.dev<float>(2));
+    });
+}
+
+int set_call(vq_index* x, const char* fn, Form form, const void* queries, int m, int k, int mode, const int32_t* groups, int32_t n_sel,
+             int exclude, void* groups_out, void* dist_out, void* match_rows) {
+    VQ_TRY(check_set_args(fn, x, m, k, groups, n_sel, exclude, queries && groups_out && dist_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    Outs o{3, {out_ids(groups_out, k), out_dist(dist_out, k), out_ids(match_rows, (int64_t)k * m)}};
+    if (x->size == 0) return outs_empty(x, form, o);
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(set_precheck(x, fn, mode, f));
+    return run_form(x, form, (const float*)queries, m, &o, [&](const float* dq) { return search_set_run(x, fn, dq, m, k, mode, f, exclude, o); });
+}
+
+int sequence_call(vq_index* x, const char* fn, Form form, const void* steps, int m, int k, int64_t min_gap, int64_t max_gap,
+                  const int32_t* groups, int32_t n_sel, int exclude, void* groups_out, void* dist_out, void* chain_rows) {
+    VQ_TRY(check_sequence_args(fn, x, m, k, min_gap, max_gap, groups, n_sel, exclude, steps && groups_out && dist_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    Outs o{3, {out_ids(groups_out, k), out_dist(dist_out, k), out_ids(chain_rows, (int64_t)k * m)}};
+    if (x->size == 0) return outs_empty(x, form, o);
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(seq_precheck(x, fn, f));
+    return run_form(x, form, (const float*)steps, m, &o, [&](const float* dq) {
+        return search_sequence_run(x, fn, dq, m, k, min_gap, max_gap, f, exclude, o);
+    });
+}
+
+int spans_call(vq_index* x, const char* fn, Form form, const void* queries, int nq, int k, float max_dist, int64_t max_gap, int64_t max_span,
+               const int32_t* groups, int32_t n_sel, int exclude, void* groups_out, void* dist_out, void* mass_out, void* len_out, void* rows_out) {
+    VQ_TRY(check_span_args(fn, x, nq, k, max_dist, max_gap, max_span, groups, n_sel, exclude, queries && groups_out && dist_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)nq * k;
+    Outs o{5, {out_ids(groups_out, count), out_dist(dist_out, count), out_zero(mass_out, count, 8), out_zero(len_out, count), out_ids(rows_out, 3 * count)}};
+    if (x->size == 0) return outs_empty(x, form, o);
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(seq_precheck(x, fn, f));
+    return run_form(x, form, (const float*)queries, nq, &o, [&](const float* dq) {
+        return search_spans_run(x, fn, dq, nq, k, max_dist, max_gap, max_span, f, exclude, o);
+    });
+}
+
+int summarize_call(vq_index* x, const char* fn, Form form, const int32_t* groups, int32_t n_sel, int k, float max_radius, void* rows_out,
+                   void* radius_out, void* members_out) {
+    VQ_TRY(check_summary_args(fn, x, groups, n_sel, k, max_radius, rows_out && radius_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t count = (int64_t)n_sel * k;
+    Outs o{3, {out_ids(rows_out, count), out_dist(radius_out, count), out_zero(members_out, count)}};
+    if (x->size == 0) return outs_empty(x, form, o);
+    VQ_TRY(sum_precheck(x, fn, groups, n_sel));
+    return run_form(x, form, nullptr, 0, &o, [&](const float*) {
+        return summarize_run(x, fn, groups, n_sel, k, max_radius, o.dev<int32_t>(0), o.dev<float>(1), o.dev<int32_t>(2));
+    });
+}
+
+int segment_call(vq_index* x, const char* fn, Form form, const int32_t* groups, int32_t n_sel, int k, float penalty, int64_t max_len,
+                 void* count_out, void* first_out, void* last_out, void* len_out, void* spread_out, void* show_out, void* mean_spread_out) {
+    VQ_TRY(check_segment_args(fn, x, groups, n_sel, k, penalty, max_len, count_out && first_out && last_out && len_out && spread_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    const int64_t slots = (int64_t)n_sel * k;
+    Outs o{7, {out_zero(count_out, n_sel), out_ids(first_out, slots), out_ids(last_out, slots), out_zero(len_out, slots), out_dist(spread_out, slots),
+               out_ids(show_out, slots), out_dist(mean_spread_out, n_sel)}};
+    if (x->size == 0) return outs_empty(x, form, o);
+    std::vector<int64_t> len;
+    VQ_TRY(seg_precheck(x, fn, groups, n_sel, k, max_len, &len));
+    return run_form(x, form, nullptr, 0, &o, [&](const float*) {
+        return segment_run(x, fn, groups, n_sel, len, k, penalty, max_len, o.dev<int32_t>(0), o.dev<int32_t>(1), o.dev<int32_t>(2), o.dev<int32_t>(3),
+                           o.dev<float>(4), o.dev<int32_t>(5), o.dev<float>(6));
+    });
+}
+
+// An empty index: the labelling and clustering calls return 0 and write nothing.  The host form's row answers come back from
+// where label_run left them (its scratch in d_lw), not from a piece of the block.
+int label_call(vq_index* x, const char* fn, Form form, const void* prompts, int P, int mode, float max_dist, void* row_label, void* row_dist, int m,
+               void* group_tags, void* group_votes, void* group_show_rows, void* group_unlabelled) {
+    const bool host = form != ON_DEVICE, groups = group_tags != nullptr;
+    VQ_TRY(check_label_args(fn, x, prompts, P, max_dist, m, groups, group_votes && group_show_rows && group_unlabelled));
+    std::lock_guard<std::mutex> lk(x->mu);
+    bool in_range = true;                                   // every |p|^2 inside what the fp16 bound covers
+    if (host) VQ_TRY(queries_in_range(fn, "prompt", (const float*)prompts, P, x->dim, &in_range));
+    if (x->size == 0) {
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    VQ_TRY(label_precheck(x, fn, mode, groups));
+    const int64_t n = x->size, G = groups ? x->n_groups : 0, gm = G * m;
+    Outs o{6, {out_owned(row_label, n), out_owned(row_dist, n), out_ids(group_tags, gm), out_zero(groups ? group_votes : nullptr, gm),
+               out_ids(groups ? group_show_rows : nullptr, gm), out_zero(groups ? group_unlabelled : nullptr, G)}};
+    return run_form(x, form, (const float*)prompts, P, &o, [&](const float* dq) {
+        int32_t* lab; float* best;
+        VQ_TRY(label_run(x, dq, P, mode, !in_range, max_dist, o.dev<int32_t>(0), o.dev<float>(1), m, o.dev<int32_t>(2), o.dev<int32_t>(3),
+                         o.dev<int32_t>(4), o.dev<int32_t>(5), &lab, &best));
+        o.f[0].dev = lab; o.f[1].dev = best;
+        return 0;
+    });
+}
+
+// The host form's results all live in memory the call has anyway: the centroids in d_q, as the label call's prompts do, the
+// rest in the cluster scratch.  It also reports the iterations it ran and their changed counts, which the device form never reads.
+int cluster_call(vq_index* x, const char* fn, Form form, const void* init, const int32_t* init_rows, int P, int iters, int mode, void* centroids,
+                 void* row_label, void* row_dist, void* counts, void* show_rows, int* iterations, int32_t* changed) {
+    const bool host = form != ON_DEVICE;
+    VQ_TRY(check_cluster_args(fn, x, init, init_rows, P, iters, centroids && counts && show_rows && (iterations || !host)));
+    std::lock_guard<std::mutex> lk(x->mu);
+    bool in_range = true;                                   // every |c|^2 inside what the fp16 bound covers
+    if (host && init) VQ_TRY(queries_in_range(fn, "initial centroid", (const float*)init, P, x->dim, &in_range));
+    if (x->size == 0) {
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return 0;
+    }
+    const int64_t n = x->size, words = (int64_t)P * x->dim;
+    VQ_CHECK(P <= n, "%s: %d clusters for an index of %lld rows", fn, P, (long long)n);
+    if (host && init_rows)
+        for (int j = 0; j < P; ++j)
+            VQ_CHECK(init_rows[j] >= 0 && init_rows[j] < n, "%s: init_rows[%d] = %d outside [0, %lld)", fn, j, (int)init_rows[j], (long long)n);
+    VQ_TRY(cluster_precheck(x, fn, mode));
+    ClusterBufs b;
+    VQ_TRY(cluster_reserve(x, P, &b));
+    if (host && x->h_clchanged.cap < iters) {               // (the device form never writes there: nothing in flight uses it)
+        VQ_HIP(hipStreamSynchronize(x->stream));
+        VQ_TRY(x->h_clchanged.reserve(iters, CL_MAX_ITER));
+    }
+    if (host) VQ_TRY(x->d_q.reserve(words));
+    float* const C = host ? x->d_q.p : (float*)centroids;
+    if (host && init) {
+        VQ_TRY(stage_queries(x, (const float*)init, P));
+    } else if (init) {
+        if (init != centroids) VQ_HIP(hipMemcpyAsync(C, init, (size_t)words * 4, hipMemcpyDeviceToDevice, x->stream));
+    } else {
+        if (host) {                                         // the row list goes up into b.show (free until the show rows are written)
+            StageSlot* slot;
+            VQ_TRY(stage_slot(x, P, &slot));
+            std::memcpy(slot->h, init_rows, (size_t)P * 4);
+            VQ_HIP(hipMemcpyAsync(b.show, slot->h.p, (size_t)P * 4, hipMemcpyHostToDevice, x->stream));
+            VQ_HIP(hipEventRecord(slot->ev, x->stream));
+            init_rows = b.show;
+        }
+        hipLaunchKernelGGL(cluster_gather_kernel, dim3(P), dim3(256), 0, x->stream, x->rows, n, x->dim, init_rows, C);
+    }
+    Outs o{5, {out_owned(centroids, words), out_owned(row_label, n), out_owned(row_dist, n), out_owned(counts, P), out_owned(show_rows, P)}};
+    o.f[0].dev = C;
+    o.f[1].dev = host || !row_label ? b.lab : row_label;
+    o.f[2].dev = host || !row_dist ? (void*)b.best : row_dist;
+    o.f[3].dev = host ? b.counts : counts;
+    o.f[4].dev = host ? b.show : show_rows;
+    std::vector<int32_t> ch(host ? (size_t)iters : 0);
+    int T = 0;
+    VQ_TRY(cluster_run(x, b, C, P, iters, mode, !in_range, o.dev<int32_t>(1), o.dev<float>(2), o.dev<int32_t>(3), o.dev<int32_t>(4),
+                       host ? ch.data() : nullptr, &T));
+    VQ_TRY(outs_return(x, form, o));
+    if (host) {
+        *iterations = T;
+        if (changed) std::copy(ch.begin(), ch.begin() + T, changed);
+    }
+    return 0;
+}
+
+int compound_call(vq_index* x, const char* fn, Form form, const void* terms, int m, const int32_t* clause_of, float margin, int k, int mode,
+                  void* ids, void* dist, void* term_dist) {
+    VQ_TRY(check_compound_args(fn, x, m, clause_of, margin, k, mode, terms && ids && dist));
+    std::lock_guard<std::mutex> lk(x->mu);
+    bool in_range = true;                                   // every |q|^2 inside what the fp16 bound covers
+    if (form != ON_DEVICE) VQ_TRY(queries_in_range(fn, "term", (const float*)terms, m, x->dim, &in_range));
+    Outs o{3, {out_ids(ids, k), out_dist(dist, k), out_dist(term_dist, (int64_t)k * m)}};
+    if (x->size == 0) return outs_empty(x, form, o);
+    VQ_TRY(compound_precheck(x, fn, k, mode));
+    return run_form(x, form, (const float*)terms, m, &o, [&](const float* dq) {
+        return compound_run(x, dq, m, clause_of, margin, k, mode, !in_range, o.dev<int32_t>(0), o.dev<float>(1), o.dev<float>(2));
+    });
+}
+
+// the seven result arrays of a shared-footage search, [k] each
+int match_call(vq_index* x, const char* fn, Form form, const void* queries, int m, int k, float max_dist, int min_len, int max_miss, int mode,
+               const int32_t* groups, int32_t n_sel, int exclude, void* groups_out, void* hits_out, void* span_out, void* q_first_out,
+               void* row_first_out, void* row_last_out, void* mean_dist_out) {
+    Outs o{7, {out_ids(groups_out, k), out_zero(hits_out, k), out_zero(span_out, k), out_ids(q_first_out, k), out_ids(row_first_out, k),
+               out_ids(row_last_out, k), out_dist(mean_dist_out, k)}};
+    VQ_TRY(check_match_args(fn, x, m, k, max_dist, min_len, max_miss, mode, groups, n_sel, exclude, queries && o.given(7)));
+    std::lock_guard<std::mutex> lk(x->mu);
+    if (x->size == 0) return outs_empty(x, form, o);
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(match_precheck(x, fn, m, mode, f));
+    // (a query outside the range is not refused here; the sum as the device takes it matters only at the range's very edge,
+    //  where either path is exact)
+    bool in_range = true;
+    if (form != ON_DEVICE) VQ_TRY(queries_in_range(fn, nullptr, (const float*)queries, m, x->dim, &in_range));
+    return run_form(x, form, (const float*)queries, m, &o, [&](const float* dq) {
+        return match_run(x, fn, dq, m, k, max_dist, min_len, max_miss, mode, !in_range, f, exclude, o);
+    });
+}
+
+int neighbors_call(vq_index* x, const char* fn, Form form, const int64_t* rows, int64_t m, int k, int exclude, int mode, void* ids, void* dist) {
+    VQ_TRY(check_neighbors_args(fn, x, m, k, exclude, mode, ids && dist));
+    std::lock_guard<std::mutex> lk(x->mu);
+    NeighborsPlan p;
+    VQ_TRY(neighbors_precheck(x, fn, rows, m, k, exclude, mode, &p));
+    if (m == 0) return 0;
+    Outs o{2, {out_ids(ids, m * k), out_dist(dist, m * k)}};
+    return run_form(x, form, nullptr, 0, &o, [&](const float*) { return neighbors_run(x, rows, m, k, exclude, p, o.dev<int32_t>(0), o.dev<float>(1)); });
 }
 
 }  // namespace
@@ -2542,7 +2931,9 @@ int vq_index_debug_rescore(vq_index* x, const float* queries, int nq, int k, con
     VQ_TRY(x->d_flags.reserve(qpad));
     VQ_TRY(x->d_slots.reserve(round_up(nq, 1024)));
     VQ_TRY(ensure_counters(x));
-    VQ_TRY(reserve_id_dist(x, count));
+    Outs o{3, {out_ids(ids, count), out_dist(dist, count), out_owned(flags, nq)}};
+    VQ_TRY(outs_place(x, HOST_PINNED, &o));
+    o.f[2].dev = x->d_flags.p;
     const float no_row = -3.0e38f;                                       // what the scans write for a row past the end
     std::vector<uint32_t> raw((size_t)words, __builtin_bit_cast(uint32_t, no_row));
     for (int64_t q = 0; q < nq; ++q)
@@ -2556,13 +2947,9 @@ int vq_index_debug_rescore(vq_index* x, const float* queries, int nq, int k, con
     VQ_HIP(hipMemcpy(x->d_keys, raw.data(), (size_t)words * 4, hipMemcpyHostToDevice));
     VQ_TRY(stage_queries(x, queries, nq));
     x->last_scan = {true, false, p.layout, nq, p.streams, 0};
-    VQ_TRY(launch_rescore(x, p, x->d_q, nq, k, x->d_ids, x->d_out, x->d_flags, x->d_counters));
+    VQ_TRY(launch_rescore(x, p, x->d_q, nq, k, o.dev<int32_t>(0), o.dev<float>(1), x->d_flags, x->d_counters));
     VQ_HIP(hipGetLastError());
-    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(flags, x->d_flags, (size_t)nq * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return outs_return(x, HOST_PINNED, o);
 }
 
 // fallback_plan's answer; needs no device
@@ -2591,7 +2978,9 @@ int vq_index_debug_fallback(vq_index* x, const float* queries, int nq, int k, co
     const int64_t count = (int64_t)nq * k;
     VQ_TRY(x->d_flags.reserve(nq));
     VQ_TRY(reserve_fallback(x, nq, k));
-    VQ_TRY(reserve_id_dist(x, count));
+    Outs o{3, {out_ids(ids, count), out_dist(dist, count), out_owned(counters, FB_NCOUNTERS)}};
+    VQ_TRY(outs_place(x, HOST_PINNED, &o));
+    o.f[2].dev = x->d_counters.p;
     GroupMask gm{};
     bool masked = false;
     if (groups) {
@@ -2601,18 +2990,14 @@ int vq_index_debug_fallback(vq_index* x, const float* queries, int nq, int k, co
         masked = !p.all;                                                  // an empty exclude list: the unmasked kernel, as the search takes it
         gm = GroupMask{x->d_group, x->d_sgroup, p.bits};
     }
-    VQ_HIP(hipMemcpyAsync(x->d_ids, ids, (size_t)count * 4, hipMemcpyHostToDevice, x->stream));
-    VQ_HIP(hipMemcpyAsync(x->d_out, dist, (size_t)count * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_HIP(hipMemcpyAsync(o.f[0].dev, ids, (size_t)count * 4, hipMemcpyHostToDevice, x->stream));
+    VQ_HIP(hipMemcpyAsync(o.f[1].dev, dist, (size_t)count * 4, hipMemcpyHostToDevice, x->stream));
     VQ_HIP(hipMemcpyAsync(x->d_flags, flags, (size_t)nq * 4, hipMemcpyHostToDevice, x->stream));
     VQ_TRY(stage_queries(x, queries, nq));
     hipLaunchKernelGGL(collect_flags_kernel, dim3(1), dim3(1024), 0, x->stream, x->d_flags, nq, x->d_slots, x->d_counters);
-    launch_fallback(x, x->d_q, nq, k, x->d_ids, x->d_out, x->d_counters, masked ? &gm : nullptr);
+    launch_fallback(x, x->d_q, nq, k, o.dev<int32_t>(0), o.dev<float>(1), x->d_counters, masked ? &gm : nullptr);
     VQ_HIP(hipGetLastError());
-    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(counters, x->d_counters, FB_NCOUNTERS * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return outs_return(x, HOST_PINNED, o);
 }
 
 int vq_index_debug_read_group_best(vq_index* x, int64_t* info, float* best, int64_t capacity) {
@@ -2944,101 +3329,27 @@ int vq_index_remove_rows(vq_index* x, const int64_t* row_numbers, int64_t n) {
 }
 
 int vq_index_search_device(vq_index* x, const void* d_queries, int nq, int k, int mode, void* d_ids, void* d_dist) {
-    VQ_TRY(check_batch_args("vq_index_search_device", x, nq, k, d_queries && d_ids && d_dist));
-    if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_ids, nullptr, (float*)d_dist);      // as vq_index_search reports it
-    return search_dispatch(x, (const float*)d_queries, nq, k, mode, (int32_t*)d_ids, (float*)d_dist);
+    return search_call(x, "vq_index_search_device", ON_DEVICE, d_queries, nq, k, mode, d_ids, d_dist);
 }
 
 int vq_index_search(vq_index* x, const float* queries, int nq, int k, int mode, int32_t* ids, float* dist) {
-    VQ_TRY(check_batch_args("vq_index_search", x, nq, k, queries && ids && dist));
-    if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int64_t count = (int64_t)nq * k;
-    if (x->size == 0) { host_empty(count, ids, nullptr, dist); return 0; }
-    const int64_t q_bytes = (int64_t)nq * x->dim * 4, res_bytes = count * 8;
-    static const bool host_fast = !(getenv("VQ_AMD_HOST_FAST") && atoi(getenv("VQ_AMD_HOST_FAST")) == 0);      // A/B switch
-    if (host_fast && q_bytes <= ((int64_t)256 << 10) && res_bytes <= ((int64_t)16 << 10)) {      // (larger results: scattered 4-byte stores across PCIe lose to one copy)
-        // The reference caller's call (one query, k * 2 results: video_search_system.py:297) and small batches: the query goes up
-        // from pinned staging, the kernels write ids | distances straight into pinned, device-mapped host memory, and the ONE
-        // wait below is the only host/device round trip — no copy-back commands, no fallback launches unless a query was flagged.
-        VQ_TRY(host_results(x, res_bytes));
-        VQ_TRY(stage_queries(x, queries, nq));
-        int32_t* r_ids = (int32_t*)x->h_res.dev;
-        float* r_dist = (float*)(x->h_res.dev + count * 4);
-        VQ_TRY(search_dispatch(x, x->d_q, nq, k, mode, r_ids, r_dist, true));
-        VQ_HIP(hipStreamSynchronize(x->stream));
-        if (x->stats_at == STATS_DEFERRED) {
-            stats_from_counters(x);
-            if (x->h_counters[0] > 0) {                      // some proof did not close: the exact redo, then one more wait
-                launch_fallback(x, x->d_q, nq, k, r_ids, r_dist, x->h_counters.dev);
-                VQ_HIP(hipGetLastError());
-                VQ_HIP(hipStreamSynchronize(x->stream));
-            }
-        }
-        std::memcpy(ids, x->h_res, (size_t)count * 4);
-        std::memcpy(dist, x->h_res + count * 4, (size_t)count * 4);
-        return 0;
-    }
-    VQ_TRY(x->d_q.reserve((int64_t)nq * x->dim));
-    VQ_TRY(reserve_id_dist(x, count));
-    VQ_HIP(hipMemcpyAsync(x->d_q, queries, (size_t)q_bytes, hipMemcpyHostToDevice, x->stream));
-    VQ_TRY(search_dispatch(x, x->d_q, nq, k, mode, x->d_ids, x->d_out));
-    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return search_call(x, "vq_index_search", HOST_PAGEABLE, queries, nq, k, mode, ids, dist);
 }
 
 int vq_index_search_grouped_device(vq_index* x, const void* d_queries, int nq, int k, int mode, void* d_groups, void* d_rows, void* d_dist) {
-    VQ_TRY(check_batch_args("vq_index_search_grouped_device", x, nq, k, d_queries && d_groups && d_rows && d_dist));
-    if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_groups, (int32_t*)d_rows, (float*)d_dist);
-    return search_grouped_dispatch(x, (const float*)d_queries, nq, k, mode, (int32_t*)d_groups, (int32_t*)d_rows, (float*)d_dist);
+    return grouped_call(x, "vq_index_search_grouped_device", ON_DEVICE, d_queries, nq, k, mode, d_groups, d_rows, d_dist);
 }
 
 int vq_index_search_grouped(vq_index* x, const float* queries, int nq, int k, int mode, int32_t* groups, int32_t* rows, float* dist) {
-    VQ_TRY(check_batch_args("vq_index_search_grouped", x, nq, k, queries && groups && rows && dist));
-    if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int64_t count = (int64_t)nq * k;
-    if (x->size == 0) { host_empty(count, groups, rows, dist); return 0; }
-    VQ_TRY(x->d_q.reserve((int64_t)nq * x->dim));
-    VQ_TRY(x->d_gout.reserve(3 * count));
-    int32_t* d_g = x->d_gout; int32_t* d_r = d_g + count; float* d_d = (float*)(d_r + count);
-    VQ_HIP(hipMemcpyAsync(x->d_q, queries, (size_t)nq * x->dim * 4, hipMemcpyHostToDevice, x->stream));
-    VQ_TRY(search_grouped_dispatch(x, x->d_q, nq, k, mode, d_g, d_r, d_d));
-    VQ_HIP(hipMemcpyAsync(groups, d_g, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(rows, d_r, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist, d_d, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return grouped_call(x, "vq_index_search_grouped", HOST_PAGEABLE, queries, nq, k, mode, groups, rows, dist);
 }
 
 int vq_index_search_distinct_device(vq_index* x, const void* d_queries, int nq, int k, int mode, int64_t min_gap, void* d_ids, void* d_dist) {
-    VQ_TRY(check_distinct_args("vq_index_search_distinct_device", x, nq, k, min_gap, d_queries && d_ids && d_dist));
-    if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_ids, nullptr, (float*)d_dist);
-    return search_distinct_dispatch(x, (const float*)d_queries, nq, k, mode, min_gap, (int32_t*)d_ids, (float*)d_dist);
+    return distinct_call(x, "vq_index_search_distinct_device", ON_DEVICE, d_queries, nq, k, mode, min_gap, d_ids, d_dist);
 }
 
 int vq_index_search_distinct(vq_index* x, const float* queries, int nq, int k, int mode, int64_t min_gap, int32_t* ids, float* dist) {
-    VQ_TRY(check_distinct_args("vq_index_search_distinct", x, nq, k, min_gap, queries && ids && dist));
-    if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int64_t count = (int64_t)nq * k;
-    if (x->size == 0) { host_empty(count, ids, nullptr, dist); return 0; }
-    VQ_TRY(x->d_q.reserve((int64_t)nq * x->dim));
-    VQ_TRY(reserve_id_dist(x, count));
-    VQ_HIP(hipMemcpyAsync(x->d_q, queries, (size_t)nq * x->dim * 4, hipMemcpyHostToDevice, x->stream));
-    VQ_TRY(search_distinct_dispatch(x, x->d_q, nq, k, mode, min_gap, x->d_ids, x->d_out));
-    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return distinct_call(x, "vq_index_search_distinct", HOST_PAGEABLE, queries, nq, k, mode, min_gap, ids, dist);
 }
 
 // plan_distinct's answer for this process's environment; needs no device
@@ -3051,28 +3362,11 @@ int vq_debug_distinct_plan(int64_t n, int nq, int k, int64_t min_gap, int mode, 
 }
 
 int vq_index_search_diverse_device(vq_index* x, const void* d_queries, int nq, int k, int mode, float min_dist, void* d_ids, void* d_dist) {
-    VQ_TRY(check_diverse_args("vq_index_search_diverse_device", x, nq, k, min_dist, d_queries && d_ids && d_dist));
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_ids, nullptr, (float*)d_dist);
-    return search_diverse_dispatch(x, (const float*)d_queries, nq, k, mode, min_dist, (int32_t*)d_ids, (float*)d_dist);
+    return diverse_call(x, "vq_index_search_diverse_device", ON_DEVICE, d_queries, nq, k, mode, min_dist, d_ids, d_dist);
 }
 
 int vq_index_search_diverse(vq_index* x, const float* queries, int nq, int k, int mode, float min_dist, int32_t* ids, float* dist) {
-    static const char* fn = "vq_index_search_diverse";
-    VQ_TRY(check_diverse_args(fn, x, nq, k, min_dist, queries && ids && dist));
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int64_t count = (int64_t)nq * k;
-    if (x->size == 0) { host_empty(count, ids, nullptr, dist); return 0; }
-    VQ_TRY(check_mode(fn, mode));                                 // refuse before staging anything
-    VQ_TRY(check_ranks(x, fn));
-    VQ_TRY(x->d_q.reserve((int64_t)nq * x->dim));
-    VQ_TRY(reserve_id_dist(x, count));
-    VQ_HIP(hipMemcpyAsync(x->d_q, queries, (size_t)nq * x->dim * 4, hipMemcpyHostToDevice, x->stream));
-    VQ_TRY(search_diverse_dispatch(x, x->d_q, nq, k, mode, min_dist, x->d_ids, x->d_out));
-    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return diverse_call(x, "vq_index_search_diverse", HOST_PAGEABLE, queries, nq, k, mode, min_dist, ids, dist);
 }
 
 // plan_diverse's answer for this process's environment; needs no device
@@ -3088,199 +3382,60 @@ int vq_debug_diverse_plan(int64_t n, int nq, int k, float min_dist, int mode, in
 
 int vq_index_search_filtered_device(vq_index* x, const void* d_queries, int nq, int k, int mode, const int32_t* groups, int32_t n_sel,
                                     int exclude, void* d_ids, void* d_dist) {
-    VQ_TRY(check_filtered_args("vq_index_search_filtered_device", x, nq, k, groups, n_sel, exclude, d_queries && d_ids && d_dist));
-    if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_ids, nullptr, (float*)d_dist);
-    return search_filtered_dispatch(x, (const float*)d_queries, nq, k, mode, groups, n_sel, exclude, (int32_t*)d_ids, (float*)d_dist);
+    return filtered_call(x, "vq_index_search_filtered_device", ON_DEVICE, d_queries, nq, k, mode, groups, n_sel, exclude, d_ids, d_dist);
 }
 
 int vq_index_search_filtered(vq_index* x, const float* queries, int nq, int k, int mode, const int32_t* groups, int32_t n_sel, int exclude,
                              int32_t* ids, float* dist) {
-    static const char* fn = "vq_index_search_filtered";
-    VQ_TRY(check_filtered_args(fn, x, nq, k, groups, n_sel, exclude, queries && ids && dist));
-    if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int64_t count = (int64_t)nq * k;
-    if (x->size == 0) { host_empty(count, ids, nullptr, dist); return 0; }
-    VQ_TRY(reserve_id_dist(x, count));
-    VQ_TRY(filter_precheck(x, fn, nq, k, mode, n_sel, exclude));      // refuse before staging anything
-    VQ_TRY(host_results(x, count * 8));
-    VQ_TRY(stage_queries(x, queries, nq));
-    VQ_TRY(search_filtered_dispatch(x, x->d_q, nq, k, mode, groups, n_sel, exclude, x->d_ids, x->d_out));
-    VQ_HIP(hipMemcpyAsync(x->h_res, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(x->h_res + count * 4, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    std::memcpy(ids, x->h_res, (size_t)count * 4);
-    std::memcpy(dist, x->h_res + count * 4, (size_t)count * 4);
-    return 0;
+    return filtered_call(x, "vq_index_search_filtered", HOST_PINNED, queries, nq, k, mode, groups, n_sel, exclude, ids, dist);
 }
 
 int vq_index_search_grouped_filtered_device(vq_index* x, const void* d_queries, int nq, int k, int mode, const int32_t* groups,
                                             int32_t n_sel, int exclude, void* d_groups, void* d_rows, void* d_dist) {
-    VQ_TRY(check_filtered_args("vq_index_search_grouped_filtered_device", x, nq, k, groups, n_sel, exclude,
-                               d_queries && d_groups && d_rows && d_dist));
-    if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) return fill_empty(x, (int64_t)nq * k, (int32_t*)d_groups, (int32_t*)d_rows, (float*)d_dist);
-    return search_grouped_filtered_dispatch(x, (const float*)d_queries, nq, k, mode, groups, n_sel, exclude, (int32_t*)d_groups,
-                                            (int32_t*)d_rows, (float*)d_dist);
+    return grouped_filtered_call(x, "vq_index_search_grouped_filtered_device", ON_DEVICE, d_queries, nq, k, mode, groups, n_sel, exclude, d_groups,
+                                 d_rows, d_dist);
 }
 
 int vq_index_search_grouped_filtered(vq_index* x, const float* queries, int nq, int k, int mode, const int32_t* groups, int32_t n_sel,
                                      int exclude, int32_t* groups_out, int32_t* rows, float* dist) {
-    static const char* fn = "vq_index_search_grouped_filtered";
-    VQ_TRY(check_filtered_args(fn, x, nq, k, groups, n_sel, exclude, queries && groups_out && rows && dist));
-    if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int64_t count = (int64_t)nq * k;
-    if (x->size == 0) { host_empty(count, groups_out, rows, dist); return 0; }
-    VQ_TRY(x->d_gout.reserve(3 * count));
-    int32_t* d_g = x->d_gout; int32_t* d_r = d_g + count; float* d_d = (float*)(d_r + count);
-    VQ_TRY(filter_precheck(x, fn, nq, k, mode, n_sel, exclude));      // refuse before staging anything
-    VQ_TRY(host_results(x, count * 12));
-    VQ_TRY(stage_queries(x, queries, nq));
-    VQ_TRY(search_grouped_filtered_dispatch(x, x->d_q, nq, k, mode, groups, n_sel, exclude, d_g, d_r, d_d));
-    VQ_HIP(hipMemcpyAsync(x->h_res, x->d_gout, (size_t)count * 12, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    std::memcpy(groups_out, x->h_res, (size_t)count * 4);
-    std::memcpy(rows, x->h_res + count * 4, (size_t)count * 4);
-    std::memcpy(dist, x->h_res + count * 8, (size_t)count * 4);
-    return 0;
+    return grouped_filtered_call(x, "vq_index_search_grouped_filtered", HOST_PINNED, queries, nq, k, mode, groups, n_sel, exclude, groups_out, rows,
+                                 dist);
 }
 
 int vq_index_search_set_device(vq_index* x, const void* d_queries, int m, int k, int mode, const int32_t* groups, int32_t n_sel,
                                int exclude, void* d_groups_out, void* d_dist_out, void* d_match_rows) {
-    static const char* fn = "vq_index_search_set_device";
-    VQ_TRY(check_set_args(fn, x, m, k, groups, n_sel, exclude, d_queries && d_groups_out && d_dist_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {
-        fill_no_result(x, (int32_t*)d_groups_out, (float*)d_dist_out, k);
-        if (d_match_rows) VQ_HIP(hipMemsetAsync(d_match_rows, 0xff, (size_t)k * m * 4, x->stream));
-        VQ_HIP(hipGetLastError());
-        return 0;
-    }
-    const FilterLabels f = filter_labels(x, groups, n_sel);
-    VQ_TRY(set_precheck(x, fn, mode, f));
-    return search_set_run(x, fn, (const float*)d_queries, m, k, mode, f, exclude, (int32_t*)d_groups_out, (float*)d_dist_out,
-                          (int32_t*)d_match_rows);
+    return set_call(x, "vq_index_search_set_device", ON_DEVICE, d_queries, m, k, mode, groups, n_sel, exclude, d_groups_out, d_dist_out, d_match_rows);
 }
 
 int vq_index_search_set(vq_index* x, const float* queries, int m, int k, int mode, const int32_t* groups, int32_t n_sel, int exclude,
                         int32_t* groups_out, float* dist_out, int32_t* match_rows) {
-    static const char* fn = "vq_index_search_set";
-    VQ_TRY(check_set_args(fn, x, m, k, groups, n_sel, exclude, queries && groups_out && dist_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int64_t nm = match_rows ? (int64_t)k * m : 0;
-    if (x->size == 0) {
-        host_empty(k, groups_out, nullptr, dist_out);
-        std::fill(match_rows, match_rows + nm, -1);
-        return 0;
-    }
-    const FilterLabels f = filter_labels(x, groups, n_sel);
-    VQ_TRY(set_precheck(x, fn, mode, f));
-    VQ_TRY(x->d_sout.reserve(2 * (int64_t)k + nm));
-    int32_t* d_g = x->d_sout; float* d_d = (float*)(d_g + k); int32_t* d_m = match_rows ? d_g + 2 * k : nullptr;
-    VQ_TRY(stage_queries(x, queries, m));
-    VQ_TRY(search_set_run(x, fn, x->d_q, m, k, mode, f, exclude, d_g, d_d, d_m));
-    VQ_HIP(hipMemcpyAsync(groups_out, d_g, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist_out, d_d, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
-    if (match_rows) VQ_HIP(hipMemcpyAsync(match_rows, d_m, (size_t)nm * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return set_call(x, "vq_index_search_set", HOST_PINNED, queries, m, k, mode, groups, n_sel, exclude, groups_out, dist_out, match_rows);
 }
 
 int vq_index_search_sequence_device(vq_index* x, const void* d_steps, int m, int k, int64_t min_gap, int64_t max_gap, const int32_t* groups,
                                     int32_t n_sel, int exclude, void* d_groups_out, void* d_dist_out, void* d_chain_rows) {
-    static const char* fn = "vq_index_search_sequence_device";
-    VQ_TRY(check_sequence_args(fn, x, m, k, min_gap, max_gap, groups, n_sel, exclude, d_steps && d_groups_out && d_dist_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {
-        fill_no_result(x, (int32_t*)d_groups_out, (float*)d_dist_out, k);
-        if (d_chain_rows) VQ_HIP(hipMemsetAsync(d_chain_rows, 0xff, (size_t)k * m * 4, x->stream));
-        VQ_HIP(hipGetLastError());
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    const FilterLabels f = filter_labels(x, groups, n_sel);
-    VQ_TRY(seq_precheck(x, fn, f));
-    return search_sequence_run(x, fn, (const float*)d_steps, m, k, min_gap, max_gap, f, exclude, (int32_t*)d_groups_out, (float*)d_dist_out,
-                               (int32_t*)d_chain_rows);
+    return sequence_call(x, "vq_index_search_sequence_device", ON_DEVICE, d_steps, m, k, min_gap, max_gap, groups, n_sel, exclude, d_groups_out,
+                         d_dist_out, d_chain_rows);
 }
 
 int vq_index_search_sequence(vq_index* x, const float* steps, int m, int k, int64_t min_gap, int64_t max_gap, const int32_t* groups,
                              int32_t n_sel, int exclude, int32_t* groups_out, float* dist_out, int32_t* chain_rows) {
-    static const char* fn = "vq_index_search_sequence";
-    VQ_TRY(check_sequence_args(fn, x, m, k, min_gap, max_gap, groups, n_sel, exclude, steps && groups_out && dist_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int64_t nc = chain_rows ? (int64_t)k * m : 0;
-    if (x->size == 0) {
-        host_empty(k, groups_out, nullptr, dist_out);
-        std::fill(chain_rows, chain_rows + nc, -1);
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    const FilterLabels f = filter_labels(x, groups, n_sel);
-    VQ_TRY(seq_precheck(x, fn, f));
-    VQ_TRY(x->d_seqout.reserve(2 * (int64_t)k + nc));
-    int32_t* d_g = x->d_seqout; float* d_d = (float*)(d_g + k); int32_t* d_c = chain_rows ? d_g + 2 * k : nullptr;
-    VQ_TRY(stage_queries(x, steps, m));
-    VQ_TRY(search_sequence_run(x, fn, x->d_q, m, k, min_gap, max_gap, f, exclude, d_g, d_d, d_c));
-    VQ_HIP(hipMemcpyAsync(groups_out, d_g, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist_out, d_d, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
-    if (chain_rows) VQ_HIP(hipMemcpyAsync(chain_rows, d_c, (size_t)nc * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return sequence_call(x, "vq_index_search_sequence", HOST_PINNED, steps, m, k, min_gap, max_gap, groups, n_sel, exclude, groups_out, dist_out,
+                         chain_rows);
 }
 
 int vq_index_search_spans_device(vq_index* x, const void* d_queries, int nq, int k, float max_dist, int64_t max_gap, int64_t max_span,
                                  const int32_t* groups, int32_t n_sel, int exclude, void* d_groups_out, void* d_dist_out, void* d_mass_out,
                                  void* d_len_out, void* d_rows_out) {
-    static const char* fn = "vq_index_search_spans_device";
-    VQ_TRY(check_span_args(fn, x, nq, k, max_dist, max_gap, max_span, groups, n_sel, exclude, d_queries && d_groups_out && d_dist_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    const SpanOut o{(int64_t*)d_mass_out, (int32_t*)d_len_out, (int32_t*)d_rows_out};
-    if (x->size == 0) {
-        VQ_TRY(span_fill_empty(x, (int64_t)nq * k, (int32_t*)d_groups_out, (float*)d_dist_out, o));
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    const FilterLabels f = filter_labels(x, groups, n_sel);
-    VQ_TRY(seq_precheck(x, fn, f));
-    return search_spans_run(x, fn, (const float*)d_queries, nq, k, max_dist, max_gap, max_span, f, exclude, (int32_t*)d_groups_out,
-                            (float*)d_dist_out, o);
+    return spans_call(x, "vq_index_search_spans_device", ON_DEVICE, d_queries, nq, k, max_dist, max_gap, max_span, groups, n_sel, exclude,
+                      d_groups_out, d_dist_out, d_mass_out, d_len_out, d_rows_out);
 }
 
 int vq_index_search_spans(vq_index* x, const float* queries, int nq, int k, float max_dist, int64_t max_gap, int64_t max_span,
                           const int32_t* groups, int32_t n_sel, int exclude, int32_t* groups_out, float* dist_out, int64_t* mass_out,
                           int32_t* len_out, int32_t* rows_out) {
-    static const char* fn = "vq_index_search_spans";
-    VQ_TRY(check_span_args(fn, x, nq, k, max_dist, max_gap, max_span, groups, n_sel, exclude, queries && groups_out && dist_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int64_t count = (int64_t)nq * k;
-    if (x->size == 0) {
-        host_empty(count, groups_out, nullptr, dist_out);
-        if (mass_out) std::fill(mass_out, mass_out + count, (int64_t)0);
-        if (len_out) std::fill(len_out, len_out + count, 0);
-        if (rows_out) std::fill(rows_out, rows_out + 3 * count, -1);
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    const FilterLabels f = filter_labels(x, groups, n_sel);
-    VQ_TRY(seq_precheck(x, fn, f));
-    VQ_TRY(x->d_spanout.reserve(4 * count));                    // masses [count] int64 | groups | distances | lengths | rows [3] (int32)
-    int64_t* d_m = x->d_spanout; int32_t* d_g = (int32_t*)(d_m + count); float* d_d = (float*)(d_g + count);
-    int32_t* d_l = d_g + 2 * count; int32_t* d_r = d_g + 3 * count;
-    const SpanOut o{mass_out ? d_m : nullptr, len_out ? d_l : nullptr, rows_out ? d_r : nullptr};
-    VQ_TRY(stage_queries(x, queries, nq));
-    VQ_TRY(search_spans_run(x, fn, x->d_q, nq, k, max_dist, max_gap, max_span, f, exclude, d_g, d_d, o));
-    VQ_HIP(hipMemcpyAsync(groups_out, d_g, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist_out, d_d, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    if (mass_out) VQ_HIP(hipMemcpyAsync(mass_out, d_m, (size_t)count * 8, hipMemcpyDeviceToHost, x->stream));
-    if (len_out) VQ_HIP(hipMemcpyAsync(len_out, d_l, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    if (rows_out) VQ_HIP(hipMemcpyAsync(rows_out, d_r, (size_t)count * 12, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return spans_call(x, "vq_index_search_spans", HOST_PINNED, queries, nq, k, max_dist, max_gap, max_span, groups, n_sel, exclude, groups_out,
+                      dist_out, mass_out, len_out, rows_out);
 }
 
 // plan_spans' answer for this process's environment; needs no device
@@ -3309,42 +3464,12 @@ int vq_debug_sequence_plan(int64_t n, int64_t largest_group, int m, int k, int* 
 
 int vq_index_summarize_groups_device(vq_index* x, const int32_t* groups, int32_t n_sel, int k, float max_radius, void* d_rows_out,
                                      void* d_radius_out, void* d_members_out) {
-    static const char* fn = "vq_index_summarize_groups_device";
-    VQ_TRY(check_summary_args(fn, x, groups, n_sel, k, max_radius, d_rows_out && d_radius_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {
-        const int64_t count = (int64_t)n_sel * k;
-        fill_no_result(x, (int32_t*)d_rows_out, (float*)d_radius_out, count);
-        if (d_members_out) VQ_HIP(hipMemsetAsync(d_members_out, 0, (size_t)count * 4, x->stream));
-        VQ_HIP(hipGetLastError());
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    VQ_TRY(sum_precheck(x, fn, groups, n_sel));
-    return summarize_run(x, fn, groups, n_sel, k, max_radius, (int32_t*)d_rows_out, (float*)d_radius_out, (int32_t*)d_members_out);
+    return summarize_call(x, "vq_index_summarize_groups_device", ON_DEVICE, groups, n_sel, k, max_radius, d_rows_out, d_radius_out, d_members_out);
 }
 
 int vq_index_summarize_groups(vq_index* x, const int32_t* groups, int32_t n_sel, int k, float max_radius, int32_t* rows_out,
                               float* radius_out, int32_t* members_out) {
-    static const char* fn = "vq_index_summarize_groups";
-    VQ_TRY(check_summary_args(fn, x, groups, n_sel, k, max_radius, rows_out && radius_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int64_t count = (int64_t)n_sel * k;
-    if (x->size == 0) {
-        host_empty(count, rows_out, nullptr, radius_out);
-        if (members_out) std::fill(members_out, members_out + count, 0);
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    VQ_TRY(sum_precheck(x, fn, groups, n_sel));
-    VQ_TRY(x->d_sumout.reserve(3 * count));
-    int32_t* d_r = x->d_sumout; float* d_f = (float*)(d_r + count); int32_t* d_m = members_out ? d_r + 2 * count : nullptr;
-    VQ_TRY(summarize_run(x, fn, groups, n_sel, k, max_radius, d_r, d_f, d_m));
-    VQ_HIP(hipMemcpyAsync(rows_out, d_r, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(radius_out, d_f, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    if (members_out) VQ_HIP(hipMemcpyAsync(members_out, d_m, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return summarize_call(x, "vq_index_summarize_groups", HOST_PINNED, groups, n_sel, k, max_radius, rows_out, radius_out, members_out);
 }
 
 // plan_summary's answer for this process's environment; needs no device
@@ -3360,59 +3485,14 @@ int vq_debug_summary_plan(int64_t n, int64_t largest_group, int dim, int k, int*
 
 int vq_index_label_rows_device(vq_index* x, const void* d_prompts, int P, int mode, float max_dist, void* d_row_label, void* d_row_dist,
                                int m, void* d_group_tags, void* d_group_votes, void* d_group_show_rows, void* d_group_unlabelled) {
-    static const char* fn = "vq_index_label_rows_device";
-    const bool groups = d_group_tags != nullptr;
-    VQ_TRY(check_label_args(fn, x, d_prompts, P, max_dist, m, groups, d_group_votes && d_group_show_rows && d_group_unlabelled));
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    VQ_TRY(label_precheck(x, fn, mode, groups));
-    return label_run(x, (const float*)d_prompts, P, mode, false, max_dist, (int32_t*)d_row_label, (float*)d_row_dist, m, (int32_t*)d_group_tags,
-                     (int32_t*)d_group_votes, (int32_t*)d_group_show_rows, (int32_t*)d_group_unlabelled, nullptr, nullptr);
+    return label_call(x, "vq_index_label_rows_device", ON_DEVICE, d_prompts, P, mode, max_dist, d_row_label, d_row_dist, m, d_group_tags,
+                      d_group_votes, d_group_show_rows, d_group_unlabelled);
 }
 
 int vq_index_label_rows(vq_index* x, const float* prompts, int P, int mode, float max_dist, int32_t* row_label, float* row_dist, int m,
                         int32_t* group_tags, int32_t* group_votes, int32_t* group_show_rows, int32_t* group_unlabelled) {
-    static const char* fn = "vq_index_label_rows";
-    const bool groups = group_tags != nullptr;
-    VQ_TRY(check_label_args(fn, x, prompts, P, max_dist, m, groups, group_votes && group_show_rows && group_unlabelled));
-    std::lock_guard<std::mutex> lk(x->mu);
-    bool in_range = true;                                   // every |p|^2 inside what the fp16 bound covers
-    for (int j = 0; j < P; ++j) {
-        double s2 = 0.0;
-        for (int i = 0; i < x->dim; ++i) {
-            const float v = prompts[(size_t)j * x->dim + i];
-            VQ_CHECK(v - v == 0.f, "%s: prompt %d holds a value that is not finite", fn, j);
-            s2 += (double)v * v;
-        }
-        if (!(s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX)) in_range = false;
-    }
-    if (x->size == 0) {
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    VQ_TRY(label_precheck(x, fn, mode, groups));
-    const int64_t n = x->size, gm = groups ? (int64_t)x->n_groups * m : 0;
-    int32_t* d_t = nullptr;
-    if (groups) {
-        VQ_TRY(x->d_lout.reserve(3 * gm + x->n_groups));
-        d_t = x->d_lout;
-    }
-    int32_t* d_lab; float* d_best;
-    VQ_TRY(stage_queries(x, prompts, P));
-    VQ_TRY(label_run(x, x->d_q, P, mode, !in_range, max_dist, nullptr, nullptr, m, d_t, d_t + gm, d_t + 2 * gm, d_t + 3 * gm, &d_lab, &d_best));
-    if (row_label) VQ_HIP(hipMemcpyAsync(row_label, d_lab, (size_t)n * 4, hipMemcpyDeviceToHost, x->stream));
-    if (row_dist) VQ_HIP(hipMemcpyAsync(row_dist, d_best, (size_t)n * 4, hipMemcpyDeviceToHost, x->stream));
-    if (groups) {
-        VQ_HIP(hipMemcpyAsync(group_tags, d_t, (size_t)gm * 4, hipMemcpyDeviceToHost, x->stream));
-        VQ_HIP(hipMemcpyAsync(group_votes, d_t + gm, (size_t)gm * 4, hipMemcpyDeviceToHost, x->stream));
-        VQ_HIP(hipMemcpyAsync(group_show_rows, d_t + 2 * gm, (size_t)gm * 4, hipMemcpyDeviceToHost, x->stream));
-        VQ_HIP(hipMemcpyAsync(group_unlabelled, d_t + 3 * gm, (size_t)x->n_groups * 4, hipMemcpyDeviceToHost, x->stream));
-    }
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return label_call(x, "vq_index_label_rows", HOST_PINNED, prompts, P, mode, max_dist, row_label, row_dist, m, group_tags, group_votes,
+                      group_show_rows, group_unlabelled);
 }
 
 // plan_label's answer for near-unit rows; needs no device
@@ -3432,85 +3512,14 @@ int vq_debug_label_plan(int64_t n, int dim, int P, int mode, int64_t largest_gro
 
 int vq_index_cluster_device(vq_index* x, const void* d_init, const void* d_init_rows, int P, int iters, int mode, void* d_centroids,
                             void* d_row_label, void* d_row_dist, void* d_counts, void* d_show_rows) {
-    static const char* fn = "vq_index_cluster_device";
-    VQ_TRY(check_cluster_args(fn, x, d_init, d_init_rows, P, iters, d_centroids && d_counts && d_show_rows));
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    VQ_CHECK(P <= x->size, "%s: %d clusters for an index of %lld rows", fn, P, (long long)x->size);
-    VQ_TRY(cluster_precheck(x, fn, mode));
-    ClusterBufs b;
-    VQ_TRY(cluster_reserve(x, P, &b));
-    float* C = (float*)d_centroids;
-    if (d_init) {
-        if (d_init != d_centroids) VQ_HIP(hipMemcpyAsync(C, d_init, (size_t)P * x->dim * 4, hipMemcpyDeviceToDevice, x->stream));
-    } else {
-        hipLaunchKernelGGL(cluster_gather_kernel, dim3(P), dim3(256), 0, x->stream, x->rows, x->size, x->dim, (const int32_t*)d_init_rows, C);
-    }
-    int T;
-    return cluster_run(x, b, C, P, iters, mode, false, d_row_label ? (int32_t*)d_row_label : b.lab, d_row_dist ? (float*)d_row_dist : b.best,
-                       (int32_t*)d_counts, (int32_t*)d_show_rows, nullptr, &T);
+    return cluster_call(x, "vq_index_cluster_device", ON_DEVICE, d_init, (const int32_t*)d_init_rows, P, iters, mode, d_centroids, d_row_label,
+                        d_row_dist, d_counts, d_show_rows, nullptr, nullptr);
 }
 
 int vq_index_cluster(vq_index* x, const float* init, const int32_t* init_rows, int P, int max_iter, int mode, float* centroids,
                      int32_t* row_label, float* row_dist, int32_t* counts, int32_t* show_rows, int* iterations, int32_t* changed) {
-    static const char* fn = "vq_index_cluster";
-    VQ_TRY(check_cluster_args(fn, x, init, init_rows, P, max_iter, centroids && counts && show_rows && iterations));
-    std::lock_guard<std::mutex> lk(x->mu);
-    bool in_range = true;                                   // every |c|^2 inside what the fp16 bound covers
-    if (init) {
-        for (int j = 0; j < P; ++j) {
-            double s2 = 0.0;
-            for (int i = 0; i < x->dim; ++i) {
-                const float v = init[(size_t)j * x->dim + i];
-                VQ_CHECK(v - v == 0.f, "%s: initial centroid %d holds a value that is not finite", fn, j);
-                s2 += (double)v * v;
-            }
-            if (!(s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX)) in_range = false;
-        }
-    }
-    if (x->size == 0) {
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    const int64_t n = x->size;
-    VQ_CHECK(P <= n, "%s: %d clusters for an index of %lld rows", fn, P, (long long)n);
-    if (init_rows)
-        for (int j = 0; j < P; ++j)
-            VQ_CHECK(init_rows[j] >= 0 && init_rows[j] < n, "%s: init_rows[%d] = %d outside [0, %lld)", fn, j, (int)init_rows[j], (long long)n);
-    VQ_TRY(cluster_precheck(x, fn, mode));
-    ClusterBufs b;
-    VQ_TRY(cluster_reserve(x, P, &b));
-    if (x->h_clchanged.cap < max_iter) {                    // (the device form never writes there: nothing in flight uses it)
-        VQ_HIP(hipStreamSynchronize(x->stream));
-        VQ_TRY(x->h_clchanged.reserve(max_iter, CL_MAX_ITER));
-    }
-    const int64_t words = (int64_t)P * x->dim;
-    if (init) {
-        VQ_TRY(stage_queries(x, init, P));                  // the centroids live in d_q, as the label call's prompts do
-    } else {
-        VQ_TRY(x->d_q.reserve(words));
-        StageSlot* slot;
-        VQ_TRY(stage_slot(x, P, &slot));
-        std::memcpy(slot->h, init_rows, (size_t)P * 4);
-        VQ_HIP(hipMemcpyAsync(b.show, slot->h.p, (size_t)P * 4, hipMemcpyHostToDevice, x->stream));      // (free until the show rows are written)
-        VQ_HIP(hipEventRecord(slot->ev, x->stream));
-        hipLaunchKernelGGL(cluster_gather_kernel, dim3(P), dim3(256), 0, x->stream, x->rows, n, x->dim, b.show, x->d_q);
-    }
-    std::vector<int32_t> ch((size_t)max_iter);
-    int T = 0;
-    VQ_TRY(cluster_run(x, b, x->d_q, P, max_iter, mode, !in_range, b.lab, b.best, b.counts, b.show, ch.data(), &T));
-    VQ_HIP(hipMemcpyAsync(centroids, x->d_q, (size_t)words * 4, hipMemcpyDeviceToHost, x->stream));
-    if (row_label) VQ_HIP(hipMemcpyAsync(row_label, b.lab, (size_t)n * 4, hipMemcpyDeviceToHost, x->stream));
-    if (row_dist) VQ_HIP(hipMemcpyAsync(row_dist, b.best, (size_t)n * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(counts, b.counts, (size_t)P * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(show_rows, b.show, (size_t)P * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    *iterations = T;
-    if (changed) std::copy(ch.begin(), ch.begin() + T, changed);
-    return 0;
+    return cluster_call(x, "vq_index_cluster", HOST_PINNED, init, init_rows, P, max_iter, mode, centroids, row_label, row_dist, counts, show_rows,
+                        iterations, changed);
 }
 
 // The update alone, on labels the caller writes (tests/test_cluster.py): centroids_out = the update of centroids_in under
@@ -3552,50 +3561,12 @@ int vq_debug_cluster_plan(int64_t n, int dim, int P, int* piece_rows, int64_t* m
 
 int vq_index_search_compound_device(vq_index* x, const void* d_terms, int m, const int32_t* clause_of, float margin, int k, int mode,
                                     void* d_ids, void* d_dist, void* d_term_dist) {
-    static const char* fn = "vq_index_search_compound_device";
-    VQ_TRY(check_compound_args(fn, x, m, clause_of, margin, k, mode, d_terms && d_ids && d_dist));
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {
-        if (d_term_dist) VQ_HIP(hipMemsetD32Async((hipDeviceptr_t)d_term_dist, 0x7f800000, (size_t)k * m, x->stream));      // +inf
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return fill_empty(x, k, (int32_t*)d_ids, nullptr, (float*)d_dist);
-    }
-    VQ_TRY(compound_precheck(x, fn, k, mode));
-    return compound_run(x, (const float*)d_terms, m, clause_of, margin, k, mode, false, (int32_t*)d_ids, (float*)d_dist, (float*)d_term_dist);
+    return compound_call(x, "vq_index_search_compound_device", ON_DEVICE, d_terms, m, clause_of, margin, k, mode, d_ids, d_dist, d_term_dist);
 }
 
 int vq_index_search_compound(vq_index* x, const float* terms, int m, const int32_t* clause_of, float margin, int k, int mode, int32_t* ids,
                              float* dist, float* term_dist) {
-    static const char* fn = "vq_index_search_compound";
-    VQ_TRY(check_compound_args(fn, x, m, clause_of, margin, k, mode, terms && ids && dist));
-    std::lock_guard<std::mutex> lk(x->mu);
-    bool in_range = true;                                   // every |q|^2 inside what the fp16 bound covers
-    for (int j = 0; j < m; ++j) {
-        double s2 = 0.0;
-        for (int i = 0; i < x->dim; ++i) {
-            const float v = terms[(size_t)j * x->dim + i];
-            VQ_CHECK(v - v == 0.f, "%s: term %d holds a value that is not finite", fn, j);
-            s2 += (double)v * v;
-        }
-        if (!(s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX)) in_range = false;
-    }
-    const int64_t km = (int64_t)k * m;
-    if (x->size == 0) {
-        host_empty(k, ids, nullptr, dist);
-        if (term_dist) for (int64_t i = 0; i < km; ++i) term_dist[i] = __builtin_inff();
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    VQ_TRY(compound_precheck(x, fn, k, mode));
-    VQ_TRY(reserve_id_dist(x, k));
-    VQ_TRY(x->d_cout.reserve(km));
-    VQ_TRY(stage_queries(x, terms, m));
-    VQ_TRY(compound_run(x, x->d_q, m, clause_of, margin, k, mode, !in_range, x->d_ids, x->d_out, term_dist ? x->d_cout.p : nullptr));
-    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
-    if (term_dist) VQ_HIP(hipMemcpyAsync(term_dist, x->d_cout, (size_t)km * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return compound_call(x, "vq_index_search_compound", HOST_PINNED, terms, m, clause_of, margin, k, mode, ids, dist, term_dist);
 }
 
 // plan_compound's answer for near-unit rows; needs no device
@@ -3611,76 +3582,17 @@ int vq_debug_compound_plan(int64_t n, int dim, int m, int k, int mode, int* fp16
     return 0;
 }
 
-// (the arguments are judged before the library is asked for its device)
-static int check_segment_args(const char* fn, const vq_index* x, const int32_t* groups, int32_t n_sel, int k, float penalty, int64_t max_len,
-                              bool arrays) {
-    VQ_CHECK(n_sel >= 1, "%s: n_sel %d: at least one group must be listed", fn, (int)n_sel);
-    VQ_CHECK(k >= 1 && k <= SEG_MAX_K, "%s: k %d outside [1, %d]", fn, k, SEG_MAX_K);
-    VQ_CHECK(penalty == penalty && penalty >= 0.0f, "%s: penalty must be >= 0 and not NaN", fn);
-    VQ_CHECK(max_len >= 0, "%s: max_len %lld is negative (0: no limit)", fn, (long long)max_len);
-    VQ_TRY(require_init());
-    VQ_CHECK(x && groups && arrays, "%s: bad argument", fn);
-    return 0;
-}
-
 int vq_index_segment_groups_device(vq_index* x, const int32_t* groups, int32_t n_sel, int k, float penalty, int64_t max_len, void* d_count_out,
                                    void* d_first_out, void* d_last_out, void* d_len_out, void* d_spread_out, void* d_show_out,
                                    void* d_mean_spread_out) {
-    static const char* fn = "vq_index_segment_groups_device";
-    VQ_TRY(check_segment_args(fn, x, groups, n_sel, k, penalty, max_len, d_count_out && d_first_out && d_last_out && d_len_out && d_spread_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {
-        const int64_t slots = (int64_t)n_sel * k;
-        fill_no_result(x, (int32_t*)d_first_out, (float*)d_spread_out, slots);
-        fill_no_result(x, (int32_t*)d_last_out, (float*)d_spread_out, slots);
-        if (d_show_out) fill_no_result(x, (int32_t*)d_show_out, (float*)d_spread_out, slots);
-        if (d_mean_spread_out) fill_no_result(x, (int32_t*)d_first_out, (float*)d_mean_spread_out, n_sel);
-        VQ_HIP(hipMemsetAsync(d_len_out, 0, (size_t)slots * 4, x->stream));
-        VQ_HIP(hipMemsetAsync(d_count_out, 0, (size_t)n_sel * 4, x->stream));
-        VQ_HIP(hipGetLastError());
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    std::vector<int64_t> len;
-    VQ_TRY(seg_precheck(x, fn, groups, n_sel, k, max_len, &len));
-    return segment_run(x, fn, groups, n_sel, len, k, penalty, max_len, (int32_t*)d_count_out, (int32_t*)d_first_out, (int32_t*)d_last_out,
-                       (int32_t*)d_len_out, (float*)d_spread_out, (int32_t*)d_show_out, (float*)d_mean_spread_out);
+    return segment_call(x, "vq_index_segment_groups_device", ON_DEVICE, groups, n_sel, k, penalty, max_len, d_count_out, d_first_out, d_last_out,
+                        d_len_out, d_spread_out, d_show_out, d_mean_spread_out);
 }
 
 int vq_index_segment_groups(vq_index* x, const int32_t* groups, int32_t n_sel, int k, float penalty, int64_t max_len, int32_t* count_out,
                             int32_t* first_out, int32_t* last_out, int32_t* len_out, float* spread_out, int32_t* show_out, float* mean_spread_out) {
-    static const char* fn = "vq_index_segment_groups";
-    VQ_TRY(check_segment_args(fn, x, groups, n_sel, k, penalty, max_len, count_out && first_out && last_out && len_out && spread_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    const int64_t slots = (int64_t)n_sel * k;
-    if (x->size == 0) {
-        host_empty(slots, first_out, last_out, spread_out);
-        std::fill(len_out, len_out + slots, 0);
-        std::fill(count_out, count_out + n_sel, 0);
-        if (show_out) std::fill(show_out, show_out + slots, -1);
-        if (mean_spread_out) std::fill(mean_spread_out, mean_spread_out + n_sel, __builtin_inff());
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    std::vector<int64_t> len;
-    VQ_TRY(seg_precheck(x, fn, groups, n_sel, k, max_len, &len));
-    // count [n_sel] | mean [n_sel] | first | last | len | show | spread [slots] each
-    VQ_TRY(x->d_segout.reserve(2 * (int64_t)n_sel + 5 * slots));
-    int32_t* d_count = x->d_segout; float* d_mean = (float*)(d_count + n_sel);
-    int32_t* d_first = d_count + 2 * (int64_t)n_sel; int32_t* d_last = d_first + slots; int32_t* d_len = d_last + slots; int32_t* d_show = d_len + slots;
-    float* d_spread = (float*)(d_show + slots);
-    VQ_TRY(segment_run(x, fn, groups, n_sel, len, k, penalty, max_len, d_count, d_first, d_last, d_len, d_spread, show_out ? d_show : nullptr,
-                       mean_spread_out ? d_mean : nullptr));
-    auto back = [&](void* dst, const void* src, int64_t words) { return hipMemcpyAsync(dst, src, (size_t)words * 4, hipMemcpyDeviceToHost, x->stream); };
-    VQ_HIP(back(count_out, d_count, n_sel));
-    VQ_HIP(back(first_out, d_first, slots));
-    VQ_HIP(back(last_out, d_last, slots));
-    VQ_HIP(back(len_out, d_len, slots));
-    VQ_HIP(back(spread_out, d_spread, slots));
-    if (show_out) VQ_HIP(back(show_out, d_show, slots));
-    if (mean_spread_out) VQ_HIP(back(mean_spread_out, d_mean, n_sel));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return segment_call(x, "vq_index_segment_groups", HOST_PINNED, groups, n_sel, k, penalty, max_len, count_out, first_out, last_out, len_out,
+                        spread_out, show_out, mean_spread_out);
 }
 
 // plan_segment's answer for this process's environment; needs no device
@@ -3703,50 +3615,15 @@ int vq_debug_segment_plan(const int64_t* lengths, int32_t n_sel, int dim, int k,
 int vq_index_match_runs_device(vq_index* x, const void* d_queries, int m, int k, float max_dist, int min_len, int max_miss, int mode,
                                const int32_t* groups, int32_t n_sel, int exclude, void* d_groups_out, void* d_hits_out, void* d_span_out,
                                void* d_q_first_out, void* d_row_first_out, void* d_row_last_out, void* d_mean_dist_out) {
-    static const char* fn = "vq_index_match_runs_device";
-    VQ_TRY(check_match_args(fn, x, m, k, max_dist, min_len, max_miss, mode, groups, n_sel, exclude,
-                            d_queries && d_groups_out && d_hits_out && d_span_out && d_q_first_out && d_row_first_out && d_row_last_out && d_mean_dist_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    const MatchOut o{(int32_t*)d_groups_out, (int32_t*)d_hits_out, (int32_t*)d_span_out, (int32_t*)d_q_first_out, (int32_t*)d_row_first_out,
-                     (int32_t*)d_row_last_out, (float*)d_mean_dist_out};
-    if (x->size == 0) return match_fill_empty(x, k, o);
-    const FilterLabels f = filter_labels(x, groups, n_sel);
-    VQ_TRY(match_precheck(x, fn, m, mode, f));
-    return match_run(x, fn, (const float*)d_queries, m, k, max_dist, min_len, max_miss, mode, false, f, exclude, o);
+    return match_call(x, "vq_index_match_runs_device", ON_DEVICE, d_queries, m, k, max_dist, min_len, max_miss, mode, groups, n_sel, exclude,
+                      d_groups_out, d_hits_out, d_span_out, d_q_first_out, d_row_first_out, d_row_last_out, d_mean_dist_out);
 }
 
 int vq_index_match_runs(vq_index* x, const float* queries, int m, int k, float max_dist, int min_len, int max_miss, int mode,
                         const int32_t* groups, int32_t n_sel, int exclude, int32_t* groups_out, int32_t* hits_out, int32_t* span_out,
                         int32_t* q_first_out, int32_t* row_first_out, int32_t* row_last_out, float* mean_dist_out) {
-    static const char* fn = "vq_index_match_runs";
-    VQ_TRY(check_match_args(fn, x, m, k, max_dist, min_len, max_miss, mode, groups, n_sel, exclude,
-                            queries && groups_out && hits_out && span_out && q_first_out && row_first_out && row_last_out && mean_dist_out));
-    std::lock_guard<std::mutex> lk(x->mu);
-    if (x->size == 0) {
-        for (int j = 0; j < k; ++j) {
-            groups_out[j] = -1; hits_out[j] = 0; span_out[j] = 0; q_first_out[j] = -1; row_first_out[j] = -1; row_last_out[j] = -1;
-            mean_dist_out[j] = __builtin_inff();
-        }
-        set_stats(x, STATS_HOST, 0, 0, 0);
-        return 0;
-    }
-    const FilterLabels f = filter_labels(x, groups, n_sel);
-    VQ_TRY(match_precheck(x, fn, m, mode, f));
-    bool in_range = true;                                   // every |q|^2 inside what the fp16 bound covers (the sum as the device takes it
-    for (int i = 0; i < m && in_range; ++i) {               // matters only at the range's very edge, where either path is exact)
-        double s2 = 0.0;
-        for (int c = 0; c < x->dim; ++c) s2 += (double)queries[(size_t)i * x->dim + c] * queries[(size_t)i * x->dim + c];
-        in_range = s2 >= SCAN_Q2_MIN && s2 <= SCAN_Q2_MAX;
-    }
-    VQ_TRY(x->d_mout.reserve(7 * (int64_t)k));
-    int32_t* d = x->d_mout;
-    const MatchOut o{d, d + k, d + 2 * k, d + 3 * k, d + 4 * k, d + 5 * k, (float*)(d + 6 * k)};
-    VQ_TRY(stage_queries(x, queries, m));
-    VQ_TRY(match_run(x, fn, x->d_q, m, k, max_dist, min_len, max_miss, mode, !in_range, f, exclude, o));
-    void* const host[7] = {groups_out, hits_out, span_out, q_first_out, row_first_out, row_last_out, mean_dist_out};
-    for (int a = 0; a < 7; ++a) VQ_HIP(hipMemcpyAsync(host[a], d + (int64_t)a * k, (size_t)k * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return match_call(x, "vq_index_match_runs", HOST_PINNED, queries, m, k, max_dist, min_len, max_miss, mode, groups, n_sel, exclude, groups_out,
+                      hits_out, span_out, q_first_out, row_first_out, row_last_out, mean_dist_out);
 }
 
 // plan_match's answer for near-unit rows and this process's environment; needs no device
@@ -3768,29 +3645,11 @@ int vq_debug_match_plan(int64_t n, int64_t n_groups, int dim, int m, int mode, i
 }
 
 int vq_index_neighbors_device(vq_index* x, const int64_t* rows, int64_t m, int k, int exclude, int mode, void* d_ids, void* d_dist) {
-    static const char* fn = "vq_index_neighbors_device";
-    VQ_TRY(check_neighbors_args(fn, x, m, k, exclude, mode, d_ids && d_dist));
-    std::lock_guard<std::mutex> lk(x->mu);
-    NeighborsPlan p;
-    VQ_TRY(neighbors_precheck(x, fn, rows, m, k, exclude, mode, &p));
-    if (m == 0) return 0;
-    return neighbors_run(x, rows, m, k, exclude, p, (int32_t*)d_ids, (float*)d_dist);
+    return neighbors_call(x, "vq_index_neighbors_device", ON_DEVICE, rows, m, k, exclude, mode, d_ids, d_dist);
 }
 
 int vq_index_neighbors(vq_index* x, const int64_t* rows, int64_t m, int k, int exclude, int mode, int32_t* ids, float* dist) {
-    static const char* fn = "vq_index_neighbors";
-    VQ_TRY(check_neighbors_args(fn, x, m, k, exclude, mode, ids && dist));
-    std::lock_guard<std::mutex> lk(x->mu);
-    NeighborsPlan p;
-    VQ_TRY(neighbors_precheck(x, fn, rows, m, k, exclude, mode, &p));
-    if (m == 0) return 0;
-    const int64_t count = m * k;
-    VQ_TRY(reserve_id_dist(x, count));
-    VQ_TRY(neighbors_run(x, rows, m, k, exclude, p, x->d_ids, x->d_out));
-    VQ_HIP(hipMemcpyAsync(ids, x->d_ids, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipMemcpyAsync(dist, x->d_out, (size_t)count * 4, hipMemcpyDeviceToHost, x->stream));
-    VQ_HIP(hipStreamSynchronize(x->stream));
-    return 0;
+    return neighbors_call(x, "vq_index_neighbors", HOST_PINNED, rows, m, k, exclude, mode, ids, dist);
 }
 
 // plan_neighbors' answer for near-unit rows; needs no device
