@@ -1035,11 +1035,32 @@ int vq_debug_scan_plan(int dim, int64_t n, int nq, int k, int force_scan, vq_sca
  *   fp16 path.  info = {q0, cur, n_groups}; best [cur][n_groups]: the largest fp16 score the group-max scan saw for the
  *   (query, group), decoded from its order-preserving key to a float.  A group no (allowed) row was seen for reads as NaN:
  *   its key is 0, which no score encodes (a score's key is never 0, and a scan never produces a NaN score from finite
- *   rows and queries).  best == NULL: info only.  A clip search overwrites the same buffer: afterwards VQ_ERR_STATE.
+ *   rows and queries).  best == NULL: info only.
  *   vq_debug_scan_row_of: the row number of index `local` (0 .. 127) of stream `stream` under key layout 1, 2 or 3, by
- *   the functions the re-score kernels use; -1 for any other argument.  Pure host arithmetic: no device. */
+ *   the functions the re-score kernels use; -1 for any other argument.  Pure host arithmetic: no device.
+ *
+ * The streamed 256 x 256 tile scans (tests/test_tile_scan_stages.py) are read back the same way:
+ *   vq_index_neighbors in mode 2 leaves its LAST chunk's keys for vq_index_debug_read_scan_keys: layout 2, streams = the
+ *   plan's, q0 / cur = that chunk's asked rows, info[4] = 2: eligibility by tag (a struck pair reads as "no row").
+ *   vq_index_search_set where it took the fp16 path leaves its LAST query chunk's maxima for vq_index_debug_read_group_best,
+ *   whichever of the two group-max scans wrote them (nothing behind the scan writes that buffer).
+ *   vq_index_debug_group_scan_kind says which: info = {kind, chunks, tile_chunks}, kind 1 = the grouped search's streaming
+ *   scan, 2 = the clip search's streaming scan (a chunk of at most 16 queries), 3 = set_group_max_kernel; chunks = the query
+ *   chunks of the call that left the record, tile_chunks = how many of them ran set_group_max_kernel.
+ *   vq_index_debug_read_label_parts: after a labelling call that took the tile path and was not flagged (flagged:
+ *   VQ_ERR_STATE).  info = {n, n_pad, ranges, P}; parts [ranges][5][n_pad]: per (prompt range, row) the words k1, j1, k2, j2, f
+ *   as label_tile_kernel wrote them: keys are order-preserving words of the fp32 score with the inverted lane-local prompt
+ *   index in the low 7 bits, 0 = nothing; j1, j2 the prompt numbers (-1: none).  Rows from n to n_pad are pad rows.
+ *   vq_index_debug_read_match_bits: after a shared-footage call that took the tile path.  info = {m, W, n, cursor, flag, cap};
+ *   bits [m][W]: the FINAL hit-bit table (tile kernel, patch and, when flag == 2, the exact redo); filed: the first
+ *   min(cursor, cap) entries of the filed list, (query << 32) | row, in the order the atomics gave them.  Either array may be
+ *   NULL. */
 int vq_index_debug_read_scan_keys(vq_index* idx, int64_t* info /*[5]*/, uint32_t* keys, int64_t capacity);
 int vq_index_debug_read_group_best(vq_index* idx, int64_t* info /*[3]*/, float* best, int64_t capacity);
+int vq_index_debug_group_scan_kind(vq_index* idx, int64_t* info /*[3]*/);
+int vq_index_debug_read_label_parts(vq_index* idx, int64_t* info /*[4]*/, uint32_t* parts, int64_t capacity);
+int vq_index_debug_read_match_bits(vq_index* idx, int64_t* info /*[6]*/, uint32_t* bits, int64_t bits_capacity, uint64_t* filed,
+                                   int64_t filed_capacity);
 int64_t vq_debug_scan_row_of(int layout, int64_t stream, int local);
 
 /* Stage entry of the fp16 re-score (tests/test_rescore_stages.py): pass 2 of an fp16 search on a key table the CALLER wrote.

@@ -86,20 +86,27 @@ def _first(mask: np.ndarray):
 def check_keys(keys: np.ndarray, rows: np.ndarray, queries: np.ndarray, table: np.ndarray, allowed_rows: np.ndarray | None = None,
                q_block: int = 1024) -> float:
     """keys uint32 [nq][streams][2] against the fp32 rows [n][dim] and queries [nq][dim] they were scanned from.  allowed_rows:
-    bool [n] of a masked scan.  Every (query, stream) takes part.  Returns max(|key - exact| / E) over the keys that name a row."""
+    bool [n] of a masked scan, or bool [nq][n]: a mask per query (the tile scan of the library neighbours strikes PAIRS).
+    Every (query, stream) takes part.  Returns max(|key - exact| / E) over the keys that name a row."""
     nq, streams, _ = keys.shape
     n = len(rows)
     assert table.shape == (streams, STREAM_ROWS) and len(queries) == nq
     in_range = table < n
     tclip = np.where(in_range, table, 0)
-    valid = in_range & (allowed_rows[tclip] if allowed_rows is not None else True)          # V of every stream [streams][128]
-    nvalid = valid.sum(1)
+    per_query = allowed_rows is not None and np.ndim(allowed_rows) == 2
+    if per_query:
+        assert allowed_rows.shape == (nq, n)
+        valid_all = None                                                                    # V of every (query, stream), built per block
+    else:
+        valid_all = (in_range & (allowed_rows[tclip] if allowed_rows is not None else True))[None]      # V of every stream [1][streams][128]
     E = bound(rows, queries)
     worst = 0.0
     q_block = max(1, min(q_block, (1 << 22) // (streams * STREAM_ROWS)))                     # <= 32 MiB per [queries][streams][128] fp64 array
     for q0 in range(0, nq, q_block):
         kb = keys[q0:q0 + q_block]
         nb = len(kb)
+        valid = in_range[None] & allowed_rows[q0:q0 + q_block][:, tclip] if per_query else valid_all          # [nb or 1][streams][128]
+        nvalid = valid.sum(2)
         kf = kb.view(np.float32).astype(np.float64)
         local = (kb & 127).astype(np.int64)
         is_row = kb.view(np.float32) > NO_ROW_BELOW
@@ -109,14 +116,13 @@ def check_keys(keys: np.ndarray, rows: np.ndarray, queries: np.ndarray, table: n
         if bad.any():
             q, s = _first(bad)
             raise StageError(f"query {q0 + q} stream {s}: key1 {kf[q, s, 0]} < key2 {kf[q, s, 1]}")
-        want_rows = np.minimum(nvalid, 2)[None, :]
+        want_rows = np.minimum(nvalid, 2)
         bad = is_row.sum(2) != want_rows
         if bad.any():
             q, s = _first(bad)
-            raise StageError(f"query {q0 + q} stream {s}: {int(is_row[q, s].sum())} keys name a row, the stream holds {int(nvalid[s])} "
+            raise StageError(f"query {q0 + q} stream {s}: {int(is_row[q, s].sum())} keys name a row, the stream holds {int(nvalid[q if per_query else 0, s])} "
                              f"(allowed) rows below n = {n}")
-        sidx = np.arange(streams)[None, :, None]
-        bad = is_row & ~valid[sidx, local]
+        bad = is_row & ~np.take_along_axis(np.broadcast_to(valid, (nb, streams, STREAM_ROWS)), local, axis=2)
         if bad.any():
             q, s, w = _first(bad)
             raise StageError(f"query {q0 + q} stream {s} key {w + 1}: names row {int(table[s, local[q, s, w]])}, which is past n = {n} "
@@ -126,7 +132,7 @@ def check_keys(keys: np.ndarray, rows: np.ndarray, queries: np.ndarray, table: n
             q, s = _first(bad)
             raise StageError(f"query {q0 + q} stream {s}: both keys name row {int(table[s, local[q, s, 0]])}")
         ex = exact_scores(rows, queries[q0:q0 + q_block])                                    # [nb][n]
-        per = np.where(valid[None], ex[:, tclip.reshape(-1)].reshape(nb, streams, STREAM_ROWS), -np.inf)     # exact score of every (stream, local)
+        per = np.where(valid, ex[:, tclip.reshape(-1)].reshape(nb, streams, STREAM_ROWS), -np.inf)     # exact score of every (stream, local)
         named = np.take_along_axis(per, local, axis=2)                                       # [nb][streams][2]
         err = np.where(is_row, np.abs(kf - named), 0.0)
         Eb = E[q0:q0 + q_block][:, None, None]
@@ -209,14 +215,21 @@ def emulate_keys(rows: np.ndarray, queries: np.ndarray, table: np.ndarray, allow
     padded[:n] = rows
     sc = fp16_scores(padded, queries, skip_slice)                                          # [nq][n_pad]
     live = table < n_mask
-    if allowed_rows is not None:
+    if allowed_rows is not None and np.ndim(allowed_rows) == 2:                              # a mask per query [nq][n] (no stream is skipped)
+        assert stream_label is None
+        ok = np.zeros((len(queries), len(padded)), bool)
+        ok[:, :n] = allowed_rows
+        live = live[None] & ok[:, table]
+    elif allowed_rows is not None:
         ok = np.zeros(len(padded), bool)
         ok[:n] = allowed_rows
         live = live & ok[table]
     if drop is not None:
         live = live.copy()
-        live[drop] = False
-    v = np.where(live[None], sc[:, table.reshape(-1)].reshape(len(queries), streams, STREAM_ROWS), SENTINEL).astype(np.float32)
+        live[..., drop[0], drop[1]] = False
+    if live.ndim == 2:
+        live = live[None]
+    v = np.where(live, sc[:, table.reshape(-1)].reshape(len(queries), streams, STREAM_ROWS), SENTINEL).astype(np.float32)
     bits = (v.view(np.uint32) & np.uint32(0xFFFFFF80)) | np.arange(STREAM_ROWS, dtype=np.uint32)[None, None, :]
     if drop is not None:                                                                    # a skipped row is not folded at all
         bits[:, drop[0], drop[1]] = np.float32(-np.inf).view(np.uint32)
@@ -224,7 +237,7 @@ def emulate_keys(rows: np.ndarray, queries: np.ndarray, table: np.ndarray, allow
     out = np.take_along_axis(bits, order, axis=2)
     if allowed_rows is not None and stream_label is not None:
         for s in range(streams):
-            if stream_label[s] >= 0 and not live[s].any():
+            if stream_label[s] >= 0 and not live[0, s].any():
                 out[:, s, :] = SENTINEL.view(np.uint32)
     return np.ascontiguousarray(out)
 

@@ -220,6 +220,10 @@ SIGNATURES = {
     "vq_debug_scan_plan": (c_int, [c_int, c_int64, c_int, c_int, c_int, POINTER(ScanPlanC)]),
     "vq_index_debug_read_scan_keys": (c_int, [c_void_p, POINTER(c_int64), POINTER(ctypes.c_uint32), c_int64]),
     "vq_index_debug_read_group_best": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_float), c_int64]),
+    "vq_index_debug_group_scan_kind": (c_int, [c_void_p, POINTER(c_int64)]),
+    "vq_index_debug_read_label_parts": (c_int, [c_void_p, POINTER(c_int64), POINTER(ctypes.c_uint32), c_int64]),
+    "vq_index_debug_read_match_bits": (c_int, [c_void_p, POINTER(c_int64), POINTER(ctypes.c_uint32), c_int64, POINTER(ctypes.c_uint64),
+                                               c_int64]),
     "vq_debug_scan_row_of": (c_int64, [c_int, c_int64, c_int]),
     "vq_index_debug_rescore": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, POINTER(ctypes.c_uint32), c_int64, POINTER(c_int32),
                                        POINTER(c_float), POINTER(c_int32)]),

@@ -223,9 +223,16 @@ struct vq_index {
     ScanSwitches scan_switches;    // the fp16 search's A/B switches (scan_plan.h), read from the environment at create
     // What pass 1 of the last fp16 search left in d_keys / d_gbest (vq_index_debug_read_scan_keys / _group_best): host
     // bookkeeping only, no launch and no wait.  Forgotten when the rows change (rows_changed) or another search takes the buffer.
-    struct LastScan { bool valid = false, masked = false; int layout = 0, cur = 0; int64_t streams = 0, q0 = 0; } last_scan;
-    struct LastGroupScan { bool valid = false; int cur = 0; int32_t n_groups = 0; int64_t q0 = 0; } last_gscan;
-    void rows_changed() { last_scan.valid = false; last_gscan.valid = false; }
+    // masked: 0 no filter, 1 a group filter's bitmap, 2 eligibility by tag (library neighbours).  kind: 1 the grouped search's
+    // scan3_group_max, 2 the clip search's scan3_group_max, 3 set_group_max_kernel; chunks / tile_chunks: the query chunks of the
+    // call that left the record, and how many of them ran set_group_max_kernel.
+    struct LastScan { bool valid = false; int masked = 0; int layout = 0, cur = 0; int64_t streams = 0, q0 = 0; } last_scan;
+    struct LastGroupScan { bool valid = false; int cur = 0; int32_t n_groups = 0; int64_t q0 = 0; int kind = 0, chunks = 0, tile_chunks = 0; } last_gscan;
+    // What the tile paths of the last labelling and shared-footage calls left in d_lparts / d_mbits + d_mfiled
+    // (vq_index_debug_read_label_parts / _match_bits), kept and forgotten like the two above.
+    struct LastLabel { bool valid = false; int64_t n = 0, n_pad = 0; int ranges = 0, P = 0; } last_label;
+    struct LastMatch { bool valid = false; int m = 0; int64_t W = 0, n = 0, cap = 0; } last_match;
+    void rows_changed() { last_scan.valid = false; last_gscan.valid = false; last_label.valid = false; last_match.valid = false; }
     bool profiling = false;
     struct Ev { int cls; hipEvent_t a, b; };
     std::vector<Ev> events;
@@ -848,7 +855,7 @@ int search_grouped_fp16(vq_index* x, const float* d_queries, int nq, int k, int3
             hipLaunchKernelGGL(scan, dim3(cdiv(streams, 4), (int)(q_pad / 16)), dim3(256), 0, x->stream, x->d_q16, x->rows16, streams,
                                x->d_group, x->d_sgroup, cur, G, x->d_gbest, allow);
         }
-        x->last_gscan = {true, cur, (int32_t)G, q0};
+        x->last_gscan = {true, cur, (int32_t)G, q0, 1, 1, 0};
         {
             Prof p(x, I_RESCORE);
             hipLaunchKernelGGL(group_threshold_kernel, dim3(cur), dim3(256), 0, x->stream, x->d_gbest, G, k_sel, qp, x->dim, eps_rows, x->d_goff,
@@ -1316,10 +1323,11 @@ int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, i
     const int nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK), lpg = lanes_per_group(n, G);
     const bool use_fp16 = mode == 2 || (mode == 0 && set_fp16_ok(x) && x->size >= FP16_AUTO_MIN_ROWS);     // the plain search's rule
     VQ_TRY(x->d_ssum.reserve(2 * (int64_t)G));
-    VQ_TRY(x->d_scand.reserve(2 * (int64_t)G + 2));
+    VQ_TRY(x->d_scand.reserve(3 * (int64_t)G + 2));
     VQ_TRY(x->d_sekey.reserve((int64_t)G + (int64_t)nblocks * kl));
     double* sum16 = x->d_ssum; double* acc = sum16 + G;
     int32_t* cand = x->d_scand; int32_t* candpos = cand + G; int32_t* cand_n = candpos + G; int32_t* flag = cand_n + 1;
+    uint32_t* skey = (uint32_t*)(flag + 1);                 // set_threshold_kernel's [G] scratch: d_gbest keeps the last chunk's maxima
     uint64_t* ekey = x->d_sekey; uint64_t* partial = ekey + G;
     const TieOrder tie = x->tie();
 
@@ -1365,9 +1373,12 @@ int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, i
         VQ_HIP(hipMemsetAsync(cand_n, 0, 8, x->stream));                                 // candidate count and the call's flag
         hipLaunchKernelGGL(set_query_norm_kernel, dim3(m), dim3(64), 0, x->stream, d_queries, x->dim, x->d_sqn, flag);
         const int ranges = cdiv(n, SCAN2_RANGE), range_groups = cdiv(ranges, 4);
+        int chunks = 0, tile_chunks = 0;
         for (int64_t q0 = 0; q0 < m; q0 += qc) {
             const int cur = (int)std::min<int64_t>(qc, m - q0);
             const bool small = cur <= 16;                   // the streaming group-max scan of the grouped search
+            ++chunks; tile_chunks += small ? 0 : 1;
+            x->last_gscan = {true, cur, (int32_t)G, q0, small ? 2 : 3, chunks, tile_chunks};     // nothing behind the scan writes d_gbest
             const int64_t q_pad = round_up(cur, small ? 16 : SCAN2_QT);
             queries_to_f16(x, d_queries + q0 * x->dim, cur, q_pad);
             VQ_HIP(hipMemsetAsync(x->d_gbest, 0, (size_t)cur * G * 4, x->stream));
@@ -1391,7 +1402,7 @@ int search_set_run(vq_index* x, const char* fn, const float* d_queries, int m, i
             Prof pr(x, I_RESCORE);
             const int nsub = 256 / lpg;
             hipLaunchKernelGGL(set_threshold_kernel, dim3(1), dim3(256), 0, x->stream, sum16, G, m, std::min(k, nA), nA, allow, x->d_sqn,
-                               scan_eps_unit(x->dim) * x->row_norm_max, x->d_goff, x->d_gbest, cand, candpos, cand_n, ekey, flag, x->d_gcounters);
+                               scan_eps_unit(x->dim) * x->row_norm_max, x->d_goff, skey, cand, candpos, cand_n, ekey, flag, x->d_gcounters);
             hipLaunchKernelGGL(set_cand_keys_kernel, dim3(std::min(cdiv(G, nsub), 64), m), dim3(256), 0, x->stream, x->rows, x->dim, d_queries, m,
                                x->d_goff, x->d_grows, cand, cand_n, lpg, x->d_sckeys, flag, tie);
             hipLaunchKernelGGL(set_cand_sum_kernel, dim3(std::min(nblocks, 256)), dim3(256), 0, x->stream, x->d_sckeys, m, cand, cand_n, ekey, flag);
@@ -1930,6 +1941,7 @@ int label_run(vq_index* x, const float* d_prompts, int P, int mode, bool force_e
     float* best = best_out ? best_out : (float*)(filed + 2 * n_pad);
     if (lab_at) *lab_at = lab;
     if (best_at) *best_at = best;
+    x->last_label.valid = false;
     if (!p.fp16 || force_exact) {
         const int64_t ld = round_up(n, 64);
         VQ_TRY(x->d_lrun.reserve(n));
@@ -1958,6 +1970,7 @@ int label_run(vq_index* x, const float* d_prompts, int P, int mode, bool force_e
             hipLaunchKernelGGL(label_tile_kernel, dim3((unsigned)(p.row_tiles * p.prompt_ranges)), dim3(G2_THREADS), LABEL_LDS_BYTES, x->stream,
                                x->rows16, x->d_q16, x->dim, P, p.prompt_tiles, p.prompt_ranges, n_pad, x->d_lparts);
         }
+        x->last_label = {true, n, n_pad, p.prompt_ranges, P};
         {
             Prof pr(x, I_RESCORE);
             hipLaunchKernelGGL(label_finalize_kernel, dim3(grid_for(n)), dim3(256), 0, x->stream, x->d_lparts, p.prompt_ranges, n_pad, n, x->rows,
@@ -2212,6 +2225,7 @@ int match_run(vq_index* x, const char* fn, const float* d_queries, int m, int k,
     const int32_t* sorder = x->d_seq;
     VQ_HIP(hipMemsetAsync(ctl, 0, sizeof(MatchCtl), x->stream));
     VQ_HIP(hipMemsetAsync(gkey, 0xff, (size_t)G * 8, x->stream));
+    x->last_match.valid = false;
     if (!tile) {
         VQ_TRY(x->d_dist.reserve((int64_t)p.exact_chunk * ld));
         for (int q0 = 0; q0 < m; q0 += p.exact_chunk) {
@@ -2247,6 +2261,7 @@ int match_run(vq_index* x, const char* fn, const float* d_queries, int m, int k,
             hipLaunchKernelGGL(match_threshold_kernel<false>, dim3(cdiv(n, 256), m), dim3(256), 0, x->stream, nullptr, 0, x->rows, n, x->dim, d_queries,
                                max_dist, bits, W, ctl);
         }
+        x->last_match = {true, m, W, n, (int64_t)cap};
     }
     {
         Prof pr(x, I_SEQ_DP);
@@ -2373,6 +2388,7 @@ int neighbors_run(vq_index* x, const int64_t* rows, int64_t m, int k, int exclud
         launch_fallback(x, qp, cur, k, ids0, out0, x->d_counters.p, nullptr, elig);
         hipLaunchKernelGGL(neighbors_stats_kernel, dim3(1), dim3(64), 0, x->stream, x->d_counters.p, x->d_gcounters.p);
         VQ_HIP(hipGetLastError());
+        x->last_scan = {true, 2, 2, cur, p.streams, q0};    // the chunk's keys stay in d_keys: the re-score and the redo only read them
     }
     VQ_HIP(hipGetLastError());
     if (!p.fp16) { set_stats(x, STATS_HOST, 0, 0, m); return 0; }
@@ -2888,7 +2904,7 @@ int vq_index_debug_read_scan_keys(vq_index* x, int64_t* info, uint32_t* keys, in
     std::lock_guard<std::mutex> lk(x->mu);
     const vq_index::LastScan& s = x->last_scan;
     if (!s.valid) return fail(VQ_ERR_STATE, "vq_index_debug_read_scan_keys: no fp16 search has run on this handle since its rows last changed");
-    info[0] = s.q0; info[1] = s.cur; info[2] = s.layout; info[3] = s.streams; info[4] = s.masked ? 1 : 0;
+    info[0] = s.q0; info[1] = s.cur; info[2] = s.layout; info[3] = s.streams; info[4] = s.masked;
     if (!keys) return 0;
     const int64_t want = (int64_t)s.cur * s.streams * 2;
     VQ_CHECK(capacity >= want, "vq_index_debug_read_scan_keys: %lld words for %d queries x %lld streams x 2", (long long)capacity, s.cur, (long long)s.streams);
@@ -3014,6 +3030,62 @@ int vq_index_debug_read_group_best(vq_index* x, int64_t* info, float* best, int6
     VQ_HIP(hipStreamSynchronize(x->stream));
     VQ_HIP(hipMemcpy(raw.data(), x->d_gbest, (size_t)want * 4, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < want; ++i) best[i] = key_score(raw[(size_t)i]);      // key 0 = no row seen -> NaN (all bits set)
+    return 0;
+}
+
+// which group-max scan left the record vq_index_debug_read_group_best hands out: info = {kind, chunks, tile_chunks} (LastGroupScan)
+int vq_index_debug_group_scan_kind(vq_index* x, int64_t* info) {
+    VQ_CHECK(x && info, "vq_index_debug_group_scan_kind: null argument");
+    std::lock_guard<std::mutex> lk(x->mu);
+    const vq_index::LastGroupScan& s = x->last_gscan;
+    if (!s.valid) return fail(VQ_ERR_STATE, "vq_index_debug_group_scan_kind: no fp16 group-max scan has run on this handle since its rows last changed");
+    info[0] = s.kind; info[1] = s.chunks; info[2] = s.tile_chunks;
+    return 0;
+}
+
+// label_tile_kernel's parts [ranges][5][n_pad] as it wrote them
+int vq_index_debug_read_label_parts(vq_index* x, int64_t* info, uint32_t* parts, int64_t capacity) {
+    static const char* fn = "vq_index_debug_read_label_parts";
+    VQ_CHECK(x && info, "%s: null argument", fn);
+    std::lock_guard<std::mutex> lk(x->mu);
+    const vq_index::LastLabel& s = x->last_label;
+    if (!s.valid) return fail(VQ_ERR_STATE, "%s: no labelling call has taken the tile path on this handle since its rows last changed", fn);
+    int32_t ctl[4];
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    VQ_HIP(hipMemcpy(ctl, x->d_lw, sizeof ctl, hipMemcpyDeviceToHost));
+    if (ctl[1] != 0) return fail(VQ_ERR_STATE, "%s: the last labelling call was flagged (a prompt outside the bound's range): the redo answered it", fn);
+    info[0] = s.n; info[1] = s.n_pad; info[2] = s.ranges; info[3] = s.P;
+    if (!parts) return 0;
+    const int64_t want = (int64_t)s.ranges * LABEL_PART_WORDS * s.n_pad;
+    VQ_CHECK(capacity >= want, "%s: %lld words for %d ranges x %d x %lld rows", fn, (long long)capacity, s.ranges, LABEL_PART_WORDS, (long long)s.n_pad);
+    VQ_CHECK(want <= x->d_lparts.cap, "%s: the buffer holds %lld words, the last call wrote %lld", fn, (long long)x->d_lparts.cap, (long long)want);
+    VQ_HIP(hipMemcpy(parts, x->d_lparts, (size_t)want * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the final bit table [m][W], the first min(cursor, cap) filed pairs ((query << 32) | row) and the control words of the last
+// shared-footage call that took the tile path
+int vq_index_debug_read_match_bits(vq_index* x, int64_t* info, uint32_t* bits, int64_t bits_capacity, uint64_t* filed, int64_t filed_capacity) {
+    static const char* fn = "vq_index_debug_read_match_bits";
+    VQ_CHECK(x && info, "%s: null argument", fn);
+    std::lock_guard<std::mutex> lk(x->mu);
+    const vq_index::LastMatch& s = x->last_match;
+    if (!s.valid) return fail(VQ_ERR_STATE, "%s: no shared-footage call has taken the tile path on this handle since its rows last changed", fn);
+    MatchCtl ctl;
+    VQ_HIP(hipStreamSynchronize(x->stream));
+    VQ_HIP(hipMemcpy(&ctl, x->d_mw, sizeof ctl, hipMemcpyDeviceToHost));
+    info[0] = s.m; info[1] = s.W; info[2] = s.n; info[3] = (int64_t)ctl.cursor; info[4] = ctl.flag; info[5] = s.cap;
+    const int64_t nbits = (int64_t)s.m * s.W, nfiled = std::min<int64_t>((int64_t)ctl.cursor, s.cap);
+    if (bits) {
+        VQ_CHECK(bits_capacity >= nbits, "%s: %lld words for %d queries x %lld words", fn, (long long)bits_capacity, s.m, (long long)s.W);
+        VQ_CHECK(nbits <= x->d_mbits.cap, "%s: the bit table holds %lld words, the last call wrote %lld", fn, (long long)x->d_mbits.cap, (long long)nbits);
+        VQ_HIP(hipMemcpy(bits, x->d_mbits, (size_t)nbits * 4, hipMemcpyDeviceToHost));
+    }
+    if (filed && nfiled > 0) {
+        VQ_CHECK(filed_capacity >= nfiled, "%s: %lld entries for %lld filed pairs", fn, (long long)filed_capacity, (long long)nfiled);
+        VQ_CHECK(nfiled <= x->d_mfiled.cap, "%s: the filed list holds %lld entries, the last call filed %lld", fn, (long long)x->d_mfiled.cap, (long long)nfiled);
+        VQ_HIP(hipMemcpy(filed, x->d_mfiled, (size_t)nfiled * 8, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 
