@@ -557,6 +557,67 @@ int vq_index_search_spans_device(vq_index* idx, const void* d_queries_f32, int n
 int vq_debug_span_plan(int64_t n, int64_t n_groups, int64_t largest_group, int nq, int* query_chunks, int* lds_rows,
                        int64_t* lds_bytes, int* groups_global_form, int64_t* scratch_bytes);
 
+/* Warped clip alignment: the k groups (videos) that show a clip under a monotone time warp, each with where it starts and ends —
+ * "which video contains this clip, played faster, slower or sampled differently, and from where to where?".  vq_index_match_runs
+ * reads diagonal runs and so needs equal sampling rates; vq_index_search_sequence joins at most 64 steps, one stored frame each;
+ * this is the subsequence dynamic time warp of the clip against every allowed group, with integer costs so that it is exact.
+ *   Clip q_0 .. q_{m-1} in time order [m][dim] fp32, used as given, 1 <= m <= 4096.  1 <= k <= 1024.  max_dist: fp32, NaN is
+ *   VQ_ERR_INVALID, +inf means no limit.  groups / n_sel / exclude: the host-memory filter of vq_index_search_sequence, with
+ *   both of its empty-list cases.  Stale or missing labels, positions or id ranks are refused as the sequence search refuses
+ *   them.  Every refusal names the argument in vq_last_error and comes before the device is asked for anything.
+ *   Cost of a cell: d(i, r) = the distance of q_i to row r exactly as vq_index_search reports it; c(i, r) = (int64)
+ *   rint((double)d(i, r) * 2^24), ties to even, kept within +-2^31; a NaN distance takes +2^31.  The scaling is exact and every
+ *   sum below is exact in int64.
+ *   Paths: s_0 .. s_{L-1} are the rows of group g in the (position, tie) order the sequence search walks.  A path is a list of
+ *   cells (i_t, j_t) with i_0 = 0 and i_last = m - 1 whose every step is (+1, +1), (+1, 0) or (0, +1); its cost C is the sum of
+ *   c(i_t, s_{j_t}), its start a = j_0 and its end b = j_last.  Both the start and the end are free.
+ *   Best path: cell (i, j) holds the smallest key (C, -a) over the paths that end there — on equal cost the later start wins.
+ *   The group's result is the end b with the smallest (C(b), b - a(b) + 1, a(b)), all integers.  D(g) = fp32((double)C * 2^-24 /
+ *   (double)m).  A group appears only if D(g) <= max_dist, compared in fp32.  The answer is the first min(k, such allowed
+ *   groups) by (C, label) ascending (so dist_out never decreases; two groups whose different costs round to one fp32 D come by
+ *   cost).
+ *   Alignment: the path of a winner is read back from (m - 1, b).  The predecessor of a cell is the first, in the order diagonal
+ *   (i - 1, j - 1), vertical (i - 1, j), [at i = 0: "starts here"], horizontal (i, j - 1), whose key equals the cell's minimum.
+ *   align_out [k][m][2] holds, per clip frame, the full-index row numbers of the first and the last stored row paired with it.
+ *   Outputs: groups_out [k] int32, dist_out [k] fp32 (D), cost_out [k] int64 or NULL, rows_out [k][2] int32 or NULL (the
+ *   full-index rows of s_a and s_b), align_out or NULL.  Unused slots hold -1 / +inf / 0 / -1 / -1.  An empty index returns
+ *   every slot empty.
+ *   Limit: with align_out, m x (rows of the largest allowed group) x 4 B <= 1 GiB, else VQ_ERR_INVALID; longer clips go in pieces.
+ *   Consequences: m = 1 gives the groups and rows of vq_index_search_grouped wherever a group's best distance is unique, with C =
+ *   c of that row.  A group of one row: C = the sum over i of c(i, that row) and a = b = 0.  A group's result does not depend on
+ *   other groups.  If every c >= 0: C(g) >= the sum over i of min_j c(i, s_j).  Reversing the clip changes the answer.
+ *   How it runs (csrc/knn_align.h): exact only, no mode.  Per chunk of clip frames the plain search's exact distances
+ *   [chunk][n] (chunks keep them within 512 MiB); the DP row [n] (int64 cost + int32 start, 12 B per row) is carried between
+ *   chunks.  One workgroup per allowed group runs the chunk's frames one after the other over the group's rows.  DP row i: P =
+ *   the exclusive prefix sums of c(i, .); E(j) = the smaller key of the previous DP row at j - 1 and at j, ties to j - 1 (at i =
+ *   0: (0, -j)); cell (i, j) = P[j + 1] + the prefix minimum over j' <= j of (E(j').C - P[j'], -E(j').a, -j') — keys that are
+ *   distinct, over 256-row tiles with the running values carried from tile to tile.  Groups of at most 4,096 rows keep the DP
+ *   row in LDS (16 B per row: cost, start, row number); longer groups run the same arithmetic on the carried state in global
+ *   memory, bit for bit the same.  A small kernel turns the last DP row into each group's (D, label) key, C and (a, b); the clip
+ *   search's selection takes the k smallest, and one workgroup per result slot puts the groups that share a D in (C, label)
+ *   order, taken over every group that holds that D.  With align_out, one workgroup per winner runs its group's DP again and writes the
+ *   entry column j' of every cell (int32, top bit = entered down the diagonal) into a table [m][L], winners batched within
+ *   256 MiB (at least one per batch), and one thread per winner walks it back.  No floating point behind the cost, no global
+ *   atomics, workgroup barriers only, every loop bounded by the shapes; the launches queued depend on the shapes and the
+ *   arguments only.  Accounted under sequence_dp; VQ_IDX_NCLASS stays 7.
+ *   The _device form takes device clip and result arrays, is asynchronous on the index's stream and reads nothing back.
+ *   vq_index_last_search_stats afterwards: [0] the groups with a result, [1] the allowed groups run by the global form, [2] the
+ *   clip chunks.
+ *   $VQ_AMD_ALIGN_LDS_ROWS (the LDS form's row limit, at most 4,096), $VQ_AMD_ALIGN_DIST_BYTES (the distance budget) and
+ *   $VQ_AMD_ALIGN_BP_BYTES (the winner tables' batch budget): tests only, read per call.
+ *   vq_debug_align_plan (host only): for n rows in n_groups groups whose longest allowed one holds largest_group rows, a clip of
+ *   m frames and k results — the clip chunks, the LDS form's row limit and the dynamic LDS bytes of a group of that many rows
+ *   (capped by largest_group), groups_global_form = 1 when that group takes the global form, the bytes of the carried DP row,
+ *   and with with_align the winner batches for min(k, n_groups) winners (0 without).  VQ_ERR_INVALID above the 1 GiB bound. */
+int vq_index_align_clip(vq_index* idx, const float* clip /*[m][dim]*/, int m, int k, float max_dist, const int32_t* groups,
+                        int32_t n_sel, int exclude, int32_t* groups_out /*[k]*/, float* dist_out /*[k]*/,
+                        int64_t* cost_out /*[k] or NULL*/, int32_t* rows_out /*[k][2] or NULL*/, int32_t* align_out /*[k][m][2] or NULL*/);
+int vq_index_align_clip_device(vq_index* idx, const void* d_clip_f32, int m, int k, float max_dist, const int32_t* groups,
+                               int32_t n_sel, int exclude, void* d_groups_i32, void* d_dist_f32, void* d_cost_i64 /*or NULL*/,
+                               void* d_rows_i32 /*or NULL*/, void* d_align_i32 /*or NULL*/);
+int vq_debug_align_plan(int64_t n, int64_t n_groups, int64_t largest_group, int m, int k, int with_align, int* clip_chunks,
+                        int* lds_rows, int64_t* lds_bytes, int* groups_global_form, int64_t* scratch_bytes, int* winner_batches);
+
 /* Keyframe summary: the k most representative rows of each listed group (video) — the poster frame and thumbnail strip of a
  * video, the few frames that stand in for a long one (as the query set of vq_index_search_set, say).  An iterative
  * farthest-point (greedy k-centre) pass per group: its covering radius is within a factor 2 of the best possible for every k,

@@ -156,6 +156,12 @@ SIGNATURES = {
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vq_debug_span_plan": (c_int, [c_int64, c_int64, c_int64, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int64), POINTER(c_int),
                                    POINTER(c_int64)]),
+    "vq_index_align_clip": (c_int, [c_void_p, POINTER(c_float), c_int, c_int, c_float, POINTER(c_int32), c_int32, c_int,
+                                    POINTER(c_int32), POINTER(c_float), POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
+    "vq_index_align_clip_device": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, POINTER(c_int32), c_int32, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vq_debug_align_plan": (c_int, [c_int64, c_int64, c_int64, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int64),
+                                    POINTER(c_int), POINTER(c_int64), POINTER(c_int)]),
     "vq_index_summarize_groups": (c_int, [c_void_p, POINTER(c_int32), c_int32, c_int, c_float, POINTER(c_int32), POINTER(c_float),
                                           POINTER(c_int32)]),
     "vq_index_summarize_groups_device": (c_int, [c_void_p, POINTER(c_int32), c_int32, c_int, c_float, c_void_p, c_void_p, c_void_p]),

@@ -15,6 +15,7 @@
 #include "knn_diverse.h"
 #include "knn_sequence.h"
 #include "knn_span.h"
+#include "knn_align.h"
 #include "knn_summary.h"
 #include "knn_segment.h"
 #include "knn_label.h"
@@ -150,6 +151,11 @@ struct vq_index {
     // global form's prefix sums [n + G]
     IdxBuf<int32_t> d_spanw;
     IdxBuf<int64_t> d_spanp;
+    // warped alignment (knn_align.h): the carried DP row's costs [n] | the groups' costs [G]; its starts [n] | the groups' (a, b)
+    // [G][2] | the selection's groups [k]; a batch of winners' entry-column tables
+    IdxBuf<int64_t> d_alignc;
+    IdxBuf<int32_t> d_aligna;
+    IdxBuf<int32_t> d_alignbp;
     // keyframe summary (knn_summary.h): the call's lists, keyframe counts and the wide form's per-row / per-block words; the
     // blocks' packed maxima; the mean's block sums and the widened mean directions
     IdxBuf<int32_t> d_sumw;
@@ -1645,6 +1651,109 @@ int search_spans_run(vq_index* x, const char* fn, const float* d_queries, int nq
     return 0;
 }
 
+// ---- warped alignment (knn_align.h) ----
+// tests only, read per call: the LDS form's row limit, the distance budget and the winner tables' batch budget in bytes
+AlignPlan align_plan_env(int64_t n, int64_t largest_group, int m, int winners, bool with_align) {
+    return plan_align(n, largest_group, m, winners, with_align, seq_env("VQ_AMD_ALIGN_LDS_ROWS"), seq_env("VQ_AMD_ALIGN_DIST_BYTES"),
+                      seq_env("VQ_AMD_ALIGN_BP_BYTES"));
+}
+
+// What the filter allows, by the host mirror of goff and the sorted filter list: the groups and the longest of them.
+struct AlignShape { int64_t allowed = 0; int64_t largest = 0; };
+template <class Visit>
+void allowed_groups(const vq_index* x, const FilterLabels& f, int exclude, Visit visit) {
+    size_t si = 0;
+    for (int32_t g = 0; g < x->n_groups; ++g) {
+        while (si < f.sel.size() && f.sel[si] < g) ++si;
+        const bool listed = si < f.sel.size() && f.sel[si] == g;
+        if (exclude ? !listed : listed) visit((int64_t)x->h_goff[(size_t)g + 1] - x->h_goff[(size_t)g]);
+    }
+}
+AlignShape align_shape(const vq_index* x, const FilterLabels& f, int exclude) {
+    AlignShape s;
+    allowed_groups(x, f, exclude, [&](int64_t rows) { ++s.allowed; s.largest = std::max(s.largest, rows); });
+    return s;
+}
+
+// d_clip [m][dim]; o: groups / distances [k], then costs [k], rows [k][2] and alignments [k][m][2], each or not asked for, placed
+// in device memory.  Asynchronous on the index's stream once the (position, tie) order is on the device.
+int align_clip_run(vq_index* x, const char* fn, const float* d_clip, int m, int k, float max_dist, const FilterLabels& f, int exclude,
+                   const AlignShape& shape, const Outs& o) {
+    int32_t* const g_out = o.dev<int32_t>(0); float* const d_out = o.dev<float>(1);
+    int64_t* const cost = o.dev<int64_t>(2); int32_t* const rows = o.dev<int32_t>(3); int32_t* const align = o.dev<int32_t>(4);
+    FilterPlan fp;
+    VQ_TRY(filter_prepare(x, fn, f, exclude, true, &fp));
+    if (!fp.all && fp.m == 0) {                             // nothing allowed: every slot empty
+        set_stats(x, STATS_HOST, 0, 0, 0);
+        return outs_empty_placed(x, o);
+    }
+    VQ_TRY(seq_order_prepare(x));
+    const uint32_t* allow = fp.all ? nullptr : fp.bits;
+    const int64_t n = x->size, ld = round_up(n, 64);
+    const int G = x->n_groups;
+    const int nblocks = cdiv(G, GRP_BLOCK), kl = std::min(k, GRP_BLOCK);
+    const int winners = (int)std::min<int64_t>(k, shape.allowed);
+    const AlignPlan p = align_plan_env(n, shape.largest, m, winners, align != nullptr);
+    int64_t global_groups = 0;
+    if (p.global_form) allowed_groups(x, f, exclude, [&](int64_t rows_of) { global_groups += rows_of > p.lds_rows; });
+    VQ_TRY(x->d_dist.reserve((int64_t)p.chunk_frames * ld));
+    VQ_TRY(x->d_alignc.reserve(n + G));
+    VQ_TRY(x->d_aligna.reserve(n + 2 * (int64_t)G + k));
+    VQ_TRY(x->d_sekey.reserve((int64_t)G + (int64_t)nblocks * kl));
+    if (align) VQ_TRY(x->d_alignbp.reserve(p.table_bytes / 4));
+    VQ_TRY(ensure_gcounters(x));
+    VQ_TRY(set_dyn_lds(x, (const void*)align_dp_lds_kernel, (size_t)p.lds_bytes));
+    const int32_t* sorder = x->d_seq;
+    int64_t* state_c = x->d_alignc; int64_t* gcost = state_c + n;
+    int32_t* state_a = x->d_aligna; int32_t* gab = state_a + n; int32_t* sel = gab + 2 * (int64_t)G;
+    uint64_t* ekey = x->d_sekey; uint64_t* partial = ekey + G;
+    for (int i0 = 0; i0 < m; i0 += p.chunk_frames) {
+        const int cur = std::min(p.chunk_frames, m - i0);
+        VQ_TRY(exact_dist(x, false, d_clip + (int64_t)i0 * x->dim, cur, ld));          // always the tiled kernel
+        Prof pr(x, I_SEQ_DP);
+        hipLaunchKernelGGL(align_dp_lds_kernel, dim3(G), dim3(ALIGN_THREADS), (size_t)p.lds_bytes, x->stream, x->d_dist, ld, i0, cur, x->d_goff,
+                           sorder, p.lds_rows, p.lds_alloc_rows, state_c, state_a, allow);
+        if (p.global_form)
+            hipLaunchKernelGGL(align_dp_global_kernel, dim3(G), dim3(ALIGN_THREADS), 0, x->stream, x->d_dist, ld, i0, cur, x->d_goff, sorder,
+                               p.lds_rows, state_c, state_a, allow);
+    }
+    {
+        Prof pr(x, I_SELECT);
+        hipLaunchKernelGGL(align_final_kernel, dim3(G), dim3(ALIGN_THREADS), 0, x->stream, state_c, state_a, x->d_goff, m, max_dist, allow, ekey,
+                           gcost, gab);
+        hipLaunchKernelGGL(set_select_block_kernel, dim3(nblocks), dim3(256), 0, x->stream, ekey, G, kl, partial);
+        hipLaunchKernelGGL(set_select_merge_kernel, dim3(1), dim3(256), 0, x->stream, partial, (int64_t)nblocks * kl, k, sel, d_out, nullptr,
+                           nullptr);
+        hipLaunchKernelGGL(align_order_kernel, dim3(k), dim3(256), 0, x->stream, ekey, G, gcost, sel, g_out);
+        hipLaunchKernelGGL(seq_stats_kernel, dim3(1), dim3(256), 0, x->stream, ekey, G, (unsigned long long)global_groups,
+                           (unsigned long long)p.frame_chunks, x->d_gcounters);
+        if (cost || rows)
+            hipLaunchKernelGGL(align_finish_kernel, dim3(cdiv(k, 64)), dim3(64), 0, x->stream, g_out, k, x->d_goff, sorder, gcost, gab, cost, rows);
+    }
+    if (align) {
+        const int64_t stride = (int64_t)m * shape.largest;
+        int32_t* table = x->d_alignbp;
+        for (int b = 0; b < p.winner_batches; ++b) {
+            const int w0 = b * p.winners_per_batch, nb = std::min(p.winners_per_batch, winners - w0);
+            for (int i0 = 0; i0 < m; i0 += p.chunk_frames) {
+                const int cur = std::min(p.chunk_frames, m - i0);
+                if (p.frame_chunks > 1) VQ_TRY(exact_dist(x, false, d_clip + (int64_t)i0 * x->dim, cur, ld));   // (one chunk: still there)
+                Prof pr(x, I_SEQ_DP);
+                hipLaunchKernelGGL(align_trace_dp_kernel, dim3(nb), dim3(ALIGN_THREADS), 0, x->stream, x->d_dist, ld, i0, cur, g_out, w0, x->d_goff,
+                                   sorder, state_c, state_a, table, stride);
+            }
+            Prof pr(x, I_SEQ_DP);
+            const int count = b == p.winner_batches - 1 ? k - w0 : nb;        // the last batch also files the slots no group can fill
+            hipLaunchKernelGGL(align_walk_kernel, dim3(cdiv(count, 64)), dim3(64), 0, x->stream, g_out, w0, count, m, x->d_goff, sorder, gab, table,
+                               stride, align);
+        }
+    }
+    VQ_HIP(hipGetLastError());
+    VQ_HIP(hipMemcpyAsync(x->h_gcounters, x->d_gcounters, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, x->stream));
+    set_stats(x, STATS_GCOUNTERS);
+    return 0;
+}
+
 // ---- keyframe summary (knn_summary.h) ----
 SummaryPlan sum_plan_env(int64_t largest_group, int dim, int k) {
     return plan_summary(largest_group, dim, k, seq_env("VQ_AMD_SUM_LDS_ROWS"));      // tests only, read per call
@@ -2465,6 +2574,19 @@ int check_span_args(const char* fn, const vq_index* x, int nq, int k, float max_
 }
 
 // (the arguments are judged before the library is asked for its device)
+int check_align_args(const char* fn, const vq_index* x, int m, int k, float max_dist, const int32_t* groups, int32_t n_sel, int exclude,
+                     bool arrays) {
+    VQ_CHECK(m >= 1 && m <= ALIGN_MAX_M, "%s: m %d outside [1, %d]", fn, m, ALIGN_MAX_M);
+    VQ_CHECK(k >= 1 && k <= 1024, "%s: k %d outside [1, 1024]", fn, k);
+    VQ_CHECK(max_dist == max_dist, "%s: max_dist is NaN (+inf: no limit)", fn);
+    VQ_CHECK(n_sel >= 0 && (n_sel == 0 || groups) && (exclude == 0 || exclude == 1), "%s: bad filter (n_sel >= 0, exclude 0 or 1)", fn);
+    VQ_CHECK(arrays, "%s: a required array is null", fn);
+    VQ_TRY(require_init());
+    VQ_CHECK(x, "%s: bad argument", fn);
+    return 0;
+}
+
+// (the arguments are judged before the library is asked for its device)
 int check_match_args(const char* fn, const vq_index* x, int m, int k, float max_dist, int min_len, int max_miss, int mode,
                      const int32_t* groups, int32_t n_sel, int exclude, bool arrays) {
     VQ_CHECK(m >= 1 && m <= MATCH_MAX_M, "%s: m %d outside [1, %d]", fn, m, MATCH_MAX_M);
@@ -2681,7 +2803,25 @@ int spans_call(vq_index* x, const char* fn, Form form, const void* queries, int 
     });
 }
 
-int summarize_call(vq_index* x, const char* fn, Form form, const int32_t* groups, int32_t n_sel, int k, float max_radius, void* rows_out,
+int align_call(vq_index* x, const char* fn, Form form, const void* clip, int m, int k, float max_dist, const int32_t* groups, int32_t n_sel,
+               int exclude, void* groups_out, void* dist_out, void* cost_out, void* rows_out, void* align_out) {
+    VQ_TRY(check_align_args(fn, x, m, k, max_dist, groups, n_sel, exclude, clip && groups_out && dist_out));
+    std::lock_guard<std::mutex> lk(x->mu);
+    Outs o{5, {out_ids(groups_out, k), out_dist(dist_out, k), out_zero(cost_out, k, 8), out_ids(rows_out, 2 * (int64_t)k),
+               out_ids(align_out, 2 * (int64_t)k * m)}};
+    if (x->size == 0) return outs_empty(x, form, o);
+    const FilterLabels f = filter_labels(x, groups, n_sel);
+    VQ_TRY(seq_precheck(x, fn, f));
+    const AlignShape shape = align_shape(x, f, exclude);
+    if (align_out)
+        VQ_CHECK((int64_t)m * shape.largest * 4 <= ALIGN_TABLE_MAX_BYTES, "%s: align_out needs m x (rows of the largest allowed group) x 4 B "
+                 "<= 1 GiB (m %d, %lld rows): align the clip in pieces", fn, m, (long long)shape.largest);
+    return run_form(x, form, (const float*)clip, m, &o, [&](const float* dq) {
+        return align_clip_run(x, fn, dq, m, k, max_dist, f, exclude, shape, o);
+    });
+}
+
+int summarize_call(vq_index* x, const char* fn, Form form,const int32_t* groups, int32_t n_sel, int k, float max_radius, void* rows_out,
                    void* radius_out, void* members_out) {
     VQ_TRY(check_summary_args(fn, x, groups, n_sel, k, max_radius, rows_out && radius_out));
     std::lock_guard<std::mutex> lk(x->mu);
@@ -3519,6 +3659,34 @@ int vq_debug_span_plan(int64_t n, int64_t n_groups, int64_t largest_group, int n
     const SpanPlan p = span_plan_env(n, n_groups, largest_group, nq);
     *query_chunks = p.query_chunks; *lds_rows = p.lds_rows; *lds_bytes = p.lds_bytes; *groups_global_form = p.global_form;
     *scratch_bytes = p.scratch_bytes;
+    return 0;
+}
+
+int vq_index_align_clip_device(vq_index* x, const void* d_clip, int m, int k, float max_dist, const int32_t* groups, int32_t n_sel, int exclude,
+                               void* d_groups_out, void* d_dist_out, void* d_cost_out, void* d_rows_out, void* d_align_out) {
+    return align_call(x, "vq_index_align_clip_device", ON_DEVICE, d_clip, m, k, max_dist, groups, n_sel, exclude, d_groups_out, d_dist_out,
+                      d_cost_out, d_rows_out, d_align_out);
+}
+
+int vq_index_align_clip(vq_index* x, const float* clip, int m, int k, float max_dist, const int32_t* groups, int32_t n_sel, int exclude,
+                        int32_t* groups_out, float* dist_out, int64_t* cost_out, int32_t* rows_out, int32_t* align_out) {
+    return align_call(x, "vq_index_align_clip", HOST_PINNED, clip, m, k, max_dist, groups, n_sel, exclude, groups_out, dist_out, cost_out,
+                      rows_out, align_out);
+}
+
+// plan_align's answer for this process's environment; needs no device.  largest_group: the largest allowed group; the winners
+// are min(k, n_groups).
+int vq_debug_align_plan(int64_t n, int64_t n_groups, int64_t largest_group, int m, int k, int with_align, int* clip_chunks, int* lds_rows,
+                        int64_t* lds_bytes, int* groups_global_form, int64_t* scratch_bytes, int* winner_batches) {
+    VQ_CHECK(clip_chunks && lds_rows && lds_bytes && groups_global_form && scratch_bytes && winner_batches && n >= 1 &&
+             n < ((int64_t)1 << 31) && n_groups >= 1 && n_groups <= n && largest_group >= 1 && largest_group <= n && m >= 1 &&
+             m <= ALIGN_MAX_M && k >= 1 && k <= 1024,
+             "vq_debug_align_plan: takes 1 <= largest_group <= n < 2^31, 1 <= n_groups <= n, 1 <= m <= %d, 1 <= k <= 1024", ALIGN_MAX_M);
+    VQ_CHECK(!with_align || (int64_t)m * largest_group * 4 <= ALIGN_TABLE_MAX_BYTES, "vq_debug_align_plan: align_out needs m x "
+             "largest_group x 4 B <= 1 GiB (m %d, %lld rows)", m, (long long)largest_group);
+    const AlignPlan p = align_plan_env(n, largest_group, m, (int)std::min<int64_t>(k, n_groups), with_align != 0);
+    *clip_chunks = p.frame_chunks; *lds_rows = p.lds_rows; *lds_bytes = p.lds_bytes; *groups_global_form = p.global_form;
+    *scratch_bytes = p.state_bytes; *winner_batches = p.winner_batches;
     return 0;
 }
 

@@ -1396,6 +1396,110 @@ class HNSWIndex:
             _lib.check(_lib.load().vq_index_read_rows(self._h, _lib.i64ptr(rn), len(rn), _lib.fptr(unit)))
             return self._shared_runs(unit, k, md, lo, miss, flt, group_of, position_of, given=True)
 
+    # -- warped alignment: the k groups (videos) that show a clip at any pace, and from where to where ----
+    ALIGN_MAX_FRAMES = 4096      # vq_index_align_clip: clip frames per call
+
+    @staticmethod
+    def _align_args(max_distance, groups, exclude) -> Tuple[np.float32, Optional[Tuple[List[Hashable], bool]]]:
+        md = np.float32(np.inf if max_distance is None else max_distance)
+        if md != md:
+            raise ValueError("max_distance is NaN")
+        if groups is None:
+            return md, None
+        if isinstance(groups, (str, bytes)) or not isinstance(groups, Iterable):
+            raise ValueError("`groups` takes an iterable of group keys (a list of video ids), not one key")
+        return md, (list(groups), bool(exclude))
+
+    def _align_clip(self, frames, k: int, max_dist: np.float32, flt, group_of, position_of, alignment: bool,
+                    given: bool = False) -> List[Dict]:
+        """frames: 1 to ALIGN_MAX_FRAMES of them, in time order (``given``: see ``_prepare``).  flt: ``_align_args``'s."""
+        ready = self._prepare(frames, k, given=given, group_of=group_of, positions=True, position_of=position_of, flt=flt, what="frame")
+        if ready is None:
+            return []
+        unit, gl, ps, labels, excl = ready
+        m, kk = unit.shape[0], min(int(k), len(gl.keys), 1024)
+        groups = np.empty(kk, dtype=np.int32)
+        dist = np.empty(kk, dtype=np.float32)
+        cost = np.empty(kk, dtype=np.int64)
+        ends = np.empty((kk, 2), dtype=np.int32)
+        pairs = np.empty((kk, m, 2), dtype=np.int32) if alignment else None
+        _lib.check(_lib.load().vq_index_align_clip(self._h, _lib.fptr(unit), m, kk, float(max_dist), _lib.i32ptr(labels), len(labels),
+                                                   int(excl), _lib.i32ptr(groups), _lib.fptr(dist),
+                                                   cost.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _lib.i32ptr(ends),
+                                                   _lib.i32ptr(pairs) if alignment else None))
+        keys, pos, to_id = gl.keys, ps.values, self._id_of()
+        out = []
+        for j, (g, d, c, (a, b)) in enumerate(zip(groups.tolist(), dist, cost.tolist(), ends.tolist())):
+            if g < 0:
+                break
+            hit = {"group": keys[g], **_scored(d), "cost": c, "start_id": to_id(a), "end_id": to_id(b), "start": int(pos[a]),
+                   "end": int(pos[b])}
+            if alignment:
+                hit["alignment"] = [(to_id(first), to_id(last)) for first, last in pairs[j].tolist()]
+            out.append(hit)
+        return out
+
+    def align_clip(self, frames: Sequence[np.ndarray], k: int = 5, max_distance: Optional[float] = None, *, group_of: GROUP_OF = None,
+                   position_of: POSITION_OF = None, groups: Optional[Iterable[Hashable]] = None, exclude: bool = False,
+                   alignment: bool = False) -> List[Dict]:
+        """The k GROUPS (videos) that show the clip ``frames`` (in time order) AT ANY PACE — played faster or slower, or sampled
+        at another rate — and from where to where: ``[{'group', 'distance', 'score', 'cost', 'start_id', 'end_id', 'start',
+        'end'}]``.  A subsequence dynamic time warp: a video's frames are taken in (position, id) order; a path pairs every clip
+        frame, in order, with one or more consecutive stored frames (a stored frame may serve several clip frames), from any
+        start to any end; its ``cost`` adds the paired distances (the clip normalised as ``search`` does), each kept as an
+        integer multiple of 2^-24.  Per video the cheapest path (then the later start; among ends: the shortest stretch, the
+        earliest); ``distance`` is its cost per clip frame, ``score = float32(1) - distance``; ``start_id`` / ``end_id`` the
+        stored frames at its ends and ``start`` / ``end`` their positions.  Videos with ``distance`` above ``max_distance`` do
+        not appear (``None``: no limit); they come back cheapest first (ties: the order in which the groups first appeared in
+        the index).  ``alignment=True`` adds ``'alignment'``: per clip frame the ``(first_id, last_id)`` of the stored frames
+        paired with it.  ``groups`` restricts the search to those group keys, or with ``exclude=True`` to all the others.
+        ``group_of`` as ``search_grouped``, ``position_of`` as ``search_distinct``.  At most 4,096 frames and 1,024 results;
+        with ``alignment`` the clip times the longest video searched is bounded (2^28 cells)."""
+        md, flt = self._align_args(max_distance, groups, exclude)
+        if len(frames) == 0:
+            raise ValueError("align_clip needs at least one frame")
+        if len(frames) > self.ALIGN_MAX_FRAMES:
+            raise ValueError(f"a clip holds at most {self.ALIGN_MAX_FRAMES} frames, got {len(frames)}")
+        if self._empty() or k <= 0:
+            return []
+        with self.lock:
+            return self._align_clip(frames, k, md, flt, group_of, position_of, bool(alignment))
+
+    def align_group(self, group: Hashable, k: int = 5, max_distance: Optional[float] = None, *, group_of: GROUP_OF = None,
+                    position_of: POSITION_OF = None, groups: Optional[Iterable[Hashable]] = None, alignment: bool = False,
+                    max_frames: Optional[int] = None) -> List[Dict]:
+        """"Which videos show this one at any pace": ``align_clip`` with the stored rows of ``group``, in (position, id) order, as
+        the clip and ``group`` itself excluded; ``groups`` restricts the answer to those groups.  ``max_frames`` takes every
+        ceil(L / max_frames)-th of the video's L frames as the clip.  ``KeyError`` for a group the index does not hold,
+        ``ValueError`` for a clip of more than 4,096 frames (pass ``max_frames``)."""
+        md, flt = self._align_args(max_distance, groups, False)
+        if max_frames is not None and int(max_frames) < 1:
+            raise ValueError(f"max_frames must be >= 1, got {max_frames}")
+        with self.lock:
+            rn = self._group_rows(group, group_of)
+            if rn is None:
+                raise KeyError(group)
+            stride = 1 if max_frames is None else -(-len(rn) // int(max_frames))
+            if -(-len(rn) // stride) > self.ALIGN_MAX_FRAMES:
+                raise ValueError(f"group {group!r} holds {len(rn)} rows; a clip holds at most {self.ALIGN_MAX_FRAMES} "
+                                 "(pass max_frames= to take every ceil(L / max_frames)-th frame)")
+            if k <= 0:
+                return []
+            flt = ([key for key in flt[0] if key != group], False) if flt is not None else ([group], True)
+            if not flt[1] and not flt[0]:
+                return []
+            self._positions = _Positions.current(self._positions, frame_of if position_of is None else position_of, self._ids)
+            self._positions.extend()
+            pos, ids = self._positions.values, self._ids
+            try:
+                rn = np.array(sorted(rn.tolist(), key=lambda r: (int(pos[r]), ids[r])), dtype=np.int64)
+            except TypeError:                                 # ids without a total order: rows at one position stay in row order
+                rn = np.array(sorted(rn.tolist(), key=lambda r: int(pos[r])), dtype=np.int64)
+            rn = np.ascontiguousarray(rn[::stride])
+            unit = np.empty((len(rn), self.dimension), dtype=np.float32)
+            _lib.check(_lib.load().vq_index_read_rows(self._h, _lib.i64ptr(rn), len(rn), _lib.fptr(unit)))
+            return self._align_clip(unit, k, md, flt, group_of, position_of, bool(alignment), given=True)
+
     # -- library neighbours: every stored row's nearest rows elsewhere ------------------------
     NEIGHBORS_MAX_K = 1024
 

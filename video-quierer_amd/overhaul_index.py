@@ -291,6 +291,25 @@ class SimpleVideoIndex:
                         "end": last["timestamp"], "query_start": stamps[r["query_first"]], "query_end": stamps[r["query_first"] + r["span"] - 1]})
         return out
 
+    def find_reuse_warped(self, video_name: str, k: int = 5, min_similarity: Optional[float] = None, max_frames: Optional[int] = None) -> List[Dict]:
+        """``find_reuse`` for footage at ANOTHER PACE — a re-upload at another frame rate, a slow-motion replay, a video sampled
+        with other settings — where the matching frames leave the diagonal ``find_reuse`` reads: the k indexed videos that
+        show ``video_name`` under a monotone time warp, itself excluded, ``[{'video_name', 'score', 'start', 'end'}]``, the
+        best first.  Every frame of ``video_name``, in timestamp order, is paired with one or more consecutive frames of the
+        other video (``HNSWIndex.align_group`` on the embeddings as stored: exact); ``score`` is the mean cosine similarity
+        over ``video_name``'s frames along the best such pairing, ``start`` / ``end`` the timestamps in the found video where
+        it begins and ends.  Videos whose score is below ``min_similarity`` do not appear (``None``: no limit).  ``KeyError``
+        for an unknown video, ``ValueError`` for a video of more than 4,096 frames unless ``max_frames`` thins it out."""
+        if min_similarity is not None and not min_similarity <= 1:    # (NaN too)
+            raise ValueError(f"min_similarity must be <= 1, got {min_similarity}")
+        if not any(md.get("video_name") == video_name for md in self.metadata):
+            raise KeyError(video_name)
+        max_distance = None if min_similarity is None else np.float32(1) - np.float32(min_similarity)
+        res = self._device(ranks=True).align_group(video_name, k, max_distance, group_of=self._group_fn, position_of=self._pos_fn,
+                                                   max_frames=max_frames)
+        return [{"video_name": r["group"], "score": float(r["score"]), "start": self.metadata[-r["start_id"]]["timestamp"],
+                 "end": self.metadata[-r["end_id"]]["timestamp"]} for r in res]
+
     def _other_video_neighbors(self, per_frame: int):
         """The library's neighbour table: for every stored frame its ``per_frame`` nearest frames of OTHER videos
         (``HNSWIndex.neighbors(other_groups=True)`` on the embeddings as stored: exact, ties between frames as ``search``).
